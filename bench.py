@@ -8,6 +8,11 @@ through the GF(2^128) LCH14 additive FFT (lib/gf2k/lch14.h:106-124) is reported 
 secondary keys.  N > 1: rows are independent, each rank owns its own 1024 rows (weak
 scaling, no data-path collective); value = all ranks' elements / max-over-ranks time.
 
+A plain run sets up, warms up, times --steps steps and prints the headline line.  --full adds everything else the benchmark
+measures or checks: the oracle check of row 0, the CPU baseline, the secondary legs (LCH14 and F64_2 FFTs, Ligero commits,
+ZK proofs and throughput) and, at N > 1, the RCCL legs.  --dump-outputs DIR writes a fixed sample of what the last timed
+step left in the batch as DIR/*.npy.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -251,6 +256,22 @@ def ligero_commit_sharded(pkg, gpu, torch, np, dist, rank, world):
             "includes": "host layout replay + upload of the slab + RS encode + all_to_all + column hash + all_gather + tree"}
 
 
+def dump_outputs(out_dir, A, rows, n, np, torch):
+    """What the timed path hands its caller after the last step: the batch A (rows x n Fp128 elements, transformed in place;
+    16 GiB at the default size), so a fixed sample of it: the first 2^20 elements of row 0 and 2^16 elements at seeded
+    positions over all rows (their flat indices beside them).  An element is written as its four 32-bit Montgomery limbs,
+    low limb first, in float64, which holds them exactly."""
+    os.makedirs(out_dir, exist_ok=True)
+    limbs = A.view(torch.int32).view(-1, 4)
+    m = min(n, 1 << 20)
+    row0 = limbs[:m].cpu().numpy().view(np.uint32).astype(np.float64)
+    idx = np.sort(np.random.default_rng(20).integers(0, rows * n, size=min(rows * n, 1 << 16), dtype=np.int64))
+    sample = limbs[torch.from_numpy(idx).to(A.device)].cpu().numpy().view(np.uint32).astype(np.float64)
+    np.save(os.path.join(out_dir, "fft_row0_limbs.npy"), row0)
+    np.save(os.path.join(out_dir, "fft_sample_limbs.npy"), sample)
+    np.save(os.path.join(out_dir, "fft_sample_index.npy"), idx.astype(np.float64))
+
+
 PUBLISHED_M4_MS = {1: 5.30, 2: 9.60, 4: 18.73, 8: 35.39, 16: 65.62, 32: 125.23, 33: 132.71}  # docs/content/en/docs/benchmarks.md:55-61
 
 
@@ -424,11 +445,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--rows", type=int, default=1024)
     ap.add_argument("--logn", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the oracle check, the CPU baseline, the secondary legs and (N > 1) the RCCL legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write a fixed sample of the batch as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baselines")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: leave out the secondary legs")
     ap.add_argument("--force-dist", action="store_true", help="initialise torch.distributed (RCCL) even with one rank: rehearses the N > 1 code path on a 1-GPU box")
     ap.add_argument("--rehearse-gloo", action="store_true", help="rehearsal of the N > 1 control flow on a ONE-GPU box: backend gloo (host-staged), every rank on device 0 (RCCL cannot put two ranks on one device); not a measurement")
     args = ap.parse_args()
+    secondary = args.full and not args.no_secondary
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # started bare with --gpus N: become the launcher.  Nothing in this process has touched the GPU (torch is not even
@@ -500,20 +524,21 @@ def main():
 
     # ---- the CPU baseline first (rank 0; bounded to ~10 s), before any GPU leg has host threads spinning; for N > 1 as well
     cpu_base = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         cpu_base = cpu_baseline(logn)
     barrier()
 
-    # ---- correctness guard (untimed): row 0 of one fftb against the oracle
-    import oracle_lib as ol
-    o = ol.oracle()
-    row0 = A[:n].cpu().numpy().view(np.uint64).copy()
-    gpu.fp128_fft(A.data_ptr(), rows, n)
-    torch.cuda.synchronize()
-    got0 = A[:n].cpu().numpy().view(np.uint64)
-    o.lfo_fp_fftb(ol.P(row0), n, o.lfo_fp_omega32(), 1 << 32)
-    if not (got0 == row0).all():
-        raise SystemExit("bench: GPU fftb row 0 differs from the oracle -- refusing to report a number")
+    if args.full:
+        # ---- correctness guard (untimed): row 0 of one fftb against the oracle
+        import oracle_lib as ol
+        o = ol.oracle()
+        row0 = A[:n].cpu().numpy().view(np.uint64).copy()
+        gpu.fp128_fft(A.data_ptr(), rows, n)
+        torch.cuda.synchronize()
+        got0 = A[:n].cpu().numpy().view(np.uint64)
+        o.lfo_fp_fftb(ol.P(row0), n, o.lfo_fp_omega32(), 1 << 32)
+        if not (got0 == row0).all():
+            raise SystemExit("bench: GPU fftb row 0 differs from the oracle -- refusing to report a number")
 
     for _ in range(args.warmup):
         gpu.fp128_fft(A.data_ptr(), rows, n)
@@ -531,6 +556,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device="cuda")
         allreduce(tt, dist.ReduceOp.MAX)
         dt = float(tt.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, A, rows, n, np, torch)  # before any secondary leg reuses A
 
     launches_per_step = 1 if logn <= 12 else 2  # fp_fft_tile passes (fft.hip: tiles of 2^12 elements)
     # HBM bytes per launch from rocprofv3 PMC (FETCH_SIZE with the gfx950 correction + WRITE_SIZE), collected
@@ -579,7 +606,7 @@ def main():
         out["alu_roofline"] = {"bound": "valu", "achieved": rate, "peak": 36.0, "unit": "T lane-instr/s", "frac": rate / 36.0,
                                "basis": "static instruction counts x live kernel time"}
 
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and secondary:
         # secondary: same batch through the GF(2^128) LCH14 additive FFT (GF2_128<5>, l = logn)
         k = 5 if logn > 16 else 4
         for _ in range(1):
@@ -597,7 +624,7 @@ def main():
         out["gf2128_lch14_fft"] = {"field_elems_per_s": nelem / (ms * 1e-3), "ms_per_step": ms, "algo_GBps": agb,
                                    "roofline": {"bound": "hbm", "achieved": agb, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": agb / HBM_PEAK_GBS,
                                                 "note": "whole transform = bs_cin + bs_bfly passes + bs_cout; per-kernel HBM bytes (PMC) in profiles/r02/pmc_bs_kernels.json"}}
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and secondary:
         # secondary: the same plan and kernel over F64_2 = Fp2<Fp<1>>, p = 2^64 - 2^32 + 1 (BM_FFT_F64_2, lib/algebra/
         # fft_test.cc:205-229; docs/content/en/docs/benchmarks.md:37 publishes 66.65 ms for ONE 2^20-point row)
         v = A.view(torch.int64)
@@ -618,13 +645,13 @@ def main():
                             "published_cpu_ms_per_row_2pow20": 66.65,
                             "roofline": {"bound": "hbm", "achieved": agb, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": agb / HBM_PEAK_GBS,
                                          "note": "same two-pass plan and kernel (fp_fft_tile) as the headline, cheaper field"}}
-    if rank == 0 and not args.no_secondary and logn == 20 and rows == 1024:
+    if rank == 0 and secondary and logn == 20 and rows == 1024:
         out["ligero_commit_slig"] = ligero_commit_slig(gpu, torch, np, A, rows, logn, pmc_all)
-    if rank == 0 and not args.no_secondary:
+    if rank == 0 and secondary:
         out["ligero_commit_flatsha32"] = ligero_commit_shape(gpu, torch, np, stream, not args.no_cpu_baseline)
     del A  # the ZK path allocates its own buffers
     torch.cuda.empty_cache()
-    if not args.no_secondary:
+    if secondary:
         # ---- BASELINE's first metric on EVERY rank (independent proofs are the N-GPU mode of the real circuits: their tableaux are
         # 2.5 - 20 MB): latency of one proof per rank, then the throughput mode, summed over the ranks below
         mine = {}
@@ -682,7 +709,7 @@ def main():
                 "rank0_sweep": thr,
                 "cpu_reference_proofs_per_s_1_thread": {"flatsha256_32_blocks": (1e3 / out["zk_prove_flatsha256"]["cpu_reference"]["total_ms"]) if isinstance(out.get("zk_prove_flatsha256"), dict) and out["zk_prove_flatsha256"].get("cpu_reference") else None}}
     watchdog = None
-    if dist is not None:
+    if dist is not None and args.full:
         # the legs below are collectives that have never run on more than one GPU in the build container: should one hang, the
         # line measured so far still goes out (rank 0) and every rank leaves, instead of the whole run being killed without a line
         import threading
@@ -698,7 +725,7 @@ def main():
         watchdog = threading.Timer(240.0, _bail)
         watchdog.daemon = True
         watchdog.start()
-    if dist is not None:
+    if dist is not None and args.full:
         # RCCL small-message latency (what a sharded sumcheck round-hand would pay per collective: all_gather of one (a0, a2)
         # pair = 32 bytes per rank; DESIGN.md section 6 weighs it against the 15 - 35 us round-hand)
         try:
@@ -719,7 +746,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             if rank == 0:
                 out["rccl_small_message"] = {"error": repr(e)[:200]}
-    if dist is not None and not args.no_secondary:
+    if dist is not None and secondary:
         try:  # the sharded Ligero commit over RCCL (every rank takes part); a failure here must not cost the headline line
             sh = ligero_commit_sharded(pkg, gpu, torch, np, dist, rank, world)
         except Exception as e:  # noqa: BLE001

@@ -145,14 +145,25 @@ def test_reference_stored_mdoc_fixtures_are_the_reference_files():
             assert open(src + "_hash_witness.bin", "rb").read() == hw and open(src + "_sig_witness.bin", "rb").read() == sw
 
 
-def test_reference_cpp_provers_reproduce_a_stored_mdoc_proof():
-    """CPU, build container only (reads the reference's artifact files where they lie): the reference's own C++ provers inside
-    run_mdoc_prover's flow write exactly the stored proof string -- which is what makes the stored files known-answer vectors
-    (oracle/ref_mdoc_stored_cpu.cc; all twelve specs reproduce, one is run here: version 6, circuit from the artifact file)."""
+def test_reference_cpp_provers_reproduce_a_stored_mdoc_proof(tmp_path):
+    """CPU: the reference's own C++ provers inside run_mdoc_prover's flow write exactly the stored proof string -- which is
+    what makes the stored files known-answer vectors (oracle/ref_mdoc_stored_cpu.cc; all twelve specs reproduce, one is run
+    here: version 6, circuit from the artifact file).  The artifact files are laid out from the committed fixtures in the
+    directory tree the program reads."""
     exe = os.path.join(ROOT, "oracle", "_ref", "mdoc_stored_cpu")
-    if not os.path.exists(exe) or not os.path.isdir("/root/reference/rust/applications/mdoc_zk/artifacts/proofs"):
-        pytest.skip("needs oracle/_ref/mdoc_stored_cpu and the reference tree (build container)")
-    out = subprocess.run([exe, "4"], capture_output=True, timeout=600)
+    if not os.path.exists(exe):
+        pytest.skip("oracle/_ref/mdoc_stored_cpu not built (needs the reference sources and zstd.h: make -C oracle ref)")
+    spec = [s for s in json.load(open(os.path.join(GOLD, "mdoc_artifacts.json")))["specs"] if s["zk_spec_index"] == 4][0]
+    stem = os.path.join(GOLD, spec["stem"])
+    art = tmp_path / "rust" / "applications" / "mdoc_zk" / "artifacts"
+    (art / "proofs").mkdir(parents=True)
+    (art / "circuits").mkdir()
+    h = spec["circuit_hash"]
+    (art / "proofs" / (h + ".bin")).write_bytes(open(stem + ".proof.bin", "rb").read())
+    (art / "proofs" / (h + "_hash_witness.bin")).write_bytes(lzma.decompress(open(stem + ".hash_witness.xz", "rb").read()))
+    (art / "proofs" / (h + "_sig_witness.bin")).write_bytes(lzma.decompress(open(stem + ".sig_witness.xz", "rb").read()))
+    (art / "circuits" / h).write_bytes(open(stem + ".circuit.zst", "rb").read())
+    out = subprocess.run([exe, "4", str(tmp_path)], capture_output=True, timeout=600)
     assert out.returncode == 0, (out.returncode, out.stdout.decode()[-500:], out.stderr.decode()[-1000:])
     res = json.loads(out.stdout.decode().strip().splitlines()[-1])
     assert res["identical"] is True and res["public_inputs_differing_from_stored"] == 0 and res["stored_bytes"] == 323932

@@ -9,7 +9,7 @@ GF2_128 the reference's C++ commitment root.
   * world 1, in process;
   * world 2 / 3, one process per rank sharing this box's single GPU: the same kernels, slabs and collectives as on a
     multi-GPU node; the transport is gloo with host staging because RCCL cannot put two ranks on one device.  (The
-    RCCL transport itself is exercised by bench.py --gpus N on the multi-GPU node and bench.py --force-dist here.)
+    RCCL transport itself is exercised by bench.py --gpus N --full on the multi-GPU node and bench.py --force-dist --full here.)
   * the ZK prover with a communicator (world 2): flatsha256 proofs with the tableau rows sharded, and replicated below the
     threshold -- wire bytes of the reference on every rank."""
 import os

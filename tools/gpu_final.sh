@@ -4,7 +4,7 @@ O=${1:-gpurun_out/final}
 mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/gputests.log 2>&1 || { tail -40 $O/gputests.log; exit 1; }
 tail -2 $O/gputests.log
-python bench.py > $O/bench.json 2> $O/bench.err
+timeout -k 10 600 python bench.py --full > $O/bench.json 2> $O/bench.err
 python - $O <<'P'
 import json,sys
 d=json.loads(open(sys.argv[1]+'/bench.json').read().strip().splitlines()[-1])
