@@ -10,6 +10,7 @@
 //               C*16-byte segments), pass B: n2-point transforms on contiguous rows.
 // Reference: lib/algebra/fft.h:70-201 (Fp128), lib/gf2k/lch14.h:92-144 (LCH14).
 #include <string>
+#include <type_traits>
 
 #include "ctx.h"
 
@@ -186,6 +187,135 @@ __global__ __launch_bounds__(FFT_THREADS) void fp_fft_tile(TilePlan p, const elt
   }
 }
 
+// ------------------------------------------------------------------ K1: the 1024 x 4 tile
+// Pass B runs T = 1024 points x C = 4 columns for every n >= 2^13, and at n = 2^20 pass A does too: fp_fft_tile_1024x4 is that
+// one tile on 512 threads (8 points each), with the round schedule, lane maps and LDS offsets fixed at compile time.
+//   round 0 (stages 0-2): in registers, straight from HBM.  Thread (kb, c) loads points k = kb + 128 a' (a' < 8), which are the
+//           radix-8 group b = bitrev7(kb) of bit-reversed positions 8b + a (a' = bitrev3(a)); all 8 loads are issued before
+//           the first wait, and the stage twiddles go from HBM to LDS beside them.  Its twiddles (j = 0) are uniform and its
+//           w^0 products are left out at compile time.
+//   round 1 (stages 3-5, radix 8), round 2 (stages 6-7, radix 4, two groups per thread): LDS -> registers -> LDS.
+//   round 3 (stages 8-9, radix 4, two groups per thread): LDS -> registers -> (pass A: x w_n^(j1 k2)) -> HBM.
+// Rounds 1-3 multiply by every twiddle, w^0 = Montgomery 1 included (fp_mul(a, 1) = a for a < p): no per-lane branch.
+// Three barriers and three LDS round trips per tile instead of the generic kernel's five.
+//
+// LDS layout, conflict-free for every access of the tile (ds_write_b128: 8 x 8 consecutive lanes on 32 banks, ds_read_b128:
+// 4 x 16 lanes on 64 banks): position p, column c at slot (4p + c) ^ (p >> 7), the XOR staying inside an aligned 16-slot row.
+// The stage twiddles w_1024^i (i < 512) sit behind the tile at slot i ^ ((i >> 4) & 15).
+__device__ __forceinline__ u32 t4_wslot(u32 i) { return i ^ ((i >> 4) & 15u); }
+
+// R radix-2 stages (from stage ST) on the register group x[a] = position i0 + a 2^ST, j = i0 mod 2^ST; as fp_radix_round.
+// ROUND0 (ST = 0, j = 0): twiddles read from HBM at uniform addresses, the w^0 products left out.
+template <class O, u32 ST, u32 R, bool ROUND0>
+__device__ __forceinline__ void t4_stages(elt_t* x, u32 j, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
+#pragma unroll
+  for (u32 t = 0; t < R; ++t) {
+    const u32 half = 1u << t;
+#pragma unroll
+    for (u32 a = 0; a < (1u << R); ++a) {
+      if (a & half) continue;
+      const u32 jj = j + (a & (half - 1)) * (1u << ST), sh = 9 - ST - t;
+      if (!ROUND0) x[a + half] = O::mul_tw(x[a + half], ld16(&wl[t4_wslot(jj << sh)]));
+      else if (a & (half - 1)) x[a + half] = O::mul_tw(x[a + half], ld16(&W[(size_t)(jj << sh) << wshift]));
+      const elt_t u = x[a], v = x[a + half];
+      x[a] = O::add(u, v);
+      x[a + half] = O::sub(u, v);
+    }
+  }
+}
+
+// KFAST_SRC: pass B (points contiguous, columns n2 apart); otherwise pass A (columns contiguous).  The store side is columns
+// contiguous in both passes (kfast_dst = 0).  TW: pass A's inter-pass product with the full [j][column] table.
+// Needs p.logT = 10, p.logC = 2, p.wlds, p.nbatch a multiple of 4 (no partial tiles).
+template <class O, bool KFAST_SRC, bool TW>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                             const elt_t* __restrict__ tw, u32 row_fast) {
+  extern __shared__ elt_t s[];
+  elt_t* const wl = s + 4096;
+  const u32 tid = threadIdx.x;
+  const u32 bx = row_fast ? blockIdx.y : blockIdx.x, by = row_fast ? blockIdx.x : blockIdx.y;  // (tile, batch row)
+  const u32 cbase = bx << 2;
+  {  // round 0.  Pass B: a wave reads 64 consecutive points of one column; pass A: 16 rows of 4 consecutive columns.
+    const u32 c = KFAST_SRC ? tid >> 7 : tid & 3, kb = KFAST_SRC ? tid & 127 : tid >> 2;
+    const elt_t* src = p.src + (long long)by * p.src_row + (long long)bx * p.src_tile + (long long)kb * p.sk + (long long)c * p.sc;
+    elt_t y[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) y[a] = ld16(src + (long long)(128 * a) * p.sk);
+    const elt_t wv = ld16(&W[(size_t)tid << wshift]);
+    __builtin_amdgcn_sched_barrier(0);  // all nine loads in flight before the first wait (the scheduler would sink them)
+    elt_t x[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];  // x[a] = y[bitrev3(a)]
+    t4_stages<O, 0, 3, true>(x, 0, wl, W, wshift);
+    // position 8b + a: slot (32b + 4a + c) ^ (b >> 4); the XOR reaches bit 2, so odd a have a base of their own
+    const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
+#pragma unroll
+    for (u32 a = 0; a < 8; a += 2) {
+      st16(&s[s0 + 4 * a], x[a]);
+      st16(&s[s1 + 4 * a], x[a + 1]);
+    }
+    st16(&wl[t4_wslot(tid)], wv);
+  }
+  __syncthreads();
+  {  // round 1: group (c, j < 8, h < 16) = positions 64h + j + 8a; (p >> 7) = h >> 1 for all eight
+    const u32 c = tid & 3, j = (tid >> 2) & 7, h = tid >> 5;
+    const u32 s0 = (((64 * h + j) << 2) | c) ^ (h >> 1);
+    elt_t x[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
+    t4_stages<O, 3, 3, false>(x, j, wl, W, wshift);
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
+  }
+  __syncthreads();
+  elt_t t[2][4];  // pass A: the inter-pass twiddles of round 3's outputs
+  {  // round 2: group (c, j < 64, h < 4) = positions 256h + j + 64a; (p >> 7) = 2h + (a >> 1)
+    u32 s0[2], j[2];
+    elt_t x[2][4];
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {
+      const u32 e = tid + 512 * g, c = e & 3, h = e >> 8;
+      j[g] = (e >> 2) & 63;
+      s0[g] = (((256 * h + j[g]) << 2) | c) ^ (2 * h);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) x[g][a] = ld16(&s[(s0[g] ^ (a >> 1)) + 256 * a]);
+    }
+    if (TW) {  // w_n^(j1 k2) = tw[j1 * nbatch + k2] for j1 = j + 256a (round 3's map), all eight in flight during rounds 2 and 3
+#pragma unroll
+      for (u32 g = 0; g < 2; ++g) {
+        const u32 e = tid + 512 * g;
+#pragma unroll
+        for (u32 a = 0; a < 4; ++a) t[g][a] = ld16(&tw[(size_t)((e >> 2) + 256 * a) * p.nbatch + cbase + (e & 3)]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {
+      t4_stages<O, 6, 2, false>(x[g], j[g], wl, W, wshift);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) st16(&s[(s0[g] ^ (a >> 1)) + 256 * a], x[g][a]);
+    }
+  }
+  __syncthreads();
+  {  // round 3: group (c, j < 256) = positions (= output points) j + 256a; (p >> 7) = (j >> 7) + 2a.  Lanes walk c, then j.
+    elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {
+      const u32 e = tid + 512 * g, c = e & 3, j = e >> 2;
+      const u32 s0 = ((j << 2) | c) ^ (j >> 7);
+      elt_t x[4];
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+      t4_stages<O, 8, 2, false>(x, j, wl, W, wshift);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) {
+        if (TW) x[a] = O::mul_tw(x[a], t[g][a]);
+        st16(dst + (long long)(j + 256 * a) * p.dk + (long long)c * p.dc, x[a]);
+      }
+    }
+  }
+}
+
 // ------------------------------------------------------------------ K2: LCH14
 // Stage ii of the tile (global stage i = i_lo + ii) uses
 //   tw = tbl[off[ii] + u_local]  (^ base[ii*nb + cbase + c] when base != null)
@@ -264,6 +394,8 @@ static int set_lds_limit(lfgpu_ctx* c) {
       if (v == 12 || v == 13) c->tile_log = v;
     }
     LF_TRY(set_lds_limit_fp<Fp128Ops>(c));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
     LF_HIP(c, hipFuncSetAttribute((const void*)lch_fft_tile<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELTS * 16));
@@ -288,6 +420,22 @@ static void launch_fp(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePlan& p, Ar
     if (p.wlds) hipLaunchKernelGGL((fp_fft_tile<O, 512, true>), grid, dim3(512), lds, c->stream, p, args...);
     else hipLaunchKernelGGL((fp_fft_tile<O, 512, false>), grid, dim3(512), lds, c->stream, p, args...);
   }
+}
+// fp_fft_tile_1024x4 takes an Fp128 tile of 1024 x 4 in the 512-thread configuration; LFGPU_FP_TILE1024=0 keeps every tile on
+// the generic fp_fft_tile (read once)
+// (returns false, launching nothing, otherwise)
+template <class O, bool KFAST_SRC, bool TW>
+static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePlan& p, const elt_t* W, u32 wshift, const elt_t* tw,
+                               u32 row_fast) {
+  static const bool on = !(getenv("LFGPU_FP_TILE1024") && atoi(getenv("LFGPU_FP_TILE1024")) == 0);
+  if constexpr (std::is_same<O, Fp128Ops>::value) {
+    if (on && c->tile_log == 12 && p.logT == 10 && p.logC == 2 && p.wlds && p.kfast_src == (KFAST_SRC ? 1u : 0u) && p.kfast_dst == 0 &&
+        (p.nbatch & 3) == 0) {
+      hipLaunchKernelGGL((fp_fft_tile_1024x4<O, KFAST_SRC, TW>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+      return true;
+    }
+  }
+  return false;
 }
 template <class... Args>
 static void launch_lch(lfgpu_ctx* c, dim3 grid, size_t lds, Args... args) {
@@ -428,10 +576,11 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
     p.kfast_src = p.kfast_dst = 0;
     size_t lds = fp_lds_bytes(p);
     static const bool row_fast_env = !(getenv("LFGPU_FP_ROWFAST") && atoi(getenv("LFGPU_FP_ROWFAST")) == 0);
-    if (!two_level && rows <= 65535 && row_fast_env)  // rows fastest: the tile's table slice is reused by every row while it is hot
-      launch_fp<O>(c, dim3((u32)rows, (u32)(n2 >> p.logC)), lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, (const elt_t*)dhi, 1u);
-    else
-      launch_fp<O>(c, dim3((u32)(n2 >> p.logC), (u32)rows), lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, (const elt_t*)dhi, 0u);
+    // rows fastest: the tile's table slice is reused by every row while it is hot
+    const u32 row_fast = (!two_level && rows <= 65535 && row_fast_env) ? 1u : 0u;
+    const dim3 grid = row_fast ? dim3((u32)rows, (u32)(n2 >> p.logC)) : dim3((u32)(n2 >> p.logC), (u32)rows);
+    if (two_level || !launch_tile_1024x4<O, false, true>(c, grid, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, row_fast))
+      launch_fp<O>(c, grid, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, (const elt_t*)dhi, row_fast);
     LF_HIP(c, hipGetLastError());
   }
   {  // pass B: n2-point transforms on contiguous rows j1; output X[j1 + n1*j2]
@@ -453,8 +602,9 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
     p.kfast_src = 1;
     p.kfast_dst = 0;
     size_t lds = fp_lds_bytes(p);
-    launch_fp<O>(c, dim3((u32)(n1 >> p.logC), (u32)rows), lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)nullptr,
-              (const elt_t*)nullptr, 0u);
+    const dim3 grid((u32)(n1 >> p.logC), (u32)rows);
+    if (!launch_tile_1024x4<O, true, false>(c, grid, lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)nullptr, 0u))
+      launch_fp<O>(c, grid, lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)nullptr, (const elt_t*)nullptr, 0u);
     LF_HIP(c, hipGetLastError());
   }
   return LFGPU_OK;
