@@ -268,7 +268,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4(TilePlan p, const e
     for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
   }
   __syncthreads();
-  elt_t t[2][4];  // pass A: the inter-pass twiddles of round 3's outputs
+  elt_t y[8], t[2][4];  // pass A: the inter-pass twiddles of round 3's outputs
   {  // round 2: group (c, j < 64, h < 4) = positions 256h + j + 64a; (p >> 7) = 2h + (a >> 1)
     u32 s0[2], j[2];
     elt_t x[2][4];
@@ -311,6 +311,117 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4(TilePlan p, const e
       for (u32 a = 0; a < 4; ++a) {
         if (TW) x[a] = O::mul_tw(x[a], t[g][a]);
         st16(dst + (long long)(j + 256 * a) * p.dk + (long long)c * p.dc, x[a]);
+      }
+    }
+  }
+}
+
+// Pass A's round-0 loads of tile (row by, column block bx): thread (kb, c) = (tid >> 2, tid & 3) reads points kb + 128 a'.
+// Offsets inside the row in 32 bits (the host keeps 1024 sk + 4 sc below 2^32).
+__device__ __forceinline__ void t4a_load(elt_t* y, const TilePlan& p, u32 by, u32 bx, u32 tid) {
+  const elt_t* src = p.src + (long long)by * p.src_row + (long long)bx * p.src_tile;
+  const u32 sk = (u32)p.sk, off = (tid >> 2) * sk + (tid & 3) * (u32)p.sc;
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) y[a] = ld16(src + (off + 128 * a * sk));
+}
+
+// Pass A (columns contiguous, inter-pass product) in an XCD-aware tile order, optionally as a tile loop: the same rounds and LDS
+// layout as fp_fft_tile_1024x4.  With parts < rows each workgroup keeps one column block bx and walks down a range of batch rows,
+// so what depends on bx alone is loaded once (with parts = rows, the default, every workgroup takes one tile):
+//   - the eight inter-pass twiddles w_n^(j1 k2) of each thread stay in registers (t) for every tile;
+//   - the stage twiddles go to LDS once.
+// Tile order: workgroup w = 8i + x (x: the blocks that share an XCD, blocks being dealt round-robin over the 8 XCDs) takes
+// column block (ncb/8) x + i mod (ncb/8) and part i / (ncb/8) of the rows.  The workgroups of one XCD then read adjacent
+// 64-byte segments of the same rows at about the same time, and its L2 holds only their 1/8 of the twiddle table.
+// Grid: ncb * parts workgroups (ncb = p.nbatch / 4 column blocks); part q covers rows [q rows / parts, (q + 1) rows / parts).
+template <class O>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                                     const elt_t* __restrict__ tw, u32 rows, u32 parts) {
+  extern __shared__ elt_t s[];
+  elt_t* const wl = s + 4096;
+  const u32 tid = threadIdx.x, ncb = p.nbatch >> 2, w = blockIdx.x;
+  u32 bx, part;
+  if ((ncb & 7) == 0) {
+    const u32 per = ncb >> 3, i = w >> 3;
+    bx = (w & 7) * per + i % per;
+    part = i / per;
+  } else {
+    bx = w % ncb;
+    part = w / ncb;
+  }
+  const u32 r0 = (u32)((u64)part * rows / parts), r1 = (u32)((u64)(part + 1) * rows / parts);
+  const u32 cbase = bx << 2;
+  elt_t y[8], t[2][4];
+#pragma unroll
+  for (u32 g = 0; g < 2; ++g) {  // w_n^(j1 k2) = tw[j1 * nbatch + k2] for round 3's outputs j1 = j + 256a
+    const u32 e = tid + 512 * g;
+#pragma unroll
+    for (u32 a = 0; a < 4; ++a) t[g][a] = ld16(&tw[(size_t)((e >> 2) + 256 * a) * p.nbatch + cbase + (e & 3)]);
+  }
+  st16(&wl[t4_wslot(tid)], ld16(&W[(size_t)tid << wshift]));  // read after the first tile's first barrier
+  for (u32 by = r0; by < r1; ++by) {
+    // every per-lane index below is recomputed per tile from lt: hoisted out of the loop, the addresses would hold more VGPRs
+    // than the 128 of four waves per SIMD
+    u32 lt = tid;
+    asm volatile("" : "+v"(lt));
+    t4a_load(y, p, by, bx, lt);
+    {  // round 0, as in fp_fft_tile_1024x4
+      const u32 c = lt & 3, kb = lt >> 2;
+      elt_t x[8];
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];
+      t4_stages<O, 0, 3, true>(x, 0, wl, W, wshift);
+      const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
+#pragma unroll
+      for (u32 a = 0; a < 8; a += 2) {
+        st16(&s[s0 + 4 * a], x[a]);
+        st16(&s[s1 + 4 * a], x[a + 1]);
+      }
+    }
+    __syncthreads();
+    {  // round 1
+      const u32 c = lt & 3, j = (lt >> 2) & 7, h = lt >> 5;
+      const u32 s0 = (((64 * h + j) << 2) | c) ^ (h >> 1);
+      elt_t x[8];
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
+      t4_stages<O, 3, 3, false>(x, j, wl, W, wshift);
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
+    }
+    __syncthreads();
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {  // round 2
+      const u32 e = lt + 512 * g, c = e & 3, h = e >> 8, j = (e >> 2) & 63;
+      const u32 s0 = (((256 * h + j) << 2) | c) ^ (2 * h);
+      elt_t x[4];
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (a >> 1)) + 256 * a]);
+      t4_stages<O, 6, 2, false>(x, j, wl, W, wshift);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ (a >> 1)) + 256 * a], x[a]);
+    }
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);  // keeps round 2's and round 3's instructions apart: interleaved, they spill
+    {  // round 3: both groups out of LDS first; after the barrier the tile's LDS belongs to the next tile's round 0 (one barrier
+       // more per tile than fp_fft_tile_1024x4; this order needs fewer VGPRs than a barrier at the end of the loop)
+      elt_t x[2][4];
+#pragma unroll
+      for (u32 g = 0; g < 2; ++g) {
+        const u32 e = lt + 512 * g, c = e & 3, j = e >> 2;
+        const u32 s0 = ((j << 2) | c) ^ (j >> 7);
+#pragma unroll
+        for (u32 a = 0; a < 4; ++a) x[g][a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+      }
+      __syncthreads();
+      elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
+      const u32 dk = (u32)p.dk, dc = (u32)p.dc;
+#pragma unroll
+      for (u32 g = 0; g < 2; ++g) {
+        const u32 e = lt + 512 * g, c = e & 3, j = e >> 2;
+        t4_stages<O, 8, 2, false>(x[g], j, wl, W, wshift);
+#pragma unroll
+        for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), O::mul_tw(x[g][a], t[g][a]));
       }
     }
   }
@@ -396,6 +507,7 @@ static int set_lds_limit(lfgpu_ctx* c) {
     LF_TRY(set_lds_limit_fp<Fp128Ops>(c));
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_persist<Fp128Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
     LF_HIP(c, hipFuncSetAttribute((const void*)lch_fft_tile<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELTS * 16));
@@ -421,6 +533,32 @@ static void launch_fp(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePlan& p, Ar
     else hipLaunchKernelGGL((fp_fft_tile<O, 512, false>), grid, dim3(512), lds, c->stream, p, args...);
   }
 }
+// Pass A through fp_fft_tile_1024x4_persist.  LFGPU_FP_PERSIST: 0 = fp_fft_tile_1024x4 in the grid order of the caller, 1 (default)
+// = one tile per workgroup in the XCD-aware tile order, 2 = the tile loop on as many workgroups as the CUs hold at once (measured
+// slower than 1: 29.7 against 28.1 ms per bench.py step).  Returns false, launching nothing, for 0.
+template <class O>
+static bool launch_tile_1024x4_persist(lfgpu_ctx* c, u32 rows, size_t lds, const TilePlan& p, const elt_t* W, u32 wshift, const elt_t* tw) {
+  static const int mode = getenv("LFGPU_FP_PERSIST") ? atoi(getenv("LFGPU_FP_PERSIST")) : 1;
+  const u32 ncb = p.nbatch >> 2;
+  u32 parts = rows;
+  if (mode <= 0 || (u64)p.sk * 1024 + (u64)p.sc * 4 > 0xffffffffu || (u64)p.dk * 1024 + (u64)p.dc * 4 > 0xffffffffu) return false;
+  if (mode >= 2) {
+    static const int per_cu = [lds] {  // 2: LDS (2 x 72 KiB) and VGPRs (<= 128) both allow two workgroups per CU
+      int n = 0;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (const void*)fp_fft_tile_1024x4_persist<O>, 512, lds) != hipSuccess)
+        n = 0;
+      return n < 1 ? 1 : n;
+    }();
+    const u32 fill = (u32)per_cu * (u32)c->num_cu;
+    parts = fill / ncb;
+    if (parts < 1) parts = 1;
+    if (parts > rows) parts = rows;
+  }
+  if ((u64)ncb * parts > 0x7fffffffu) return false;
+  const dim3 grid(ncb * parts);
+  hipLaunchKernelGGL((fp_fft_tile_1024x4_persist<O>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, rows, parts);
+  return true;
+}
 // fp_fft_tile_1024x4 takes an Fp128 tile of 1024 x 4 in the 512-thread configuration; LFGPU_FP_TILE1024=0 keeps every tile on
 // the generic fp_fft_tile (read once)
 // (returns false, launching nothing, otherwise)
@@ -431,6 +569,8 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
   if constexpr (std::is_same<O, Fp128Ops>::value) {
     if (on && c->tile_log == 12 && p.logT == 10 && p.logC == 2 && p.wlds && p.kfast_src == (KFAST_SRC ? 1u : 0u) && p.kfast_dst == 0 &&
         (p.nbatch & 3) == 0) {
+      if constexpr (!KFAST_SRC && TW)
+        if (launch_tile_1024x4_persist<O>(c, row_fast ? grid.x : grid.y, lds, p, W, wshift, tw)) return true;
       hipLaunchKernelGGL((fp_fft_tile_1024x4<O, KFAST_SRC, TW>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
       return true;
     }
