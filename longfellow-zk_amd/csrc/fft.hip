@@ -13,6 +13,7 @@
 #include <type_traits>
 
 #include "ctx.h"
+#include "fp_tile_arith.h"
 
 int lf_lch14_fft_bitsliced(lfgpu_ctx* c, int k, int inverse, size_t rows, unsigned l, u64 coset, void* d_B, size_t ld);
 
@@ -204,6 +205,19 @@ __global__ __launch_bounds__(FFT_THREADS) void fp_fft_tile(TilePlan p, const elt
 // The stage twiddles w_1024^i (i < 512) sit behind the tile at slot i ^ ((i >> 4) & 15).
 __device__ __forceinline__ u32 t4_wslot(u32 i) { return i ^ ((i >> 4) & 15u); }
 
+// The arithmetic of the 1024 x 4 tiles: O's own, except for Fp128, whose add, sub and twiddle product come from
+// fp_tile_arith.h (same values, fewer VALU instructions).
+template <class O>
+struct T4Ops : O {};
+#if defined(__HIP_DEVICE_COMPILE__)
+template <>
+struct T4Ops<Fp128Ops> : Fp128Ops {
+  static __device__ __forceinline__ elt_t add(elt_t a, elt_t b) { return fpt_add(a, b); }
+  static __device__ __forceinline__ elt_t sub(elt_t a, elt_t b) { return fpt_sub(a, b); }
+  static __device__ __forceinline__ elt_t mul_tw(elt_t a, elt_t w) { return fpt_mul(a, w); }
+};
+#endif
+
 // R radix-2 stages (from stage ST) on the register group x[a] = position i0 + a 2^ST, j = i0 mod 2^ST; as fp_radix_round.
 // ROUND0 (ST = 0, j = 0): twiddles read from HBM at uniform addresses, the w^0 products left out.
 template <class O, u32 ST, u32 R, bool ROUND0>
@@ -215,11 +229,11 @@ __device__ __forceinline__ void t4_stages(elt_t* x, u32 j, const elt_t* wl, cons
     for (u32 a = 0; a < (1u << R); ++a) {
       if (a & half) continue;
       const u32 jj = j + (a & (half - 1)) * (1u << ST), sh = 9 - ST - t;
-      if (!ROUND0) x[a + half] = O::mul_tw(x[a + half], ld16(&wl[t4_wslot(jj << sh)]));
-      else if (a & (half - 1)) x[a + half] = O::mul_tw(x[a + half], ld16(&W[(size_t)(jj << sh) << wshift]));
+      if (!ROUND0) x[a + half] = T4Ops<O>::mul_tw(x[a + half], ld16(&wl[t4_wslot(jj << sh)]));
+      else if (a & (half - 1)) x[a + half] = T4Ops<O>::mul_tw(x[a + half], ld16(&W[(size_t)(jj << sh) << wshift]));
       const elt_t u = x[a], v = x[a + half];
-      x[a] = O::add(u, v);
-      x[a + half] = O::sub(u, v);
+      x[a] = T4Ops<O>::add(u, v);
+      x[a + half] = T4Ops<O>::sub(u, v);
     }
   }
 }
@@ -309,7 +323,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4(TilePlan p, const e
       t4_stages<O, 8, 2, false>(x, j, wl, W, wshift);
 #pragma unroll
       for (u32 a = 0; a < 4; ++a) {
-        if (TW) x[a] = O::mul_tw(x[a], t[g][a]);
+        if (TW) x[a] = T4Ops<O>::mul_tw(x[a], t[g][a]);
         st16(dst + (long long)(j + 256 * a) * p.dk + (long long)c * p.dc, x[a]);
       }
     }
@@ -365,6 +379,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p,
     u32 lt = tid;
     asm volatile("" : "+v"(lt));
     t4a_load(y, p, by, bx, lt);
+    __builtin_amdgcn_sched_barrier(0);  // all eight in flight before the first wait, as in fp_fft_tile_1024x4
     {  // round 0, as in fp_fft_tile_1024x4
       const u32 c = lt & 3, kb = lt >> 2;
       elt_t x[8];
@@ -421,7 +436,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p,
         const u32 e = lt + 512 * g, c = e & 3, j = e >> 2;
         t4_stages<O, 8, 2, false>(x[g], j, wl, W, wshift);
 #pragma unroll
-        for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), O::mul_tw(x[g][a], t[g][a]));
+        for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), T4Ops<O>::mul_tw(x[g][a], t[g][a]));
       }
     }
   }

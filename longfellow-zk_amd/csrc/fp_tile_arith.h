@@ -1,0 +1,194 @@
+// fp_tile_arith.h -- the Fp128 add, sub and twiddle product of K1's 1024 x 4 tile kernels (csrc/fft.hip).
+//
+// Same values as fp_add / fp_sub / fp_mul of fields.h for canonical inputs (< p), with fewer VALU instructions:
+//   - fpt_mul: the first carry of every product column is written into the high half of the next column's accumulator
+//     instead of added to a zeroed one (one v_mov per column instead of two); the REDC's delta and the final carry stay
+//     lane masks in SGPR pairs (v_add_co / v_cmp with an SGPR destination, combined by SALU) instead of two carry chains
+//     of their own; 71 -> 63 VALU instructions per product.
+//   - fpt_add: the carry-out of a + b stays a lane mask and is merged with the borrow of (a + b) - p by one SALU
+//     instruction: 14 -> 12 VALU instructions.
+//   - fpt_sub: the borrow of a - b, kept in an SGPR pair, is the carry-in of the + p chain: 10 -> 9.
+// Every value stays canonical, so what the tiles keep in LDS and write to HBM is unchanged.
+//
+// Wait states: gfx950 needs 2 between a VALU that writes an SGPR or VCC and a VALU that reads it (carry-in, mask), and
+// hipcc inserts none inside an asm statement, so every such link carries an `s_nop 1`, as in fields.h.  The same is kept
+// in front of the SALU instructions that read a mask a VALU wrote.  Each asm statement keeps VCC and its SGPR masks live
+// only inside itself, and the ones with SALU instructions clobber SCC: the compiler may hold a live SCC across them (the carry
+// of a 64-bit address add, a loop's branch condition).
+#pragma once
+#include "fields.h"
+
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ elt_t fpt_add(elt_t a, elt_t b) {
+  FP_W(a, a0, a1, a2, a3);
+  FP_W(b, b0, b1, b2, b3);
+  u32 s0, s1, s2, s3, d0, d1, d2, d3;
+  u64 c;
+  asm("v_add_co_u32 %0, vcc, %9, %13\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %1, vcc, %10, %14, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %2, vcc, %11, %15, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %3, %8, %12, %16, vcc\n\t"  // carry-out of a + b: lane mask c
+      // s - p, p = {1, 0, 0, 0xfffff000}; final borrow set <=> s < p
+      "v_subrev_co_u32 %4, vcc, 1, %0\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32 %5, vcc, 0, %1, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32 %6, vcc, 0, %2, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subb_co_u32 %7, vcc, %3, %17, vcc\n\t"
+      "s_nop 1\n\t"
+      "s_andn2_b64 vcc, vcc, %8\n\t"  // keep s <=> (c:s) < p <=> borrow and no carry
+      "v_cndmask_b32 %4, %4, %0, vcc\n\t"
+      "v_cndmask_b32 %5, %5, %1, vcc\n\t"
+      "v_cndmask_b32 %6, %6, %2, vcc\n\t"
+      "v_cndmask_b32 %7, %7, %3, vcc"
+      : "=&v"(s0), "=&v"(s1), "=&v"(s2), "=&v"(s3), "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&s"(c)
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(0xfffff000u)
+      : "vcc", "scc");
+  return FP_PACK(d0, d1, d2, d3);
+}
+
+__device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
+  FP_W(a, a0, a1, a2, a3);
+  FP_W(b, b0, b1, b2, b3);
+  u32 d0, d1, d2, d3, e3;
+  u64 bw;
+  asm("v_sub_co_u32 %0, vcc, %6, %10\n\t"
+      "s_nop 1\n\t"
+      "v_subb_co_u32 %1, vcc, %7, %11, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subb_co_u32 %2, vcc, %8, %12, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subb_co_u32 %3, %5, %9, %13, vcc\n\t"  // borrow of a - b: lane mask bw
+      "s_nop 1\n\t"
+      // borrow => + p: + bw at limb 0 (the mask is the carry-in), + 0xfffff000 at limb 3
+      "v_cndmask_b32 %4, 0, %14, %5\n\t"
+      "v_addc_co_u32 %0, vcc, 0, %0, %5\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %1, vcc, 0, %1, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %2, vcc, 0, %2, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %3, vcc, %4, %3, vcc"
+      : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(e3), "=&s"(bw)
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(0xfffff000u)
+      : "vcc");
+  return FP_PACK(d0, d1, d2, d3);
+}
+
+// acc(64) += x*y; the carry-out is WRITTEN to ov (the first carry of a column: ov would be 0) or added to it
+#define FPT_MADW(acc, ov, x, y) \
+  asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\ts_nop 1\n\tv_addc_co_u32 %1, vcc, 0, 0, vcc" : "+v"(acc), "=v"(ov) : "v"(x), "v"(y) : "vcc")
+#define FPT_COL(tk, acc, ov) \
+  tk = (u32)(acc);           \
+  acc = ((acc) >> 32) | ((u64)(ov) << 32)
+
+// a * w / 2^128 mod p for a, w < p (Montgomery), as fp_mul.  Product scanning with 16 v_mad_u64_u32; the carries of column k
+// go to ov, which becomes the high half of column k + 1's accumulator {acc.hi, ov}.
+__device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
+  FP_W(a, a0, a1, a2, a3);
+  FP_W(b, b0, b1, b2, b3);
+  u32 t0, t1, t2, t3, t4, t5, t6, t7, ov;
+  u64 acc;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(acc) : "v"(a0), "v"(b0) : "vcc");
+  t0 = (u32)acc;
+  acc >>= 32;
+  FP_MAD(acc, a0, b1);  // < 2^64: (2^32 - 1)^2 + 2^32 - 1
+  FPT_MADW(acc, ov, a1, b0);
+  FPT_COL(t1, acc, ov);
+  FPT_MADW(acc, ov, a0, b2);
+  FP_MADC(acc, ov, a1, b1);
+  FP_MADC(acc, ov, a2, b0);
+  FPT_COL(t2, acc, ov);
+  FPT_MADW(acc, ov, a0, b3);
+  FP_MADC(acc, ov, a1, b2);
+  FP_MADC(acc, ov, a2, b1);
+  FP_MADC(acc, ov, a3, b0);
+  FPT_COL(t3, acc, ov);
+  FPT_MADW(acc, ov, a1, b3);
+  FP_MADC(acc, ov, a2, b2);
+  FP_MADC(acc, ov, a3, b1);
+  FPT_COL(t4, acc, ov);
+  FPT_MADW(acc, ov, a2, b3);
+  FP_MADC(acc, ov, a3, b2);
+  FPT_COL(t5, acc, ov);
+  FP_MAD(acc, a3, b3);
+  t6 = (u32)acc;
+  t7 = (u32)(acc >> 32);
+  // REDC in one 128-bit step, as fp_mul: m = -U, U = (t0, t1, t2, u3), u3 = t3 + k, k = t0 << 12 (mod 2^32), and
+  //   (T + m p) / 2^128 = T_hi + m - (m >> 20) + delta,   delta = carry-out of T_lo + m.
+  // delta without the T_lo + m chain: U = 0 gives m = 0 and delta = 0; otherwise T_lo + m = 2^128 + (T_lo - U) and
+  // T_lo - U = (t3 - u3) 2^96, so delta = [t3 >= u3] = [k = 0 or t3 + k carries].  A carry implies k != 0, hence U != 0:
+  //   delta = cy | (kz & nz),   cy = carry of t3 + k,  kz = [k = 0],  nz = [U != 0] = borrow-out of 0 - U.
+  const u32 k = t0 << 12;
+  u32 m0, m1, m2, m3, u3;
+  u64 dl;
+  {
+    u64 cy, kz, nz;
+    asm("v_add_co_u32 %4, %5, %8, %12\n\t"
+        "v_cmp_eq_u32 %6, 0, %12\n\t"
+        "v_sub_co_u32 %0, vcc, 0, %9\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, 0, %10, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %2, vcc, 0, %11, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %3, %7, 0, %4, vcc\n\t"
+        "s_nop 1\n\t"
+        "s_and_b64 %7, %7, %6\n\t"
+        "s_or_b64 %5, %5, %7"
+        : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3), "=&v"(u3), "=&s"(cy), "=&s"(kz), "=&s"(nz)
+        : "v"(t3), "v"(t0), "v"(t1), "v"(t2), "v"(k)
+        : "vcc", "scc");
+    dl = cy;
+  }
+  const u32 s0 = __builtin_amdgcn_alignbit(m1, m0, 20), s1 = __builtin_amdgcn_alignbit(m2, m1, 20), s2 = __builtin_amdgcn_alignbit(m3, m2, 20),
+            s3 = m3 >> 20;
+  u32 d0, d1, d2, d3;
+  {
+    u32 q0, q1, q2, q3;
+    u64 c8;
+    asm("v_sub_co_u32 %0, vcc, %9, %13\n\t"  // q = m - (m >> 20): never borrows out
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %1, vcc, %10, %14, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %2, vcc, %11, %15, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %3, vcc, %12, %16, vcc\n\t"
+        "v_addc_co_u32 %4, vcc, %4, %0, %18\n\t"  // r = T_hi + q + delta = c8 2^128 + (t7..t4), < 2p
+        "s_nop 1\n\t"
+        "v_addc_co_u32 %5, vcc, %5, %1, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_addc_co_u32 %6, vcc, %6, %2, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_addc_co_u32 %7, %8, %7, %3, vcc\n\t"
+        // (t7..t4) - p; keep r <=> r < p <=> borrow and no c8
+        "v_subrev_co_u32 %0, vcc, 1, %4\n\t"
+        "s_nop 1\n\t"
+        "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subbrev_co_u32 %2, vcc, 0, %6, vcc\n\t"
+        "s_nop 1\n\t"
+        "v_subb_co_u32 %3, vcc, %7, %17, vcc\n\t"
+        "s_nop 1\n\t"
+        "s_andn2_b64 vcc, vcc, %8\n\t"
+        "v_cndmask_b32 %0, %0, %4, vcc\n\t"
+        "v_cndmask_b32 %1, %1, %5, vcc\n\t"
+        "v_cndmask_b32 %2, %2, %6, vcc\n\t"
+        "v_cndmask_b32 %3, %3, %7, vcc"
+        : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "+v"(t4), "+v"(t5), "+v"(t6), "+v"(t7), "=&s"(c8)
+        : "v"(m0), "v"(m1), "v"(m2), "v"(m3), "v"(s0), "v"(s1), "v"(s2), "v"(s3), "v"(0xfffff000u), "s"(dl)
+        : "vcc", "scc");
+    d0 = q0; d1 = q1; d2 = q2; d3 = q3;
+  }
+  return FP_PACK(d0, d1, d2, d3);
+}
+#else
+// the host pass of a kernel that calls them, and host code: the portable forms (same values)
+LF_HD elt_t fpt_add(elt_t a, elt_t b) { return fp_add_c(a, b); }
+LF_HD elt_t fpt_sub(elt_t a, elt_t b) { return fp_sub_c(a, b); }
+LF_HD elt_t fpt_mul(elt_t a, elt_t b) { return fp_mul_c(a, b); }
+#endif

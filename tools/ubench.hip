@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "../longfellow-zk_amd/csrc/fields.h"
 
 #define ITERS 4096
@@ -64,6 +65,38 @@ __global__ __launch_bounds__(256) void k(u32* out, u32 seed) {
     if (OP == 17)  // the two-instruction form: v_and + v_xor
       asm volatile("v_and_b32 %4, %0, %5\n\tv_xor_b32 %1, %1, %4\n\tv_and_b32 %4, %2, %5\n\tv_xor_b32 %3, %3, %4"
                    : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b) : "v"(seed ^ 0x55u));
+    // the instructions of K1's tile arithmetic (fp_tile_arith.h) and its alternatives, priced at 4 waves per SIMD (--rates4)
+    if (OP == 18)
+      asm volatile("v_mov_b32 %0, %1\n\tv_mov_b32 %1, %2\n\tv_mov_b32 %2, %3\n\tv_mov_b32 %3, %0" : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
+    if (OP == 19)  // select on VCC (written once, outside the loop's dependence chains)
+      asm volatile("v_cndmask_b32 %0, %0, %4, vcc\n\tv_cndmask_b32 %1, %1, %4, vcc\n\tv_cndmask_b32 %2, %2, %4, vcc\n\tv_cndmask_b32 %3, %3, %4, vcc"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b) : "vcc");
+    if (OP == 20)  // select on an SGPR-pair lane mask
+      asm volatile("v_cndmask_b32 %0, %0, %4, %5\n\tv_cndmask_b32 %1, %1, %4, %5\n\tv_cndmask_b32 %2, %2, %4, %5\n\tv_cndmask_b32 %3, %3, %4, %5"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b), "s"((u64)seed * 0x9E3779B97F4A7C15ull));
+    if (OP == 21)  // {hi of one pair, lo of another} in one instruction
+      asm volatile("v_pk_mov_b32 %0, %0, %1 op_sel:[1,0]\n\tv_pk_mov_b32 %1, %1, %2 op_sel:[1,0]\n\tv_pk_mov_b32 %2, %2, %3 op_sel:[1,0]\n\tv_pk_mov_b32 %3, %3, %0 op_sel:[1,0]"
+                   : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
+    if (OP == 22)
+      asm volatile("v_mov_b64 %0, %1\n\tv_mov_b64 %1, %2\n\tv_mov_b64 %2, %3\n\tv_mov_b64 %3, %0" : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3));
+    if (OP == 23)
+      asm volatile("v_lshl_add_u32 %0, %0, 3, %4\n\tv_lshl_add_u32 %1, %1, 3, %4\n\tv_lshl_add_u32 %2, %2, 3, %4\n\tv_lshl_add_u32 %3, %3, 3, %4"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b));
+    if (OP == 24) A4("v_add_u32", "%4");
+    if (OP == 25) A4("v_sub_u32", "%4");
+    if (OP == 26)
+      asm volatile("v_bfe_u32 %0, %0, 3, 27\n\tv_bfe_u32 %1, %1, 3, 27\n\tv_bfe_u32 %2, %2, 3, 27\n\tv_bfe_u32 %3, %3, 3, 27"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
+    if (OP == 27)
+      asm volatile("v_lshrrev_b32 %0, 3, %0\n\tv_lshrrev_b32 %1, 3, %1\n\tv_lshrrev_b32 %2, 3, %2\n\tv_lshrrev_b32 %3, 3, %3"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3));
+    if (OP == 28)  // compare into an SGPR pair (the lane masks of fpt_mul's REDC)
+      asm volatile("v_cmp_eq_u32 s[60:61], %0, %4\n\tv_cmp_eq_u32 s[62:63], %1, %4\n\tv_cmp_eq_u32 s[64:65], %2, %4\n\tv_cmp_eq_u32 s[66:67], %3, %4"
+                   : : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b) : "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67");
+    if (OP == 29)  // carry chain with the carry-in from an SGPR pair and the carry-out to another
+      asm volatile("v_addc_co_u32 %0, s[60:61], %0, %4, s[62:63]\n\tv_addc_co_u32 %1, s[64:65], %1, %4, s[62:63]\n\t"
+                   "v_addc_co_u32 %2, s[66:67], %2, %4, s[62:63]\n\tv_addc_co_u32 %3, s[68:69], %3, %4, s[62:63]"
+                   : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : "v"(b) : "s60", "s61", "s62", "s63", "s64", "s65", "s66", "s67", "s68", "s69");
     if (OP == 14)  // v_mad_u64_u32 with the accumulate chain only through the 64-bit addend (the schoolbook-row shape)
       asm volatile("v_mad_u64_u32 %0, vcc, %4, %5, %0\n\tv_mad_u64_u32 %1, vcc, %4, %6, %1\n\tv_mad_u64_u32 %2, vcc, %4, %7, %2\n\tv_mad_u64_u32 %3, vcc, %4, %8, %3"
                    : "+v"(c0), "+v"(c1), "+v"(c2), "+v"(c3) : "v"(b), "v"(a0), "v"(a1), "v"(a2), "v"(a3) : "vcc");
@@ -152,7 +185,29 @@ void runf(const char* name) {
   CHK(hipFree(d));
 }
 
-int main() {
+int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "--rates4")) {  // 40 KiB of LDS per 256-thread workgroup: 4 waves per SIMD
+    const size_t lds = 40 * 1024;
+    run_occ<4>("v_xor_b32 (fast ref)", 4, lds);
+    run_occ<8>("v_add_co+v_addc_co (slow ref)", 4, lds);
+    run_occ<14>("v_mad_u64_u32", 4, lds);
+    run_occ<18>("v_mov_b32", 4, lds);
+    run_occ<19>("v_cndmask_b32 (vcc)", 4, lds);
+    run_occ<20>("v_cndmask_b32 (sgpr pair)", 4, lds);
+    run_occ<21>("v_pk_mov_b32", 4, lds);
+    run_occ<22>("v_mov_b64", 4, lds);
+    run_occ<9>("v_lshl_add_u64", 4, lds);
+    run_occ<23>("v_lshl_add_u32", 4, lds);
+    run_occ<24>("v_add_u32", 4, lds);
+    run_occ<25>("v_sub_u32", 4, lds);
+    run_occ<26>("v_bfe_u32", 4, lds);
+    run_occ<27>("v_lshrrev_b32", 4, lds);
+    run_occ<12>("v_mad_u32_u24", 4, lds);
+    run_occ<7>("v_alignbit_b32", 4, lds);
+    run_occ<28>("v_cmp_eq_u32 (sgpr dst)", 4, lds);
+    run_occ<29>("v_addc_co_u32 (sgpr c-in/out)", 4, lds);
+    return 0;
+  }
   run<4>("v_xor_b32", 4);
   run<6>("v_add3_u32", 4);
   run<7>("v_alignbit_b32", 4);
