@@ -2,9 +2,9 @@
 //
 // Same values as fp_add / fp_sub / fp_mul of fields.h for canonical inputs (< p), with fewer VALU instructions:
 //   - fpt_mul: the first carry of every product column is written into the high half of the next column's accumulator
-//     instead of added to a zeroed one (one v_mov per column instead of two); the REDC's delta and the final carry stay
-//     lane masks in SGPR pairs (v_add_co / v_cmp with an SGPR destination, combined by SALU) instead of two carry chains
-//     of their own; 71 -> 63 VALU instructions per product.
+//     instead of added to a zeroed one (one v_mov per column instead of two); the REDC never forms m = -U: it computes
+//     T_hi - U + (U >> 20) + cy and adds p when that is negative (a sign from two carry masks merged by one SALU
+//     instruction): 27 -> 19 VALU instructions for the REDC, 71 -> 63 -> 55 per product.
 //   - fpt_add: the carry-out of a + b stays a lane mask and is merged with the borrow of (a + b) - p by one SALU
 //     instruction: 14 -> 12 VALU instructions.
 //   - fpt_sub: the borrow of a - b, kept in an SGPR pair, is the carry-in of the + p chain: 10 -> 9.
@@ -118,71 +118,53 @@ __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   FP_MAD(acc, a3, b3);
   t6 = (u32)acc;
   t7 = (u32)(acc >> 32);
-  // REDC in one 128-bit step, as fp_mul: m = -U, U = (t0, t1, t2, u3), u3 = t3 + k, k = t0 << 12 (mod 2^32), and
-  //   (T + m p) / 2^128 = T_hi + m - (m >> 20) + delta,   delta = carry-out of T_lo + m.
-  // delta without the T_lo + m chain: U = 0 gives m = 0 and delta = 0; otherwise T_lo + m = 2^128 + (T_lo - U) and
-  // T_lo - U = (t3 - u3) 2^96, so delta = [t3 >= u3] = [k = 0 or t3 + k carries].  A carry implies k != 0, hence U != 0:
-  //   delta = cy | (kz & nz),   cy = carry of t3 + k,  kz = [k = 0],  nz = [U != 0] = borrow-out of 0 - U.
+  // REDC in one 128-bit step, with U = (t0, t1, t2, u3), u3 = t3 + k, k = t0 << 12 (mod 2^32), cy = carry of t3 + k.
+  // fp_mul computes m = -U and (T + m p) / 2^128 = T_hi + m - (m >> 20) + delta, delta = carry-out of T_lo + m, which is
+  // cy | ([k = 0] & [U != 0]).  For U != 0, m >> 20 = 2^108 - ceil(U / 2^20) with ceil(U / 2^20) = (U >> 20) + [k != 0]
+  // (U and t0 share their low 20 bits), and m - 2^108 = p - 1 - U; a carry implies k != 0, so the small terms sum to cy:
+  //   W = T_hi - U + (U >> 20) + cy = (T + m p) / 2^128 - p,   -p <= W < p,   result W, or W + p if W < 0.
+  // U = 0 gives k = cy = 0 and W = T_hi < p, as fp_mul.  The sign: with b = borrow-out of T_hi - U and c = carry-out of
+  // + (U >> 20) + cy, W = (d3..d0) + (c - b) 2^128, so W < 0 <=> b and no c.  The cy link needs no s_nop: eight VALU
+  // instructions lie between its write and its read.  d0..d3 are outputs of their own, not T_hi's registers, so the
+  // allocator can put the result where its user wants it (tied to T_hi, pass A's one-tile kernel needed 23 more VALU).
   const u32 k = t0 << 12;
-  u32 m0, m1, m2, m3, u3;
-  u64 dl;
-  {
-    u64 cy, kz, nz;
-    asm("v_add_co_u32 %4, %5, %8, %12\n\t"
-        "v_cmp_eq_u32 %6, 0, %12\n\t"
-        "v_sub_co_u32 %0, vcc, 0, %9\n\t"
-        "s_nop 1\n\t"
-        "v_subb_co_u32 %1, vcc, 0, %10, vcc\n\t"
-        "s_nop 1\n\t"
-        "v_subb_co_u32 %2, vcc, 0, %11, vcc\n\t"
-        "s_nop 1\n\t"
-        "v_subb_co_u32 %3, %7, 0, %4, vcc\n\t"
-        "s_nop 1\n\t"
-        "s_and_b64 %7, %7, %6\n\t"
-        "s_or_b64 %5, %5, %7"
-        : "=&v"(m0), "=&v"(m1), "=&v"(m2), "=&v"(m3), "=&v"(u3), "=&s"(cy), "=&s"(kz), "=&s"(nz)
-        : "v"(t3), "v"(t0), "v"(t1), "v"(t2), "v"(k)
-        : "vcc", "scc");
-    dl = cy;
-  }
-  const u32 s0 = __builtin_amdgcn_alignbit(m1, m0, 20), s1 = __builtin_amdgcn_alignbit(m2, m1, 20), s2 = __builtin_amdgcn_alignbit(m3, m2, 20),
-            s3 = m3 >> 20;
   u32 d0, d1, d2, d3;
   {
-    u32 q0, q1, q2, q3;
-    u64 c8;
-    asm("v_sub_co_u32 %0, vcc, %9, %13\n\t"  // q = m - (m >> 20): never borrows out
+    u32 u3, s0, s1, s2, s3, e3;
+    u64 cy, b;
+    asm("v_add_co_u32 %4, %10, %12, %16\n\t"  // u3, cy
+        "v_alignbit_b32 %5, %14, %13, 20\n\t"  // U >> 20
+        "v_alignbit_b32 %6, %15, %14, 20\n\t"
+        "v_alignbit_b32 %7, %4, %15, 20\n\t"
+        "v_lshrrev_b32 %8, 20, %4\n\t"
+        "v_sub_co_u32 %0, vcc, %18, %13\n\t"  // T_hi - U
         "s_nop 1\n\t"
-        "v_subb_co_u32 %1, vcc, %10, %14, vcc\n\t"
+        "v_subb_co_u32 %1, vcc, %19, %14, vcc\n\t"
         "s_nop 1\n\t"
-        "v_subb_co_u32 %2, vcc, %11, %15, vcc\n\t"
+        "v_subb_co_u32 %2, vcc, %20, %15, vcc\n\t"
         "s_nop 1\n\t"
-        "v_subb_co_u32 %3, vcc, %12, %16, vcc\n\t"
-        "v_addc_co_u32 %4, vcc, %4, %0, %18\n\t"  // r = T_hi + q + delta = c8 2^128 + (t7..t4), < 2p
+        "v_subb_co_u32 %3, %11, %21, %4, vcc\n\t"  // borrow-out: lane mask b
+        "v_addc_co_u32 %0, vcc, %0, %5, %10\n\t"  // + (U >> 20) + cy, cy the carry-in
         "s_nop 1\n\t"
-        "v_addc_co_u32 %5, vcc, %5, %1, vcc\n\t"
+        "v_addc_co_u32 %1, vcc, %1, %6, vcc\n\t"
         "s_nop 1\n\t"
-        "v_addc_co_u32 %6, vcc, %6, %2, vcc\n\t"
+        "v_addc_co_u32 %2, vcc, %2, %7, vcc\n\t"
         "s_nop 1\n\t"
-        "v_addc_co_u32 %7, %8, %7, %3, vcc\n\t"
-        // (t7..t4) - p; keep r <=> r < p <=> borrow and no c8
-        "v_subrev_co_u32 %0, vcc, 1, %4\n\t"
+        "v_addc_co_u32 %3, %10, %3, %8, vcc\n\t"  // carry-out: lane mask c (in cy's SGPR pair)
         "s_nop 1\n\t"
-        "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
+        "s_andn2_b64 %10, %11, %10\n\t"  // W < 0 <=> b and no c
+        // W < 0 => + p: + 1 at limb 0 (the mask is the carry-in), + 0xfffff000 at limb 3, as fpt_sub
+        "v_cndmask_b32 %9, 0, %17, %10\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, %10\n\t"
         "s_nop 1\n\t"
-        "v_subbrev_co_u32 %2, vcc, 0, %6, vcc\n\t"
+        "v_addc_co_u32 %1, vcc, 0, %1, vcc\n\t"
         "s_nop 1\n\t"
-        "v_subb_co_u32 %3, vcc, %7, %17, vcc\n\t"
+        "v_addc_co_u32 %2, vcc, 0, %2, vcc\n\t"
         "s_nop 1\n\t"
-        "s_andn2_b64 vcc, vcc, %8\n\t"
-        "v_cndmask_b32 %0, %0, %4, vcc\n\t"
-        "v_cndmask_b32 %1, %1, %5, vcc\n\t"
-        "v_cndmask_b32 %2, %2, %6, vcc\n\t"
-        "v_cndmask_b32 %3, %3, %7, vcc"
-        : "=&v"(q0), "=&v"(q1), "=&v"(q2), "=&v"(q3), "+v"(t4), "+v"(t5), "+v"(t6), "+v"(t7), "=&s"(c8)
-        : "v"(m0), "v"(m1), "v"(m2), "v"(m3), "v"(s0), "v"(s1), "v"(s2), "v"(s3), "v"(0xfffff000u), "s"(dl)
+        "v_addc_co_u32 %3, vcc, %9, %3, vcc"
+        : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(u3), "=&v"(s0), "=&v"(s1), "=&v"(s2), "=&v"(s3), "=&v"(e3), "=&s"(cy), "=&s"(b)
+        : "v"(t3), "v"(t0), "v"(t1), "v"(t2), "v"(k), "v"(0xfffff000u), "v"(t4), "v"(t5), "v"(t6), "v"(t7)
         : "vcc", "scc");
-    d0 = q0; d1 = q1; d2 = q2; d3 = q3;
   }
   return FP_PACK(d0, d1, d2, d3);
 }
