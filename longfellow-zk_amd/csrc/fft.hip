@@ -442,6 +442,107 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p,
   }
 }
 
+// The 1024 x 4 tile with the inter-pass product on pass B's load side (n = 2^20, the default): same rounds, lane maps and LDS
+// layout as fp_fft_tile_1024x4, every offset inside a tile in 32 bits (the host keeps 1024 sk + 4 sc and 1024 dk + 4 dc below 2^32).
+//   pass A (KFAST_SRC = false): no table and no product.  1-D grid of ncb * rows workgroups in the XCD-aware tile order of
+//           fp_fft_tile_1024x4_persist (parts = rows): the workgroups of one XCD read adjacent 64-byte segments of the same rows.
+//   pass B (KFAST_SRC = true): what pass A wrote is laid out [j1][k2] like the full table tw[j1 * 1024 + k2], so thread (kb, c)
+//           loads w_n^(j1 k2) at the offset of its point (j1 = 4 bx + c, k2 = kb + 128 a'), coalesced, all 17 loads in flight
+//           before the first wait, and multiplies before round 0.  Row j1 = 0 and column k2 = 0 hold Montgomery 1: no branch.
+//           Grid (tile, row), or (row, tile) with row_fast.
+template <class O, bool KFAST_SRC>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                                 const elt_t* __restrict__ tw, u32 row_fast) {
+  extern __shared__ elt_t s[];
+  elt_t* const wl = s + 4096;
+  const u32 tid = threadIdx.x;
+  u32 bx, by;  // (tile, batch row)
+  if (KFAST_SRC) {
+    bx = row_fast ? blockIdx.y : blockIdx.x;
+    by = row_fast ? blockIdx.x : blockIdx.y;
+  } else {
+    const u32 ncb = p.nbatch >> 2, w = blockIdx.x;
+    if ((ncb & 7) == 0) {
+      const u32 per = ncb >> 3, i = w >> 3;
+      bx = (w & 7) * per + i % per;
+      by = i / per;
+    } else {
+      bx = w % ncb;
+      by = w / ncb;
+    }
+  }
+  {  // round 0
+    const u32 c = KFAST_SRC ? tid >> 7 : tid & 3, kb = KFAST_SRC ? tid & 127 : tid >> 2;
+    const elt_t* src = p.src + (long long)by * p.src_row + (long long)bx * p.src_tile;
+    const u32 sk = (u32)p.sk, off = kb * sk + c * (u32)p.sc;
+    elt_t y[8], t[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) y[a] = ld16(src + (off + 128 * a * sk));
+    if (KFAST_SRC) {
+      const elt_t* twt = tw + ((size_t)bx << 12);
+      const u32 toff = (c << 10) + kb;
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) t[a] = ld16(twt + (toff + 128 * a));
+    }
+    const elt_t wv = ld16(&W[(size_t)tid << wshift]);
+    __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first wait, as in fp_fft_tile_1024x4
+    if (KFAST_SRC) {
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) y[a] = T4Ops<O>::mul_tw(y[a], t[a]);
+    }
+    elt_t x[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];  // x[a] = y[bitrev3(a)]
+    t4_stages<O, 0, 3, true>(x, 0, wl, W, wshift);
+    const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
+#pragma unroll
+    for (u32 a = 0; a < 8; a += 2) {
+      st16(&s[s0 + 4 * a], x[a]);
+      st16(&s[s1 + 4 * a], x[a + 1]);
+    }
+    st16(&wl[t4_wslot(tid)], wv);
+  }
+  __syncthreads();
+  {  // round 1
+    const u32 c = tid & 3, j = (tid >> 2) & 7, h = tid >> 5;
+    const u32 s0 = (((64 * h + j) << 2) | c) ^ (h >> 1);
+    elt_t x[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
+    t4_stages<O, 3, 3, false>(x, j, wl, W, wshift);
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
+  }
+  __syncthreads();
+#pragma unroll
+  for (u32 g = 0; g < 2; ++g) {  // round 2
+    const u32 e = tid + 512 * g, c = e & 3, h = e >> 8, j = (e >> 2) & 63;
+    const u32 s0 = (((256 * h + j) << 2) | c) ^ (2 * h);
+    elt_t x[4];
+#pragma unroll
+    for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (a >> 1)) + 256 * a]);
+    t4_stages<O, 6, 2, false>(x, j, wl, W, wshift);
+#pragma unroll
+    for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ (a >> 1)) + 256 * a], x[a]);
+  }
+  __syncthreads();
+  {  // round 3
+    elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
+    const u32 dk = (u32)p.dk, dc = (u32)p.dc;
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {
+      const u32 e = tid + 512 * g, c = e & 3, j = e >> 2;
+      const u32 s0 = ((j << 2) | c) ^ (j >> 7);
+      elt_t x[4];
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+      t4_stages<O, 8, 2, false>(x, j, wl, W, wshift);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), x[a]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ K2: LCH14
 // Stage ii of the tile (global stage i = i_lo + ii) uses
 //   tw = tbl[off[ii] + u_local]  (^ base[ii*nb + cbase + c] when base != null)
@@ -523,6 +624,8 @@ static int set_lds_limit(lfgpu_ctx* c) {
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_persist<Fp128Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws<Fp128Ops, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws<Fp128Ops, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
     LF_HIP(c, hipFuncSetAttribute((const void*)lch_fft_tile<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELTS * 16));
@@ -589,6 +692,35 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
       hipLaunchKernelGGL((fp_fft_tile_1024x4<O, KFAST_SRC, TW>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
       return true;
     }
+  }
+  return false;
+}
+// The pair fp_fft_tile_1024x4_tws (inter-pass product on pass B's load side): the default for Fp128 when both passes are 1024 x 4
+// tiles (n = 2^20) and the full table is in use.  LFGPU_FP_TWSIDE=0, or any setting of LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 (which
+// choose among the kernels of the other plan), keeps the product in pass A; =2 runs pass B with the rows fastest in the grid.
+template <class O>
+static int fp_twside_mode(const lfgpu_ctx* c, u32 logn1, size_t rows, bool two_level) {
+  static const int mode = (getenv("LFGPU_FP_PERSIST") || getenv("LFGPU_FP_TILE1024")) ? 0
+                          : getenv("LFGPU_FP_TWSIDE")                                  ? atoi(getenv("LFGPU_FP_TWSIDE"))
+                                                                                       : 1;
+  if (!std::is_same<O, Fp128Ops>::value || two_level || c->tile_log != 12 || logn1 != 10 || rows > (0x7fffffffu >> 8)) return 0;
+  return mode < 0 ? 0 : mode;
+}
+// one pass of the pair; false, launching nothing, when the plan is not a 1024 x 4 tile with 32-bit offsets
+template <class O, bool KFAST_SRC>
+static bool launch_tile_1024x4_tws(lfgpu_ctx* c, u32 rows, size_t lds, const TilePlan& p, const elt_t* W, u32 wshift, const elt_t* tw,
+                                   u32 row_fast) {
+  if constexpr (std::is_same<O, Fp128Ops>::value) {
+    const u32 ncb = p.nbatch >> 2;
+    if (p.logT != 10 || p.logC != 2 || !p.wlds || p.kfast_src != (KFAST_SRC ? 1u : 0u) || p.kfast_dst != 0 || (p.nbatch & 3) != 0 ||
+        p.sk < 0 || p.sc < 0 || p.dk < 0 || p.dc < 0 || (u64)p.sk * 1024 + (u64)p.sc * 4 > 0xffffffffu ||
+        (u64)p.dk * 1024 + (u64)p.dc * 4 > 0xffffffffu || (u64)ncb * rows > 0x7fffffffu)
+      return false;
+    if (KFAST_SRC && (p.sk != 1 || p.sc != 1024 || p.src_tile != 4096)) return false;  // the table's layout [j1][k2]
+    if (KFAST_SRC && (row_fast ? ncb : rows) > 65535) row_fast = !row_fast;
+    const dim3 grid = !KFAST_SRC ? dim3(ncb * rows) : row_fast ? dim3(rows, ncb) : dim3(ncb, rows);
+    hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    return true;
   }
   return false;
 }
@@ -715,6 +847,7 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
   }
   void* scratch = nullptr;
   LF_TRY(lf_scratch(c, rows * n * 16, &scratch));
+  const int twside = fp_twside_mode<O>(c, logn1, rows, two_level);  // the inter-pass product: in pass B (default at n = 2^20), or in pass A
   {  // pass A: n1-point transforms over k1 (stride n2), C consecutive k2 per tile
     TilePlan p{};
     p.logT = logn1;
@@ -734,7 +867,10 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
     // rows fastest: the tile's table slice is reused by every row while it is hot
     const u32 row_fast = (!two_level && rows <= 65535 && row_fast_env) ? 1u : 0u;
     const dim3 grid = row_fast ? dim3((u32)rows, (u32)(n2 >> p.logC)) : dim3((u32)(n2 >> p.logC), (u32)rows);
-    if (two_level || !launch_tile_1024x4<O, false, true>(c, grid, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, row_fast))
+    if (twside) {
+      if (!launch_tile_1024x4_tws<O, false>(c, (u32)rows, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)nullptr, 0u))
+        return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "fp_fft: pass A does not fit the 1024 x 4 tile");
+    } else if (two_level || !launch_tile_1024x4<O, false, true>(c, grid, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, row_fast))
       launch_fp<O>(c, grid, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)dlo, (const elt_t*)dhi, row_fast);
     LF_HIP(c, hipGetLastError());
   }
@@ -758,7 +894,10 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
     p.kfast_dst = 0;
     size_t lds = fp_lds_bytes(p);
     const dim3 grid((u32)(n1 >> p.logC), (u32)rows);
-    if (!launch_tile_1024x4<O, true, false>(c, grid, lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)nullptr, 0u))
+    if (twside) {
+      if (!launch_tile_1024x4_tws<O, true>(c, (u32)rows, lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)dlo, twside == 2 ? 1u : 0u))
+        return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "fp_fft: pass B does not fit the 1024 x 4 tile");
+    } else if (!launch_tile_1024x4<O, true, false>(c, grid, lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)nullptr, 0u))
       launch_fp<O>(c, grid, lds, p, (const elt_t*)dW, logTw - logn2, (const elt_t*)nullptr, (const elt_t*)nullptr, 0u);
     LF_HIP(c, hipGetLastError());
   }
