@@ -58,6 +58,17 @@ CASES = [
     ("32", {"LFGPU_SC_MODE": "off", "LFGPU_EQ_FUSED": "1"}),
     ("1 fp128", {"LFGPU_SC_MODE": "off"}),
     ("32", {"LFGPU_SC_MODE": "off", "LFGPU_SC_BIND_SPLIT": "1"}),
+] + [
+    # Fp256Base on the synthetic circuits of test_zk_p256_synth.py -- layers beyond 2^16 wires and beyond the grid's 131072 hand
+    # pairs (wide), wire counts that are or turn odd (odd): no resident grid, no single-wave tail, the full 128-workgroup grid
+    # from the first round-hand it may take, a late hand-off with large workgroup shares, and no CU budget
+    ("synth:" + case, env)
+    for case in ("wide", "odd")
+    for env in ({"LFGPU_P256_GRID": "0"},
+                {"LFGPU_P256_WAVE_TAIL": "0"},
+                {"LFGPU_P256_GRID_MAX": "131072", "LFGPU_P256_PER_WG": "1024"},
+                {"LFGPU_P256_GRID_MAX": "300", "LFGPU_P256_PER_WG": "2048"},
+                {"LFGPU_CU_BUDGET": "0"})
 ]
 
 

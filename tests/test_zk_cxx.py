@@ -559,7 +559,8 @@ def test_zk_small_p256_circuit_matches_reference():
     2 n = (s - 2) m^2 - (s - 4) m; 2 layers, 4 inputs of which 2 public) compiled over the P-256 base field and proved by the
     reference's ZkProver<Fp256Base, .> with rate 4, 6 queries, block_enc chosen by LigeroParam's search (oracle/ref_small_p256.cc
     -> tests/golden/small_p256.json, `./oracle/_ref/gen_small_p256 > tests/golden/small_p256.json`): the library's wire bytes
-    must be identical, its verifier must accept them and reject tampered copies; a witness with m changed does not prove."""
+    must be identical, its verifier must accept them and reject tampered copies; a witness with m changed does not prove.
+    (Layers of 1 .. 9 variables and everything else between and beyond this toy and the signature circuit: test_zk_p256_synth.py.)"""
     import gpu_util as G
     import ligero_fixture as lf
     fx = json.load(open(os.path.join(GOLD, "small_p256.json")))

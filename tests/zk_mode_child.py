@@ -1,6 +1,6 @@
 """Child process of test_sumcheck_drivers.py: the tuning switches are read once per process, so every combination
 gets its own.  Proves the fixture circuit with the fixture's RandomEngine / transcript seed, requires the wire bytes
-of the reference and that the verifier accepts them.  Usage: zk_mode_child.py <nb> [fp128] | sig"""
+of the reference and that the verifier accepts them.  Usage: zk_mode_child.py <nb> [fp128] | sig | synth:<case>"""
 import hashlib, json, lzma, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -10,10 +10,16 @@ import ligero_fixture as lf
 
 gold = os.path.join(ROOT, "tests", "golden")
 sig = sys.argv[1] == "sig"  # the mdoc signature circuit over Fp256Base (32-byte elements, csrc/zk256.hip)
+synth = sys.argv[1].startswith("synth:")  # a synthetic Fp256Base circuit of test_zk_p256_synth.py, with its own rate / query count
+rate, nreq = 7, 132
 if sig:
     stem = "mdoc_sig"
     info = json.load(open(os.path.join(gold, "mdoc.json")))["sig"]
     be = info["block_enc"]
+elif synth:
+    stem = "synth_p256_" + sys.argv[1][6:]
+    info = {r["case"]: r for r in json.load(open(os.path.join(gold, "synth_p256.json")))["cases"]}[sys.argv[1][6:]]
+    rate, nreq, be = info["rate"], info["nreq"], info["block_enc_arg"]
 else:
     nb = int(sys.argv[1])
     fp = len(sys.argv) > 2 and sys.argv[2] == "fp128"
@@ -21,10 +27,10 @@ else:
     info = json.load(open(os.path.join(gold, stem + ".json")))
     be = 0
 raw = lzma.decompress(open(os.path.join(gold, stem + ".lfc1.xz"), "rb").read())
-W = np.frombuffer(lzma.decompress(open(os.path.join(gold, stem + ".w.xz"), "rb").read()), dtype=np.uint64).reshape(-1, 4 if sig else 2).copy()
+W = np.frombuffer(lzma.decompress(open(os.path.join(gold, stem + ".w.xz"), "rb").read()), dtype=np.uint64).reshape(-1, 4 if sig or synth else 2).copy()
 pkg, gpu = G.pkg, G.gpu()
 circ = pkg.Circuit(gpu, raw)
-zk = pkg.ZkProver(gpu, circ, 7, 132, be)
+zk = pkg.ZkProver(gpu, circ, rate, nreq, be)
 for rep in range(2):  # twice: the second run reuses cached buffers and the warmed-up drivers
     ts = pkg.FsTranscript(b"test")
     zk.commit(W, lf.LcgRng(100).bytes, ts)
@@ -33,7 +39,7 @@ for rep in range(2):  # twice: the second run reuses cached buffers and the warm
     ts.close()
     assert len(wire) == info["zk_wire_bytes"] and hashlib.sha256(wire).hexdigest() == info["zk_wire_sha256"], "wire differs from the reference"
 ts = pkg.FsTranscript(b"test")
-ok, why = pkg.zk_verify(gpu, circ, wire, W[:circ.info.npub_in], ts, 7, 132, be)
+ok, why = pkg.zk_verify(gpu, circ, wire, W[:circ.info.npub_in], ts, rate, nreq, be)
 ts.close()
 assert ok, why
 print("OK", stem)
