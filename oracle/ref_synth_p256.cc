@@ -2,7 +2,7 @@
 // P-256 circuits (the mdoc signature circuit, the 2-layer "sgonal" toy of ref_small_p256.cc) leave most of the shape
 // space of csrc/zk256.hip untouched; this program builds layered arithmetic circuits from a short seeded description
 // with the reference's own compiler (QuadCircuit + CompilerBackend + Logic, mkcircuit(1)), proves them with
-// ZkProver<Fp256Base, .> under the fixtures' transcript ("test") and LCG RandomEngine, checks the proof with the
+// ZkProver<Field, .> under the fixtures' transcript ("test") and LCG RandomEngine, checks the proof with the
 // reference's ZkVerifier and records what a test needs to pin the library on the same bytes.
 //
 //   gen_synth_p256 <case> <outdir>   ->  <outdir>/synth_p256_<case>.lfc1  CircuitWriter bytes
@@ -11,6 +11,9 @@
 //                                                                         proof and of every section of ZkProof::write
 //   gen_synth_p256 --list            ->  the case names
 // oracle/gen_synth_p256_fixtures.py compresses the two binary files and collects the records in tests/golden/synth_p256.json.
+//
+// ref_synth_fp128.cc compiles this same text over Fp128 (REF_SYNTH_FP128: 16-byte elements, the file stem synth_fp128_, the
+// FFT Reed-Solomon factory of ref_flatsha.cc under REF_FP128, a case table of its own) into gen_synth_fp128.
 //
 // A layer of B gates over the A wires below it: gate j is a sum of T products P[a] * P[b], the pairs taken in order from
 // pair(m) = (2m mod A, 2m + 1 + 2 floor(2m / A) mod A), m = jT .. jT + T - 1, T >= ceil(A / 2B) so that every wire below is
@@ -27,6 +30,7 @@
 
 #include "algebra/convolution.h"
 #include "algebra/fp2.h"
+#include "algebra/fp_p128.h"
 #include "algebra/reed_solomon.h"
 #include "arrays/dense.h"
 #include "circuits/compiler/compiler.h"
@@ -61,6 +65,43 @@ class LcgRng : public RandomEngine {
   uint64_t s_;
 };
 
+#ifdef REF_SYNTH_FP128
+using Field = Fp128<>;
+static const Field kField;
+static const FieldID kFieldId = FP128_ID;
+#define SYNTH_STEM "synth_fp128_"
+// the FFT Reed-Solomon factory as lib/zk/zk_test.cc sets it up for Fp128 (ref_flatsha.cc under REF_FP128)
+using FftConv = FFTConvolutionFactory<Field>;
+using RSFactory_b = ReedSolomonFactory<Field, FftConv>;
+struct RSSetup {
+  const FftConv fft;
+  const RSFactory_b rsf;
+  explicit RSSetup(const Field& F) : fft(F, F.of_string("164956748514267535023998284330560247862"), 1ull << 32), rsf(fft, F) {}
+};
+#else
+using Field = Fp256Base;
+static const Field& kField = p256_base;
+static const FieldID kFieldId = P256_ID;
+#define SYNTH_STEM "synth_p256_"
+using f2_p256 = Fp2<Fp256Base>;
+using FftExtConvolutionFactory = FFTExtConvolutionFactory<Fp256Base, f2_p256>;
+using RSFactory_b = ReedSolomonFactory<Fp256Base, FftExtConvolutionFactory>;
+struct RSSetup {
+  const f2_p256 p256_2;
+  const FftExtConvolutionFactory fft;
+  const RSFactory_b rsf;
+  // the root of unity of order 2^31 in the quadratic extension (lib/circuits/mdoc/mdoc_zk.cc:82-88)
+  explicit RSSetup(const Field& F)
+      : p256_2(F),
+        fft(F, p256_2,
+            p256_2.of_string("112649224146410281873500457609690258373018840430489408729223714171582664680802",
+                             "84087994358540907695740461427818660560182168997182378749313018254450460212908"),
+            1ull << 31),
+        rsf(fft, F) {}
+};
+#endif
+constexpr size_t kEltBytes = sizeof(Field::Elt);  // the in-memory image is the wire size in both fields
+
 struct LayerSpec {
   size_t gates;  // gates of this layer (the copy wires of wire 0 and of the outputs' values come on top)
   size_t tmin;   // least number of pair products per gate
@@ -80,6 +121,26 @@ struct CaseSpec {
 
 static const std::vector<CaseSpec>& cases() {
   static const std::vector<CaseSpec> c = {
+#ifdef REF_SYNTH_FP128
+      // wide: two layers beyond 2^18 wires and beyond 262144 hand pairs (two round-hands on the per-launch kernels before the
+      // resident grid's hand-off point of 131072), a wire read by every gate of such a layer, gates of more than 1024 terms;
+      // rate and query count other than the flatsha fixture's (7, 132), block_enc by the reference's search
+      {"wide", 21, 5, 40, 0, 0, false, 0, 2000, {{263000, 2, false, false}, {263000, 1, true, false}, {30, 4384, false, false}, {5, 3, false, false}}},
+      // odd: as over Fp256Base -- 2^12 + 1 inputs, then 3 * 2^10, 5000 and 2^10 + 1 wires; one hand pair in every gate of the 5000
+      {"odd", 22, 7, 132, 0, 0, false, 0, 4093, {{3068, 1, false, false}, {4996, 1, false, true}, {1021, 3, false, false}, {100, 6, false, false}, {3, 17, false, false}}},
+      // funnel: 9 down to 2 output variables and 0 (one output), layers that start within one wave (<= 64 wires), ending in
+      // layers of 6 wires and 4 hand pairs, 4 wires and 2
+      {"funnel", 23, 4, 6, 0, 0, false, 0, 300, {{398, 1, false, false}, {198, 1, false, false}, {98, 1, false, false}, {48, 1, false, false}, {22, 1, false, false},
+                                                  {10, 1, false, false}, {4, 1, false, false}, {2, 1, false, false}, {1, 1, false, false}}},
+      // tall: 40000 inputs in a tableau of 16384 columns (the two-pass FFT plan), public inputs (data and outputs);
+      // begin_full_field() several witness rows in, which only the header shows in this field
+      {"tall", 24, 4, 30, 16384, 5, true, 9000, 40000, {{2000, 10, false, false}, {100, 10, false, false}, {4, 13, false, false}}},
+      // long: a small circuit in a tableau of 2^18 columns, so that the commitment's RS encode runs the FFT at 2^18 points
+      // (at 2^20 the reference takes 17 s and the GPU test 9.5 s; 2^18 keeps both within a few seconds);
+      // two outputs (one output variable: the layer under a single output has wire 0, the output's input and a gate, so
+      // the funnel cannot hold it)
+      {"long", 25, 4, 20, 1 << 18, 0, false, 0, 3000, {{500, 3, false, false}, {40, 7, false, false}, {2, 10, false, false}}},
+#else
       // wide: layers beyond 2^16 wires and beyond 131072 hand pairs, a wire read by every gate of such a layer, gates of more
       // than 1024 terms; rate and query count of neither fixed fixture, block_enc by the reference's search
       {"wide", 11, 5, 40, 0, 0, false, 0, 1000, {{70000, 2, false, false}, {70000, 1, true, false}, {30, 1167, false, false}, {5, 3, false, false}}},
@@ -91,6 +152,7 @@ static const std::vector<CaseSpec>& cases() {
                                                   {10, 1, false, false}, {4, 1, false, false}, {2, 1, false, false}, {1, 1, false, false}}},
       // tall: 40000 inputs in a tableau of 16384 columns, public inputs, a subfield boundary several witness rows in
       {"tall", 14, 4, 30, 16384, 5, true, 9000, 40000, {{2000, 10, false, false}, {100, 10, false, false}, {4, 13, false, false}}},
+#endif
   };
   return c;
 }
@@ -135,11 +197,11 @@ int main(int argc, char** argv) {
     fprintf(stderr, "unknown case %s\n", argv[1]);
     return 2;
   }
-  using Backend = CompilerBackend<Fp256Base>;
-  using LogicCircuit = Logic<Fp256Base, Backend>;
+  using Backend = CompilerBackend<Field>;
+  using LogicCircuit = Logic<Field, Backend>;
   using EltW = LogicCircuit::EltW;
-  using Elt = Fp256Base::Elt;
-  const Fp256Base& F = p256_base;
+  using Elt = Field::Elt;
+  const Field& F = kField;
 
   // the value pool
   Elt pool[61];
@@ -150,10 +212,10 @@ int main(int argc, char** argv) {
   const size_t nout = cs->layers.back().gates;
   std::vector<Elt> wit;  // by input index
   std::vector<size_t> out_input(nout);
-  std::unique_ptr<Circuit<Fp256Base>> circuit;
+  std::unique_ptr<Circuit<Field>> circuit;
   size_t special[3] = {0, 0, 0};
   {
-    QuadCircuit<Fp256Base> Q(F);
+    QuadCircuit<Field> Q(F);
     Backend cbk(&Q);
     const LogicCircuit LC(&cbk, F);
     wit.push_back(F.one());  // wire 0
@@ -221,27 +283,20 @@ int main(int argc, char** argv) {
     }
     circuit = Q.mkcircuit(1);
   }
-  const Circuit<Fp256Base>& c = *circuit;
+  const Circuit<Field>& c = *circuit;
   if (wit.size() != c.ninputs) return 3;
 
   std::vector<uint8_t> cb;
-  CircuitWriter<Fp256Base> cw(F, P256_ID);
+  CircuitWriter<Field> cw(F, kFieldId);
   cw.to_bytes(c, cb);
-  auto W = Dense<Fp256Base>(1, c.ninputs);
+  auto W = Dense<Field>(1, c.ninputs);
   for (size_t i = 0; i < c.ninputs; ++i) W.v_[i] = wit[i];
 
-  using f2_p256 = Fp2<Fp256Base>;
-  using FftExtConvolutionFactory = FFTExtConvolutionFactory<Fp256Base, f2_p256>;
-  using RSFactory_b = ReedSolomonFactory<Fp256Base, FftExtConvolutionFactory>;
-  const f2_p256 p256_2(F);
-  // the root of unity of order 2^31 in the quadratic extension (lib/circuits/mdoc/mdoc_zk.cc:82-88)
-  const auto omega = p256_2.of_string("112649224146410281873500457609690258373018840430489408729223714171582664680802",
-                                      "84087994358540907695740461427818660560182168997182378749313018254450460212908");
-  const FftExtConvolutionFactory fft_b(F, p256_2, omega, 1ull << 31);
-  const RSFactory_b rsf(fft_b, F);
-  auto mkproof = [&]() { return cs->block_enc ? ZkProof<Fp256Base>(c, cs->rate, cs->nreq, cs->block_enc) : ZkProof<Fp256Base>(c, cs->rate, cs->nreq); };
-  ZkProof<Fp256Base> zk = mkproof();
-  ZkProver<Fp256Base, RSFactory_b> zp(c, F, rsf);
+  const RSSetup rs(F);
+  const RSFactory_b& rsf = rs.rsf;
+  auto mkproof = [&]() { return cs->block_enc ? ZkProof<Field>(c, cs->rate, cs->nreq, cs->block_enc) : ZkProof<Field>(c, cs->rate, cs->nreq); };
+  ZkProof<Field> zk = mkproof();
+  ZkProver<Field, RSFactory_b> zp(c, F, rsf);
   Transcript tp((const uint8_t*)"test", 4);
   LcgRng rng(100);
   zp.commit(zk, W, tp, rng);
@@ -252,37 +307,37 @@ int main(int argc, char** argv) {
   // the reference's verifier on the bytes as a verifier gets them
   bool vok = false;
   {
-    ZkProof<Fp256Base> zr = mkproof();
+    ZkProof<Field> zr = mkproof();
     ReadBuffer rb(wire);
     if (!zr.read(rb, F) || rb.remaining() != 0) return 6;
-    std::unique_ptr<ZkVerifier<Fp256Base, RSFactory_b>> zv;
+    std::unique_ptr<ZkVerifier<Field, RSFactory_b>> zv;
     if (cs->block_enc)
-      zv = std::make_unique<ZkVerifier<Fp256Base, RSFactory_b>>(c, rsf, cs->rate, cs->nreq, cs->block_enc, F);
+      zv = std::make_unique<ZkVerifier<Field, RSFactory_b>>(c, rsf, cs->rate, cs->nreq, cs->block_enc, F);
     else
-      zv = std::make_unique<ZkVerifier<Fp256Base, RSFactory_b>>(c, rsf, cs->rate, cs->nreq, F);
+      zv = std::make_unique<ZkVerifier<Field, RSFactory_b>>(c, rsf, cs->rate, cs->nreq, F);
     Transcript tv((const uint8_t*)"test", 4);
     zv->recv_commitment(zr, tv);
-    auto pub = Dense<Fp256Base>(1, c.npub_in);
+    auto pub = Dense<Field>(1, c.npub_in);
     for (size_t i = 0; i < c.npub_in; ++i) pub.v_[i] = W.v_[i];
     vok = zv->verify(zr, pub, tv);
   }
 
   // the record
-  const std::string stem = std::string(argv[2]) + "/synth_p256_" + cs->name;
-  if (!write_file(stem + ".lfc1", cb.data(), cb.size()) || !write_file(stem + ".w", W.v_.data(), 32 * c.ninputs)) return 7;
+  const std::string stem = std::string(argv[2]) + "/" SYNTH_STEM + cs->name;
+  if (!write_file(stem + ".lfc1", cb.data(), cb.size()) || !write_file(stem + ".w", W.v_.data(), kEltBytes * c.ninputs)) return 7;
   FILE* js = fopen((stem + ".json").c_str(), "w");
   if (!js) return 7;
   const auto& p = zk.param;
   fprintf(js, "{\"case\": \"%s\", \"nl\": %zu, \"ninputs\": %zu, \"npub_in\": %zu, \"nv\": %zu, \"logv\": %zu, \"subfield_boundary\": %zu, \"nterms\": %zu, \"nconst\": ", cs->name,
           c.nl, c.ninputs, c.npub_in, (size_t)c.nv, c.logv, c.subfield_boundary, c.nterms());
   {
-    KvecBuilder<Fp256Base> kb(F);
+    KvecBuilder<Field> kb(F);
     for (const auto& layer : c.l)
       for (const auto& ec : *layer.quad) kb.kstore(ec.v);
     fprintf(js, "%zu, ", kb.kvec()->size());
   }
   fprintf(js, "\"lfc1_bytes\": %zu, \"lfc1_sha256\": \"%s\", \"witness_sha256\": \"%s\", ", cb.size(), sha_hex(cb.data(), cb.size()).c_str(),
-          sha_hex((const uint8_t*)W.v_.data(), 32 * c.ninputs).c_str());
+          sha_hex((const uint8_t*)W.v_.data(), kEltBytes * c.ninputs).c_str());
   fprintf(js, "\"input_zero\": %zu, \"input_one\": %zu, \"input_mone\": %zu, \"first_output_input\": %zu, \"noutput_inputs\": %zu, ", special[0], special[1], special[2],
           out_input[0], nout);
   fprintf(js, "\"layers\": [");
@@ -313,11 +368,11 @@ int main(int argc, char** argv) {
   const size_t npath = zk.com_proof.merkle.path.size();
   std::vector<std::pair<std::string, size_t>> sec;
   sec.push_back({"root", 32});
-  for (size_t i = 0; i < c.nl; ++i) sec.push_back({"sumcheck_layer_" + std::to_string(i), (4 * c.l[i].logw + 2) * 32});
-  sec.push_back({"y_ldt", p.block * 32});
-  sec.push_back({"y_dot", p.dblock * 32});
-  sec.push_back({"y_quad_0", p.r * 32});
-  sec.push_back({"y_quad_2", (p.dblock - p.block) * 32});
+  for (size_t i = 0; i < c.nl; ++i) sec.push_back({"sumcheck_layer_" + std::to_string(i), (4 * c.l[i].logw + 2) * kEltBytes});
+  sec.push_back({"y_ldt", p.block * kEltBytes});
+  sec.push_back({"y_dot", p.dblock * kEltBytes});
+  sec.push_back({"y_quad_0", p.r * kEltBytes});
+  sec.push_back({"y_quad_2", (p.dblock - p.block) * kEltBytes});
   sec.push_back({"nonces", p.nreq * 32});
   size_t fixed = 4 + 32 * npath;
   for (const auto& s : sec) fixed += s.second;

@@ -13,6 +13,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 GF, FP = 4, 6  # FieldID (lib/proto/circuit_io.h:24-36)
+# csrc/quad.hip, lfgpu_sumcheck_layer: the default of LFGPU_SC_GRID_MAX, the largest array at which the resident grid takes over;
+# above it a round-hand runs on the whole-GPU per-launch kernels
+SC_GRID_MAX = 128 * 1024
 
 
 class Elt(C.Structure):

@@ -69,6 +69,22 @@ CASES = [
                 {"LFGPU_P256_GRID_MAX": "131072", "LFGPU_P256_PER_WG": "1024"},
                 {"LFGPU_P256_GRID_MAX": "300", "LFGPU_P256_PER_WG": "2048"},
                 {"LFGPU_CU_BUDGET": "0"})
+] + [
+    # Fp128 on the synthetic circuits of test_zk_fp128_synth.py -- layers of 263006 wires and 526006 hand pairs (wide), wire
+    # counts that are or turn odd (odd), layers of 1 .. 512 outputs that start within one wave (funnel): per-launch kernels
+    # all the way, the single resident workgroup, one fused launch per round-hand, no single-wave tail, an early hand-off
+    # point with large workgroup shares, the fused EQ kernel, and no CU budget.  funnel has no array above 400 entries, so
+    # the hand-off point and the workgroup share cannot change its path: left out there.
+    ("synthfp:" + case, env)
+    for case in ("wide", "odd", "funnel")
+    for env in ({"LFGPU_SC_MODE": "off"},
+                {"LFGPU_SC_MODE": "resident"},
+                {"LFGPU_SC_MODE": "launch"},
+                {"LFGPU_SC_WAVE_TAIL": "0"},
+                {"LFGPU_SC_GRID_MAX": "4096", "LFGPU_SC_PER_WG": "2048"},
+                {"LFGPU_EQ_FUSED": "1"},
+                {"LFGPU_CU_BUDGET": "0"})
+    if not (case == "funnel" and "LFGPU_SC_GRID_MAX" in env)
 ]
 
 

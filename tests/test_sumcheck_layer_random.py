@@ -3,6 +3,11 @@ step-by-step replay on the oracle, for BOTH fields and for sizes that exercise e
   small  (a few hundred entries)   single workgroup from the first round
   mid    (thousands)               several workgroups of the cooperative grid, shrinking to one
   large  (> 64K entries)           multi-kernel path for the first rounds, then the grid
+and for sizes that are no powers of two (every halving is (n + 1) // 2: an odd count passes its last entry through):
+  odd_large  4097 outputs, 2^16 + 1 wires, > 131072 hand pairs   starts on the per-launch path, odd at every halving
+  three      3 * 2^8 outputs, 3 * 2^10 wires                      odd after the power of two is halved away
+  tiny       3 outputs, 5 wires, <= 8 terms                       single wave from the first round-hand
+  one        1 output (no output variable), 2 wires, 1 term
 The reference semantics are ProverLayers::layer with logc = 0 (lib/sumcheck/prover_layers.h:185-271)."""
 import ctypes as C
 
@@ -11,6 +16,7 @@ import pytest
 
 import oracle_lib as ol
 from oracle_lib import FP, GF, P, arr, elt
+from oracle_lib import SC_GRID_MAX as GRID_MAX
 
 
 def _morton(a, b):
@@ -23,9 +29,11 @@ def _morton(a, b):
     return m
 
 
-def make_layer_vec(rng, field, logv, logw, nterms, nk=9):
-    """canonical-order synthetic layer (EQuad::canonicalize, lib/sumcheck/equad.h:79-106), vectorised"""
-    nv, nw = 1 << logv, 1 << logw
+def make_layer_vec(rng, field, logv, logw, nterms, nk=9, nv=None, nw=None):
+    """canonical-order synthetic layer (EQuad::canonicalize, lib/sumcheck/equad.h:79-106), vectorised; nv <= 2^logv outputs
+    and nw <= 2^logw wires (the full powers of two unless given), indices drawn below them"""
+    nv, nw = nv or 1 << logv, nw or 1 << logw
+    assert 0 < nv <= 1 << logv and 0 < nw <= 1 << logw
     g = rng.integers(0, nv, size=2 * nterms, dtype=np.uint32)
     a = rng.integers(0, nw, size=2 * nterms, dtype=np.uint32)
     b = rng.integers(0, nw, size=2 * nterms, dtype=np.uint32)
@@ -63,7 +71,7 @@ class HostField:
 
 
 def oracle_layer(field, L, logv, G0, G1, alpha, beta, wc_in, chal):
-    """-> (evals per round-hand [(e0,e1,e2)], wc_out, bound_quad)"""
+    """-> (evals per round-hand [(e0,e1,e2)], wc_out, bound_quad, hand pairs left by bind_g)"""
     o, F = ol.oracle(), HostField(field)
     ctx = ol.gf_ctx(4)
     n = L["n"]
@@ -71,6 +79,7 @@ def oracle_layer(field, L, logv, G0, G1, alpha, beta, wc_in, chal):
     vc = np.zeros((n, 2), dtype=np.uint64)
     nh = o.lfo_quad_bind_g(field, n, P(L["g"]), P(L["h0"]), P(L["h1"]), P(L["vi"]), P(L["kvec"]), logv, P(G0), P(G1),
                            elt(alpha), elt(beta), P(hc), P(vc))
+    nh0 = nh
     WH = [L["W"].copy(), L["W"].copy()]
     nW = [L["nw"], L["nw"]]
     s = F.add(wc_in[0], F.mul(alpha, wc_in[1]))
@@ -95,20 +104,24 @@ def oracle_layer(field, L, logv, G0, G1, alpha, beta, wc_in, chal):
             WH[hand], nW[hand] = out, (nW[hand] + 1) // 2
             nh = o.lfo_hquad_bind_h(field, nh, P(hc), P(vc), elt(r), hand)
     wc = [tuple(int(x) for x in WH[0][0]), tuple(int(x) for x in WH[1][0])]
-    return evs, wc, tuple(int(x) for x in vc[0])
+    return evs, wc, tuple(int(x) for x in vc[0]), nh0
 
 
 CASES = [("small", 5, 6, 300), ("mid", 9, 12, 7000), ("large", 12, 17, 150000)]
+# (name, logv, logw, terms, nv, nw) with nv and nw no powers of two
+ODD_CASES = [("odd_large", 13, 17, 170000, 4097, (1 << 16) + 1), ("three", 10, 12, 7000, 3 << 8, 3 << 10), ("tiny", 2, 3, 8, 3, 5), ("one", 0, 1, 1, 1, 2)]
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("field", [GF, FP])
-@pytest.mark.parametrize("case", CASES, ids=[c[0] for c in CASES])
+@pytest.mark.parametrize("case", CASES + ODD_CASES, ids=[c[0] for c in CASES + ODD_CASES])
 def test_sumcheck_layer_matches_oracle_replay(field, case):
     import gpu_util as G
-    _, logv, logw, nterms = case
+    name, logv, logw, nterms, *shape = case
     rng = np.random.default_rng(1000 * field + logw)
-    L = make_layer_vec(rng, field, logv, logw, nterms)
+    L = make_layer_vec(rng, field, logv, logw, nterms, *([9] + shape if shape else []))
+    if shape:
+        assert (L["nv"], L["nw"]) == tuple(shape) and 0 < L["n"] <= nterms and L["g"].max() < L["nv"] and L["h1"].max() < L["nw"]
     G0, G1 = ol.rand_elts(rng, max(1, logv), field), ol.rand_elts(rng, max(1, logv), field)
     alpha, beta = (tuple(int(x) for x in ol.rand_elts(rng, 1, field)[0]) for _ in range(2))
     wc_in = [tuple(int(x) for x in ol.rand_elts(rng, 1, field)[0]) for _ in range(2)]
@@ -125,7 +138,10 @@ def test_sumcheck_layer_matches_oracle_replay(field, case):
     wc, ch, bq = q.sumcheck_layer(logv, G0, G1, alpha, beta, logw, L["nw"], dW.data_ptr(), wc_in, round_cb)
     q.close()
     assert order == [(r, h) for r in range(logw) for h in (0, 1)]
-    want_ev, want_wc, want_bq = oracle_layer(field, L, logv, G0, G1, alpha, beta, wc_in, chal)
+    want_ev, want_wc, want_bq, nh0 = oracle_layer(field, L, logv, G0, G1, alpha, beta, wc_in, chal)
+    if name == "odd_large":  # it is there for the per-launch path
+        assert nh0 > GRID_MAX
+    assert len(got_ev) == len(want_ev) == 2 * logw
     for i, (a, b) in enumerate(zip(got_ev, want_ev)):
         assert a == b, "round-hand %d" % i
     assert [tuple(int(x) for x in w) for w in wc] == want_wc
@@ -150,21 +166,24 @@ def test_oracle_bind_gh_all_equals_bind_g_then_bind_h(field):
     G0, G1 = ol.rand_elts(rng, logv, field), ol.rand_elts(rng, logv, field)
     alpha, beta = (tuple(int(x) for x in ol.rand_elts(rng, 1, field)[0]) for _ in range(2))
     chal = [tuple(int(x) for x in e) for e in ol.rand_elts(rng, 2 * logw, field)]
-    _, _, bq = oracle_layer(field, L, logv, G0, G1, alpha, beta, [(0, 0), (0, 0)], chal)
+    _, _, bq, _ = oracle_layer(field, L, logv, G0, G1, alpha, beta, [(0, 0), (0, 0)], chal)
     H0 = np.array([chal[2 * r] for r in range(logw)], dtype=np.uint64)
     H1 = np.array([chal[2 * r + 1] for r in range(logw)], dtype=np.uint64)
     assert _bind_gh_all_oracle(field, L, logv, G0, G1, alpha, beta, H0, H1) == bq
 
 
+BIND_CASES = CASES[:2] + [("big", 12, 16, 400000)] + ODD_CASES
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("field", [GF, FP])
-@pytest.mark.parametrize("case", CASES[:2] + [("big", 12, 16, 400000)], ids=["small", "mid", "big"])
+@pytest.mark.parametrize("case", BIND_CASES, ids=[c[0] for c in BIND_CASES])
 def test_quad_bind_gh_all_matches_oracle(field, case):
     import gpu_util as G
-    _, logv, logw, nterms = case
+    _, logv, logw, nterms, *shape = case
     rng = np.random.default_rng(7000 + field + logw)
-    L = make_layer_vec(rng, field, logv, logw, nterms)
-    G0, G1 = ol.rand_elts(rng, logv, field), ol.rand_elts(rng, logv, field)
+    L = make_layer_vec(rng, field, logv, logw, nterms, *([9] + shape if shape else []))
+    G0, G1 = ol.rand_elts(rng, max(1, logv), field), ol.rand_elts(rng, max(1, logv), field)
     H0, H1 = ol.rand_elts(rng, logw, field), ol.rand_elts(rng, logw, field)
     alpha, beta = (tuple(int(x) for x in ol.rand_elts(rng, 1, field)[0]) for _ in range(2))
     q = G.pkg.Quad(G.gpu(), field, L["g"], L["h0"], L["h1"], L["vi"], L["kvec"], L["nv"])
