@@ -206,13 +206,19 @@ __global__ __launch_bounds__(FFT_THREADS) void fp_fft_tile(TilePlan p, const elt
 __device__ __forceinline__ u32 t4_wslot(u32 i) { return i ^ ((i >> 4) & 15u); }
 
 // The arithmetic of the 1024 x 4 tiles: O's own, except for Fp128, whose add, sub and twiddle product come from
-// fp_tile_arith.h (same values, fewer VALU instructions).
+// fp_tile_arith.h (same values, fewer VALU instructions).  add_lazy / canon: the lazy u side of a butterfly (fp_tile_arith.h),
+// for Fp128 only; any other field adds as usual and has nothing to make canonical.
 template <class O>
-struct T4Ops : O {};
+struct T4Ops : O {
+  static __device__ __forceinline__ elt_t add_lazy(elt_t a, elt_t b) { return O::add(a, b); }
+  static __device__ __forceinline__ elt_t canon(elt_t a) { return a; }
+};
 #if defined(__HIP_DEVICE_COMPILE__)
 template <>
 struct T4Ops<Fp128Ops> : Fp128Ops {
   static __device__ __forceinline__ elt_t add(elt_t a, elt_t b) { return fpt_add(a, b); }
+  static __device__ __forceinline__ elt_t add_lazy(elt_t a, elt_t b) { return fpt_add_lazy(a, b); }
+  static __device__ __forceinline__ elt_t canon(elt_t a) { return fpt_canon(a); }
   static __device__ __forceinline__ elt_t sub(elt_t a, elt_t b) { return fpt_sub(a, b); }
   static __device__ __forceinline__ elt_t mul_tw(elt_t a, elt_t w) { return fpt_mul(a, w); }
 };
@@ -220,7 +226,13 @@ struct T4Ops<Fp128Ops> : Fp128Ops {
 
 // R radix-2 stages (from stage ST) on the register group x[a] = position i0 + a 2^ST, j = i0 mod 2^ST; as fp_radix_round.
 // ROUND0 (ST = 0, j = 0): twiddles read from HBM at uniform addresses, the w^0 products left out.
-template <class O, u32 ST, u32 R, bool ROUND0>
+// LZ, which sums are canonical.  T4_CANON: all of them (inputs canonical).  T4_LAZY: x[] may come in and go out lazy; u + w v is
+// add_lazy, whose v must be canonical: it is wherever v has just been multiplied, which leaves the w^0 butterflies of ROUND0.
+// Their v are x[2], x[6] at stage 1 and x[4] at stage 2, so the sums that make them stay full adds on canonical inputs: (2,3),
+// (6,7), (4,5) at stage 0 (a round 0's inputs are canonical) and (4,6) at stage 1.  T4_LAZY_OUT: as T4_LAZY, and the outputs are
+// canonical: the last stage makes its u canonical and adds in full.
+enum : u32 { T4_CANON = 0, T4_LAZY = 1, T4_LAZY_OUT = 2 };
+template <class O, u32 ST, u32 R, bool ROUND0, u32 LZ = T4_CANON>
 __device__ __forceinline__ void t4_stages(elt_t* x, u32 j, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
 #pragma unroll
   for (u32 t = 0; t < R; ++t) {
@@ -231,8 +243,10 @@ __device__ __forceinline__ void t4_stages(elt_t* x, u32 j, const elt_t* wl, cons
       const u32 jj = j + (a & (half - 1)) * (1u << ST), sh = 9 - ST - t;
       if (!ROUND0) x[a + half] = T4Ops<O>::mul_tw(x[a + half], ld16(&wl[t4_wslot(jj << sh)]));
       else if (a & (half - 1)) x[a + half] = T4Ops<O>::mul_tw(x[a + half], ld16(&W[(size_t)(jj << sh) << wshift]));
-      const elt_t u = x[a], v = x[a + half];
-      x[a] = T4Ops<O>::add(u, v);
+      const bool last = LZ == T4_LAZY_OUT && t == R - 1;
+      const bool full = LZ == T4_CANON || last || (ROUND0 && ((t == 0 && a != 0) || (t == 1 && a == 4)));
+      const elt_t u = last ? T4Ops<O>::canon(x[a]) : x[a], v = x[a + half];
+      x[a] = full ? T4Ops<O>::add(u, v) : T4Ops<O>::add_lazy(u, v);
       x[a + half] = T4Ops<O>::sub(u, v);
     }
   }
@@ -450,9 +464,19 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p,
 //           loads w_n^(j1 k2) at the offset of its point (j1 = 4 bx + c, k2 = kb + 128 a'), coalesced, all 17 loads in flight
 //           before the first wait, and multiplies before round 0.  Row j1 = 0 and column k2 = 0 hold Montgomery 1: no branch.
 //           Grid (tile, row), or (row, tile) with row_fast.
-template <class O, bool KFAST_SRC>
-__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
-                                                                 const elt_t* __restrict__ tw, u32 row_fast) {
+// LAZY (the default, fp_fft_tile_1024x4_tws; LFGPU_FP_LAZY=0 launches fp_fft_tile_1024x4_tws_canon, the same body with LAZY = false):
+// the butterflies keep their u side lazy (t4_stages, fp_tile_arith.h), which takes 3 of the 21 instructions off 36 of a thread's 40
+// butterflies in pass A and off 32 in pass B.  What the tile keeps in LDS may then be any 128-bit representative, and so may what
+// pass A stores; pass B's last stage makes its outputs canonical, so the transform's result is the same bytes.  Pass A's destination
+// in this plan is fp_fft_two_pass's scratch buffer and nothing else, and the only reader of that buffer is the pass B launched right
+// behind it, tiles or rows fastest (LFGPU_FP_TWSIDE=2), which multiplies every point by its inter-pass twiddle before anything
+// else: a product takes a lazy operand and gives a canonical one.  The inner 2^20-point transforms of n = 2^21 .. 2^23 are the same
+// two launches through the same scratch buffer; their pass A reads what fp_fft_tile stored (canonical) and their pass B stores
+// canonical values with a stride.  Every other kernel of this file keeps canonical arithmetic.
+template <class O, bool KFAST_SRC, bool LAZY>
+__device__ __forceinline__ void fp_fft_tile_1024x4_tws_body(const TilePlan& p, const elt_t* __restrict__ W, u32 wshift,
+                                                            const elt_t* __restrict__ tw, u32 row_fast) {
+  constexpr u32 LZ = LAZY ? T4_LAZY : T4_CANON, LZ_OUT = !LAZY ? T4_CANON : KFAST_SRC ? T4_LAZY_OUT : T4_LAZY;
   extern __shared__ elt_t s[];
   elt_t* const wl = s + 4096;
   const u32 tid = threadIdx.x;
@@ -493,7 +517,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, con
     elt_t x[8];
 #pragma unroll
     for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];  // x[a] = y[bitrev3(a)]
-    t4_stages<O, 0, 3, true>(x, 0, wl, W, wshift);
+    t4_stages<O, 0, 3, true, LZ>(x, 0, wl, W, wshift);
     const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
 #pragma unroll
     for (u32 a = 0; a < 8; a += 2) {
@@ -509,7 +533,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, con
     elt_t x[8];
 #pragma unroll
     for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
-    t4_stages<O, 3, 3, false>(x, j, wl, W, wshift);
+    t4_stages<O, 3, 3, false, LZ>(x, j, wl, W, wshift);
 #pragma unroll
     for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
   }
@@ -521,7 +545,7 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, con
     elt_t x[4];
 #pragma unroll
     for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (a >> 1)) + 256 * a]);
-    t4_stages<O, 6, 2, false>(x, j, wl, W, wshift);
+    t4_stages<O, 6, 2, false, LZ>(x, j, wl, W, wshift);
 #pragma unroll
     for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ (a >> 1)) + 256 * a], x[a]);
   }
@@ -536,11 +560,22 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, con
       elt_t x[4];
 #pragma unroll
       for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
-      t4_stages<O, 8, 2, false>(x, j, wl, W, wshift);
+      t4_stages<O, 8, 2, false, LZ_OUT>(x, j, wl, W, wshift);
 #pragma unroll
       for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), x[a]);
     }
   }
+}
+
+template <class O, bool KFAST_SRC>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                                 const elt_t* __restrict__ tw, u32 row_fast) {
+  fp_fft_tile_1024x4_tws_body<O, KFAST_SRC, true>(p, W, wshift, tw, row_fast);
+}
+template <class O, bool KFAST_SRC>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws_canon(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                                       const elt_t* __restrict__ tw, u32 row_fast) {
+  fp_fft_tile_1024x4_tws_body<O, KFAST_SRC, false>(p, W, wshift, tw, row_fast);
 }
 
 // ------------------------------------------------------------------ K2: LCH14
@@ -626,6 +661,8 @@ static int set_lds_limit(lfgpu_ctx* c) {
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_persist<Fp128Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws<Fp128Ops, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws<Fp128Ops, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
     LF_HIP(c, hipFuncSetAttribute((const void*)lch_fft_tile<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELTS * 16));
@@ -698,6 +735,8 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
 // The pair fp_fft_tile_1024x4_tws (inter-pass product on pass B's load side): the default for Fp128 when both passes are 1024 x 4
 // tiles (n = 2^20) and the full table is in use.  LFGPU_FP_TWSIDE=0, or any setting of LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 (which
 // choose among the kernels of the other plan), keeps the product in pass A; =2 runs pass B with the rows fastest in the grid.
+// LFGPU_FP_LAZY=0 (read once) launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; it has
+// no effect where this plan is not taken.
 template <class O>
 static int fp_twside_mode(const lfgpu_ctx* c, u32 logn1, size_t rows, bool two_level) {
   static const int mode = (getenv("LFGPU_FP_PERSIST") || getenv("LFGPU_FP_TILE1024")) ? 0
@@ -719,7 +758,9 @@ static bool launch_tile_1024x4_tws(lfgpu_ctx* c, u32 rows, size_t lds, const Til
     if (KFAST_SRC && (p.sk != 1 || p.sc != 1024 || p.src_tile != 4096)) return false;  // the table's layout [j1][k2]
     if (KFAST_SRC && (row_fast ? ncb : rows) > 65535) row_fast = !row_fast;
     const dim3 grid = !KFAST_SRC ? dim3(ncb * rows) : row_fast ? dim3(rows, ncb) : dim3(ncb, rows);
-    hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    static const bool lazy = !(getenv("LFGPU_FP_LAZY") && atoi(getenv("LFGPU_FP_LAZY")) == 0);
+    if (lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    else hipLaunchKernelGGL((fp_fft_tile_1024x4_tws_canon<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     return true;
   }
   return false;

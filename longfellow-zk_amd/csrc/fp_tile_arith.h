@@ -8,7 +8,13 @@
 //   - fpt_add: the carry-out of a + b stays a lane mask and is merged with the borrow of (a + b) - p by one SALU
 //     instruction: 14 -> 12 VALU instructions.
 //   - fpt_sub: the borrow of a - b, kept in an SGPR pair, is the carry-in of the + p chain: 10 -> 9.
-// Every value stays canonical, so what the tiles keep in LDS and write to HBM is unchanged.
+// With these three every value stays canonical, so what the tiles keep in LDS and write to HBM is unchanged.
+//
+// The pair fp_fft_tile_1024x4_tws also lets a butterfly's u side be *lazy*: any 128-bit value congruent to the element, not
+// necessarily < p.  In x = u + w v, y = u - w v the product w v is canonical whatever v was (see fpt_mul), so
+//   - fpt_add_lazy(u, t), u lazy, t < p: u + t < 2^128 + p, one fold under the carry mask, 9 instructions instead of 12;
+//   - fpt_sub(u, t) as it is: u - t in (-p, 2^128), + p on borrow;
+//   - fpt_canon(u): lazy -> canonical, 8 instructions, where a value leaves the scheme (what pass B stores).
 //
 // Wait states: gfx950 needs 2 between a VALU that writes an SGPR or VCC and a VALU that reads it (carry-in, mask), and
 // hipcc inserts none inside an asm statement, so every such link carries an `s_nop 1`, as in fields.h.  The same is kept
@@ -51,6 +57,61 @@ __device__ __forceinline__ elt_t fpt_add(elt_t a, elt_t b) {
   return FP_PACK(d0, d1, d2, d3);
 }
 
+// a + b for a lazy (any 128-bit value), b < p; the result is lazy.  s = a + b < 2^128 + p: if the 128-bit add carries, s - p lies
+// in [2^108 - 1, 2^128) and is s_low - p mod 2^128 (s_low < p then, so that subtraction borrows: the two 2^128 cancel); otherwise
+// s_low is the result.  - p under the carry mask c: - c at limb 0 (the mask is the borrow-in), - 0xfffff000 at limb 3, the mirror
+// image of fpt_sub's + p.  No SALU instruction, so SCC is left alone.
+__device__ __forceinline__ elt_t fpt_add_lazy(elt_t a, elt_t b) {
+  FP_W(a, a0, a1, a2, a3);
+  FP_W(b, b0, b1, b2, b3);
+  u32 d0, d1, d2, d3, e3;
+  u64 c;
+  asm("v_add_co_u32 %0, vcc, %6, %10\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %1, vcc, %7, %11, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %2, vcc, %8, %12, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_addc_co_u32 %3, %5, %9, %13, vcc\n\t"  // carry-out of a + b: lane mask c
+      "s_nop 1\n\t"
+      "v_cndmask_b32 %4, 0, %14, %5\n\t"
+      "v_subbrev_co_u32 %0, vcc, 0, %0, %5\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32 %1, vcc, 0, %1, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32 %2, vcc, 0, %2, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subb_co_u32 %3, vcc, %3, %4, vcc"
+      : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(e3), "=&s"(c)
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(b0), "v"(b1), "v"(b2), "v"(b3), "v"(0xfffff000u)
+      : "vcc");
+  return FP_PACK(d0, d1, d2, d3);
+}
+
+// a lazy -> the canonical value: a - p if that does not borrow (a >= p; a < 2^128 < 2p, so once is enough), else a
+__device__ __forceinline__ elt_t fpt_canon(elt_t a) {
+  FP_W(a, a0, a1, a2, a3);
+  u32 d0, d1, d2, d3;
+  asm("v_subrev_co_u32 %0, vcc, 1, %4\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32 %1, vcc, 0, %5, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subbrev_co_u32 %2, vcc, 0, %6, vcc\n\t"
+      "s_nop 1\n\t"
+      "v_subb_co_u32 %3, vcc, %7, %8, vcc\n\t"  // borrow <=> a < p: keep a
+      "s_nop 1\n\t"
+      "v_cndmask_b32 %0, %0, %4, vcc\n\t"
+      "v_cndmask_b32 %1, %1, %5, vcc\n\t"
+      "v_cndmask_b32 %2, %2, %6, vcc\n\t"
+      "v_cndmask_b32 %3, %3, %7, vcc"
+      : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3)
+      : "v"(a0), "v"(a1), "v"(a2), "v"(a3), "v"(0xfffff000u)
+      : "vcc");
+  return FP_PACK(d0, d1, d2, d3);
+}
+
+// a - b for a < p or a lazy, b < p.  With a < p the result is canonical; with a lazy, d = a - b lies in (-p, 2^128): a borrow
+// means d < 0 and d + p in (0, p), no borrow leaves d in [0, 2^128), so the result is lazy: this is the lazy subtraction as well.
 __device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
   FP_W(a, a0, a1, a2, a3);
   FP_W(b, b0, b1, b2, b3);
@@ -86,7 +147,8 @@ __device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
   tk = (u32)(acc);           \
   acc = ((acc) >> 32) | ((u64)(ov) << 32)
 
-// a * w / 2^128 mod p for a, w < p (Montgomery), as fp_mul.  Product scanning with 16 v_mad_u64_u32; the carries of column k
+// a * w / 2^128 mod p (Montgomery), as fp_mul for a, w < p.  a may be any 128-bit value (lazy) as long as w < p: T = a w < 2^128 p,
+// so T_hi < p, (T + m p) / 2^128 < 2p and W in [-p, p) as below, and the result is canonical.  Product scanning with 16 v_mad_u64_u32; the carries of column k
 // go to ov, which becomes the high half of column k + 1's accumulator {acc.hi, ov}.
 __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   FP_W(a, a0, a1, a2, a3);
@@ -172,5 +234,11 @@ __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
 // the host pass of a kernel that calls them, and host code: the portable forms (same values)
 LF_HD elt_t fpt_add(elt_t a, elt_t b) { return fp_add_c(a, b); }
 LF_HD elt_t fpt_sub(elt_t a, elt_t b) { return fp_sub_c(a, b); }
-LF_HD elt_t fpt_mul(elt_t a, elt_t b) { return fp_mul_c(a, b); }
+LF_HD elt_t fpt_canon(elt_t a) { return fp_canon128(a); }
+LF_HD elt_t fpt_add_lazy(elt_t a, elt_t b) {  // the fold of the carry: 2^128 = p + (2^128 - p)
+  const u64 lo = a.lo + b.lo, c0 = lo < a.lo, h0 = a.hi + b.hi, hi = h0 + c0;
+  if (!((h0 < a.hi) | (hi < c0))) return elt_t{lo, hi};
+  return elt_t{lo - FP_P_LO, hi - FP_P_HI - (lo < FP_P_LO)};
+}
+LF_HD elt_t fpt_mul(elt_t a, elt_t b) { return fp_mul_c(fp_canon128(a), b); }
 #endif
