@@ -223,6 +223,46 @@ int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0, const voi
                          lfgpu_sc_round_fn round, void* user, uint64_t wc_out[2][2], uint64_t* g_out /*[2][logw][2]*/,
                          uint64_t bound_quad[2]);
 
+/* ---- circuits with nc > 1 copies: the copy rounds of the sumcheck (K13) ------------------------------
+ * The reference's data-parallel axis: every wire array is Dense(n0 = nc, n1 = nw), stored W[wire * nc + c] (copy index
+ * fastest, lib/arrays/dense.h:44-45), and every layer opens with logc cubic rounds that bind the copy variable
+ * (lib/sumcheck/prover_layers.h:196-216) before the hand rounds above.  Fields: GF2_128 and Fp128; LFGPU_ERR_UNSUPPORTED for
+ * P256.  The prover-level ABI of lfgpu_zk.h stays at nc = 1, as the reference's ZkProver does (lib/zk/zk_common.h:72). */
+/* ProverLayers::eval_quad over all copies (lib/sumcheck/prover_layers.h:278-305): V[g * nc + c] = sum kvec[vi] *
+ * W[h1 * nc + c] * W[h0 * nc + c]; the assert-zero terms are checked in every copy, *ok = 0 if any copy fails.
+ * d_W: nw * nc elements, d_V: nv * nc elements. */
+int lfgpu_eval_quad_copies(lfgpu_quad* q, size_t nc, size_t nw, const void* d_W, void* d_V, int* ok);
+/* The loop of ProverLayers::evaluations_c (lib/sumcheck/prover_layers.h:418-477, odd tail :460-472) and the three
+ * F.reduce of :480-482: acc_out[0], [1], [2] = the coefficients coefs[0], coefs[2], coefs[3] of the round's cubic.
+ * d_hc / d_vc: the nh HQUAD terms (as lfgpu_quad_bind_g leaves them); d_W: [nrows][n0];
+ * d_eq: the current EQ vector, n0 elements.  Outputs to host.  nrows states the shape of d_W and is checked only for 0:
+ * the hand indices live on the device and are NOT validated, so the caller guarantees that every one is < nrows (an
+ * index past it reads outside d_W). */
+int lfgpu_sumcheck_evaluations_c(lfgpu_ctx* ctx, int field, size_t nh, const void* d_hc, const void* d_vc, size_t n0,
+                                 size_t nrows, const void* d_W, const void* d_eq, uint64_t acc_out[3][2]);
+/* Dense::bind with n1 = nrows (lib/arrays/dense.h:70-87): out[i1][i] = in[i1][2i] + r (in[i1][2i+1] - in[i1][2i]), the
+ * rows re-packed to stride (n0 + 1) / 2 (:74-85).  Out of place only (the compaction makes a parallel bind in place a
+ * race): LFGPU_ERR_ARG if the two buffers overlap. */
+int lfgpu_dense_bind_rows(lfgpu_ctx* ctx, int field, size_t n0, size_t nrows, const uint64_t r[2], const void* d_in,
+                          void* d_out);
+/* Eqs::filleq, i.e. the Eqs(logn, n, Q) constructor (lib/arrays/eqs.h:36-39,104-134): eq[i] = EQ(Q, i), i < n <= 2^logn.
+ * h_Q: logn host elements; d_eq: n device elements.  Eqs::bind is Dense::bind: lfgpu_dense_bind. */
+int lfgpu_eqs(lfgpu_ctx* ctx, int field, size_t logn, size_t n, const void* h_Q, void* d_eq);
+/* The whole of ProverLayers::layer (lib/sumcheck/prover_layers.h:185-271) with the Eqs constructor and the bind_g in
+ * front of it (:155-157): lfgpu_sumcheck_layer plus the copy rounds.  For round < logc: evaluations_c -> the 4 evaluations
+ * of the round's cubic at poly_evaluation_point(0..3) -> `round_c` callback (the caller's round_c, :307-318: subtract pad,
+ * store in the proof, ts.round(poly) -> challenge) -> bind EQ and W.  Then eq0 = EQ->scalar() and the hand rounds of
+ * lfgpu_sumcheck_layer run on the [nw] vector that is left, their coefficients scaled by eq0.  d_W: [nw][nc] (device;
+ * consumed); h_Q: logc host elements (the previous layer's q_out); q_out[round] = the copy challenges (bnd.q, the next
+ * layer's Q); the other arguments as for lfgpu_sumcheck_layer.  0 < nc <= 2^logc <= 2^40; logc = 0, nc = 1 is
+ * lfgpu_sumcheck_layer (h_Q, round_c and q_out may then be NULL). */
+typedef void (*lfgpu_sc_round_c_fn)(void* user, size_t round, const uint64_t evals[4][2], uint64_t challenge_out[2]);
+int lfgpu_sumcheck_layer_copies(lfgpu_quad* q, size_t logc, size_t nc, const void* h_Q, size_t logv, const void* h_G0,
+                                const void* h_G1, const uint64_t alpha[2], const uint64_t beta[2], size_t logw, size_t nw,
+                                void* d_W, const uint64_t wc_in[2][2], lfgpu_sc_round_c_fn round_c, lfgpu_sc_round_fn round_h,
+                                void* user, uint64_t wc_out[2][2], uint64_t* q_out /*[logc][2]*/,
+                                uint64_t* g_out /*[2][logw][2]*/, uint64_t bound_quad[2]);
+
 /* ---- element-wise field ops (Field::addf / subf / mulf, lib/gf2k/gf2_128.h:227-237,
  * lib/algebra/fp_generic.h:203-214): out[i] = a[i] op b[i], op 0 add, 1 sub, 2 mul.  Used by the
  * parity tests to pin the device arithmetic directly. */

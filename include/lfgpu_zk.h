@@ -80,7 +80,10 @@ typedef struct {
   uint8_t id[32];
 } lfgpu_circuit_info;
 /* CircuitRep::from_bytes (lib/proto/circuit.h): parses the LFC1 bytes, delta-decodes every layer's corners
- * (circuit_reader.h:55-233) and uploads them with lfgpu_quad_upload.  LFGPU_ERR_ARG on malformed input. */
+ * (circuit_reader.h:55-233) and uploads them with lfgpu_quad_upload.  LFGPU_ERR_ARG on malformed input.
+ * The ZK entry points of this header stay at nc = 1: the reference's ZkProver requires logc = 0 (lib/zk/zk_common.h:72), so
+ * a circuit with nc != 1 is LFGPU_ERR_UNSUPPORTED here.  The sumcheck over nc > 1 copies is in the kernel-level ABI
+ * (lfgpu_eval_quad_copies, lfgpu_sumcheck_layer_copies in lfgpu.h). */
 int lfgpu_circuit_from_lfc1(lfgpu_ctx* ctx, const uint8_t* bytes, size_t len, lfgpu_circuit** out);
 /* A second handle on the same uploaded circuit for ANOTHER context of the same device (throughput mode: K host threads, each
  * with its own context -- lfgpu_own_stream -- prover and transcript, one copy of the circuit in HBM).  The device arrays are

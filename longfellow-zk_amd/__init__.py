@@ -36,6 +36,7 @@ ABI_SYMBOLS = [
     "lfgpu_ligero_inner_product_rows", "lfgpu_ligero_dot_proof_sparse",
     "lfgpu_ligero_quadratic_proof", "lfgpu_ligero_open", "lfgpu_ligero_tableau", "lfgpu_ligero_free",
     "lfgpu_quad_upload", "lfgpu_quad_free", "lfgpu_eval_quad", "lfgpu_quad_bind_g", "lfgpu_sumcheck_layer", "lfgpu_raw_eq2", "lfgpu_quad_bind_gh_all",
+    "lfgpu_eval_quad_copies", "lfgpu_sumcheck_evaluations_c", "lfgpu_dense_bind_rows", "lfgpu_eqs", "lfgpu_sumcheck_layer_copies",
     # include/lfgpu_zk.h
     "lfgpu_transcript_new", "lfgpu_transcript_free", "lfgpu_transcript_get_ops", "lfgpu_transcript_write_bytes",
     "lfgpu_transcript_write_elt", "lfgpu_transcript_write_elt_array", "lfgpu_transcript_bytes", "lfgpu_transcript_write_elt_sized", "lfgpu_transcript_write_elt_array_sized", "lfgpu_sha256",
@@ -55,6 +56,8 @@ class LigeroParam(C.Structure):
 RNG_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)  # RandomEngine::bytes
 # round callback of lfgpu_sumcheck_layer: (user, hand, round, evals[3][2], challenge_out[2])
 SC_ROUND_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+# copy-round callback of lfgpu_sumcheck_layer_copies: (user, round, evals[4][2], challenge_out[2])
+SC_ROUND_C_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 
 
 class TranscriptOps(C.Structure):
@@ -149,6 +152,11 @@ def load_library():
         "lfgpu_sumcheck_layer": [vp, sz, vp, vp, pu64, pu64, sz, sz, vp, pu64, SC_ROUND_FN, vp, pu64, pu64, pu64],
         "lfgpu_raw_eq2": [vp, ci, sz, sz, vp, vp, pu64, vp],
         "lfgpu_quad_bind_gh_all": [vp, sz, vp, vp, pu64, pu64, sz, sz, vp, vp, pu64],
+        "lfgpu_eval_quad_copies": [vp, sz, sz, vp, vp, C.POINTER(ci)],
+        "lfgpu_sumcheck_evaluations_c": [vp, ci, sz, vp, vp, sz, sz, vp, vp, pu64],
+        "lfgpu_dense_bind_rows": [vp, ci, sz, sz, pu64, vp, vp],
+        "lfgpu_eqs": [vp, ci, sz, sz, vp, vp],
+        "lfgpu_sumcheck_layer_copies": [vp, sz, sz, vp, sz, vp, vp, pu64, pu64, sz, sz, vp, pu64, SC_ROUND_C_FN, SC_ROUND_FN, vp, pu64, pu64, pu64, pu64],
         "lfgpu_circuit_from_lfc1": [vp, vp, sz, C.POINTER(vp)],
         "lfgpu_circuit_share": [vp, vp, C.POINTER(vp)],
         "lfgpu_circuit_get_info": [vp, C.POINTER(CircuitInfo)],
@@ -356,6 +364,25 @@ class LfGpu:
         self._ck(self.L.lfgpu_raw_eq2(self.h, field, logn, n, C.c_void_p(G0.ctypes.data), C.c_void_p(G1.ctypes.data),
                                       _u64x2(alpha), C.c_void_p(d_eq)))
 
+    # --- the copy rounds of a circuit with nc > 1 copies (reference lib/sumcheck/prover_layers.h:196-216,415-496)
+    def sumcheck_evaluations_c(self, field, nh, d_hc, d_vc, n0, nrows, d_W, d_eq):
+        """the accumulators of ProverLayers::evaluations_c -> [coefs[0], coefs[2], coefs[3]] as (lo, hi) pairs"""
+        acc = (C.c_uint64 * 6)()
+        self._ck(self.L.lfgpu_sumcheck_evaluations_c(self.h, field, nh, C.c_void_p(d_hc), C.c_void_p(d_vc), n0, nrows,
+                                                     C.c_void_p(d_W), C.c_void_p(d_eq), acc))
+        return [(acc[2 * k], acc[2 * k + 1]) for k in range(3)]
+
+    def dense_bind_rows(self, field, n0, nrows, r, d_in, d_out):
+        """Dense::bind with n1 = nrows, out of place -> the new row length (n0 + 1) // 2"""
+        self._ck(self.L.lfgpu_dense_bind_rows(self.h, field, n0, nrows, _u64x2(r), C.c_void_p(d_in), C.c_void_p(d_out)))
+        return (n0 + 1) // 2
+
+    def eqs(self, field, logn, n, Q, d_eq):
+        """Eqs::filleq: eq[i] = EQ(Q, i), i < n; Q: numpy uint64[logn][2] host array"""
+        import numpy as np
+        Q = np.ascontiguousarray(Q, dtype=np.uint64)
+        self._ck(self.L.lfgpu_eqs(self.h, field, logn, n, C.c_void_p(Q.ctypes.data) if logn else None, C.c_void_p(d_eq)))
+
     def field_binop(self, field, op, n, d_a, d_b, d_out):
         """element-wise Field::addf/subf/mulf (op 0/1/2)"""
         self._ck(self.L.lfgpu_field_binop(self.h, field, op, n, C.c_void_p(d_a), C.c_void_p(d_b), C.c_void_p(d_out)))
@@ -514,6 +541,12 @@ class Quad:
         self.gpu._ck(self.gpu.L.lfgpu_eval_quad(self.h, nw, C.c_void_p(d_W), C.c_void_p(d_V), C.byref(ok)))
         return bool(ok.value)
 
+    def eval_copies(self, nc, nw, d_W, d_V):
+        """ProverLayers::eval_quad over nc copies: W[h * nc + c] -> V[g * nc + c]; False if an assert-zero term fails in any copy"""
+        ok = C.c_int()
+        self.gpu._ck(self.gpu.L.lfgpu_eval_quad_copies(self.h, nc, nw, C.c_void_p(d_W), C.c_void_p(d_V), C.byref(ok)))
+        return bool(ok.value)
+
     def bind_g(self, logv, G0, G1, alpha, beta, d_hc_out, d_vc_out):
         import numpy as np
         G0, G1 = np.ascontiguousarray(G0), np.ascontiguousarray(G1)
@@ -554,6 +587,35 @@ class Quad:
                                                      wco, gout, bq))
         ch = [[(gout[(h * logw + r) * 2], gout[(h * logw + r) * 2 + 1]) for r in range(logw)] for h in range(2)]
         return [(wco[0], wco[1]), (wco[2], wco[3])], ch, (bq[0], bq[1])
+
+    def sumcheck_layer_copies(self, logc, nc, Q, logv, G0, G1, alpha, beta, logw, nw, d_W, wc_in, round_c_cb, round_cb):
+        """ProverLayers::layer with nc copies incl. the Eqs constructor and bind_g; d_W: [nw][nc] on the device (consumed).
+        round_c_cb(round, evals[4]) -> challenge for the logc copy rounds, round_cb(hand, round, evals[3]) -> challenge for
+        the hand rounds.  Returns (wc_out[2], q_out[logc], challenges[2][logw], bound_quad)."""
+        import numpy as np
+        G0, G1 = np.ascontiguousarray(G0), np.ascontiguousarray(G1)
+        Q = np.ascontiguousarray(Q, dtype=np.uint64)
+
+        def cbc(_user, rnd, evals, out):
+            r = round_c_cb(rnd, [(evals[2 * k], evals[2 * k + 1]) for k in range(4)])
+            out[0], out[1] = int(r[0]), int(r[1])
+
+        def cb(_user, hand, rnd, evals, out):
+            r = round_cb(hand, rnd, [(evals[2 * k], evals[2 * k + 1]) for k in range(3)])
+            out[0], out[1] = int(r[0]), int(r[1])
+
+        cfc, cfn = SC_ROUND_C_FN(cbc), SC_ROUND_FN(cb)
+        wci = (C.c_uint64 * 4)(int(wc_in[0][0]), int(wc_in[0][1]), int(wc_in[1][0]), int(wc_in[1][1]))
+        wco = (C.c_uint64 * 4)()
+        qout = (C.c_uint64 * (2 * max(1, logc)))()
+        gout = (C.c_uint64 * (4 * max(1, logw)))()
+        bq = (C.c_uint64 * 2)()
+        self.gpu._ck(self.gpu.L.lfgpu_sumcheck_layer_copies(self.h, logc, nc, C.c_void_p(Q.ctypes.data) if logc else None, logv,
+                                                            C.c_void_p(G0.ctypes.data), C.c_void_p(G1.ctypes.data), _u64x2(alpha),
+                                                            _u64x2(beta), logw, nw, C.c_void_p(d_W), wci, cfc, cfn, None, wco, qout,
+                                                            gout, bq))
+        ch = [[(gout[(h * logw + r) * 2], gout[(h * logw + r) * 2 + 1]) for r in range(logw)] for h in range(2)]
+        return [(wco[0], wco[1]), (wco[2], wco[3])], [(qout[2 * r], qout[2 * r + 1]) for r in range(logc)], ch, (bq[0], bq[1])
 
     def close(self):
         if self.h:

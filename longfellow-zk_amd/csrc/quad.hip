@@ -46,6 +46,32 @@ __global__ __launch_bounds__(QD_THREADS) void eval_quad_kernel(u32 nv, const u32
   if (bad) atomicOr(fail, 1);
 }
 
+// The same over nc copies of the circuit (the loop over c of prover_layers.h:288-302): W[h * nc + c], V[g * nc + c], one
+// thread per (gate, copy) with the copy index fastest, so the lanes of a wave read consecutive elements of a wire's row.
+// An assert-zero term is checked in every copy.
+template <int F>
+__global__ __launch_bounds__(QD_THREADS) void eval_quad_copies_kernel(u32 nv, u32 nc, const u32* __restrict__ goff, const corner4* __restrict__ terms,
+                                                                      const elt_t* __restrict__ kvec, const elt_t* __restrict__ W, elt_t* __restrict__ V,
+                                                                      int* __restrict__ fail) {
+  const size_t idx = (size_t)blockIdx.x * QD_THREADS + threadIdx.x;
+  if (idx >= (size_t)nv * nc) return;
+  const u32 g = (u32)(idx / nc), cp = (u32)(idx - (size_t)g * nc);
+  elt_t acc = elt_zero();
+  bool bad = false;
+  for (u32 t = goff[g]; t < goff[g + 1]; ++t) {
+    const corner4 cr = terms[t];
+    const elt_t v = ld16(&kvec[cr.vi]);
+    const elt_t p = Fld<F>::mul(ld16(&W[(size_t)cr.h1 * nc + cp]), ld16(&W[(size_t)cr.h0 * nc + cp]));
+    if ((v.lo | v.hi) == 0) {
+      bad |= (p.lo | p.hi) != 0;
+    } else {
+      acc = Fld<F>::add(acc, Fld<F>::mul(v, p));
+    }
+  }
+  st16(&V[idx], acc);
+  if (bad) atomicOr(fail, 1);
+}
+
 // ---- K10 step 1: eq[i] = EQ(G0,i) + alpha*EQ(G1,i), EQ(G,i) = prod_l (bit_l(i) ? G[l] : 1 - G[l])
 // The binding points travel as a KERNEL ARGUMENT (4 * logn + 1 <= 161 elements = 2.6 KB of the 4 KB kernarg segment; dynamic
 // indexing compiles to loads from that segment, no scratch): no staging copy, i.e. one dispatch less per EQ table -- a layer of a
@@ -480,6 +506,25 @@ extern "C" int lfgpu_eval_quad(lfgpu_quad* q, size_t nw, const void* d_W, void* 
   return LFGPU_OK;
 }
 
+extern "C" int lfgpu_eval_quad_copies(lfgpu_quad* q, size_t nc, size_t nw, const void* d_W, void* d_V, int* ok_out) {
+  if (!q || !d_W || !d_V || !ok_out) return q ? lf_fail(q->c, LFGPU_ERR_ARG, "eval_quad_copies: null argument") : LFGPU_ERR_ARG;
+  lfgpu_ctx* c = q->c;
+  if (q->field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "eval_quad_copies: not built for Fp256Base");
+  if (nc == 0 || (nc >> 32) || ((q->nv * nc) >> 38)) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_copies: nc = %zu out of range", nc);
+  if (nw <= q->hmax) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_copies: nw = %zu but a corner reads wire %zu", nw, q->hmax);
+  LF_HIP(c, hipSetDevice(c->device));
+  int* d_fail = (int*)((uint8_t*)c->mailbox_d + 128);
+  LF_HIP(c, hipMemsetAsync(d_fail, 0, 4, c->stream));
+  const u32 nb = (u32)((q->nv * nc + QD_THREADS - 1) / QD_THREADS);
+  QD_DISPATCH(q->field, eval_quad_copies_kernel, dim3(nb), dim3(QD_THREADS), (u32)q->nv, (u32)nc, (const u32*)q->d_goff, (const corner4*)q->d_bygate,
+              (const elt_t*)q->d_kvec, (const elt_t*)d_W, (elt_t*)d_V, d_fail);
+  LF_HIP(c, hipGetLastError());
+  LF_HIP(c, hipMemcpyAsync(c->mailbox_h, d_fail, 4, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  *ok_out = *(const int*)c->mailbox_h ? 0 : 1;
+  return LFGPU_OK;
+}
+
 // d_zero / zero_bytes (a multiple of 8, < 32 GiB): device words cleared on the side (eq_side_clear), or nullptr
 static int lf_raw_eq2_clear(lfgpu_ctx* c, int field, size_t logn, size_t n, const void* h_G0, const void* h_G1, const uint64_t alpha[2], void* d_eq,
                             void* d_zero, size_t zero_bytes) {
@@ -534,6 +579,16 @@ static int lf_raw_eq2_clear(lfgpu_ctx* c, int field, size_t logn, size_t n, cons
 extern "C" int lfgpu_raw_eq2(lfgpu_ctx* c, int field, size_t logn, size_t n, const void* h_G0, const void* h_G1,
                              const uint64_t alpha[2], void* d_eq) {
   return lf_raw_eq2_clear(c, field, logn, n, h_G0, h_G1, alpha, d_eq, nullptr, 0);
+}
+
+// Eqs::filleq (lib/arrays/eqs.h:104-134): eq[i] = EQ(Q, i), i < n <= 2^logn.  The entries are the products
+// prod_l (bit_l(i) ? Q[l] : 1 - Q[l]) whichever way they are associated, i.e. raw_eq2 with alpha = 0.
+extern "C" int lfgpu_eqs(lfgpu_ctx* c, int field, size_t logn, size_t n, const void* h_Q, void* d_eq) {
+  if (!c) return LFGPU_ERR_ARG;
+  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "eqs: not built for Fp256Base");
+  if (!d_eq || n == 0 || (logn && !h_Q)) return lf_fail(c, LFGPU_ERR_ARG, "eqs: null argument or n = 0 (Eqs::filleq n > 0)");
+  const uint64_t zero[2] = {0, 0};
+  return lf_raw_eq2_clear(c, field, logn, n, h_Q, h_Q, zero, d_eq, nullptr, 0);
 }
 
 // Enqueue only: the outputs are ordered on the context's stream; the HQUAD size is a property of the circuit (nh0,
@@ -693,24 +748,45 @@ int lf_bind_both_cached(lfgpu_ctx* c, int field, size_t n0, const uint64_t r[2],
 
 #include "hostfield.h"
 
-extern "C" int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0, const void* h_G1, const uint64_t alpha[2],
-                                    const uint64_t beta[2], size_t logw, size_t nw, void* d_W, const uint64_t wc_in[2][2],
-                                    lfgpu_sc_round_fn round, void* user, uint64_t wc_out[2][2], uint64_t* g_out,
-                                    uint64_t bound_quad[2]) {
+extern "C" int lfgpu_sumcheck_evaluations_c(lfgpu_ctx*, int, size_t, const void*, const void*, size_t, size_t, const void*, const void*, uint64_t (*)[2]);
+extern "C" int lfgpu_dense_bind_rows(lfgpu_ctx*, int, size_t, size_t, const uint64_t*, const void*, void*);
+
+// The copy rounds of a layer (ProverLayers::layer, lib/sumcheck/prover_layers.h:196-216): nullptr for a circuit of one copy
+struct ScCopies {
+  size_t logc, nc;
+  const void* h_Q;  // logc elements: the binding of the copy variable (the previous layer's q_out)
+  lfgpu_sc_round_c_fn round_c;
+  uint64_t* q_out;  // [logc][2]
+};
+
+// ProverLayers::layer with the bind_g in front of it, for lfgpu_sumcheck_layer (cp == nullptr: eq0 = 1, no copy rounds) and
+// lfgpu_sumcheck_layer_copies.  The copy rounds run between bind_g and the hand rounds: they read the HQUAD that bind_g
+// leaves in the layer's scratch, fold d_W [nw][nc] down to the [nw] vector the hand rounds start from, and leave eq0 =
+// EQ->scalar(), which scales the two coefficients of every hand round on the host.
+static int sc_layer(lfgpu_quad* q, size_t logv, const void* h_G0, const void* h_G1, const uint64_t alpha[2], const uint64_t beta[2], size_t logw,
+                    size_t nw, void* d_W, const uint64_t wc_in[2][2], lfgpu_sc_round_fn round, void* user, uint64_t wc_out[2][2], uint64_t* g_out,
+                    uint64_t bound_quad[2], const ScCopies* cp) {
+  const char* const who = cp ? "sumcheck_layer_copies" : "sumcheck_layer";  // the entry point that error messages name
   if (!q || !alpha || !beta || !d_W || !wc_in || !round || !wc_out || !g_out || nw == 0 || logw > 40 || nw > ((size_t)1 << logw) || nw <= q->hmax)
-    return q ? lf_fail(q->c, LFGPU_ERR_ARG, "sumcheck_layer: bad argument (nw must exceed the largest hand index)") : LFGPU_ERR_ARG;
+    return q ? lf_fail(q->c, LFGPU_ERR_ARG, "%s: bad argument (nw must exceed the largest hand index)", who) : LFGPU_ERR_ARG;
   lfgpu_ctx* c = q->c;
   const int field = q->field;
-  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "sumcheck_layer: Fp256Base layers run inside the ZK driver (zk256.hip)");
+  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: Fp256Base layers run inside the ZK driver (zk256.hip)", who);
   LF_HIP(c, hipSetDevice(c->device));
-  const HostField F(c, field);
+  const bool copies = cp && cp->logc > 0;
+  const HostField F(c, field, copies);
   // device state: HQUAD ping-pong, QW, out-of-place buffer for the first bind of hand 0 (context scratch: no
   // allocation per layer)
   void* sc = nullptr;
   const size_t nt = q->n;
   const size_t qw_bytes = nw * (field == LFGPU_FIELD_FP128 ? 32 : 16);  // Fp128 fused steps keep 4 limb words per target
   const size_t half = ((nw + 1) / 2) * 16;
-  const size_t bytes = 2 * (nt * 8 + nt * 16) + qw_bytes + 4 * half + LF_SC_GRID_STATE_BYTES + 256;
+  size_t bytes = 2 * (nt * 8 + nt * 16) + qw_bytes + 4 * half + LF_SC_GRID_STATE_BYTES + 256;
+  // copy rounds: W ping-pongs between two buffers of [nw][ceil(nc / 2)] and [nw][ceil(nc / 4)], EQ between two of nc and ceil(nc / 2)
+  const size_t cw0 = copies ? nw * ((cp->nc + 1) / 2) * 16 : 0, cw1 = copies ? nw * ((cp->nc + 3) / 4) * 16 : 0;
+  const size_t ce0 = copies ? cp->nc * 16 : 0, ce1 = copies ? ((cp->nc + 1) / 2) * 16 : 0;
+  const size_t copies_off = bytes;
+  bytes += cw0 + cw1 + ce0 + ce1;
   LF_TRY(lf_scratch(c, bytes, &sc));
   uint8_t* base = (uint8_t*)sc;
   void* hc[2] = {base, base + nt * 8};
@@ -761,6 +837,48 @@ extern "C" int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0
                         qw_side ? qw : nullptr, qw_side ? qw_bytes : 0));
   const double tv1 = verbose ? clk() : 0;
   const size_t nh0 = nh;
+  elt_t eq0 = F.one;
+  if (copies) {
+    uint8_t* const cb = base + copies_off;
+    void* wbuf[2] = {cb, cb + cw0};
+    void* ebuf[2] = {cb + cw0 + cw1, cb + cw0 + cw1 + ce0};
+    LF_TRY(lfgpu_eqs(c, field, cp->logc, cp->nc, cp->h_Q, ebuf[0]));
+    const void* Wc = d_W;
+    size_t n0 = cp->nc;
+    for (size_t rnd = 0; rnd < cp->logc; ++rnd) {
+      // evaluations_c (:415-496): the coefficients 0, 2, 3 of the cubic; coefs[1] from the sum
+      uint64_t acc[3][2];
+      LF_TRY(lfgpu_sumcheck_evaluations_c(c, field, nh, hc[0], vc[0], n0, nw, Wc, ebuf[rnd & 1], acc));
+      elt_t coefs[4];
+      coefs[0] = elt_t{acc[0][0], acc[0][1]};
+      coefs[2] = elt_t{acc[1][0], acc[1][1]};
+      coefs[3] = elt_t{acc[2][0], acc[2][1]};
+      coefs[1] = F.sub(F.sub(F.sub(F.sub(sum, coefs[0]), coefs[0]), coefs[2]), coefs[3]);
+      elt_t ev[4];
+      uint64_t evw[4][2], r[2];
+      for (int k = 0; k < 4; ++k) {
+        ev[k] = F.eval_monomial4(coefs, F.pts[k]);
+        evw[k][0] = ev[k].lo;
+        evw[k][1] = ev[k].hi;
+      }
+      cp->round_c(user, rnd, evw, r);
+      cp->q_out[2 * rnd] = r[0];
+      cp->q_out[2 * rnd + 1] = r[1];
+      // bind the copy variable in EQ and W (:208-211)
+      LF_TRY(lfgpu_dense_bind(c, field, n0, r, ebuf[rnd & 1], ebuf[1 - (rnd & 1)]));
+      LF_TRY(lfgpu_dense_bind_rows(c, field, n0, nw, r, Wc, wbuf[rnd & 1]));
+      Wc = wbuf[rnd & 1];
+      sum = F.eval_lagrange4(ev, elt_t{r[0], r[1]});
+      n0 = (n0 + 1) / 2;
+    }
+    // (nc <= 2^logc: one copy is left) eq0 = EQ->scalar(); the hand rounds go on with the [nw] vector
+    uint64_t e[2];
+    LF_HIP(c, hipMemcpyAsync(e, ebuf[cp->logc & 1], 16, hipMemcpyDeviceToHost, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    eq0 = elt_t{e[0], e[1]};
+    d_W = const_cast<void*>(Wc);
+    WH[0] = WH[1] = d_W;
+  }
   bool resident = false, have_r = false;
   // A resident kernel holds CUs of the device's budget (ctx.h); whatever way this function is left, they go back -- after
   // the kernel has ended, so that the budget never undercounts workgroups that still spin.
@@ -909,10 +1027,14 @@ extern "C" int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0
           }
         }
       }
-      // coef[0] = eq0*a0, coef[2] = eq0*a2 with eq0 = 1 (logc = 0); coef[1] from sum (prover_layers.h:390-396)
+      // coef[0] = eq0*a0, coef[2] = eq0*a2 (eq0 = 1 without copy rounds: no products); coef[1] from sum (prover_layers.h:390-396)
       elt_t coef[3];
       coef[0] = elt_t{a0[0], a0[1]};
       coef[2] = elt_t{a2[0], a2[1]};
+      if (copies) {
+        coef[0] = F.mul(eq0, coef[0]);
+        coef[2] = F.mul(eq0, coef[2]);
+      }
       coef[1] = F.sub(F.sub(F.sub(sum, coef[0]), coef[0]), coef[2]);
       elt_t ev[3];
       uint64_t evw[3][2], r[2];
@@ -1010,4 +1132,23 @@ extern "C" int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0
     bound_quad[1] = tmp[5];
   }
   return LFGPU_OK;
+}
+
+extern "C" int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0, const void* h_G1, const uint64_t alpha[2],
+                                    const uint64_t beta[2], size_t logw, size_t nw, void* d_W, const uint64_t wc_in[2][2],
+                                    lfgpu_sc_round_fn round, void* user, uint64_t wc_out[2][2], uint64_t* g_out,
+                                    uint64_t bound_quad[2]) {
+  return sc_layer(q, logv, h_G0, h_G1, alpha, beta, logw, nw, d_W, wc_in, round, user, wc_out, g_out, bound_quad, nullptr);
+}
+
+extern "C" int lfgpu_sumcheck_layer_copies(lfgpu_quad* q, size_t logc, size_t nc, const void* h_Q, size_t logv, const void* h_G0, const void* h_G1,
+                                           const uint64_t alpha[2], const uint64_t beta[2], size_t logw, size_t nw, void* d_W,
+                                           const uint64_t wc_in[2][2], lfgpu_sc_round_c_fn round_c, lfgpu_sc_round_fn round_h, void* user,
+                                           uint64_t wc_out[2][2], uint64_t* q_out, uint64_t* g_out, uint64_t bound_quad[2]) {
+  if (!q) return LFGPU_ERR_ARG;
+  if (logc > 40 || nc == 0 || nc > ((size_t)1 << logc) || (logc && (!h_Q || !round_c || !q_out)))
+    return lf_fail(q->c, LFGPU_ERR_ARG, "sumcheck_layer_copies: bad argument (0 < nc <= 2^logc, logc <= 40; Q, round_c and q_out for logc > 0)");
+  if (nw != 0 && ((nc >> 32) || ((nw * ((nc + 1) / 2)) >> 38))) return lf_fail(q->c, LFGPU_ERR_ARG, "sumcheck_layer_copies: nw * nc too large");
+  const ScCopies cp{logc, nc, h_Q, round_c, q_out};
+  return sc_layer(q, logv, h_G0, h_G1, alpha, beta, logw, nw, d_W, wc_in, round_h, user, wc_out, g_out, bound_quad, &cp);
 }

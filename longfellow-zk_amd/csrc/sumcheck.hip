@@ -1844,3 +1844,175 @@ extern "C" int lfgpu_field_binop(lfgpu_ctx* c, int field, int op, size_t n, cons
   LF_HIP(c, hipGetLastError());
   return LFGPU_OK;
 }
+
+// ------------------------------------------------------------------ K13: the copy rounds (circuits with nc > 1 copies)
+// ProverLayers::evaluations_c (lib/sumcheck/prover_layers.h:415-496) and Dense::bind with n1 > 1 (lib/arrays/dense.h:70-87).
+// W is the reference's Dense(n0 = copies, n1 = wires): W[wire * n0 + c], copy index fastest.
+//
+// evaluations_c: for every HQUAD term (r, l, v) and copy pair c the cubic EQ(t) Wr(t) Wl(t) without its linear coefficient
+// (seven products, the Karatsuba form of :438-457), summed over c, times v, summed over the terms.  Lanes run along the
+// copy pairs of one term -- wr[2c], wr[2c + 1] are 32 contiguous bytes per lane, consecutive lanes consecutive pairs -- in
+// groups of gw = 2^gw_log <= 64 lanes (the smallest power of two that holds the (n0 + 1) / 2 pairs), so 64 / gw terms share
+// a wave when there are few copies and a lane walks several pairs when there are more than 128.  The EQ pair of a lane's
+// first pair stays in registers for all terms; further pairs come from an LDS copy of the EQ vector (up to EC_EQ_LDS
+// entries; from memory beyond).  A term's three sums are folded over its lane group with shuffles BEFORE the single product
+// with v, as the reference does (:474-476); the term sums are added per lane over a grid-stride loop, folded over the
+// workgroup, and each workgroup commits once: XOR words for GF(2^128), 32-bit-limb integer sums for Fp128 (reduced once
+// by the host).  Every value is a canonical field element and the arithmetic is exact, so the order of summation does
+// not show in the bytes.
+#define EC_EQ_LDS 1024
+#define EC_MAX_BLOCKS 2048
+template <int F>
+__global__ __launch_bounds__(SC_THREADS) void evaluations_c_kernel(u32 nh, const uint2* __restrict__ hc, const elt_t* __restrict__ vc, u32 n0, u32 gw_log,
+                                                                   const elt_t* __restrict__ W, const elt_t* __restrict__ eq, u64* __restrict__ acc) {
+  __shared__ elt_t sh_eq[EC_EQ_LDS];
+  __shared__ elt_t sh_red[SC_THREADS / 64];
+  const u32 P = (n0 + 1) / 2;  // pairs, the odd tail (:460-472) counted as one
+  const u32 gw = 1u << gw_log;
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const u32 sub = lane & (gw - 1), slot = lane >> gw_log;
+  const u32 tpw = 64u >> gw_log, tpb = tpw * (SC_THREADS / 64);  // terms per wave / workgroup and pass
+  const bool eq_lds = P > gw && n0 <= EC_EQ_LDS;
+  if (eq_lds) {
+    for (u32 i = threadIdx.x; i < n0; i += SC_THREADS) sh_eq[i] = ld16(&eq[i]);
+    __syncthreads();
+  }
+  elt_t e0 = elt_zero(), e1 = elt_zero();  // EQ of the lane's first pair
+  if (sub < P) {
+    e0 = ld16(&eq[2 * sub]);
+    if (2 * sub + 1 < n0) e1 = ld16(&eq[2 * sub + 1]);
+  }
+  elt_t A0 = elt_zero(), A2 = elt_zero(), A3 = elt_zero();
+  for (u64 tb = (u64)blockIdx.x * tpb; tb < nh; tb += (u64)gridDim.x * tpb) {  // (uniform over the workgroup)
+    const u64 t = tb + wave * tpw + slot;
+    const bool live = t < nh;
+    elt_t l0 = elt_zero(), l2 = elt_zero(), l3 = elt_zero();
+    if (live) {
+      const uint2 h = hc[t];
+      const elt_t* __restrict__ wr = W + (size_t)h.x * n0;
+      const elt_t* __restrict__ wl = W + (size_t)h.y * n0;
+      for (u32 c = sub; c < P; c += gw) {
+        elt_t q0 = e0, q1 = e1;
+        const bool pair = 2 * c + 1 < n0;
+        if (c != sub) {
+          q0 = eq_lds ? sh_eq[2 * c] : ld16(&eq[2 * c]);
+          if (pair) q1 = eq_lds ? sh_eq[2 * c + 1] : ld16(&eq[2 * c + 1]);
+        }
+        const elt_t wr0 = ld16(&wr[2 * c]), wl0 = ld16(&wl[2 * c]);
+        const elt_t d0 = Fld<F>::mul(q0, wr0);
+        if (pair) {
+          const elt_t wr1 = ld16(&wr[2 * c + 1]), wl1 = ld16(&wl[2 * c + 1]);
+          const elt_t c1 = Fld<F>::sub(wl1, wl0);
+          const elt_t d2 = Fld<F>::mul(Fld<F>::sub(q1, q0), Fld<F>::sub(wr1, wr0));
+          const elt_t d1 = Fld<F>::sub(Fld<F>::sub(Fld<F>::mul(q1, wr1), d0), d2);
+          l0 = Fld<F>::add(l0, Fld<F>::mul(d0, wl0));
+          l2 = Fld<F>::add(l2, Fld<F>::add(Fld<F>::mul(d1, c1), Fld<F>::mul(d2, wl0)));
+          l3 = Fld<F>::add(l3, Fld<F>::mul(d2, c1));
+        } else {  // odd tail: d0 wl0 into l0, three times into l2, negated into l3
+          const elt_t x = Fld<F>::mul(d0, wl0);
+          l0 = Fld<F>::add(l0, x);
+          l2 = Fld<F>::add(l2, Fld<F>::add(x, Fld<F>::add(x, x)));
+          l3 = Fld<F>::sub(l3, x);
+        }
+      }
+    }
+    for (u32 off = gw >> 1; off > 0; off >>= 1) {  // fold over the term's lane group (every lane of the wave takes part)
+      elt_t o;
+      o.lo = __shfl_xor(l0.lo, off, 64); o.hi = __shfl_xor(l0.hi, off, 64);
+      l0 = Fld<F>::add(l0, o);
+      o.lo = __shfl_xor(l2.lo, off, 64); o.hi = __shfl_xor(l2.hi, off, 64);
+      l2 = Fld<F>::add(l2, o);
+      o.lo = __shfl_xor(l3.lo, off, 64); o.hi = __shfl_xor(l3.hi, off, 64);
+      l3 = Fld<F>::add(l3, o);
+    }
+    if (live && sub == 0) {
+      const elt_t v = ld16(&vc[t]);
+      A0 = Fld<F>::add(A0, Fld<F>::mul(l0, v));
+      A2 = Fld<F>::add(A2, Fld<F>::mul(l2, v));
+      A3 = Fld<F>::add(A3, Fld<F>::mul(l3, v));
+    }
+  }
+  const elt_t S[3] = {block_reduce<F>(A0, sh_red), block_reduce<F>(A2, sh_red), block_reduce<F>(A3, sh_red)};
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      u64* a = acc + 4 * k;
+      if (F == FIELD_GF2_128) {
+        atomicXor(&a[0], S[k].lo);
+        atomicXor(&a[1], S[k].hi);
+      } else {
+        atomicAdd(&a[0], (u64)(u32)S[k].lo);
+        atomicAdd(&a[1], S[k].lo >> 32);
+        atomicAdd(&a[2], (u64)(u32)S[k].hi);
+        atomicAdd(&a[3], S[k].hi >> 32);
+      }
+    }
+  }
+}
+
+// Dense::bind over n1 = nrows rows: every row of n0 entries is bound as in dense_bind_body and the rows are re-packed to
+// stride nout = (n0 + 1) / 2 (dense.h:74-85).  One thread per output entry, consecutive threads consecutive entries.
+template <int F>
+__global__ __launch_bounds__(SC_THREADS) void dense_bind_rows_kernel(size_t n0, size_t nout, size_t total, elt_t r, const elt_t* __restrict__ in,
+                                                                     elt_t* __restrict__ out) {
+  const size_t idx = (size_t)blockIdx.x * SC_THREADS + threadIdx.x;
+  if (idx >= total) return;
+  const size_t row = idx / nout, i = idx - row * nout;
+  const elt_t* __restrict__ p = in + row * n0;
+  const elt_t f0 = ld16(&p[2 * i]);
+  elt_t v;
+  if (2 * i + 1 < n0) {
+    const elt_t f1 = ld16(&p[2 * i + 1]);
+    v = Fld<F>::add(f0, Fld<F>::mul(Fld<F>::sub(f1, f0), r));
+  } else {
+    v = Fld<F>::sub(f0, Fld<F>::mul(f0, r));
+  }
+  st16(&out[idx], v);
+}
+
+extern "C" int lfgpu_sumcheck_evaluations_c(lfgpu_ctx* c, int field, size_t nh, const void* d_hc, const void* d_vc, size_t n0, size_t nrows,
+                                            const void* d_W, const void* d_eq, uint64_t acc_out[3][2]) {
+  if (!c) return LFGPU_ERR_ARG;
+  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "sumcheck_evaluations_c: not built for Fp256Base");
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_evaluations_c: unknown field %d", field);
+  if (!acc_out || !d_eq || n0 == 0 || (n0 >> 32) || nrows == 0 || nh > 0xfffffff0u || (nh && (!d_hc || !d_vc || !d_W)))
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_evaluations_c: bad argument (null pointer, n0 = 0 or >= 2^32, nrows = 0, nh >= 2^32)");
+  memset(acc_out, 0, 48);
+  if (nh == 0) return LFGPU_OK;
+  LF_HIP(c, hipSetDevice(c->device));
+  const size_t P = (n0 + 1) / 2;
+  u32 gw_log = 0;
+  while (gw_log < 6 && ((size_t)1 << gw_log) < P) ++gw_log;
+  const size_t tpb = (size_t)(64u >> gw_log) * (SC_THREADS / 64);
+  const u32 nb = (u32)std::min<size_t>((nh + tpb - 1) / tpb, EC_MAX_BLOCKS);
+  u64* d_acc = (u64*)((uint8_t*)c->mailbox_d + 320);  // 3 x 4 words
+  LF_HIP(c, hipMemsetAsync(d_acc, 0, 96, c->stream));
+  DISPATCH_FIELD(field, evaluations_c_kernel, dim3(nb), dim3(SC_THREADS), (u32)nh, (const uint2*)d_hc, (const elt_t*)d_vc, (u32)n0, gw_log,
+                 (const elt_t*)d_W, (const elt_t*)d_eq, d_acc);
+  LF_HIP(c, hipGetLastError());
+  u64* w = (u64*)c->mailbox_h;
+  LF_HIP(c, hipMemcpyAsync(w, d_acc, 96, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 3; ++k) lf_quad_bind_gh_all_fold(field, w + 4 * k, acc_out[k]);  // XOR words as they are / the limb sums reduced mod p
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_dense_bind_rows(lfgpu_ctx* c, int field, size_t n0, size_t nrows, const uint64_t r[2], const void* d_in, void* d_out) {
+  if (!c) return LFGPU_ERR_ARG;
+  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "dense_bind_rows: not built for Fp256Base");
+  if (!r || ((n0 && nrows) && (!d_in || !d_out))) return lf_fail(c, LFGPU_ERR_ARG, "dense_bind_rows: null argument");
+  if (n0 == 0 || nrows == 0) return LFGPU_OK;
+  const size_t nout = (n0 + 1) / 2;
+  if ((n0 >> 40) || (nrows >> 40) || ((nout * nrows) >> 39)) return lf_fail(c, LFGPU_ERR_ARG, "dense_bind_rows: too large");
+  const size_t total = nout * nrows;
+  {  // the rows are compacted, so a parallel bind in place would race: out of place only
+    const uintptr_t a0 = (uintptr_t)d_in, a1 = a0 + n0 * nrows * 16, b0 = (uintptr_t)d_out, b1 = b0 + total * 16;
+    if (a0 < b1 && b0 < a1) return lf_fail(c, LFGPU_ERR_ARG, "dense_bind_rows: d_out overlaps d_in");
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+  const u32 nb = (u32)((total + SC_THREADS - 1) / SC_THREADS);
+  const elt_t rr{r[0], r[1]};
+  DISPATCH_FIELD(field, dense_bind_rows_kernel, dim3(nb), dim3(SC_THREADS), n0, nout, total, rr, (const elt_t*)d_in, (elt_t*)d_out);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
