@@ -293,7 +293,8 @@ def _bitsliced_batch(G, k, l, coset, rows, inverse, sample=False):
         want = a[r].copy()
         (o.lfo_lch14_ifft if inverse else o.lfo_lch14_fft)(C.byref(c), l, coset, P(want))
         assert (got[r] == want).all(), r
-    if sample:  # the untouched tail of every row and a checksum over all rows against a second run through the LDS-tile kernel
+    if sample:  # only the sampled rows were compared above; here the untouched tail (columns >= 2^l) of EVERY row.  The all-rows
+        # comparison with the oracle, under every A/B setting of this path, is tests/test_lch_bs_variants.py
         assert (got[:, 1 << l:] == a[:, 1 << l:]).all()
 
 
