@@ -208,6 +208,10 @@ __device__ __forceinline__ u32 t4_wslot(u32 i) { return i ^ ((i >> 4) & 15u); }
 // The arithmetic of the 1024 x 4 tiles: O's own, except for Fp128, whose add, sub and twiddle product come from
 // fp_tile_arith.h (same values, fewer VALU instructions).  add_lazy / canon: the lazy u side of a butterfly (fp_tile_arith.h),
 // for Fp128 only; any other field adds as usual and has nothing to make canonical.
+// mul_tw(x, w): the SECOND argument is a twiddle, canonical (< p) as the host builds every table (fp_root_table and the full table
+// of fp_fft_two_pass: O::one() and outputs of the host product O::hmul): a stage twiddle out of LDS or W
+// (t4_stages) or an entry of the inter-pass table (pass A's store side, pass B's load side).  fpt_mul rests on that: it leaves
+// out three carry captures that b3 <= 0xfffff000 makes impossible.  x may be lazy.  Never swap the two.
 template <class O>
 struct T4Ops : O {
   static __device__ __forceinline__ elt_t add_lazy(elt_t a, elt_t b) { return O::add(a, b); }

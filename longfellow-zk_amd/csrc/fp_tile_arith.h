@@ -4,7 +4,8 @@
 //   - fpt_mul: the first carry of every product column is written into the high half of the next column's accumulator
 //     instead of added to a zeroed one (one v_mov per column instead of two); the REDC never forms m = -U: it computes
 //     T_hi - U + (U >> 20) + cy and adds p when that is negative (a sign from two carry masks merged by one SALU
-//     instruction): 27 -> 19 VALU instructions for the REDC, 71 -> 63 -> 55 per product.
+//     instruction): 27 -> 19 VALU instructions for the REDC, 71 -> 63 -> 55 per product; the first mad of columns 3, 4 and
+//     5 (a_i b3) cannot carry for w < p and has no capture: 52.
 //   - fpt_add: the carry-out of a + b stays a lane mask and is merged with the borrow of (a + b) - p by one SALU
 //     instruction: 14 -> 12 VALU instructions.
 //   - fpt_sub: the borrow of a - b, kept in an SGPR pair, is the carry-in of the + p chain: 10 -> 9.
@@ -150,6 +151,16 @@ __device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
 // a * w / 2^128 mod p (Montgomery), as fp_mul for a, w < p.  a may be any 128-bit value (lazy) as long as w < p: T = a w < 2^128 p,
 // so T_hi < p, (T + m p) / 2^128 < 2p and W in [-p, p) as below, and the result is canonical.  Product scanning with 16 v_mad_u64_u32; the carries of column k
 // go to ov, which becomes the high half of column k + 1's accumulator {acc.hi, ov}.
+//
+// PRECONDITION: the SECOND argument is < p (a twiddle; T4Ops<Fp128Ops>::mul_tw in fft.hip passes nothing else).  Besides the
+// range of the REDC, three carry captures rest on it.  p = 2^128 - 2^108 + 1, so the top limb of w < p is b3 <= 0xfffff000.
+// Columns 3, 4 and 5 start with a0 b3, a1 b3 and a2 b3.  The accumulator that enters such a column is {acc.hi, ov} with
+// acc.hi < 2^32 and ov <= 3 (at most three captures in the column before), so it is < 2^34; the first product is at most
+// (2^32 - 1) 0xfffff000 = 2^64 - 2^44 - 2^32 + 2^12; the sum is < 2^64 - 2^44 + 2^34 < 2^64 whatever a is, lazy values
+// included.  That mad cannot carry and is a bare FP_MAD; the column's second mad is the one whose capture writes ov.  Column 2
+// starts with a0 b2, which this bound does not cover (b2 may be 0xffffffff), and keeps its three captures.  13 -> 10 captures,
+// 55 -> 52 VALU instructions per product, same values.  With b3 = 0xffffffff (no field element) column 3's first mad does
+// wrap: tests/test_fp_tile_mul_carries.py has the model, the case and the inputs that reach these carries on the device.
 __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   FP_W(a, a0, a1, a2, a3);
   FP_W(b, b0, b1, b2, b3);
@@ -165,17 +176,17 @@ __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   FP_MADC(acc, ov, a1, b1);
   FP_MADC(acc, ov, a2, b0);
   FPT_COL(t2, acc, ov);
-  FPT_MADW(acc, ov, a0, b3);
-  FP_MADC(acc, ov, a1, b2);
+  FP_MAD(acc, a0, b3);  // < 2^64 for b3 <= 0xfffff000: no capture (see above), and so in columns 4 and 5
+  FPT_MADW(acc, ov, a1, b2);
   FP_MADC(acc, ov, a2, b1);
   FP_MADC(acc, ov, a3, b0);
   FPT_COL(t3, acc, ov);
-  FPT_MADW(acc, ov, a1, b3);
-  FP_MADC(acc, ov, a2, b2);
+  FP_MAD(acc, a1, b3);
+  FPT_MADW(acc, ov, a2, b2);
   FP_MADC(acc, ov, a3, b1);
   FPT_COL(t4, acc, ov);
-  FPT_MADW(acc, ov, a2, b3);
-  FP_MADC(acc, ov, a3, b2);
+  FP_MAD(acc, a2, b3);
+  FPT_MADW(acc, ov, a3, b2);
   FPT_COL(t5, acc, ov);
   FP_MAD(acc, a3, b3);
   t6 = (u32)acc;
