@@ -199,12 +199,9 @@ __global__ __launch_bounds__(FFT_THREADS) void fp_fft_tile(TilePlan p, const elt
 //   round 3 (stages 8-9, radix 4, two groups per thread): LDS -> registers -> (pass A: x w_n^(j1 k2)) -> HBM.
 // Rounds 1-3 multiply by every twiddle, w^0 = Montgomery 1 included (fp_mul(a, 1) = a for a < p): no per-lane branch.
 // Three barriers and three LDS round trips per tile instead of the generic kernel's five.
+// The rounds are the t4_round* helpers below, shared by the three kernel bodies (fp_fft_tile_1024x4, _persist, _tws_body); what a
+// body keeps to itself is its global loads and stores, the inter-pass product and its barriers.
 //
-// LDS layout, conflict-free for every access of the tile (ds_write_b128: 8 x 8 consecutive lanes on 32 banks, ds_read_b128:
-// 4 x 16 lanes on 64 banks): position p, column c at slot (4p + c) ^ (p >> 7), the XOR staying inside an aligned 16-slot row.
-// The stage twiddles w_1024^i (i < 512) sit behind the tile at slot i ^ ((i >> 4) & 15).
-__device__ __forceinline__ u32 t4_wslot(u32 i) { return i ^ ((i >> 4) & 15u); }
-
 // The arithmetic of the 1024 x 4 tiles: O's own, except for Fp128, whose add, sub and twiddle product come from
 // fp_tile_arith.h (same values, fewer VALU instructions).  add_lazy / canon: the lazy u side of a butterfly (fp_tile_arith.h),
 // for Fp128 only; any other field adds as usual and has nothing to make canonical.
@@ -227,6 +224,15 @@ struct T4Ops<Fp128Ops> : Fp128Ops {
   static __device__ __forceinline__ elt_t mul_tw(elt_t a, elt_t w) { return fpt_mul(a, w); }
 };
 #endif
+
+// LDS layout of the tile, defined here and nowhere else: position p (bit-reversed order), column c at slot (4p + c) ^ (p >> 7),
+// the XOR staying inside an aligned 16-slot row.  It is conflict-free for every access of the four rounds (ds_write_b128: 8 x 8
+// consecutive lanes on 32 banks, ds_read_b128: 4 x 16 lanes on 64 banks).  Each round's lanes hold positions base + stride a;
+// t4_slot gives the slot of the base, and since p >> 7 moves with a only in rounds 2 and 3, the other slots are that one plus an
+// immediate offset, with one more XOR of a constant where a reaches bit 7 of the position.
+// The stage twiddles w_1024^i (i < 512) sit behind the tile (wl = s + 4096) at slot i ^ ((i >> 4) & 15).
+__device__ __forceinline__ u32 t4_slot(u32 p, u32 c, u32 p7) { return ((p << 2) | c) ^ p7; }  // p7 = p >> 7, as the round knows it
+__device__ __forceinline__ u32 t4_wslot(u32 i) { return i ^ ((i >> 4) & 15u); }
 
 // R radix-2 stages (from stage ST) on the register group x[a] = position i0 + a 2^ST, j = i0 mod 2^ST; as fp_radix_round.
 // ROUND0 (ST = 0, j = 0): twiddles read from HBM at uniform addresses, the w^0 products left out.
@@ -256,6 +262,88 @@ __device__ __forceinline__ void t4_stages(elt_t* x, u32 j, const elt_t* wl, cons
   }
 }
 
+// Round 0 of thread (kb, c), whose y[a'] is point kb + 128 a' of column c: stages 0-2 on x[a] = y[bitrev3(a)], then positions
+// 8b + a to LDS.  8b >> 7 = b >> 4 reaches bit 2 of the slot, so odd a have a base of their own.
+template <class O, u32 LZ>
+__device__ __forceinline__ void t4_round0(elt_t* s, const elt_t* y, u32 kb, u32 c, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
+  elt_t x[8];
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];
+  t4_stages<O, 0, 3, true, LZ>(x, 0, wl, W, wshift);
+  const u32 b = __brev(kb) >> 25, s0 = t4_slot(8 * b, c, b >> 4), s1 = t4_slot(8 * b + 1, c, b >> 4);
+#pragma unroll
+  for (u32 a = 0; a < 8; a += 2) {
+    st16(&s[s0 + 4 * a], x[a]);
+    st16(&s[s1 + 4 * a], x[a + 1]);
+  }
+}
+// Round 1: group (c, j < 8, h < 16) = positions 64h + j + 8a; (p >> 7) = h >> 1 for all eight.
+template <class O, u32 LZ>
+__device__ __forceinline__ void t4_round1(elt_t* s, u32 tid, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
+  const u32 c = tid & 3, j = (tid >> 2) & 7, h = tid >> 5;
+  const u32 s0 = t4_slot(64 * h + j, c, h >> 1);
+  elt_t x[8];
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
+  t4_stages<O, 3, 3, false, LZ>(x, j, wl, W, wshift);
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
+}
+// Round 2, one group e = tid + 512 g: (c, j < 64, h < 4) = positions 256h + j + 64a; (p >> 7) = 2h + (a >> 1).  In two halves,
+// because fp_fft_tile_1024x4 issues its table loads between the LDS loads and the stages; the first returns the group's base
+// slot for the second.
+__device__ __forceinline__ u32 t4_round2_load(elt_t* x, const elt_t* s, u32 e) {
+  const u32 c = e & 3, h = e >> 8, j = (e >> 2) & 63;
+  const u32 s0 = t4_slot(256 * h + j, c, 2 * h);
+#pragma unroll
+  for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (a >> 1)) + 256 * a]);
+  return s0;
+}
+template <class O, u32 LZ>
+__device__ __forceinline__ void t4_round2_finish(elt_t* s, elt_t* x, u32 e, u32 s0, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
+  t4_stages<O, 6, 2, false, LZ>(x, (e >> 2) & 63, wl, W, wshift);
+#pragma unroll
+  for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ (a >> 1)) + 256 * a], x[a]);
+}
+template <class O, u32 LZ>
+__device__ __forceinline__ void t4_round2(elt_t* s, u32 e, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
+  elt_t x[4];
+  const u32 s0 = t4_round2_load(x, s, e);
+  t4_round2_finish<O, LZ>(s, x, e, s0, wl, W, wshift);
+}
+// Round 3's LDS loads of one group e = tid + 512 g: (c, j < 256) = (e & 3, e >> 2), positions (= output points) j + 256a;
+// (p >> 7) = (j >> 7) + 2a.  Lanes walk c, then j.  The stages t4_stages<O, 8, 2, false, LZ>(x, e >> 2, ..) and the stores are the caller's.
+__device__ __forceinline__ void t4_round3_load(elt_t* x, const elt_t* s, u32 e) {
+  const u32 c = e & 3, j = e >> 2;
+  const u32 s0 = t4_slot(j, c, j >> 7);
+#pragma unroll
+  for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+}
+
+// XCD-aware tile order of pass A's 1-D grids: workgroup w = 8i + x (x: the blocks that share an XCD, blocks being dealt round-robin
+// over the 8 XCDs) takes column block bx = (ncb/8) x + i mod (ncb/8) and part i / (ncb/8) of the rows.  The workgroups of one XCD
+// then read adjacent 64-byte segments of the same rows at about the same time, and its L2 holds only their 1/8 of the twiddle table.
+__device__ __forceinline__ void t4_xcd_order(u32 ncb, u32 w, u32& bx, u32& part) {
+  if ((ncb & 7) == 0) {
+    const u32 per = ncb >> 3, i = w >> 3;
+    bx = (w & 7) * per + i % per;
+    part = i / per;
+  } else {
+    bx = w % ncb;
+    part = w / ncb;
+  }
+}
+// Pass A's inter-pass twiddles of a thread's eight round-3 outputs j1 = j + 256a of column block cbase / 4, from the full table:
+// w_n^(j1 k2) = tw[j1 * nbatch + k2]
+__device__ __forceinline__ void t4a_tw_load(elt_t (*t)[4], const elt_t* __restrict__ tw, u32 nbatch, u32 cbase, u32 tid) {
+#pragma unroll
+  for (u32 g = 0; g < 2; ++g) {
+    const u32 e = tid + 512 * g;
+#pragma unroll
+    for (u32 a = 0; a < 4; ++a) t[g][a] = ld16(&tw[(size_t)((e >> 2) + 256 * a) * nbatch + cbase + (e & 3)]);
+  }
+}
+
 // KFAST_SRC: pass B (points contiguous, columns n2 apart); otherwise pass A (columns contiguous).  The store side is columns
 // contiguous in both passes (kfast_dst = 0).  TW: pass A's inter-pass product with the full [j][column] table.
 // Needs p.logT = 10, p.logC = 2, p.wlds, p.nbatch a multiple of 4 (no partial tiles).
@@ -266,7 +354,6 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4(TilePlan p, const e
   elt_t* const wl = s + 4096;
   const u32 tid = threadIdx.x;
   const u32 bx = row_fast ? blockIdx.y : blockIdx.x, by = row_fast ? blockIdx.x : blockIdx.y;  // (tile, batch row)
-  const u32 cbase = bx << 2;
   {  // round 0.  Pass B: a wave reads 64 consecutive points of one column; pass A: 16 rows of 4 consecutive columns.
     const u32 c = KFAST_SRC ? tid >> 7 : tid & 3, kb = KFAST_SRC ? tid & 127 : tid >> 2;
     const elt_t* src = p.src + (long long)by * p.src_row + (long long)bx * p.src_tile + (long long)kb * p.sk + (long long)c * p.sc;
@@ -275,69 +362,33 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4(TilePlan p, const e
     for (u32 a = 0; a < 8; ++a) y[a] = ld16(src + (long long)(128 * a) * p.sk);
     const elt_t wv = ld16(&W[(size_t)tid << wshift]);
     __builtin_amdgcn_sched_barrier(0);  // all nine loads in flight before the first wait (the scheduler would sink them)
-    elt_t x[8];
-#pragma unroll
-    for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];  // x[a] = y[bitrev3(a)]
-    t4_stages<O, 0, 3, true>(x, 0, wl, W, wshift);
-    // position 8b + a: slot (32b + 4a + c) ^ (b >> 4); the XOR reaches bit 2, so odd a have a base of their own
-    const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
-#pragma unroll
-    for (u32 a = 0; a < 8; a += 2) {
-      st16(&s[s0 + 4 * a], x[a]);
-      st16(&s[s1 + 4 * a], x[a + 1]);
-    }
+    t4_round0<O, T4_CANON>(s, y, kb, c, wl, W, wshift);
     st16(&wl[t4_wslot(tid)], wv);
   }
   __syncthreads();
-  {  // round 1: group (c, j < 8, h < 16) = positions 64h + j + 8a; (p >> 7) = h >> 1 for all eight
-    const u32 c = tid & 3, j = (tid >> 2) & 7, h = tid >> 5;
-    const u32 s0 = (((64 * h + j) << 2) | c) ^ (h >> 1);
-    elt_t x[8];
-#pragma unroll
-    for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
-    t4_stages<O, 3, 3, false>(x, j, wl, W, wshift);
-#pragma unroll
-    for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
-  }
+  t4_round1<O, T4_CANON>(s, tid, wl, W, wshift);
   __syncthreads();
-  elt_t y[8], t[2][4];  // pass A: the inter-pass twiddles of round 3's outputs
-  {  // round 2: group (c, j < 64, h < 4) = positions 256h + j + 64a; (p >> 7) = 2h + (a >> 1)
-    u32 s0[2], j[2];
+  elt_t t[2][4];  // pass A: the inter-pass twiddles of round 3's outputs
+  {  // round 2, with pass A's eight table loads in flight during rounds 2 and 3
     elt_t x[2][4];
+    u32 s0[2];
 #pragma unroll
-    for (u32 g = 0; g < 2; ++g) {
-      const u32 e = tid + 512 * g, c = e & 3, h = e >> 8;
-      j[g] = (e >> 2) & 63;
-      s0[g] = (((256 * h + j[g]) << 2) | c) ^ (2 * h);
-#pragma unroll
-      for (u32 a = 0; a < 4; ++a) x[g][a] = ld16(&s[(s0[g] ^ (a >> 1)) + 256 * a]);
-    }
-    if (TW) {  // w_n^(j1 k2) = tw[j1 * nbatch + k2] for j1 = j + 256a (round 3's map), all eight in flight during rounds 2 and 3
-#pragma unroll
-      for (u32 g = 0; g < 2; ++g) {
-        const u32 e = tid + 512 * g;
-#pragma unroll
-        for (u32 a = 0; a < 4; ++a) t[g][a] = ld16(&tw[(size_t)((e >> 2) + 256 * a) * p.nbatch + cbase + (e & 3)]);
-      }
+    for (u32 g = 0; g < 2; ++g) s0[g] = t4_round2_load(x[g], s, tid + 512 * g);
+    if (TW) {
+      t4a_tw_load(t, tw, p.nbatch, bx << 2, tid);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
-    for (u32 g = 0; g < 2; ++g) {
-      t4_stages<O, 6, 2, false>(x[g], j[g], wl, W, wshift);
-#pragma unroll
-      for (u32 a = 0; a < 4; ++a) st16(&s[(s0[g] ^ (a >> 1)) + 256 * a], x[g][a]);
-    }
+    for (u32 g = 0; g < 2; ++g) t4_round2_finish<O, T4_CANON>(s, x[g], tid + 512 * g, s0[g], wl, W, wshift);
   }
   __syncthreads();
-  {  // round 3: group (c, j < 256) = positions (= output points) j + 256a; (p >> 7) = (j >> 7) + 2a.  Lanes walk c, then j.
+  {  // round 3
     elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
 #pragma unroll
     for (u32 g = 0; g < 2; ++g) {
       const u32 e = tid + 512 * g, c = e & 3, j = e >> 2;
-      const u32 s0 = ((j << 2) | c) ^ (j >> 7);
       elt_t x[4];
-#pragma unroll
-      for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+      t4_round3_load(x, s, e);
       t4_stages<O, 8, 2, false>(x, j, wl, W, wshift);
 #pragma unroll
       for (u32 a = 0; a < 4; ++a) {
@@ -357,39 +408,23 @@ __device__ __forceinline__ void t4a_load(elt_t* y, const TilePlan& p, u32 by, u3
   for (u32 a = 0; a < 8; ++a) y[a] = ld16(src + (off + 128 * a * sk));
 }
 
-// Pass A (columns contiguous, inter-pass product) in an XCD-aware tile order, optionally as a tile loop: the same rounds and LDS
-// layout as fp_fft_tile_1024x4.  With parts < rows each workgroup keeps one column block bx and walks down a range of batch rows,
+// Pass A (columns contiguous, inter-pass product) in the XCD-aware tile order (t4_xcd_order), optionally as a tile loop: the same
+// rounds as fp_fft_tile_1024x4.  With parts < rows each workgroup keeps one column block bx and walks down a range of batch rows,
 // so what depends on bx alone is loaded once (with parts = rows, the default, every workgroup takes one tile):
 //   - the eight inter-pass twiddles w_n^(j1 k2) of each thread stay in registers (t) for every tile;
 //   - the stage twiddles go to LDS once.
-// Tile order: workgroup w = 8i + x (x: the blocks that share an XCD, blocks being dealt round-robin over the 8 XCDs) takes
-// column block (ncb/8) x + i mod (ncb/8) and part i / (ncb/8) of the rows.  The workgroups of one XCD then read adjacent
-// 64-byte segments of the same rows at about the same time, and its L2 holds only their 1/8 of the twiddle table.
 // Grid: ncb * parts workgroups (ncb = p.nbatch / 4 column blocks); part q covers rows [q rows / parts, (q + 1) rows / parts).
 template <class O>
 __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
                                                                      const elt_t* __restrict__ tw, u32 rows, u32 parts) {
   extern __shared__ elt_t s[];
   elt_t* const wl = s + 4096;
-  const u32 tid = threadIdx.x, ncb = p.nbatch >> 2, w = blockIdx.x;
+  const u32 tid = threadIdx.x;
   u32 bx, part;
-  if ((ncb & 7) == 0) {
-    const u32 per = ncb >> 3, i = w >> 3;
-    bx = (w & 7) * per + i % per;
-    part = i / per;
-  } else {
-    bx = w % ncb;
-    part = w / ncb;
-  }
+  t4_xcd_order(p.nbatch >> 2, blockIdx.x, bx, part);
   const u32 r0 = (u32)((u64)part * rows / parts), r1 = (u32)((u64)(part + 1) * rows / parts);
-  const u32 cbase = bx << 2;
   elt_t y[8], t[2][4];
-#pragma unroll
-  for (u32 g = 0; g < 2; ++g) {  // w_n^(j1 k2) = tw[j1 * nbatch + k2] for round 3's outputs j1 = j + 256a
-    const u32 e = tid + 512 * g;
-#pragma unroll
-    for (u32 a = 0; a < 4; ++a) t[g][a] = ld16(&tw[(size_t)((e >> 2) + 256 * a) * p.nbatch + cbase + (e & 3)]);
-  }
+  t4a_tw_load(t, tw, p.nbatch, bx << 2, tid);
   st16(&wl[t4_wslot(tid)], ld16(&W[(size_t)tid << wshift]));  // read after the first tile's first barrier
   for (u32 by = r0; by < r1; ++by) {
     // every per-lane index below is recomputed per tile from lt: hoisted out of the loop, the addresses would hold more VGPRs
@@ -398,54 +433,19 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p,
     asm volatile("" : "+v"(lt));
     t4a_load(y, p, by, bx, lt);
     __builtin_amdgcn_sched_barrier(0);  // all eight in flight before the first wait, as in fp_fft_tile_1024x4
-    {  // round 0, as in fp_fft_tile_1024x4
-      const u32 c = lt & 3, kb = lt >> 2;
-      elt_t x[8];
-#pragma unroll
-      for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];
-      t4_stages<O, 0, 3, true>(x, 0, wl, W, wshift);
-      const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
-#pragma unroll
-      for (u32 a = 0; a < 8; a += 2) {
-        st16(&s[s0 + 4 * a], x[a]);
-        st16(&s[s1 + 4 * a], x[a + 1]);
-      }
-    }
+    t4_round0<O, T4_CANON>(s, y, lt >> 2, lt & 3, wl, W, wshift);
     __syncthreads();
-    {  // round 1
-      const u32 c = lt & 3, j = (lt >> 2) & 7, h = lt >> 5;
-      const u32 s0 = (((64 * h + j) << 2) | c) ^ (h >> 1);
-      elt_t x[8];
-#pragma unroll
-      for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
-      t4_stages<O, 3, 3, false>(x, j, wl, W, wshift);
-#pragma unroll
-      for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
-    }
+    t4_round1<O, T4_CANON>(s, lt, wl, W, wshift);
     __syncthreads();
 #pragma unroll
-    for (u32 g = 0; g < 2; ++g) {  // round 2
-      const u32 e = lt + 512 * g, c = e & 3, h = e >> 8, j = (e >> 2) & 63;
-      const u32 s0 = (((256 * h + j) << 2) | c) ^ (2 * h);
-      elt_t x[4];
-#pragma unroll
-      for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (a >> 1)) + 256 * a]);
-      t4_stages<O, 6, 2, false>(x, j, wl, W, wshift);
-#pragma unroll
-      for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ (a >> 1)) + 256 * a], x[a]);
-    }
+    for (u32 g = 0; g < 2; ++g) t4_round2<O, T4_CANON>(s, lt + 512 * g, wl, W, wshift);
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);  // keeps round 2's and round 3's instructions apart: interleaved, they spill
     {  // round 3: both groups out of LDS first; after the barrier the tile's LDS belongs to the next tile's round 0 (one barrier
        // more per tile than fp_fft_tile_1024x4; this order needs fewer VGPRs than a barrier at the end of the loop)
       elt_t x[2][4];
 #pragma unroll
-      for (u32 g = 0; g < 2; ++g) {
-        const u32 e = lt + 512 * g, c = e & 3, j = e >> 2;
-        const u32 s0 = ((j << 2) | c) ^ (j >> 7);
-#pragma unroll
-        for (u32 a = 0; a < 4; ++a) x[g][a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
-      }
+      for (u32 g = 0; g < 2; ++g) t4_round3_load(x[g], s, lt + 512 * g);
       __syncthreads();
       elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
       const u32 dk = (u32)p.dk, dc = (u32)p.dc;
@@ -460,10 +460,10 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_persist(TilePlan p,
   }
 }
 
-// The 1024 x 4 tile with the inter-pass product on pass B's load side (n = 2^20, the default): same rounds, lane maps and LDS
-// layout as fp_fft_tile_1024x4, every offset inside a tile in 32 bits (the host keeps 1024 sk + 4 sc and 1024 dk + 4 dc below 2^32).
-//   pass A (KFAST_SRC = false): no table and no product.  1-D grid of ncb * rows workgroups in the XCD-aware tile order of
-//           fp_fft_tile_1024x4_persist (parts = rows): the workgroups of one XCD read adjacent 64-byte segments of the same rows.
+// The 1024 x 4 tile with the inter-pass product on pass B's load side (n = 2^20, the default): same rounds as fp_fft_tile_1024x4,
+// every offset inside a tile in 32 bits (the host keeps 1024 sk + 4 sc and 1024 dk + 4 dc below 2^32).
+//   pass A (KFAST_SRC = false): no table and no product.  1-D grid of ncb * rows workgroups in the XCD-aware tile order
+//           (t4_xcd_order, parts = rows): the workgroups of one XCD read adjacent 64-byte segments of the same rows.
 //   pass B (KFAST_SRC = true): what pass A wrote is laid out [j1][k2] like the full table tw[j1 * 1024 + k2], so thread (kb, c)
 //           loads w_n^(j1 k2) at the offset of its point (j1 = 4 bx + c, k2 = kb + 128 a'), coalesced, all 17 loads in flight
 //           before the first wait, and multiplies before round 0.  Row j1 = 0 and column k2 = 0 hold Montgomery 1: no branch.
@@ -489,15 +489,7 @@ __device__ __forceinline__ void fp_fft_tile_1024x4_tws_body(const TilePlan& p, c
     bx = row_fast ? blockIdx.y : blockIdx.x;
     by = row_fast ? blockIdx.x : blockIdx.y;
   } else {
-    const u32 ncb = p.nbatch >> 2, w = blockIdx.x;
-    if ((ncb & 7) == 0) {
-      const u32 per = ncb >> 3, i = w >> 3;
-      bx = (w & 7) * per + i % per;
-      by = i / per;
-    } else {
-      bx = w % ncb;
-      by = w / ncb;
-    }
+    t4_xcd_order(p.nbatch >> 2, blockIdx.x, bx, by);
   }
   {  // round 0
     const u32 c = KFAST_SRC ? tid >> 7 : tid & 3, kb = KFAST_SRC ? tid & 127 : tid >> 2;
@@ -518,41 +510,14 @@ __device__ __forceinline__ void fp_fft_tile_1024x4_tws_body(const TilePlan& p, c
 #pragma unroll
       for (u32 a = 0; a < 8; ++a) y[a] = T4Ops<O>::mul_tw(y[a], t[a]);
     }
-    elt_t x[8];
-#pragma unroll
-    for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];  // x[a] = y[bitrev3(a)]
-    t4_stages<O, 0, 3, true, LZ>(x, 0, wl, W, wshift);
-    const u32 b = __brev(kb) >> 25, s0 = ((b << 5) | c) ^ (b >> 4), s1 = ((b << 5) | 4 | c) ^ (b >> 4);
-#pragma unroll
-    for (u32 a = 0; a < 8; a += 2) {
-      st16(&s[s0 + 4 * a], x[a]);
-      st16(&s[s1 + 4 * a], x[a + 1]);
-    }
+    t4_round0<O, LZ>(s, y, kb, c, wl, W, wshift);
     st16(&wl[t4_wslot(tid)], wv);
   }
   __syncthreads();
-  {  // round 1
-    const u32 c = tid & 3, j = (tid >> 2) & 7, h = tid >> 5;
-    const u32 s0 = (((64 * h + j) << 2) | c) ^ (h >> 1);
-    elt_t x[8];
-#pragma unroll
-    for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
-    t4_stages<O, 3, 3, false, LZ>(x, j, wl, W, wshift);
-#pragma unroll
-    for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
-  }
+  t4_round1<O, LZ>(s, tid, wl, W, wshift);
   __syncthreads();
 #pragma unroll
-  for (u32 g = 0; g < 2; ++g) {  // round 2
-    const u32 e = tid + 512 * g, c = e & 3, h = e >> 8, j = (e >> 2) & 63;
-    const u32 s0 = (((256 * h + j) << 2) | c) ^ (2 * h);
-    elt_t x[4];
-#pragma unroll
-    for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (a >> 1)) + 256 * a]);
-    t4_stages<O, 6, 2, false, LZ>(x, j, wl, W, wshift);
-#pragma unroll
-    for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ (a >> 1)) + 256 * a], x[a]);
-  }
+  for (u32 g = 0; g < 2; ++g) t4_round2<O, LZ>(s, tid + 512 * g, wl, W, wshift);
   __syncthreads();
   {  // round 3
     elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
@@ -560,10 +525,8 @@ __device__ __forceinline__ void fp_fft_tile_1024x4_tws_body(const TilePlan& p, c
 #pragma unroll
     for (u32 g = 0; g < 2; ++g) {
       const u32 e = tid + 512 * g, c = e & 3, j = e >> 2;
-      const u32 s0 = ((j << 2) | c) ^ (j >> 7);
       elt_t x[4];
-#pragma unroll
-      for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+      t4_round3_load(x, s, e);
       t4_stages<O, 8, 2, false, LZ_OUT>(x, j, wl, W, wshift);
 #pragma unroll
       for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), x[a]);
@@ -660,13 +623,14 @@ static int set_lds_limit(lfgpu_ctx* c) {
       if (v == 12 || v == 13) c->tile_log = v;
     }
     LF_TRY(set_lds_limit_fp<Fp128Ops>(c));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4<Fp128Ops, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_persist<Fp128Ops>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws<Fp128Ops, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws<Fp128Ops, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    LF_HIP(c, hipFuncSetAttribute((const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+    const void* const t4[] = {(const void*)fp_fft_tile_1024x4<Fp128Ops, false, true>,
+                              (const void*)fp_fft_tile_1024x4<Fp128Ops, true, false>,
+                              (const void*)fp_fft_tile_1024x4_persist<Fp128Ops>,
+                              (const void*)fp_fft_tile_1024x4_tws<Fp128Ops, false>,
+                              (const void*)fp_fft_tile_1024x4_tws<Fp128Ops, true>,
+                              (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, false>,
+                              (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, true>};
+    for (const void* k : t4) LF_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
     LF_HIP(c, hipFuncSetAttribute((const void*)lch_fft_tile<1024>, hipFuncAttributeMaxDynamicSharedMemorySize, TILE_ELTS * 16));
@@ -692,15 +656,47 @@ static void launch_fp(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePlan& p, Ar
     else hipLaunchKernelGGL((fp_fft_tile<O, 512, false>), grid, dim3(512), lds, c->stream, p, args...);
   }
 }
+// The LFGPU_FP_* switches of K1, all read once per process, at the first transform.
+struct FpSwitches {
+  bool tile1024;    // LFGPU_FP_TILE1024 (default 1): 0 keeps every tile on the generic fp_fft_tile
+  int persist;      // LFGPU_FP_PERSIST (default 1): see launch_tile_1024x4_persist
+  int twside;       // LFGPU_FP_TWSIDE (default 1): see fp_twside_mode
+  bool other_plan;  // LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 is set at all, to whatever value
+  bool lazy;        // LFGPU_FP_LAZY (default 1): 0 launches fp_fft_tile_1024x4_tws_canon
+  bool two_level;   // LFGPU_FP_TW=2: the two-level inter-pass table
+  bool row_fast;    // LFGPU_FP_ROWFAST (default 1): 0 keeps pass A's tiles fastest in the grid
+};
+static const FpSwitches& fp_switches() {
+  static const FpSwitches sw = [] {
+    const auto num = [](const char* name, int dflt) { return getenv(name) ? atoi(getenv(name)) : dflt; };
+    FpSwitches w;
+    w.tile1024 = num("LFGPU_FP_TILE1024", 1) != 0;
+    w.persist = num("LFGPU_FP_PERSIST", 1);
+    w.twside = num("LFGPU_FP_TWSIDE", 1);
+    w.other_plan = getenv("LFGPU_FP_PERSIST") || getenv("LFGPU_FP_TILE1024");
+    w.lazy = num("LFGPU_FP_LAZY", 1) != 0;
+    w.two_level = num("LFGPU_FP_TW", 0) == 2;
+    w.row_fast = num("LFGPU_FP_ROWFAST", 1) != 0;
+    return w;
+  }();
+  return sw;
+}
+// Is the plan a tile of the 1024 x 4 kernels (pass B with kfast_src, pass A without)?  offsets32: also every offset inside a
+// tile, on the load and the store side, non-negative and in 32 bits, as _persist and _tws compute them.
+static bool tile_1024x4_fits(const TilePlan& p, bool kfast_src, bool offsets32) {
+  if (p.logT != 10 || p.logC != 2 || !p.wlds || p.kfast_src != (kfast_src ? 1u : 0u) || p.kfast_dst != 0 || (p.nbatch & 3) != 0) return false;
+  return !offsets32 || (p.sk >= 0 && p.sc >= 0 && p.dk >= 0 && p.dc >= 0 && (u64)p.sk * 1024 + (u64)p.sc * 4 <= 0xffffffffu &&
+                        (u64)p.dk * 1024 + (u64)p.dc * 4 <= 0xffffffffu);
+}
 // Pass A through fp_fft_tile_1024x4_persist.  LFGPU_FP_PERSIST: 0 = fp_fft_tile_1024x4 in the grid order of the caller, 1 (default)
 // = one tile per workgroup in the XCD-aware tile order, 2 = the tile loop on as many workgroups as the CUs hold at once (measured
 // slower than 1: 29.7 against 28.1 ms per bench.py step).  Returns false, launching nothing, for 0.
 template <class O>
 static bool launch_tile_1024x4_persist(lfgpu_ctx* c, u32 rows, size_t lds, const TilePlan& p, const elt_t* W, u32 wshift, const elt_t* tw) {
-  static const int mode = getenv("LFGPU_FP_PERSIST") ? atoi(getenv("LFGPU_FP_PERSIST")) : 1;
+  const int mode = fp_switches().persist;
   const u32 ncb = p.nbatch >> 2;
   u32 parts = rows;
-  if (mode <= 0 || (u64)p.sk * 1024 + (u64)p.sc * 4 > 0xffffffffu || (u64)p.dk * 1024 + (u64)p.dc * 4 > 0xffffffffu) return false;
+  if (mode <= 0 || !tile_1024x4_fits(p, false, true)) return false;
   if (mode >= 2) {
     static const int per_cu = [lds] {  // 2: LDS (2 x 72 KiB) and VGPRs (<= 128) both allow two workgroups per CU
       int n = 0;
@@ -719,15 +715,12 @@ static bool launch_tile_1024x4_persist(lfgpu_ctx* c, u32 rows, size_t lds, const
   return true;
 }
 // fp_fft_tile_1024x4 takes an Fp128 tile of 1024 x 4 in the 512-thread configuration; LFGPU_FP_TILE1024=0 keeps every tile on
-// the generic fp_fft_tile (read once)
-// (returns false, launching nothing, otherwise)
+// the generic fp_fft_tile (returns false, launching nothing, otherwise)
 template <class O, bool KFAST_SRC, bool TW>
 static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePlan& p, const elt_t* W, u32 wshift, const elt_t* tw,
                                u32 row_fast) {
-  static const bool on = !(getenv("LFGPU_FP_TILE1024") && atoi(getenv("LFGPU_FP_TILE1024")) == 0);
   if constexpr (std::is_same<O, Fp128Ops>::value) {
-    if (on && c->tile_log == 12 && p.logT == 10 && p.logC == 2 && p.wlds && p.kfast_src == (KFAST_SRC ? 1u : 0u) && p.kfast_dst == 0 &&
-        (p.nbatch & 3) == 0) {
+    if (fp_switches().tile1024 && c->tile_log == 12 && tile_1024x4_fits(p, KFAST_SRC, false)) {
       if constexpr (!KFAST_SRC && TW)
         if (launch_tile_1024x4_persist<O>(c, row_fast ? grid.x : grid.y, lds, p, W, wshift, tw)) return true;
       hipLaunchKernelGGL((fp_fft_tile_1024x4<O, KFAST_SRC, TW>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
@@ -739,13 +732,11 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
 // The pair fp_fft_tile_1024x4_tws (inter-pass product on pass B's load side): the default for Fp128 when both passes are 1024 x 4
 // tiles (n = 2^20) and the full table is in use.  LFGPU_FP_TWSIDE=0, or any setting of LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 (which
 // choose among the kernels of the other plan), keeps the product in pass A; =2 runs pass B with the rows fastest in the grid.
-// LFGPU_FP_LAZY=0 (read once) launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; it has
+// LFGPU_FP_LAZY=0 launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; it has
 // no effect where this plan is not taken.
 template <class O>
 static int fp_twside_mode(const lfgpu_ctx* c, u32 logn1, size_t rows, bool two_level) {
-  static const int mode = (getenv("LFGPU_FP_PERSIST") || getenv("LFGPU_FP_TILE1024")) ? 0
-                          : getenv("LFGPU_FP_TWSIDE")                                  ? atoi(getenv("LFGPU_FP_TWSIDE"))
-                                                                                       : 1;
+  const int mode = fp_switches().other_plan ? 0 : fp_switches().twside;
   if (!std::is_same<O, Fp128Ops>::value || two_level || c->tile_log != 12 || logn1 != 10 || rows > (0x7fffffffu >> 8)) return 0;
   return mode < 0 ? 0 : mode;
 }
@@ -755,15 +746,11 @@ static bool launch_tile_1024x4_tws(lfgpu_ctx* c, u32 rows, size_t lds, const Til
                                    u32 row_fast) {
   if constexpr (std::is_same<O, Fp128Ops>::value) {
     const u32 ncb = p.nbatch >> 2;
-    if (p.logT != 10 || p.logC != 2 || !p.wlds || p.kfast_src != (KFAST_SRC ? 1u : 0u) || p.kfast_dst != 0 || (p.nbatch & 3) != 0 ||
-        p.sk < 0 || p.sc < 0 || p.dk < 0 || p.dc < 0 || (u64)p.sk * 1024 + (u64)p.sc * 4 > 0xffffffffu ||
-        (u64)p.dk * 1024 + (u64)p.dc * 4 > 0xffffffffu || (u64)ncb * rows > 0x7fffffffu)
-      return false;
+    if (!tile_1024x4_fits(p, KFAST_SRC, true) || (u64)ncb * rows > 0x7fffffffu) return false;
     if (KFAST_SRC && (p.sk != 1 || p.sc != 1024 || p.src_tile != 4096)) return false;  // the table's layout [j1][k2]
     if (KFAST_SRC && (row_fast ? ncb : rows) > 65535) row_fast = !row_fast;
     const dim3 grid = !KFAST_SRC ? dim3(ncb * rows) : row_fast ? dim3(rows, ncb) : dim3(ncb, rows);
-    static const bool lazy = !(getenv("LFGPU_FP_LAZY") && atoi(getenv("LFGPU_FP_LAZY")) == 0);
-    if (lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    if (fp_switches().lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     else hipLaunchKernelGGL((fp_fft_tile_1024x4_tws_canon<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     return true;
   }
@@ -868,7 +855,7 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
   // Inter-pass twiddles w_n^(j1*k2): either the full [j1][k2] table (n elements, default: one product
   // per element, table slices stay in L2 because batch rows vary fastest in the grid) or, with LFGPU_FP_TW=2, the
   // two-level form lo[e & 1023] * hi[e >> 10] (2 KiB + n/64 bytes of tables, two products per element).
-  static const bool two_level = getenv("LFGPU_FP_TW") && atoi(getenv("LFGPU_FP_TW")) == 2;
+  const bool two_level = fp_switches().two_level;
   const size_t n1 = (size_t)1 << logn1, n2 = (size_t)1 << logn2;
   if (two_level) {
     LF_TRY(fp_two_level_tables<O>(c, wn, logn, key, &dlo, &dhi));
@@ -908,9 +895,8 @@ static int fp_fft_two_pass(lfgpu_ctx* c, const elt_t wn, u32 logn, size_t rows, 
     p.nbatch = (u32)n2;
     p.kfast_src = p.kfast_dst = 0;
     size_t lds = fp_lds_bytes(p);
-    static const bool row_fast_env = !(getenv("LFGPU_FP_ROWFAST") && atoi(getenv("LFGPU_FP_ROWFAST")) == 0);
     // rows fastest: the tile's table slice is reused by every row while it is hot
-    const u32 row_fast = (!two_level && rows <= 65535 && row_fast_env) ? 1u : 0u;
+    const u32 row_fast = (!two_level && rows <= 65535 && fp_switches().row_fast) ? 1u : 0u;
     const dim3 grid = row_fast ? dim3((u32)rows, (u32)(n2 >> p.logC)) : dim3((u32)(n2 >> p.logC), (u32)rows);
     if (twside) {
       if (!launch_tile_1024x4_tws<O, false>(c, (u32)rows, lds, p, (const elt_t*)dW, logTw - logn1, (const elt_t*)nullptr, 0u))

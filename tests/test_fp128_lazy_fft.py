@@ -10,15 +10,15 @@ A value in [p, 2^128) turns up with probability 2^-20 per intermediate on random
 A Python-integer model of one 1024-point transform of a tile under the kernel's policy counts what these inputs reach."""
 import functools
 import os
-import re
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import fft_isa
 import oracle_lib as ol
-from test_fp_tile_arith import FFT, P, R_INV, ROOT, SCC_READ, SCC_WRITE, _hipcc
+from test_fp_tile_arith import P, R_INV, ROOT
 from test_fp128_twside import EDGES, P_HI
 
 CHILD = os.path.join(ROOT, "tests", "fp_tile_child.py")
@@ -36,40 +36,18 @@ N = 1 << 20
 PAD = [0xDEADBEEFDEADBEEF, 0xFFFFFFFFFFFFFFFF]
 
 
-def test_lazy_kernels_isa(tmp_path):
+def test_lazy_kernels_isa():
     """No scratch, at most 128 VGPRs, every global load a dwordx4 and all of them issued before the first wait on vector memory;
     VALU counts pinned; no SCC reader of the compiler's after an SCC write inside an asm statement."""
-    out = tmp_path / "fft.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), FFT])
-    s = out.read_text()
     for k, (nloads, pinned) in KERNELS.items():
-        desc = s.split(".amdhsa_kernel " + k + "\n", 1)[1].split(".end_amdhsa_kernel", 1)[0]
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, k
-        assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 128, k
-        body = s.split("\n" + k + ":", 1)[1].split(".Lfunc_end", 1)[0]
-        lines = [l.strip() for l in body.splitlines()]
-        ops = [l.split()[0] for l in lines if l and not l.startswith((";", ".")) and not l.endswith(":")]
-        assert not any(op.startswith(("scratch_", "buffer_")) for op in ops), k
-        ins = [l for l in lines if l.startswith(("global_load", "s_waitcnt"))]
-        loads = [i for i, l in enumerate(ins) if l.startswith("global_load")]
-        assert len(loads) == nloads and all(ins[i].startswith("global_load_dwordx4") for i in loads), (k, ins)
-        assert not any(l.startswith("s_waitcnt") and "vmcnt" in l for l in ins[loads[0]:loads[-1]]), (k, ins)
-        valu = sum(op.startswith("v_") for op in ops)
+        fft_isa.assert_no_scratch_within_128_vgprs(k)
+        assert not any(op.startswith(("scratch_", "buffer_")) for op in fft_isa.kernel(k).ops), k
+        fft_isa.assert_global_loads(k, nloads)
+        fft_isa.assert_no_vmcnt_wait_among_loads(k)
+        valu = fft_isa.valu(k)
         print(k, "VALU", valu)
         assert valu <= pinned, (k, valu, pinned)
-        in_asm, last = False, None
-        for l in lines:
-            if l.startswith(";;#ASMSTART") or l.startswith(";;#ASMEND"):
-                in_asm = l.startswith(";;#ASMSTART")
-            elif l.endswith(":"):
-                last = None
-            elif l and not l.startswith((";", ".")):
-                op = l.split()[0]
-                if SCC_READ.match(op):
-                    assert last != "asm", (k, l)
-                if SCC_WRITE.match(op):
-                    last = "asm" if in_asm else "c"
+        fft_isa.assert_scc_clean(k)
 
 
 # ------------------------------------------------------------------ inputs

@@ -3,14 +3,13 @@ per-workgroup launches and the oracle.  LFGPU_FP_PERSIST is read once per proces
 its own (tests/fp_tile_child.py) on the same inputs: 0 = fp_fft_tile_1024x4 in the caller's grid order, unset = one tile per
 workgroup in the XCD-aware tile order (default), 2 = the tile loop."""
 import os
-import re
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import fft_isa
 import oracle_lib as ol
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -22,26 +21,13 @@ MONT_ONE = [0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFF]
 EDGES = [[0, 0], [1, 0], [0, P_HI], MONT_ONE, [0xFFFFFFFFFFFFFFFF, P_HI - 1], [0, 1 << 44]]
 
 
-def test_pass_a_persistent_isa(tmp_path):
+def test_pass_a_persistent_isa():
     """No scratch, at most 128 VGPRs (two 512-thread workgroups per CU), and the inter-pass twiddles loaded once per workgroup:
     the kernel holds 17 global loads in all (one stage twiddle, eight inter-pass twiddles, the eight tile loads of the loop),
     and the tile's eight are all issued before the loop's first wait on vector memory."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = tmp_path / "fft.s"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "longfellow-zk_amd", "csrc", "fft.hip")])
-    s = out.read_text()
-    desc = s.split(".amdhsa_kernel " + KERNEL + "\n", 1)[1].split(".end_amdhsa_kernel", 1)[0]
-    assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0
-    assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 128
-    body = s.split("\n" + KERNEL + ":", 1)[1].split(".Lfunc_end", 1)[0]
-    ins = [l.strip() for l in body.splitlines() if l.strip().startswith(("global_load", "s_waitcnt"))]
-    loads = [i for i, l in enumerate(ins) if l.startswith("global_load")]
-    assert len(loads) == 17 and all(ins[i].startswith("global_load_dwordx4") for i in loads), ins
-    tile = loads[-8:]
-    assert not any(l.startswith("s_waitcnt") and "vmcnt" in l for l in ins[tile[0]:tile[-1]]), ins
+    fft_isa.assert_no_scratch_within_128_vgprs(KERNEL)
+    fft_isa.assert_global_loads(KERNEL, 17)
+    fft_isa.assert_no_vmcnt_wait_among_loads(KERNEL, last=8)
 
 
 # (logn, rows, ld, direction): the flagship n = 2^20 both ways with 1, 2, 3 and 5 rows (3 and 5 split unevenly between the two

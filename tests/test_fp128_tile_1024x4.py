@@ -2,14 +2,13 @@
 the generic fp_fft_tile's and the oracle's.  LFGPU_FP_TILE1024 is read once per process, so each path runs in a child process
 of its own (tests/fp_tile_child.py) on the same inputs."""
 import os
-import re
-import shutil
 import subprocess
 import sys
 
 import numpy as np
 import pytest
 
+import fft_isa
 import oracle_lib as ol
 from oracle_lib import FP, P, arr, elt
 
@@ -23,24 +22,12 @@ MONT_ONE = [0xFFFFFFFFFFFFFFFF, 0xFFFFFFFFFFF]  # 2^128 mod p = 2^108 - 1
 EDGES = [[0, 0], [1, 0], [0, P_HI], MONT_ONE, [0xFFFFFFFFFFFFFFFF, P_HI - 1], [0, 1 << 44]]  # p - 1 = {0, P_HI}
 
 
-def test_tile_1024x4_isa(tmp_path):
+def test_tile_1024x4_isa():
     """Both instantiations compile for gfx950 without scratch, within 128 VGPRs (4 waves per SIMD, two 512-thread workgroups
     per CU) and with all eight tile loads (and the stage twiddle's) issued before the first wait on vector memory."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("no hipcc")
-    out = tmp_path / "fft.s"
-    subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), os.path.join(ROOT, "longfellow-zk_amd", "csrc", "fft.hip")])
-    s = out.read_text()
     for k in KERNELS:
-        desc = s.split(".amdhsa_kernel " + k + "\n", 1)[1].split(".end_amdhsa_kernel", 1)[0]
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, k
-        assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 128, k
-        body = s.split("\n" + k + ":", 1)[1].split(".Lfunc_end", 1)[0]
-        ins = [l.strip() for l in body.splitlines() if l.strip().startswith(("global_load", "s_waitcnt"))]
-        first_wait = next(i for i, l in enumerate(ins) if l.startswith("s_waitcnt") and "vmcnt" in l)
-        assert sum(l.startswith("global_load_dwordx4") for l in ins[:first_wait]) >= 8, (k, ins[:first_wait + 1])
+        fft_isa.assert_no_scratch_within_128_vgprs(k)
+        assert fft_isa.dwordx4_loads_before_first_vmcnt_wait(k) >= 8, (k, fft_isa.vm_stream(k)[0])
 
 
 # (logn, rows, ld, direction): n = 2^13 .. 2^23 both ways (pass B's tile from 2^13, pass A's as well at 2^20, both passes of

@@ -2,16 +2,15 @@
 Python integers and against fields.h's fp_mul / fp_add / fp_sub on the GPU, and the VALU instruction counts of the kernels
 that use it, pinned from the gfx950 ISA so that later edits cannot raise them unnoticed."""
 import os
-import re
-import shutil
 import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import fft_isa
+from fft_isa import FFT, ROOT, SCC_READ, SCC_WRITE, hipcc as _hipcc  # noqa: F401 (other test files import them from here)
+
 CHECK = os.path.join(ROOT, "tests", "fp_tile_arith_check.hip")
-FFT = os.path.join(ROOT, "longfellow-zk_amd", "csrc", "fft.hip")
 
 P = 2**128 - 2**108 + 1
 R_INV = pow(2**128, -1, P)
@@ -29,45 +28,12 @@ KERNELS = {
 }
 
 
-SCC_READ = re.compile(r"(s_cbranch_scc[01]|s_addc_u32|s_subb_u32|s_cselect_b(32|64)|s_cmov_b(32|64)|s_cmovk_i32)$")
-SCC_WRITE = re.compile(r"(s_cmp\w*|s_bitcmp\w*|s_add_[iu]32|s_addc_u32|s_sub_[iu]32|s_subb_u32|s_(and|or|xor|andn2|orn2|nand|nor|xnor|not)_\w+|"
-                       r"s_lshl\w*|s_lshr\w*|s_ashr\w*|s_bfe_\w+|s_min_\w+|s_max_\w+|s_abs\w*|s_bcnt\w*|s_quadmask\w*|s_wqm\w*)$")
-
-
-def _hipcc():
-    h = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(h):
-        pytest.skip("no hipcc")
-    return h
-
-
-def test_tile_kernels_valu_counts(tmp_path):
-    out = tmp_path / "fft.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), FFT])
-    s = out.read_text()
+def test_tile_kernels_valu_counts():
     for k, pinned in KERNELS.items():
-        desc = s.split(".amdhsa_kernel " + k + "\n", 1)[1].split(".end_amdhsa_kernel", 1)[0]
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, k
-        assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 128, k
-        body = s.split("\n" + k + ":", 1)[1].split(".Lfunc_end", 1)[0]
-        ops = [l.split()[0] for l in body.splitlines() if l.strip() and not l.strip().startswith((";", ".")) and not l.strip().endswith(":")]
-        valu = sum(op.startswith("v_") for op in ops)
+        fft_isa.assert_no_scratch_within_128_vgprs(k)
+        valu = fft_isa.valu(k)
         assert valu <= pinned, (k, valu, pinned)
-        # the SALU instructions inside the arithmetic's asm write SCC: no SCC reader of the compiler's may follow one of them
-        # without an SCC write of its own in between (the asm statements declare the clobber)
-        in_asm, last = False, None
-        for l in (l.strip() for l in body.splitlines()):
-            if l.startswith(";;#ASMSTART") or l.startswith(";;#ASMEND"):
-                in_asm = l.startswith(";;#ASMSTART")
-            elif l.endswith(":"):
-                last = None
-            elif l and not l.startswith((";", ".")):
-                op = l.split()[0]
-                if SCC_READ.match(op):
-                    assert last != "asm", (k, l)
-                if SCC_WRITE.match(op):
-                    last = "asm" if in_asm else "c"
+        fft_isa.assert_scc_clean(k)
 
 
 def _limbs(x):

@@ -13,13 +13,13 @@ mad wraps, and with column 3's second mad uncaptured as well (a1 b2: nothing bou
 GPU fpt_mul runs on the same structured pairs and on random ones, 2^20 in all; the VALU counts of the four 2^20-point tile kernels
 are pinned at the derived figures, 3 less per product than in test_fp128_lazy_fft.py."""
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_fp_tile_arith import EDGES, FFT, MONT_ONE, P, R_INV, ROOT, _hipcc
+import fft_isa
+from test_fp_tile_arith import EDGES, MONT_ONE, P, R_INV, ROOT, _hipcc
 from test_fp_tile_redc import M32, redc_model
 
 CHECK = os.path.join(ROOT, "tests", "fp_tile_mul_check.hip")
@@ -195,18 +195,9 @@ KERNELS = {
 }
 
 
-def test_tile_kernels_valu_after_dead_captures(tmp_path):
-    out = tmp_path / "fft.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), FFT])
-    s = out.read_text()
+def test_tile_kernels_valu_after_dead_captures():
     for k, pinned in KERNELS.items():
-        desc = s.split(".amdhsa_kernel " + k + "\n", 1)[1].split(".end_amdhsa_kernel", 1)[0]
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, k
-        assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 128, k
-        body = s.split("\n" + k + ":", 1)[1].split(".Lfunc_end", 1)[0]
-        lines = [l.strip() for l in body.splitlines()]
-        ops = [l.split()[0] for l in lines if l and not l.startswith((";", ".")) and not l.endswith(":")]
-        valu = sum(op.startswith("v_") for op in ops)
+        fft_isa.assert_no_scratch_within_128_vgprs(k)
+        valu = fft_isa.valu(k)
         print(k, "VALU", valu)
         assert valu <= pinned, (k, valu, pinned)

@@ -4,13 +4,13 @@ A word-by-word model of the asm on Python integers (the same words, carries and 
 a * b / 2^128 mod p on products and against T / 2^128 mod p on structured 256-bit T, with each of the step's five cases
 reached at least 100 times: U = 0, t0 mod 2^20 = 0 with U != 0, cy = 1, the + p fix taken and not taken.  The tile
 kernels' VALU counts are pinned from the gfx950 ISA, and on the GPU fpt_mul runs on inputs that reach every case."""
-import re
 import subprocess
 
 import numpy as np
 import pytest
 
-from test_fp_tile_arith import CHECK, EDGES, FFT, P, P_HI, R_INV, SCC_READ, SCC_WRITE, _hipcc, _limbs
+import fft_isa
+from test_fp_tile_arith import CHECK, EDGES, P, P_HI, R_INV, _hipcc, _limbs
 
 M32 = 2**32 - 1
 P3 = 0xFFFFF000  # p's top word
@@ -166,31 +166,10 @@ KERNELS = {
 }
 
 
-def test_tile_kernels_redc_isa(tmp_path):
-    out = tmp_path / "fft.s"
-    subprocess.check_call([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-unused-value", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", "-o", str(out), FFT])
-    s = out.read_text()
+def test_tile_kernels_redc_isa():
     for k, pinned in KERNELS.items():
-        desc = s.split(".amdhsa_kernel " + k + "\n", 1)[1].split(".end_amdhsa_kernel", 1)[0]
-        assert int(re.search(r"\.amdhsa_private_segment_fixed_size (\d+)", desc).group(1)) == 0, k
-        assert int(re.search(r"\.amdhsa_next_free_vgpr (\d+)", desc).group(1)) <= 128, k
-        body = s.split("\n" + k + ":", 1)[1].split(".Lfunc_end", 1)[0]
-        lines = [l.strip() for l in body.splitlines()]
-        ops = [l.split()[0] for l in lines if l and not l.startswith((";", ".")) and not l.endswith(":")]
-        valu = sum(op.startswith("v_") for op in ops)
+        fft_isa.assert_no_scratch_within_128_vgprs(k)
+        valu = fft_isa.valu(k)
         print(k, "VALU", valu)
         assert valu <= pinned, (k, valu, pinned)
-        # no SCC reader of the compiler's after an SCC write inside an asm statement without an SCC write of its own between
-        in_asm, last = False, None
-        for l in lines:
-            if l.startswith(";;#ASMSTART") or l.startswith(";;#ASMEND"):
-                in_asm = l.startswith(";;#ASMSTART")
-            elif l.endswith(":"):
-                last = None
-            elif l and not l.startswith((";", ".")):
-                op = l.split()[0]
-                if SCC_READ.match(op):
-                    assert last != "asm", (k, l)
-                if SCC_WRITE.match(op):
-                    last = "asm" if in_asm else "c"
+        fft_isa.assert_scc_clean(k)
