@@ -8,12 +8,11 @@
 //   round body              ProverLayers::layer / evaluations  lib/sumcheck/prover_layers.h:230-263,357-402
 //   binds                   Dense::bind, HQuad::bind_h         lib/arrays/dense.h:70-87, lib/sumcheck/hquad.h:90-123
 //   Ligero                  LigeroProver::commit / prove       lib/ligero/ligero_prover.h:58-146,171-351
-//   driver                  ZkProver::commit / prove, ZkCommon::verifier_constraints, ZkProof::write
-//                           lib/zk/zk_prover.h:72-188, lib/zk/zk_common.h:49-136,406-439, lib/zk/zk_proof.h:90-185
+//   driver                  ZkProver::commit (lib/zk/zk_prover.h:72-96) here; prove, verifier_constraints, ZkProof::write / read
+//                           and the verifier are csrc/zk_proto.h, instantiated with the policy P32 at the end of this file
 // Sums over many terms (run sums of bind_g, the QW scatter) add the 32-bit limbs of canonical residues into 64-bit integer
 // accumulators with atomics and reduce once (fp256_reduce_limbs): exact and independent of arrival order, as for Fp128.
-// Row extension and column hashing are csrc/p256.hip.  The verifier (ZkVerifier::verify, lib/zk/zk_verifier.h:68-94) is at
-// the end of the file.
+// Row extension and column hashing are csrc/p256.hip.
 #include <sched.h>
 
 #include <algorithm>
@@ -22,9 +21,7 @@
 #include <memory>
 #include <string>
 
-#include "fp256.h"
-#include "fs_crypto.h"
-#include "zkint.h"
+#include "zk_proto.h"  // F256 (the host field), the protocol layer and Wire32
 
 typedef elt32_t E;
 #define Z_THREADS 256
@@ -1107,40 +1104,6 @@ __global__ __launch_bounds__(Z_THREADS) void bind_gh_all256_kernel(size_t n, con
 inline u32 nblk(size_t n, u32 per = Z_THREADS) { return (u32)((n + per - 1) / per ? (n + per - 1) / per : 1); }
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-// ------------------------------------------------------------------ host field (FpGeneric over the P-256 prime)
-struct F256 {
-  E zero = e32_zero(), one, pts[3], invden[3], rsq;
-  F256() {
-    rsq = h256_rsq();
-    one = h256_of_scalar(1);
-    pts[0] = zero;  // poly_evaluation_points 0, 1, 2 (fp_generic.h:114-121)
-    pts[1] = one;
-    pts[2] = h256_of_scalar(2);
-    for (int i = 0; i < 3; ++i) {
-      E d = one;
-      for (int j = 0; j < 3; ++j)
-        if (j != i) d = fp256_mul(d, fp256_sub(pts[i], pts[j]));
-      invden[i] = h256_inv(d);
-    }
-  }
-  static E add(const E& a, const E& b) { return fp256_add(a, b); }
-  static E sub(const E& a, const E& b) { return fp256_sub(a, b); }
-  static E mul(const E& a, const E& b) { return fp256_mul(a, b); }
-  // Poly<3>::eval_monomial (lib/algebra/poly.h:100-108)
-  E eval_monomial(const E coef[3], const E& x) const { return add(mul(add(mul(coef[2], x), coef[1]), x), coef[0]); }
-  // the quadratic through (pts[i], ev[i]) at x = Poly<3>::eval_lagrange (poly.h:72-98)
-  E eval_lagrange(const E ev[3], const E& x) const {
-    E acc = zero;
-    for (int i = 0; i < 3; ++i) {
-      E num = one;
-      for (int j = 0; j < 3; ++j)
-        if (j != i) num = mul(num, sub(x, pts[j]));
-      acc = add(acc, mul(ev[i], mul(num, invden[i])));
-    }
-    return acc;
-  }
-};
-
 // ------------------------------------------------------------------ device steps
 int raw_eq2_256(lfgpu_ctx* c, const F256& F, size_t logn, size_t n, const E* G0, const E* G1, const E& alpha, E* d_eq) {
   if (n == 0) return LFGPU_OK;
@@ -1806,131 +1769,8 @@ int lig256_open(Lig256* L, const size_t* idx, E* req, uint8_t* nonces, uint8_t* 
 }
 }  // namespace
 
-// ------------------------------------------------------------------ ZkProver<Fp256Base>
-struct Zk256 {
-  lfgpu_ctx* c = nullptr;
-  const lfgpu_circuit* C = nullptr;
-  lfgpu_ligero_param param{};
-  size_t npub = 0, n_witness = 0, pad_size = 0;
-  struct LayerPad {  // Proof-shaped pad (zk_prover.h:152-188): hp[hand][2 round + {0, 1}] = {p(0), p(2)}, wc[2]
-    std::vector<E> hp[2];
-    E wc[2];
-  };
-  std::vector<LayerPad> pad, proof;
-  std::vector<E> aux;  // ProofAux::bound_quad per layer
-  std::vector<size_t> lqc;
-  Lig256* lp = nullptr;
-  uint8_t root[32] = {0};
-  std::vector<E> y_ldt, y_dot, y_q0, y_q2, req;
-  std::vector<uint8_t> nonces, path;
-  size_t npath = 0;
-  bool have_proof = false;
-  mutable std::vector<uint8_t> wire;  // ZkProof::write bytes of the held proof (zk256_proof_write fills it once)
-  mutable bool wire_valid = false;
-  std::vector<void*> d_in;  // the layers' inputs (eval_circuit), resident for the sumcheck
-  void* d_V = nullptr;
-  void* h_V = nullptr;  // pinned: outputs then the assert-zero flag
-  void* d_eq = nullptr;  // EQ table of the input constraint
-  double ms[6] = {0, 0, 0, 0, 0, 0};
-  // lfgpu_zk_prover_set_comm: a tableau of at least comm_min_bytes is committed with its rows sharded over the communicator's GPUs
-  bool have_comm = false;
-  lfgpu_comm_ops comm{};
-  size_t comm_min_bytes = 0;
-  ~Zk256() {
-    delete lp;
-    // the layers' wire values are functions of the witness: scrubbed before the memory goes back to the allocator (as the
-    // tableau is, Lig256), and so are the host copies of the pads
-    for (size_t l = 0; l < d_in.size(); ++l)
-      if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, C->layers[l].nw * 32, c->stream);
-    if (d_V) (void)hipMemsetAsync(d_V, 0, C->info.nv * 32, c->stream);
-    if (d_eq) (void)hipMemsetAsync(d_eq, 0, C->info.ninputs * 32, c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    for (void* p : d_in)
-      if (p) (void)hipFree(p);
-    if (d_V) (void)hipFree(d_V);
-    if (d_eq) (void)hipFree(d_eq);
-    if (h_V) {
-      memset(h_V, 0, C->info.nv * 32 + 16);
-      (void)hipHostFree(h_V);
-    }
-    for (auto& P : pad) {
-      for (auto& v : P.hp) std::fill(v.begin(), v.end(), E{});
-      P.wc[0] = P.wc[1] = E{};
-    }
-  }
-};
-
+// ------------------------------------------------------------------ the Fp256Base policy
 namespace {
-constexpr size_t kMaxBindings256 = 40;  // Proof::kMaxBindings (lib/sumcheck/circuit.h:84)
-inline size_t layer_size256(size_t logw) { return 4 * logw + 3; }  // PadLayout::layer_size (zk_common.h:210-222)
-
-struct Ts256 {  // the caller's transcript seen through the hooks
-  const lfgpu_transcript_ops* o;
-  void* u;
-  void write_bytes(const uint8_t* d, size_t n) const { o->write_bytes(u, d, n); }
-  void write_elt(const E& e) const {
-    uint8_t b[32];
-    h256_to_bytes(e, b);
-    o->write_elt_sized(u, b, 32);
-  }
-  void write_array(const E* e, size_t n) const {
-    std::vector<uint8_t> b(32 * (n ? n : 1));
-    for (size_t i = 0; i < n; ++i) h256_to_bytes(e[i], &b[32 * i]);
-    o->write_elt_array_sized(u, b.data(), n, 32);
-  }
-  E elt() const {
-    return h256_sample([&](uint8_t* b, size_t n) { o->gen_bytes(u, b, n); });
-  }
-  size_t nat(size_t n) const {  // RandomEngine::nat (lib/random/random.h:57-87)
-    size_t l = 0, mask = 0;
-    for (size_t nn = n; nn; nn >>= 8) ++l;
-    while ((n & mask) != n) mask = (mask << 1) | 1;
-    for (;;) {
-      uint8_t b[8] = {0};
-      o->gen_bytes(u, b, l);
-      size_t r = 0;
-      for (size_t i = 0; i < l; ++i) r |= (size_t)b[i] << (8 * i);
-      r &= mask;
-      if (r < n) return r;
-    }
-  }
-  void choose(size_t n, size_t k, size_t* res) const {  // RandomEngine::choose (:89-105)
-    std::vector<size_t> A(n);
-    for (size_t i = 0; i < n; ++i) A[i] = i;
-    for (size_t i = 0; i < k; ++i) {
-      const size_t j = i + nat(n - i);
-      std::swap(A[i], A[j]);
-      res[i] = A[i];
-    }
-  }
-};
-
-struct Round256 {  // round_h of the padded prover (prover_layers.h:320-329): transmit poly - pad
-  const Ts256* tst;
-  const Zk256::LayerPad* pad;
-  Zk256::LayerPad* out;
-};
-void zk256_round_cb(void* user, size_t hand, size_t rnd, const E ev[3], E* chal) {
-  Round256* r = (Round256*)user;
-  const E t0 = fp256_sub(ev[0], r->pad->hp[hand][2 * rnd]), t2 = fp256_sub(ev[2], r->pad->hp[hand][2 * rnd + 1]);
-  r->out->hp[hand][2 * rnd] = t0;
-  r->out->hp[hand][2 * rnd + 1] = t2;
-  r->tst->write_elt(t0);
-  r->tst->write_elt(t2);
-  *chal = r->tst->elt();
-}
-
-// ZkCommon::verifier_constraints (zk_common.h:49-136) + input_constraint (:406-439) on the prover's side (aux = the bound
-// quads the sumcheck recorded): the sparse rows of A, b, and the EQ vector of the input constraint on the device
-struct LinTerm256 {
-  size_t c, w;
-  E k;
-};
-struct Constraints256 {
-  std::vector<LinTerm256> a;
-  std::vector<E> b;
-  size_t n = 0;
-};
 int bind_gh_all256(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, const E* G1, const E& alpha, const E& beta, size_t logw, size_t nw, const E* H0,
                    const E* H1, E* out) {
   lfgpu_ctx* c = q->c;
@@ -1955,134 +1795,122 @@ int bind_gh_all256(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, const
   return LFGPU_OK;
 }
 
-// aux = the bound quads the prover's sumcheck recorded, or nullptr (verifier): Quad::bind_gh_all on the device per layer
-int build_constraints256(lfgpu_ctx* c, const lfgpu_circuit* C, const F256& F, const Ts256& ts, const std::vector<Zk256::LayerPad>& proof,
-                         const std::vector<E>* aux, const E* pub, E* d_eq, Constraints256& out) {
-  const lfgpu_circuit_info& I = C->info;
-  const size_t nl = C->layers.size(), npub = I.npub_in;
-  std::vector<E> gh[2], G[2];
-  for (size_t i = 0; i < kMaxBindings256; ++i) (void)ts.elt();  // begin_circuit: Q (unused for logc = 0), then G
-  G[0].resize(kMaxBindings256);
-  for (size_t i = 0; i < kMaxBindings256; ++i) G[0][i] = ts.elt();
-  G[1] = G[0];
-  size_t logv = I.logv;
-  size_t ci = 0, pi = I.ninputs - npub;
-  E claims[2] = {F.zero, F.zero};
-  std::vector<E> sym;
-  for (size_t ly = 0; ly < nl; ++ly) {
-    const size_t logw = C->layers[ly].logw;
-    const E alpha = ts.elt(), beta = ts.elt();
-    const size_t n = 3 + layer_size256(logw);
-    E known = F.zero;
-    sym.assign(n, F.zero);
-    auto axpy = [&](size_t var, const E& kv, const E& k) {  // Expression::axpy
-      known = F.add(known, F.mul(k, kv));
-      sym[var] = F.add(sym[var], k);
-    };
-    auto axmy = [&](size_t var, const E& kv, const E& k) {  // Expression::axmy
-      known = F.sub(known, F.mul(k, kv));
-      sym[var] = F.sub(sym[var], k);
-    };
-    axpy(0, claims[0], F.one);  // ConstraintBuilder::first
-    axpy(1, claims[1], alpha);
-    gh[0].assign(logw ? logw : 1, F.zero);
-    gh[1].assign(logw ? logw : 1, F.zero);
-    const auto& P = proof[ly];
-    for (size_t rnd = 0; rnd < logw; ++rnd)
-      for (int hand = 0; hand < 2; ++hand) {
-        const size_t r = 2 * rnd + hand;
-        const E t0e = P.hp[hand][2 * rnd], t2e = P.hp[hand][2 * rnd + 1];
-        ts.write_elt(t0e);
-        ts.write_elt(t2e);
-        const E chal = ts.elt();
-        gh[hand][rnd] = chal;
-        E lag[3];  // dot_interpolation: p(chal) = sum_i lag[i] p(P_i)
-        for (int i = 0; i < 3; ++i) {
-          E num = F.one;
-          for (int j = 0; j < 3; ++j)
-            if (j != i) num = F.mul(num, F.sub(chal, F.pts[j]));
-          lag[i] = F.mul(num, F.invden[i]);
-        }
-        axmy(3 + 2 * r, t0e, F.one);   // ConstraintBuilder::next: p(1) = claim - p(0)
-        known = F.mul(known, lag[1]);  // scale
-        for (auto& s : sym)
-          if (!e32_is_zero(s)) s = F.mul(s, lag[1]);
-        axpy(3 + 2 * r, t0e, lag[0]);
-        axpy(3 + 2 * r + 1, t2e, lag[2]);
-      }
-    E eqq;  // EQ[Q,C] QUAD[R,L] (Eq::eval with logc = 0 is 1)
-    if (aux) eqq = (*aux)[ly];
-    else LF_TRY(bind_gh_all256(C->layers[ly].q, F, logv, G[0].data(), G[1].data(), alpha, beta, logw, C->layers[ly].nw, gh[0].data(), gh[1].data(), &eqq));
-    const size_t cp = 3 + 4 * logw, skip = ly == 0 ? 3 : 0;  // ConstraintBuilder::finalize
-    out.b.push_back(F.sub(F.mul(eqq, F.mul(P.wc[0], P.wc[1])), known));
-    sym[cp] = F.sub(sym[cp], F.mul(eqq, P.wc[1]));
-    sym[cp + 1] = F.sub(sym[cp + 1], F.mul(eqq, P.wc[0]));
-    sym[cp + 2] = F.sub(sym[cp + 2], eqq);
-    for (size_t i = skip; i < n; ++i) out.a.push_back({ci, pi + i - 3, sym[i]});
-    ++ci;
-    ts.write_array(P.wc, 2);
-    claims[0] = P.wc[0];
-    claims[1] = P.wc[1];
-    for (int h = 0; h < 2; ++h) {
-      G[h].assign(kMaxBindings256, F.zero);
-      for (size_t r = 0; r < logw; ++r) G[h][r] = gh[h][r];
-    }
-    logv = logw;
-    pi += layer_size256(logw);
+// Wire32 (zk_proto.h) plus the device steps of this file
+struct P32 : zkp::Wire32 {
+  using Lig = Lig256;
+  using Layer = lfgpu_circuit::Layer;
+  static constexpr const char* kProveName = "zk256_prove";
+  static F256 host_field(lfgpu_ctx*) { return F256(); }
+  static constexpr bool kDeferGh = false;  // Quad::bind_gh_all synchronises per layer
+  static int eval_layer(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail) { return lf256_eval_quad_async(q, d_W, d_V, d_fail); }
+  static int sumcheck_layer(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, const E* G1, const E& alpha, const E& beta, size_t logw, size_t nw,
+                            void* d_W, const E wc_in[2], round256_fn round, void* user, E wc_out[2], E* g_out, E* bound_quad) {
+    return sumcheck_layer256(q, F, logv, G0, G1, alpha, beta, logw, nw, (const E*)d_W, wc_in, round, user, wc_out, g_out, bound_quad);
   }
-  const E alpha = ts.elt();
-  out.a.push_back({ci, pi - 3, F.sub(F.zero, F.one)});  // input_constraint: -1, -alpha on the input layer's claim pads
-  out.a.push_back({ci, pi - 2, F.sub(F.zero, alpha)});
-  out.n = ci + 1;
-  const size_t logn = C->layers[nl - 1].logw;
-  LF_TRY(raw_eq2_256(c, F, logn, I.ninputs, gh[0].data(), gh[1].data(), alpha, d_eq));
-  std::vector<E> eq_in(npub ? npub : 1);
-  if (npub) LF_TRY(lfgpu_memcpy_d2h(c, eq_in.data(), d_eq, npub * 32));
-  const auto& P = proof[nl - 1];
-  E pub_binding = F.zero;
-  for (size_t i = 0; i < npub; ++i) pub_binding = F.add(pub_binding, F.mul(eq_in[i], pub[i]));
-  out.b.push_back(F.sub(F.add(P.wc[0], F.mul(alpha, P.wc[1])), pub_binding));
-  return LFGPU_OK;
-}
-
-// LigeroCommon::inner_product_vector (ligero_param.h:382-421), host share: the sparse terms of A as (flat index, value),
-// sorted with duplicates folded (the dense private-input block is built on the device)
-void inner_product_sparse256(const F256& F, const lfgpu_ligero_param& p, const Constraints256& cs, const std::vector<E>& alphal, const std::vector<size_t>& lqc,
-                             const std::vector<E>& alphaq, std::vector<uint64_t>& idx, std::vector<E>& val) {
-  std::vector<std::pair<uint64_t, E>> t;
-  t.reserve(cs.a.size() + 6 * p.nq);
-  for (const LinTerm256& l : cs.a) t.emplace_back((uint64_t)l.w, F.mul(l.k, alphal[l.c]));
-  const size_t base = p.nwrow * p.w;
-  const size_t Ax = base, Ay = base + p.nqtriples * p.w, Az = base + 2 * p.nqtriples * p.w;
-  for (size_t iw = 0; iw < p.nq; ++iw) {
-    const size_t off[3] = {Ax + iw, Ay + iw, Az + iw};
-    for (int j = 0; j < 3; ++j) {
-      const E aq = alphaq[3 * iw + j];
-      t.emplace_back((uint64_t)off[j], aq);
-      t.emplace_back((uint64_t)lqc[3 * iw + j], F.sub(F.zero, aq));
-    }
+  static int bind_gh_all(lfgpu_ctx*, const F256& F, const Layer& L, size_t logv, const E* G0, const E* G1, const E& alpha, const E& beta, const E* H0,
+                         const E* H1, E* out) {
+    return bind_gh_all256(L.q, F, logv, G0, G1, alpha, beta, L.logw, L.nw, H0, H1, out);
   }
-  std::stable_sort(t.begin(), t.end(), [](const std::pair<uint64_t, E>& a, const std::pair<uint64_t, E>& b) { return a.first < b.first; });
-  idx.clear();
-  val.clear();
-  for (const auto& e : t) {
-    if (!idx.empty() && idx.back() == e.first) val.back() = F.add(val.back(), e.second);
-    else {
-      idx.push_back(e.first);
-      val.push_back(e.second);
-    }
+  // EQ(H0, i) + alpha EQ(H1, i), i < n, into d_eq; its first npub entries back to the host
+  static int eq_table(lfgpu_ctx* c, const F256& F, size_t logn, size_t n, const E* H0, const E* H1, const E& alpha, E* d_eq, size_t npub, E* eq_in) {
+    LF_TRY(raw_eq2_256(c, F, logn, n, H0, H1, alpha, d_eq));
+    if (npub) LF_TRY(lfgpu_memcpy_d2h(c, eq_in, d_eq, npub * 32));
+    return LFGPU_OK;
   }
-}
+  static int low_degree(Lig* lp, const E* u, E* y) { return lig256_low_degree(lp, u, y); }
+  static int dot(Lig* lp, const E* d_dense, size_t ndense, const E& scale, const uint64_t* idx, const E* val, size_t nsparse, E* y) {
+    return lig256_dot(lp, d_dense, ndense, scale, idx, val, nsparse, y);
+  }
+  static int quadratic(Lig* lp, const E* u, E* y0, E* y2) { return lig256_quadratic(lp, u, y0, y2); }
+  static int open(Lig* lp, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t cap, size_t* npath) {
+    return lig256_open(lp, idx, req, nonces, path, cap, npath);
+  }
+  static size_t verifier_bytes(const lfgpu_circuit_info& I, const lfgpu_ligero_param& p) {
+    return (I.ninputs + (p.nwqrow + 3) * p.block_enc + (p.nwqrow + 3) * p.nreq) * 32 + 256;
+  }
+  // LigeroVerifier: rows [0, nwqrow) = [0^r | A_i] (inner_product_vector + layout_Aext), then y_ldt, y_dot, y_quad, extended
+  // to block_enc; ext = those rows at the opened columns.  The verifier's device buffer (lf_scratch4, verifier_bytes) is
+  // EQ table of the input constraint | the rows | the gathered columns.
+  static int verifier_ext(lfgpu_ctx* c, const F256&, const lfgpu_circuit_info& I, const lfgpu_ligero_param& p, const E* d_eq, const E& scale,
+                          const std::vector<uint64_t>& a_idx, const std::vector<E>& a_val, const zkp::ProofBody<E>& pr, const size_t* idx, std::vector<E>& ext) {
+    const size_t nrows_dev = p.nwqrow + 3, ld = p.block_enc, n_witness = I.ninputs - I.npub_in;
+    E* d_T = (E*)d_eq + I.ninputs;
+    E* d_req = d_T + nrows_dev * ld;
+    LF_HIP(c, hipMemset2DAsync(d_T, ld * 32, 0, p.dblock * 32, nrows_dev, c->stream));
+    hipLaunchKernelGGL(a_rows_dense256_kernel, dim3(nblk(n_witness)), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, scale, d_eq + I.npub_in, n_witness, d_T);
+    if (!a_idx.empty()) {
+      void* d_sp = nullptr;
+      LF_TRY(lf_scratch2(c, a_idx.size() * 40 + 64, &d_sp));
+      E* d_val = (E*)d_sp;
+      u64* d_idx = (u64*)(d_val + a_idx.size());
+      LF_HIP(c, hipMemcpyAsync(d_val, a_val.data(), a_idx.size() * 32, hipMemcpyHostToDevice, c->stream));
+      LF_HIP(c, hipMemcpyAsync(d_idx, a_idx.data(), a_idx.size() * 8, hipMemcpyHostToDevice, c->stream));
+      hipLaunchKernelGGL(a_rows_sparse256_kernel, dim3(nblk(a_idx.size())), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, (const u64*)d_idx, (const E*)d_val,
+                         a_idx.size(), d_T);
+    }
+    LF_HIP(c, hipGetLastError());
+    LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 0) * ld, pr.y_ldt.data(), p.block * 32, hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 1) * ld, pr.y_dot.data(), p.dblock * 32, hipMemcpyHostToDevice, c->stream));
+    E* yq = d_T + (p.nwqrow + 2) * ld;  // y_quad = y_quad_0 | 0^w | y_quad_2
+    LF_HIP(c, hipMemcpyAsync(yq, pr.y_q0.data(), p.r * 32, hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipMemcpyAsync(yq + p.block, pr.y_q2.data(), (p.dblock - p.block) * 32, hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipStreamSynchronize(c->stream));  // the staging area is the Reed-Solomon encoder's work space next
+    LF_TRY(lfgpu_fp256_rs_encode_rows(c, p.nwqrow + 1, p.block, p.block_enc, d_T, ld));             // A rows and y_ldt
+    LF_TRY(lfgpu_fp256_rs_encode_rows(c, 2, p.dblock, p.block_enc, d_T + (p.nwqrow + 1) * ld, ld));  // y_dot, y_quad
+    void* di = nullptr;
+    LF_TRY(lf_scratch2(c, p.nreq * 8 + 64, &di));
+    std::vector<u64> ix(idx, idx + p.nreq);
+    LF_HIP(c, hipMemcpyAsync(di, ix.data(), p.nreq * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(gather_columns256_kernel, dim3(nblk(nrows_dev * p.nreq)), dim3(Z_THREADS), 0, c->stream, (u32)nrows_dev, ld, p.dblock, (const E*)d_T,
+                       (const u64*)di, (u32)p.nreq, d_req);
+    LF_HIP(c, hipGetLastError());
+    LF_HIP(c, hipStreamSynchronize(c->stream));
+    ext.resize(nrows_dev * p.nreq);
+    return lfgpu_memcpy_d2h(c, ext.data(), d_req, ext.size() * 32);
+  }
+};
 }  // namespace
+
+// ------------------------------------------------------------------ ZkProver<Fp256Base>
+struct Zk256 {
+  lfgpu_ctx* c = nullptr;
+  const lfgpu_circuit* C = nullptr;
+  zkp::ProverState<P32> st;  // pads, the held proof, its wire bytes, timings
+  Lig256* lp = nullptr;
+  std::vector<void*> d_in;  // the layers' inputs (eval_circuit), resident for the sumcheck
+  void* d_V = nullptr;
+  void* h_V = nullptr;  // pinned: outputs then the assert-zero flag
+  void* d_eq = nullptr;  // EQ table of the input constraint
+  // lfgpu_zk_prover_set_comm: a tableau of at least comm_min_bytes is committed with its rows sharded over the communicator's GPUs
+  bool have_comm = false;
+  lfgpu_comm_ops comm{};
+  size_t comm_min_bytes = 0;
+  ~Zk256() {
+    delete lp;
+    // the layers' wire values are functions of the witness: scrubbed before the memory goes back to the allocator (as the
+    // tableau is, Lig256; the host copies of the pads: ~ProverState)
+    for (size_t l = 0; l < d_in.size(); ++l)
+      if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, C->layers[l].nw * 32, c->stream);
+    if (d_V) (void)hipMemsetAsync(d_V, 0, C->info.nv * 32, c->stream);
+    if (d_eq) (void)hipMemsetAsync(d_eq, 0, C->info.ninputs * 32, c->stream);
+    (void)hipStreamSynchronize(c->stream);
+    for (void* p : d_in)
+      if (p) (void)hipFree(p);
+    if (d_V) (void)hipFree(d_V);
+    if (d_eq) (void)hipFree(d_eq);
+    if (h_V) {
+      memset(h_V, 0, C->info.nv * 32 + 16);
+      (void)hipHostFree(h_V);
+    }
+  }
+};
 
 int zk256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, Zk256** out) {
   std::unique_ptr<Zk256> z(new Zk256());
   z->c = c;
   z->C = C;
-  z->npub = C->info.npub_in;
-  z->n_witness = C->info.ninputs - C->info.npub_in;
-  for (const auto& l : C->layers) z->pad_size += layer_size256(l.logw);
-  LF_TRY(lfgpu_ligero_param_init(&z->param, LFGPU_FIELD_P256, 0, z->n_witness + z->pad_size, C->info.nl, rateinv, nreq, block_enc));
+  z->st.init(C);
+  LF_TRY(lfgpu_ligero_param_init(&z->st.param, LFGPU_FIELD_P256, 0, z->st.n_witness + z->st.pad_size, C->info.nl, rateinv, nreq, block_enc));
   LF_HIP(c, hipSetDevice(c->device));
   z->d_in.assign(C->layers.size(), nullptr);
   for (size_t l = 0; l < C->layers.size(); ++l)
@@ -2094,7 +1922,7 @@ int zk256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq,
   return LFGPU_OK;
 }
 int zk256_param(const Zk256* z, lfgpu_ligero_param* p) {
-  *p = z->param;
+  *p = z->st.param;
   return LFGPU_OK;
 }
 void zk256_set_comm(Zk256* z, const lfgpu_comm_ops* comm, size_t min_tableau_bytes) {
@@ -2104,7 +1932,7 @@ void zk256_set_comm(Zk256* z, const lfgpu_comm_ops* comm, size_t min_tableau_byt
 }
 void zk256_free(Zk256* z) { delete z; }
 int zk256_timings(const Zk256* z, double ms[6]) {
-  memcpy(ms, z->ms, sizeof(z->ms));
+  memcpy(ms, z->st.ms, sizeof(z->st.ms));
   return LFGPU_OK;
 }
 
@@ -2121,486 +1949,65 @@ int zk256_commit(Zk256* z, const void* h_W, lfgpu_rng_fn rng, void* rng_user, co
   lfgpu_ctx* c = z->c;
   LF_TRY(ts256_ok(c, ts));
   const double t0 = now_ms();
-  const lfgpu_circuit* C = z->C;
-  const size_t nl = C->layers.size();
+  auto& st = z->st;
+  const size_t nl = z->C->layers.size();
   LF_HIP(c, hipSetDevice(c->device));
-  std::vector<E> pads(z->pad_size - nl);  // every element fill_pad draws (the product wc0 * wc1 is computed), in order
+  std::vector<E> pads(st.pad_size - nl);  // every element fill_pad draws (the product wc0 * wc1 is computed), in order
   LF_SCRUB_ON_EXIT(pads);
   if (c->rng_exact) for (size_t i = 0; i < pads.size(); ++i) h256_sample_many(&pads[i], 1, [&](uint8_t* b, size_t n) { rng(rng_user, b, n); });
   else h256_sample_many(pads.data(), pads.size(), [&](uint8_t* b, size_t n) { rng(rng_user, b, n); });
   size_t pd = 0;
   auto draw = [&] { return pads[pd++]; };
-  std::vector<E> Wv(z->param.nw);  // witness || pads
+  std::vector<E> Wv(st.param.nw);  // witness || pads
   LF_SCRUB_ON_EXIT(Wv);
-  memcpy(Wv.data(), (const E*)h_W + z->npub, z->n_witness * 32);
-  z->pad.assign(nl, {});
-  z->lqc.assign(3 * nl, 0);
-  size_t pi = z->n_witness;
-  for (size_t ly = 0; ly < nl; ++ly) {  // fill_pad (zk_prover.h:152-188, logc = 0)
-    const size_t logw = C->layers[ly].logw;
-    auto& P = z->pad[ly];
-    P.hp[0].resize(2 * logw);
-    P.hp[1].resize(2 * logw);
-    size_t w = pi;
-    for (size_t j = 0; j < logw; ++j)
-      for (int h = 0; h < 2; ++h) {
-        P.hp[h][2 * j] = draw();
-        P.hp[h][2 * j + 1] = draw();
-        Wv[w++] = P.hp[h][2 * j];
-        Wv[w++] = P.hp[h][2 * j + 1];
-      }
-    P.wc[0] = draw();
-    P.wc[1] = draw();
-    Wv[w++] = P.wc[0];
-    Wv[w++] = P.wc[1];
-    Wv[w++] = fp256_mul(P.wc[0], P.wc[1]);
-    const size_t cp = pi + 4 * logw;  // setup_lqc (zk_common.h:149-160)
-    z->lqc[3 * ly] = cp;
-    z->lqc[3 * ly + 1] = cp + 1;
-    z->lqc[3 * ly + 2] = cp + 2;
-    pi += layer_size256(logw);
-  }
-  if (pi != z->param.nw) return lf_fail(c, LFGPU_ERR_ASSERT, "zk256_commit: witness layout");
+  memcpy(Wv.data(), (const E*)h_W + st.npub, st.n_witness * 32);
+  static const F256 F;  // (for fill_pad's wc0 * wc1: the constants are built once)
+  const size_t pi = zkp::pad_layout<P32>(F, z->C, st.n_witness, st.lqc, draw, &st.pad, Wv.data());
+  if (pi != st.param.nw) return lf_fail(c, LFGPU_ERR_ASSERT, "zk256_commit: witness layout");
   if (draws_only) {
-    std::vector<E> H(z->param.nrow * z->param.dblock);
+    std::vector<E> H(st.param.nrow * st.param.dblock);
     LF_SCRUB_ON_EXIT(H);
-    std::vector<uint8_t> nz(32 * z->param.block_ext);
+    std::vector<uint8_t> nz(32 * st.param.block_ext);
     char err[256] = {0};
-    const int rc = lig256_layout(z->param, Wv.data(), z->lqc.data(), rng, rng_user, H.data(), nz.data(), err, c->rng_exact != 0);
+    const int rc = lig256_layout(st.param, Wv.data(), st.lqc.data(), rng, rng_user, H.data(), nz.data(), err, c->rng_exact != 0);
     return rc ? lf_fail(c, rc, "%s", err) : LFGPU_OK;
   }
   delete z->lp;
   z->lp = nullptr;
-  z->have_proof = false;
-  z->wire_valid = false;
-  const bool shard_rows = z->have_comm && z->comm.world > 1 && z->param.nrow * z->param.block_enc * 32 >= z->comm_min_bytes;
-  LF_TRY(lig256_commit(c, z->param, Wv.data(), z->lqc.data(), rng, rng_user, z->root, &z->lp, shard_rows ? &z->comm : nullptr));
-  ts->write_bytes(ts->user, z->root, 32);  // LigeroTranscript::write_commitment
-  if (root_out) memcpy(root_out, z->root, 32);
-  z->ms[0] = now_ms() - t0;
+  st.have_proof = false;
+  st.wire_valid = false;
+  const bool shard_rows = z->have_comm && z->comm.world > 1 && st.param.nrow * st.param.block_enc * 32 >= z->comm_min_bytes;
+  LF_TRY(lig256_commit(c, st.param, Wv.data(), st.lqc.data(), rng, rng_user, st.proof.root, &z->lp, shard_rows ? &z->comm : nullptr));
+  ts->write_bytes(ts->user, st.proof.root, 32);  // LigeroTranscript::write_commitment
+  if (root_out) memcpy(root_out, st.proof.root, 32);
+  st.ms[0] = now_ms() - t0;
   return LFGPU_OK;
 }
 
-// ZkProver::prove (zk_prover.h:98-149)
+// ZkProver::prove (zk_prover.h:98-149), ZkProof::write (zk_proof.h:90-185), ZkVerifier::verify (zk_verifier.h:68-94): zk_proto.h
 int zk256_prove(Zk256* z, const void* h_W, const lfgpu_transcript_ops* tso, int* ok) {
-  lfgpu_ctx* c = z->c;
-  LF_TRY(ts256_ok(c, tso));
-  if (!z->lp) return lf_fail(c, LFGPU_ERR_ARG, "zk256_prove: must run commit before prove");
-  const double t_start = now_ms();
-  const lfgpu_circuit* C = z->C;
-  const lfgpu_circuit_info& I = C->info;
-  const size_t nl = C->layers.size();
-  const E* W = (const E*)h_W;
-  const F256 F;
-  const Ts256 ts{tso, tso->user};
-  *ok = 0;
-  z->have_proof = false;
-  z->wire_valid = false;
-  LF_HIP(c, hipSetDevice(c->device));
-
-  // eval_circuit (prover_layers.h:52-104): all layers back to back while the host hashes the Fiat-Shamir preamble
-  double t0 = now_ms();
-  const E* V = (const E*)z->h_V;
-  const int* failed = (const int*)((const uint8_t*)z->h_V + I.nv * 32);
-  {
-    LF_HIP(c, hipMemcpyAsync(z->d_in[nl - 1], W, I.ninputs * 32, hipMemcpyHostToDevice, c->stream));
-    int* d_fail = (int*)((uint8_t*)c->mailbox_d + 128);
-    LF_HIP(c, hipMemsetAsync(d_fail, 0, 4, c->stream));
-    for (size_t l = nl; l-- > 0;) LF_TRY(lf256_eval_quad_async(C->layers[l].q, z->d_in[l], l ? z->d_in[l - 1] : z->d_V, d_fail));
-    LF_HIP(c, hipMemcpyAsync(z->h_V, z->d_V, I.nv * 32, hipMemcpyDeviceToHost, c->stream));
-    LF_HIP(c, hipMemcpyAsync((uint8_t*)z->h_V + I.nv * 32, d_fail, 4, hipMemcpyDeviceToHost, c->stream));
-  }
-  const double t_enq = now_ms() - t0;
-  // initialize_sumcheck_fiat_shamir (zk_common.h:163-180)
-  ts.write_bytes(I.id, 32);
-  for (size_t i = 0; i < z->npub; ++i) ts.write_elt(W[i]);
-  ts.write_elt(F.zero);
-  ts.write_bytes(C->zeros->data(), I.nterms);
-  void* cl = tso->clone(tso->user);
-  if (!cl) {
-    (void)hipStreamSynchronize(c->stream);
-    return lf_fail(c, LFGPU_ERR_NOMEM, "zk256_prove: transcript clone");
-  }
-  struct CloneGuard {
-    const lfgpu_transcript_ops* o;
-    void* u;
-    ~CloneGuard() { o->free_clone(u); }
-  } cg{tso, cl};
-  const Ts256 tst{tso, cl};
-  t0 = now_ms();
-  LF_HIP(c, hipStreamSynchronize(c->stream));
-  if (*failed) return LFGPU_OK;  // an assert-zero term is non-zero: eval_circuit returns nullptr
-  for (size_t i = 0; i < I.nv; ++i)
-    if (!e32_is_zero(V[i])) return LFGPU_OK;
-  z->ms[2] = t_enq + now_ms() - t0;
-
-  // padded sumcheck (ProverLayers::prove with pad, on the transcript copy)
-  t0 = now_ms();
-  z->proof.assign(nl, {});
-  z->aux.assign(nl, F.zero);
-  std::vector<E> G[2];
-  {
-    for (size_t i = 0; i < kMaxBindings256; ++i) (void)tst.elt();  // begin_circuit: Q then G (transcript_sumcheck.h:49-52)
-    G[0].resize(kMaxBindings256);
-    for (size_t i = 0; i < kMaxBindings256; ++i) G[0][i] = tst.elt();
-    G[1] = G[0];
-  }
-  size_t logv = I.logv;
-  E WC[2] = {F.zero, F.zero};
-  std::vector<E> gout;
-  for (size_t ly = 0; ly < nl; ++ly) {
-    const auto& L = C->layers[ly];
-    const E alpha = tst.elt(), beta = tst.elt();
-    auto& P = z->proof[ly];
-    P.hp[0].resize(2 * L.logw);
-    P.hp[1].resize(2 * L.logw);
-    Round256 rc{&tst, &z->pad[ly], &P};
-    gout.assign(2 * L.logw + 1, F.zero);
-    E wc_out[2], bq;
-    LF_TRY(sumcheck_layer256(L.q, F, logv, G[0].data(), G[1].data(), alpha, beta, L.logw, L.nw, (const E*)z->d_in[ly], WC, zk256_round_cb, &rc, wc_out,
-                             gout.data(), &bq));
-    P.wc[0] = F.sub(wc_out[0], z->pad[ly].wc[0]);  // end_layer (:331-344): transmit wc - pad
-    P.wc[1] = F.sub(wc_out[1], z->pad[ly].wc[1]);
-    tst.write_array(P.wc, 2);
-    z->aux[ly] = bq;
-    WC[0] = wc_out[0];
-    WC[1] = wc_out[1];
-    for (int h = 0; h < 2; ++h) {
-      G[h].assign(kMaxBindings256, F.zero);
-      for (size_t r = 0; r < L.logw; ++r) G[h][r] = gout[h * L.logw + r];
-    }
-    logv = L.logw;
-  }
-  z->ms[3] = now_ms() - t0;
-
-  // verifier_constraints with aux: replay the verifier symbolically on the ORIGINAL transcript
-  t0 = now_ms();
-  Constraints256 cs;
-  LF_TRY(build_constraints256(c, C, F, ts, z->proof, &z->aux, W, (E*)z->d_eq, cs));
-  const lfgpu_ligero_param& p = z->param;
-  z->ms[4] = now_ms() - t0;
-
-  // LigeroProver::prove (ligero_prover.h:84-146)
-  t0 = now_ms();
-  {
-    uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};  // zk_prover.h:143
-    ts.write_bytes(hash_of_A, 32);
-    std::vector<E> u_ldt(p.nwqrow);
-    for (auto& e : u_ldt) e = ts.elt();
-    z->y_ldt.assign(p.block, F.zero);
-    LF_TRY(lig256_low_degree(z->lp, u_ldt.data(), z->y_ldt.data()));
-    std::vector<E> alphal(cs.n), alphaq(3 * p.nq);
-    for (auto& e : alphal) e = ts.elt();
-    for (auto& e : alphaq) e = ts.elt();
-    std::vector<uint64_t> a_idx;
-    std::vector<E> a_val;
-    inner_product_sparse256(F, p, cs, alphal, z->lqc, alphaq, a_idx, a_val);
-    z->y_dot.assign(p.dblock, F.zero);
-    LF_TRY(lig256_dot(z->lp, (const E*)z->d_eq + z->npub, z->n_witness, alphal[cs.n - 1], a_idx.data(), a_val.data(), a_idx.size(), z->y_dot.data()));
-    std::vector<E> u_quad(p.nqtriples ? p.nqtriples : 1);
-    for (size_t i = 0; i < p.nqtriples; ++i) u_quad[i] = ts.elt();
-    z->y_q0.assign(p.r, F.zero);
-    z->y_q2.assign(p.dblock - p.block, F.zero);
-    LF_TRY(lig256_quadratic(z->lp, u_quad.data(), z->y_q0.data(), z->y_q2.data()));
-    ts.write_array(z->y_ldt.data(), z->y_ldt.size());
-    ts.write_array(z->y_dot.data(), z->y_dot.size());
-    ts.write_array(z->y_q0.data(), z->y_q0.size());
-    ts.write_array(z->y_q2.data(), z->y_q2.size());
-    std::vector<size_t> idx(p.nreq);
-    ts.choose(p.block_ext, p.nreq, idx.data());
-    z->req.assign(p.nrow * p.nreq, F.zero);
-    z->nonces.assign(p.nreq * 32, 0);
-    const size_t cap = p.nreq * p.mc_pathlen + 1;
-    z->path.assign(cap * 32, 0);
-    LF_TRY(lig256_open(z->lp, idx.data(), z->req.data(), z->nonces.data(), z->path.data(), cap, &z->npath));
-  }
-  z->ms[5] = now_ms() - t0;
-  z->ms[1] = now_ms() - t_start;
-  z->have_proof = true;
-  *ok = 1;
-  return LFGPU_OK;
+  LF_TRY(ts256_ok(z->c, tso));
+  if (!z->lp) return lf_fail(z->c, LFGPU_ERR_ARG, "zk256_prove: must run commit before prove");
+  auto eq_table = [&](E** d_eq) {  // the prover's own
+    *d_eq = (E*)z->d_eq;
+    return (int)LFGPU_OK;
+  };
+  return zkp::prove<P32>(z->c, z->C, P32(), z->st, z->lp, z->d_in.data(), z->d_V, z->h_V, eq_table, h_W, tso, ok);
 }
-
-// ZkProof::write (zk_proof.h:90-185); the subfield of a prime field is the field, so the opened columns are one
-// "subfield" run after an empty full-field run
-int zk256_proof_write(const Zk256* z, uint8_t* buf, size_t cap, size_t* nbytes) {
-  if (!z->have_proof) return lf_fail(z->c, LFGPU_ERR_ARG, "zk_proof_write: no proof");
-  std::vector<uint8_t>& o = z->wire;  // serialised once per proof: the size query and the copy share it
-  if (!z->wire_valid) {
-  o.clear();
-  auto pute = [&](const E& e) {
-    uint8_t b[32];
-    h256_to_bytes(e, b);
-    o.insert(o.end(), b, b + 32);
-  };
-  auto putsz = [&](size_t g) {
-    for (int i = 0; i < 4; ++i) o.push_back((uint8_t)(g >> (8 * i)));
-  };
-  o.insert(o.end(), z->root, z->root + 32);
-  for (size_t ly = 0; ly < z->proof.size(); ++ly) {
-    const auto& P = z->proof[ly];
-    const size_t logw = z->C->layers[ly].logw;
-    for (size_t wi = 0; wi < logw; ++wi)
-      for (int k = 0; k < 2; ++k) {
-        pute(P.hp[0][2 * wi + k]);
-        pute(P.hp[1][2 * wi + k]);
-      }
-    pute(P.wc[0]);
-    pute(P.wc[1]);
-  }
-  for (const E& e : z->y_ldt) pute(e);
-  for (const E& e : z->y_dot) pute(e);
-  for (const E& e : z->y_q0) pute(e);
-  for (const E& e : z->y_q2) pute(e);
-  o.insert(o.end(), z->nonces.begin(), z->nonces.end());
-  constexpr size_t kMaxRunLen = (size_t)1 << 25;
-  const size_t nreq_elts = z->req.size();
-  size_t ci = 0;
-  bool subfield_run = false;
-  while (ci < nreq_elts) {
-    size_t runlen = 0;
-    if (subfield_run) runlen = std::min(nreq_elts - ci, kMaxRunLen);  // in_subfield(e) is true for every element
-    putsz(runlen);
-    for (size_t i = ci; i < ci + runlen; ++i) pute(z->req[i]);
-    ci += runlen;
-    subfield_run = !subfield_run;
-  }
-  putsz(z->npath);
-  o.insert(o.end(), z->path.begin(), z->path.begin() + 32 * z->npath);
-  z->wire_valid = true;
-  }
-  *nbytes = o.size();
-  if (buf) {
-    if (cap < o.size()) return lf_fail(z->c, LFGPU_ERR_ARG, "zk_proof_write: buffer too small (%zu < %zu)", cap, o.size());
-    memcpy(buf, o.data(), o.size());
-  }
-  return LFGPU_OK;
-}
-
-// ------------------------------------------------------------------ ZkVerifier<Fp256Base>
-// ZkVerifier::recv_commitment + verify (lib/zk/zk_verifier.h:68-94) over the wire bytes, as zk.hip does for the 16-byte
-// fields: ZkProof::read (zk_proof.h:107-112,218-345), verifier_constraints with aux == nullptr (Quad::bind_gh_all on the
-// device), LigeroVerifier::verify (lib/ligero/ligero_verifier.h:42-270: Reed-Solomon extension of the rows of A and of the
-// three y vectors on the device, checks at the opened columns on the host), MerkleCommitmentVerifier::verify.
-namespace {
-struct Parsed256 {
-  uint8_t root[32];
-  std::vector<Zk256::LayerPad> sc;
-  std::vector<E> y_ldt, y_dot, y_q0, y_q2, req;
-  std::vector<uint8_t> nonces, path;
-  size_t npath = 0;
-};
-bool parse_proof256(const lfgpu_circuit* C, const lfgpu_ligero_param& p, const uint8_t* buf, size_t len, Parsed256& pr) {
-  const uint8_t* q = buf;
-  size_t left = len;
-  bool bad = false;
-  auto have = [&](size_t n) { return left >= n; };
-  auto next = [&](size_t n) {
-    const uint8_t* r = q;
-    q += n;
-    left -= n;
-    return r;
-  };
-  auto elt = [&] {
-    E e = e32_zero();
-    if (!h256_of_bytes(next(32), e)) bad = true;  // of_bytes_field: value >= p
-    return e;
-  };
-  auto size4 = [&] {
-    const uint8_t* b = next(4);
-    return (size_t)b[0] | (size_t)b[1] << 8 | (size_t)b[2] << 16 | (size_t)b[3] << 24;
-  };
-  if (!have(32)) return false;
-  memcpy(pr.root, next(32), 32);
-  pr.sc.assign(C->layers.size(), {});
-  for (size_t ly = 0; ly < C->layers.size(); ++ly) {
-    const size_t logw = C->layers[ly].logw;
-    if (!have((logw * 4 + 2) * 32)) return false;
-    auto& P = pr.sc[ly];
-    P.hp[0].resize(2 * logw);
-    P.hp[1].resize(2 * logw);
-    for (size_t wi = 0; wi < logw; ++wi)
-      for (int k = 0; k < 2; ++k) {
-        P.hp[0][2 * wi + k] = elt();
-        P.hp[1][2 * wi + k] = elt();
-      }
-    P.wc[0] = elt();
-    P.wc[1] = elt();
-  }
-  auto vec = [&](std::vector<E>& v, size_t n) {
-    if (!have(n * 32)) return false;
-    v.resize(n);
-    for (auto& e : v) e = elt();
-    return true;
-  };
-  if (!vec(pr.y_ldt, p.block) || !vec(pr.y_dot, p.dblock) || !vec(pr.y_q0, p.r) || !vec(pr.y_q2, p.dblock - p.block)) return false;
-  if (!have(p.nreq * 32)) return false;
-  pr.nonces.assign(q, q + p.nreq * 32);
-  next(p.nreq * 32);
-  const size_t total = p.nreq * p.nrow;
-  constexpr size_t kMaxRunLen = (size_t)1 << 25, kMaxNumDigests = (size_t)1 << 25;
-  pr.req.assign(total, e32_zero());
-  size_t ci = 0;
-  while (ci < total) {  // alternating full-field / subfield runs; both are 32-byte images for a prime field
-    if (!have(4)) return false;
-    const size_t runlen = size4();
-    if (runlen >= kMaxRunLen || ci + runlen > total || !have(runlen * 32)) return false;
-    for (size_t i = ci; i < ci + runlen; ++i) pr.req[i] = elt();
-    ci += runlen;
-  }
-  if (!have(4)) return false;
-  const size_t sz = size4();
-  if (sz < p.nreq || sz >= kMaxNumDigests || sz > p.nreq * p.mc_pathlen || !have(sz * 32)) return false;
-  pr.npath = sz;
-  pr.path.assign(q, q + sz * 32);
-  next(sz * 32);
-  return !bad;
-}
-}  // namespace
+int zk256_proof_write(const Zk256* z, uint8_t* buf, size_t cap, size_t* nbytes) { return zkp::proof_write_cached(z->c, P32(), z->C, z->st, buf, cap, nbytes); }
 
 int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof, size_t proof_len, const void* h_pub,
                  const lfgpu_transcript_ops* tso, bool committed, int* ok, const char** why_out) {
-  static const char* kWhy[] = {"ok", "proof does not parse", "merkle_check failed", "low_degree_check failed", "dot_check failed", "wrong dot product",
-                               "quadratic_check failed"};
   *ok = 0;
   LF_TRY(ts256_ok(c, tso));
-  auto fail = [&](int w) {
-    if (why_out) *why_out = kWhy[w];
-    return LFGPU_OK;
-  };
   const lfgpu_circuit_info& I = C->info;
-  const size_t nl = C->layers.size(), npub = I.npub_in, n_witness = I.ninputs - npub;
-  size_t pad_size = 0;
-  for (const auto& l : C->layers) pad_size += layer_size256(l.logw);
   lfgpu_ligero_param p{};
-  LF_TRY(lfgpu_ligero_param_init(&p, LFGPU_FIELD_P256, 0, n_witness + pad_size, nl, rateinv, nreq, block_enc));
-  Parsed256 pr;
-  if (!parse_proof256(C, p, proof, proof_len, pr)) return fail(1);
-  LF_HIP(c, hipSetDevice(c->device));
-  const F256 F;
-  const Ts256 ts{tso, tso->user};
-  const E* pub = (const E*)h_pub;
-  // recv_commitment (unless the caller did it), initialize_sumcheck_fiat_shamir
-  if (!committed) ts.write_bytes(pr.root, 32);
-  ts.write_bytes(I.id, 32);
-  for (size_t i = 0; i < npub; ++i) ts.write_elt(pub[i]);
-  ts.write_elt(F.zero);
-  ts.write_bytes(C->zeros->data(), I.nterms);
-  // device buffers: EQ table of the input constraint | rows [0, nwqrow) = [0^r | A_i], then y_ldt, y_dot, y_quad | gathered columns
-  const size_t nrows_dev = p.nwqrow + 3, ld = p.block_enc;
-  void* dv = nullptr;
-  LF_TRY(lf_scratch4(c, (I.ninputs + nrows_dev * ld + nrows_dev * p.nreq) * 32 + 256, &dv));
-  E* d_eq = (E*)dv;
-  E* d_T = d_eq + I.ninputs;
-  E* d_req = d_T + nrows_dev * ld;
-  Constraints256 cs;
-  LF_TRY(build_constraints256(c, C, F, ts, pr.sc, nullptr, pub, d_eq, cs));
-  std::vector<size_t> lqc(3 * nl);
-  {
-    size_t pi = n_witness;
-    for (size_t ly = 0; ly < nl; ++ly) {  // setup_lqc (zk_common.h:149-160)
-      const size_t cp = pi + 4 * C->layers[ly].logw;
-      lqc[3 * ly] = cp;
-      lqc[3 * ly + 1] = cp + 1;
-      lqc[3 * ly + 2] = cp + 2;
-      pi += layer_size256(C->layers[ly].logw);
-    }
-  }
-  // LigeroVerifier::verify: replay the challenges
-  uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};
-  ts.write_bytes(hash_of_A, 32);
-  std::vector<E> u_ldt(p.nwqrow), alphal(cs.n), alphaq(3 * p.nq), u_quad(p.nqtriples ? p.nqtriples : 1);
-  for (auto& e : u_ldt) e = ts.elt();
-  for (auto& e : alphal) e = ts.elt();
-  for (auto& e : alphaq) e = ts.elt();
-  for (size_t i = 0; i < p.nqtriples; ++i) u_quad[i] = ts.elt();
-  ts.write_array(pr.y_ldt.data(), pr.y_ldt.size());
-  ts.write_array(pr.y_dot.data(), pr.y_dot.size());
-  ts.write_array(pr.y_q0.data(), pr.y_q0.size());
-  ts.write_array(pr.y_q2.data(), pr.y_q2.size());
-  std::vector<size_t> idx(p.nreq);
-  ts.choose(p.block_ext, p.nreq, idx.data());
-  auto req_at = [&](size_t i, size_t j) -> const E& { return pr.req[i * p.nreq + j]; };
-  {  // merkle_check: leaf r = SHA-256(nonce_r || column r of the opening)
-    std::vector<uint8_t> leaves(p.nreq * 32);
-    for (size_t r = 0; r < p.nreq; ++r) {
-      Sha256 sh;
-      sh.update(&pr.nonces[32 * r], 32);
-      for (size_t i = 0; i < p.nrow; ++i) {
-        uint8_t eb[32];
-        h256_to_bytes(req_at(i, r), eb);
-        sh.update(eb, 32);
-      }
-      sh.digest(&leaves[32 * r]);
-    }
-    if (!lf_merkle_verify(p.block_ext, pr.root, pr.path.data(), pr.npath, leaves.data(), idx.data(), p.nreq)) return fail(2);
-  }
-  // rows of A (inner_product_vector + layout_Aext), y vectors; extension to block_enc; the opened columns
-  std::vector<uint64_t> a_idx;
-  std::vector<E> a_val;
-  inner_product_sparse256(F, p, cs, alphal, lqc, alphaq, a_idx, a_val);
-  LF_HIP(c, hipMemset2DAsync(d_T, ld * 32, 0, p.dblock * 32, nrows_dev, c->stream));
-  hipLaunchKernelGGL(a_rows_dense256_kernel, dim3(nblk(n_witness)), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, alphal[cs.n - 1], (const E*)d_eq + npub,
-                     n_witness, d_T);
-  if (!a_idx.empty()) {
-    void* d_sp = nullptr;
-    LF_TRY(lf_scratch2(c, a_idx.size() * 40 + 64, &d_sp));
-    E* d_val = (E*)d_sp;
-    u64* d_idx = (u64*)(d_val + a_idx.size());
-    LF_HIP(c, hipMemcpyAsync(d_val, a_val.data(), a_idx.size() * 32, hipMemcpyHostToDevice, c->stream));
-    LF_HIP(c, hipMemcpyAsync(d_idx, a_idx.data(), a_idx.size() * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(a_rows_sparse256_kernel, dim3(nblk(a_idx.size())), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, (const u64*)d_idx, (const E*)d_val,
-                       a_idx.size(), d_T);
-  }
-  LF_HIP(c, hipGetLastError());
-  LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 0) * ld, pr.y_ldt.data(), p.block * 32, hipMemcpyHostToDevice, c->stream));
-  LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 1) * ld, pr.y_dot.data(), p.dblock * 32, hipMemcpyHostToDevice, c->stream));
-  E* yq = d_T + (p.nwqrow + 2) * ld;  // y_quad = y_quad_0 | 0^w | y_quad_2
-  LF_HIP(c, hipMemcpyAsync(yq, pr.y_q0.data(), p.r * 32, hipMemcpyHostToDevice, c->stream));
-  LF_HIP(c, hipMemcpyAsync(yq + p.block, pr.y_q2.data(), (p.dblock - p.block) * 32, hipMemcpyHostToDevice, c->stream));
-  LF_HIP(c, hipStreamSynchronize(c->stream));  // the staging area is the Reed-Solomon encoder's work space next
-  LF_TRY(lfgpu_fp256_rs_encode_rows(c, p.nwqrow + 1, p.block, p.block_enc, d_T, ld));                    // A rows and y_ldt
-  LF_TRY(lfgpu_fp256_rs_encode_rows(c, 2, p.dblock, p.block_enc, d_T + (p.nwqrow + 1) * ld, ld));         // y_dot, y_quad
-  {
-    void* di = nullptr;
-    LF_TRY(lf_scratch2(c, p.nreq * 8 + 64, &di));
-    std::vector<u64> ix(idx.begin(), idx.end());
-    LF_HIP(c, hipMemcpyAsync(di, ix.data(), p.nreq * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(gather_columns256_kernel, dim3(nblk(nrows_dev * p.nreq)), dim3(Z_THREADS), 0, c->stream, (u32)nrows_dev, ld, p.dblock, (const E*)d_T,
-                       (const u64*)di, (u32)p.nreq, d_req);
-    LF_HIP(c, hipGetLastError());
-    LF_HIP(c, hipStreamSynchronize(c->stream));
-  }
-  std::vector<E> ext(nrows_dev * p.nreq);
-  LF_TRY(lfgpu_memcpy_d2h(c, ext.data(), d_req, ext.size() * 32));
-  auto ext_at = [&](size_t row, size_t j) -> const E& { return ext[row * p.nreq + j]; };
-  for (size_t j = 0; j < p.nreq; ++j) {  // low_degree_check
-    E yc = req_at(p.ildt, j);
-    for (size_t i = 0; i < p.nwqrow; ++i) yc = F.add(yc, F.mul(u_ldt[i], req_at(i + p.iw, j)));
-    if (!e32_eq(yc, ext_at(p.nwqrow, j))) return fail(3);
-  }
-  for (size_t j = 0; j < p.nreq; ++j) {  // dot_check
-    E yc = req_at(p.idot, j);
-    for (size_t i = 0; i < p.nwqrow; ++i) yc = F.add(yc, F.mul(ext_at(i, j), req_at(i + p.iw, j)));
-    if (!e32_eq(yc, ext_at(p.nwqrow + 1, j))) return fail(4);
-  }
-  {  // the putative value of the inner product
-    E want = F.zero, got = F.zero;
-    for (size_t k = 0; k < cs.n; ++k) want = F.add(want, F.mul(cs.b[k], alphal[k]));
-    for (size_t j = 0; j < p.w; ++j) got = F.add(got, pr.y_dot[p.r + j]);
-    if (!e32_eq(want, got)) return fail(5);
-  }
-  {  // quadratic_check
-    const size_t iqx = p.iq, iqy = iqx + p.nqtriples, iqz = iqy + p.nqtriples;
-    for (size_t j = 0; j < p.nreq; ++j) {
-      E yc = req_at(p.iquad, j);
-      for (size_t i = 0; i < p.nqtriples; ++i) {
-        const E tmp = F.sub(req_at(iqz + i, j), F.mul(req_at(iqx + i, j), req_at(iqy + i, j)));  // z - x y
-        yc = F.add(yc, F.mul(u_quad[i], tmp));
-      }
-      if (!e32_eq(yc, ext_at(p.nwqrow + 2, j))) return fail(6);
-    }
-  }
-  *ok = 1;
-  return fail(0);
+  LF_TRY(lfgpu_ligero_param_init(&p, LFGPU_FIELD_P256, 0, I.ninputs - I.npub_in + zkp::pad_size(C), C->layers.size(), rateinv, nreq, block_enc));
+  auto eq_table = [&](E** d_eq) {  // the head of the verifier's device buffer (P32::verifier_ext)
+    void* dv = nullptr;
+    LF_TRY(lf_scratch4(c, P32::verifier_bytes(I, p), &dv));
+    *d_eq = (E*)dv;
+    return (int)LFGPU_OK;
+  };
+  return zkp::verify<P32>(c, C, P32(), p, proof, proof_len, h_pub, tso, committed, eq_table, ok, why_out);
 }

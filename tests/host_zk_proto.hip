@@ -1,0 +1,175 @@
+// Host-only harness of tests/test_zk_proto_host.py: the parts of csrc/zk_proto.h that need no device context (transcript
+// view, ZkProof::write / read, inner_product_sparse) behind a small C ABI.  Compiled with hipcc --cuda-host-only and linked
+// against liblfgpu.so for the host helpers the header calls (field inverses, the GF(2^128) constants).
+// Elements cross this ABI as their to_bytes_field images (canonical little-endian values), never in Montgomery form.
+#include "../longfellow-zk_amd/csrc/zk_proto.h"
+
+namespace {
+struct Gf {  // GF(2^128): the subfield tables without a context
+  GfHostCtx g;
+  zkp::SubfieldSolver sub;
+  Gf() {
+    lf_gf_ctx_build(&g, 4);
+    sub.build(&g);
+  }
+};
+zkp::Wire16 wire16(int field) {
+  zkp::Wire16 w;
+  w.field = field;
+  if (field == LFGPU_FIELD_GF2_128) {
+    static const Gf gf;
+    w.g = &gf.g;
+    w.sub = &gf.sub;
+  }
+  return w;
+}
+// f(policy, host field) for the field id; the prime fields' host fields need no context
+template <class Fn>
+int with_field(int field, Fn f) {
+  if (field == LFGPU_FIELD_P256) return f(zkp::Wire32(), F256());
+  if (field == LFGPU_FIELD_FP128) return f(wire16(field), HostField(nullptr, field));
+  return LFGPU_ERR_UNSUPPORTED;
+}
+template <class Fn>
+int with_wire(int field, Fn f) {
+  if (field == LFGPU_FIELD_P256) return f(zkp::Wire32());
+  return f(wire16(field));
+}
+template <class P>
+bool get(const P& pol, const uint8_t* b, size_t n, std::vector<typename P::E>& v) {
+  v.assign(n, P::zero());
+  bool ok = true;
+  for (size_t i = 0; i < n; ++i) ok &= pol.of_bytes(b + P::kBytes * i, v[i]);
+  return ok;
+}
+template <class P>
+void put(const P& pol, const std::vector<typename P::E>& v, uint8_t* b) {
+  for (size_t i = 0; i < v.size(); ++i) pol.to_bytes(v[i], b + P::kBytes * i);
+}
+void layers_of(lfgpu_circuit& C, const size_t* logw, size_t nl) {
+  for (size_t i = 0; i < nl; ++i) C.layers.push_back({logw[i], (size_t)1 << logw[i], 1, nullptr});
+}
+}  // namespace
+
+extern "C" {
+// sc: per layer hp[0][0 .. 2 logw) | hp[1][0 .. 2 logw) | wc[0] | wc[1]; the other members as in zkp::ProofBody
+struct hzp_proof {
+  uint8_t root[32];
+  uint8_t *sc, *y_ldt, *y_dot, *y_q0, *y_q2, *req, *nonces, *path;
+  size_t npath;
+};
+
+// ZkProof::write of the proof in `in` (nreq * nrow opened elements); 0, or -1 when an input element is not canonical
+int hzp_write(int field, const size_t* logw, size_t nl, const lfgpu_ligero_param* p, const hzp_proof* in, uint8_t* out, size_t cap, size_t* nbytes) {
+  return with_wire(field, [&](auto pol) {
+    using P = decltype(pol);
+    lfgpu_circuit C;
+    layers_of(C, logw, nl);
+    zkp::ProofBody<typename P::E> pr;
+    memcpy(pr.root, in->root, 32);
+    pr.sc.assign(nl, {});
+    const uint8_t* s = in->sc;
+    bool ok = true;
+    for (size_t ly = 0; ly < nl; ++ly) {
+      std::vector<typename P::E> wc;
+      ok &= get(pol, s, 2 * logw[ly], pr.sc[ly].hp[0]) && get(pol, s + 2 * logw[ly] * P::kBytes, 2 * logw[ly], pr.sc[ly].hp[1]) &&
+            get(pol, s + 4 * logw[ly] * P::kBytes, 2, wc);
+      pr.sc[ly].wc[0] = wc[0];
+      pr.sc[ly].wc[1] = wc[1];
+      s += (4 * logw[ly] + 2) * P::kBytes;
+    }
+    ok &= get(pol, in->y_ldt, p->block, pr.y_ldt) && get(pol, in->y_dot, p->dblock, pr.y_dot) && get(pol, in->y_q0, p->r, pr.y_q0) &&
+          get(pol, in->y_q2, p->dblock - p->block, pr.y_q2) && get(pol, in->req, p->nreq * p->nrow, pr.req);
+    if (!ok) return -1;
+    pr.nonces.assign(in->nonces, in->nonces + 32 * p->nreq);
+    pr.path.assign(in->path, in->path + 32 * in->npath);
+    pr.npath = in->npath;
+    std::vector<uint8_t> o;
+    zkp::proof_write(pol, &C, pr, o);
+    *nbytes = o.size();
+    if (o.size() > cap) return -1;
+    memcpy(out, o.data(), o.size());
+    return 0;
+  });
+}
+
+// ZkProof::read: 1 and the proof in `out` (buffers of the sizes p fixes; path: nreq * mc_pathlen digests), or 0 when refused
+int hzp_read(int field, const size_t* logw, size_t nl, const lfgpu_ligero_param* p, const uint8_t* buf, size_t len, hzp_proof* out) {
+  return with_wire(field, [&](auto pol) {
+    using P = decltype(pol);
+    lfgpu_circuit C;
+    layers_of(C, logw, nl);
+    zkp::ProofBody<typename P::E> pr;
+    if (!zkp::proof_read(pol, &C, *p, buf, len, pr)) return 0;
+    memcpy(out->root, pr.root, 32);
+    uint8_t* s = out->sc;
+    for (size_t ly = 0; ly < nl; ++ly) {
+      put(pol, pr.sc[ly].hp[0], s);
+      put(pol, pr.sc[ly].hp[1], s + 2 * logw[ly] * P::kBytes);
+      put(pol, {pr.sc[ly].wc[0], pr.sc[ly].wc[1]}, s + 4 * logw[ly] * P::kBytes);
+      s += (4 * logw[ly] + 2) * P::kBytes;
+    }
+    put(pol, pr.y_ldt, out->y_ldt);
+    put(pol, pr.y_dot, out->y_dot);
+    put(pol, pr.y_q0, out->y_q0);
+    put(pol, pr.y_q2, out->y_q2);
+    put(pol, pr.req, out->req);
+    memcpy(out->nonces, pr.nonces.data(), pr.nonces.size());
+    memcpy(out->path, pr.path.data(), pr.path.size());
+    out->npath = pr.npath;
+    return 1;
+  });
+}
+
+// inner_product_sparse over na linear terms (constraint a_c, witness index a_w, coefficient a_k), alphal[nalphal], lqc[3 nq],
+// alphaq[3 nq]; idx_out / val_out have room for na + 6 nq entries
+int hzp_inner_product_sparse(int field, const lfgpu_ligero_param* p, size_t na, const size_t* a_c, const size_t* a_w, const uint8_t* a_k, size_t nalphal,
+                             const uint8_t* alphal, const size_t* lqc, const uint8_t* alphaq, uint64_t* idx_out, uint8_t* val_out, size_t* n_out) {
+  return with_field(field, [&](auto pol, const auto& F) {
+    using P = decltype(pol);
+    using E = typename P::E;
+    std::vector<E> k, al, aq, val;
+    if (!get(pol, a_k, na, k) || !get(pol, alphal, nalphal, al) || !get(pol, alphaq, 3 * p->nq, aq)) return -1;
+    std::vector<zkp::LinTerm<E>> a(na);
+    for (size_t i = 0; i < na; ++i) a[i] = {a_c[i], a_w[i], k[i]};
+    std::vector<uint64_t> idx;
+    zkp::inner_product_sparse<P>(F, *p, a, al, std::vector<size_t>(lqc, lqc + 3 * p->nq), aq, idx, val);
+    std::copy(idx.begin(), idx.end(), idx_out);
+    put(pol, val, val_out);
+    *n_out = idx.size();
+    return 0;
+  });
+}
+
+// the transcript view over the caller's hooks
+size_t hzp_nat(int field, const lfgpu_transcript_ops* ops, size_t n) {
+  size_t r = 0;
+  with_wire(field, [&](auto pol) {
+    r = zkp::Ts<decltype(pol)>{&pol, ops, ops->user}.nat(n);
+    return 0;
+  });
+  return r;
+}
+void hzp_choose(int field, const lfgpu_transcript_ops* ops, size_t n, size_t k, size_t* res) {
+  with_wire(field, [&](auto pol) {
+    zkp::Ts<decltype(pol)>{&pol, ops, ops->user}.choose(n, k, res);
+    return 0;
+  });
+}
+int hzp_write_array(int field, const lfgpu_transcript_ops* ops, const uint8_t* elts, size_t n) {
+  return with_wire(field, [&](auto pol) {
+    std::vector<typename decltype(pol)::E> v;
+    if (!get(pol, elts, n, v)) return -1;
+    zkp::Ts<decltype(pol)>{&pol, ops, ops->user}.write_array(v.data(), n);
+    return 0;
+  });
+}
+int hzp_write_elt(int field, const lfgpu_transcript_ops* ops, const uint8_t* elt) {
+  return with_wire(field, [&](auto pol) {
+    std::vector<typename decltype(pol)::E> v;
+    if (!get(pol, elt, 1, v)) return -1;
+    zkp::Ts<decltype(pol)>{&pol, ops, ops->user}.write_elt(v[0]);
+    return 0;
+  });
+}
+}  // extern "C"
