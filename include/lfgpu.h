@@ -223,6 +223,27 @@ int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0, const voi
                          lfgpu_sc_round_fn round, void* user, uint64_t wc_out[2][2], uint64_t* g_out /*[2][logw][2]*/,
                          uint64_t bound_quad[2]);
 
+/* ---- the same layer for a batch of statements in lock-step (K14) -------------------------------------
+ * nb statements of ONE quad (one circuit layer, nb witnesses) go through the same launches: bind_g per statement, then every
+ * round-hand of all statements in a number of launches that does not depend on nb, with ONE host round trip -- one call of
+ * `round` -- per round-hand.  Statement b's evaluations, wc_out, g_out and bound_quad are byte-identical to what
+ * lfgpu_sumcheck_layer produces for statement b alone when its callback returns the same challenges.
+ * `round` is called 2 * logw times, in the order (round 0, hand 0), (round 0, hand 1), (round 1, hand 0), ...: evals[b] = the
+ * 3 evaluations of statement b's round polynomial, challenge_out[b] = its challenge.
+ * h_G0 / h_G1: [nb][logv] host elements, statement b at offset b * logv; alpha, beta: [nb][2]; d_W: statement b's nw wires at
+ * d_W + b * ldw elements, ldw >= nw (device; consumed); wc_in: [nb][2][2]; wc_out: [nb][2][2]; g_out: [nb][2][logw][2];
+ * bound_quad: [nb][2] or NULL.  1 <= nb <= LFGPU_SC_BATCH_MAX (the challenges of a round-hand are then 1 KiB of kernel
+ * arguments and the mailbox 8 KiB: a condition of the design, not a tuned number).  Fields: GF2_128 and Fp128;
+ * LFGPU_ERR_UNSUPPORTED for P256.  The driver launches one kernel chain per round-hand and no resident kernel: the
+ * LFGPU_SC_* switches of lfgpu_sumcheck_layer have no effect on it. */
+#define LFGPU_SC_BATCH_MAX 64
+typedef void (*lfgpu_sc_round_batch_fn)(void* user, size_t hand, size_t round, size_t nb, const uint64_t (*evals)[3][2],
+                                        uint64_t (*challenge_out)[2]);
+int lfgpu_sumcheck_layer_batch(lfgpu_quad* q, size_t nb, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha,
+                               const uint64_t* beta, size_t logw, size_t nw, void* d_W, size_t ldw, const uint64_t* wc_in,
+                               lfgpu_sc_round_batch_fn round, void* user, uint64_t* wc_out, uint64_t* g_out,
+                               uint64_t* bound_quad);
+
 /* ---- circuits with nc > 1 copies: the copy rounds of the sumcheck (K13) ------------------------------
  * The reference's data-parallel axis: every wire array is Dense(n0 = nc, n1 = nw), stored W[wire * nc + c] (copy index
  * fastest, lib/arrays/dense.h:44-45), and every layer opens with logc cubic rounds that bind the copy variable

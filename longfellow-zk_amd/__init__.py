@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "lfgpu_ligero_quadratic_proof", "lfgpu_ligero_open", "lfgpu_ligero_tableau", "lfgpu_ligero_free",
     "lfgpu_quad_upload", "lfgpu_quad_free", "lfgpu_eval_quad", "lfgpu_quad_bind_g", "lfgpu_sumcheck_layer", "lfgpu_raw_eq2", "lfgpu_quad_bind_gh_all",
     "lfgpu_eval_quad_copies", "lfgpu_sumcheck_evaluations_c", "lfgpu_dense_bind_rows", "lfgpu_eqs", "lfgpu_sumcheck_layer_copies",
+    "lfgpu_sumcheck_layer_batch",
     # include/lfgpu_zk.h
     "lfgpu_transcript_new", "lfgpu_transcript_free", "lfgpu_transcript_get_ops", "lfgpu_transcript_write_bytes",
     "lfgpu_transcript_write_elt", "lfgpu_transcript_write_elt_array", "lfgpu_transcript_bytes", "lfgpu_transcript_write_elt_sized", "lfgpu_transcript_write_elt_array_sized", "lfgpu_sha256",
@@ -58,6 +59,9 @@ RNG_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_size_t)  # Rand
 SC_ROUND_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 # copy-round callback of lfgpu_sumcheck_layer_copies: (user, round, evals[4][2], challenge_out[2])
 SC_ROUND_C_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+# round callback of lfgpu_sumcheck_layer_batch: (user, hand, round, nb, evals[nb][3][2], challenge_out[nb][2])
+SC_ROUND_BATCH_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+SC_BATCH_MAX = 64  # LFGPU_SC_BATCH_MAX
 
 
 class TranscriptOps(C.Structure):
@@ -157,6 +161,7 @@ def load_library():
         "lfgpu_dense_bind_rows": [vp, ci, sz, sz, pu64, vp, vp],
         "lfgpu_eqs": [vp, ci, sz, sz, vp, vp],
         "lfgpu_sumcheck_layer_copies": [vp, sz, sz, vp, sz, vp, vp, pu64, pu64, sz, sz, vp, pu64, SC_ROUND_C_FN, SC_ROUND_FN, vp, pu64, pu64, pu64, pu64],
+        "lfgpu_sumcheck_layer_batch": [vp, sz, sz, vp, vp, pu64, pu64, sz, sz, vp, sz, pu64, SC_ROUND_BATCH_FN, vp, pu64, pu64, pu64],
         "lfgpu_circuit_from_lfc1": [vp, vp, sz, C.POINTER(vp)],
         "lfgpu_circuit_share": [vp, vp, C.POINTER(vp)],
         "lfgpu_circuit_get_info": [vp, C.POINTER(CircuitInfo)],
@@ -616,6 +621,37 @@ class Quad:
                                                             gout, bq))
         ch = [[(gout[(h * logw + r) * 2], gout[(h * logw + r) * 2 + 1]) for r in range(logw)] for h in range(2)]
         return [(wco[0], wco[1]), (wco[2], wco[3])], [(qout[2 * r], qout[2 * r + 1]) for r in range(logc)], ch, (bq[0], bq[1])
+
+    def sumcheck_layer_batch(self, logv, G0, G1, alphas, betas, logw, nw, d_W, ldw, wc_ins, round_cb):
+        """ProverLayers::layer (logc = 0) incl. bind_g for B = len(alphas) statements of this quad in lock-step.  G0, G1:
+        [B][logv] elements; alphas, betas: B (lo, hi) pairs; d_W: statement b's nw wires at d_W + b * ldw elements (device,
+        consumed); wc_ins: B pairs of (lo, hi) pairs.  round_cb(hand, round, evals) is called once per round-hand with
+        evals[b] = the 3 evaluations of statement b as (lo, hi) pairs and returns B (lo, hi) challenges.
+        Returns (wc_out[B], challenges[B][2][logw], bound_quad[B])."""
+        import numpy as np
+        B = len(alphas)
+        G0, G1 = np.ascontiguousarray(G0, dtype=np.uint64), np.ascontiguousarray(G1, dtype=np.uint64)
+
+        def cb(_user, hand, rnd, nb, evals, out):
+            ev = [tuple((evals[6 * b + 2 * k], evals[6 * b + 2 * k + 1]) for k in range(3)) for b in range(nb)]
+            rs = round_cb(hand, rnd, ev)
+            for b in range(nb):
+                out[2 * b], out[2 * b + 1] = int(rs[b][0]), int(rs[b][1])
+
+        cfn = SC_ROUND_BATCH_FN(cb)
+        n = max(1, B)
+        al = (C.c_uint64 * (2 * n))(*[int(x) for a in alphas for x in _u64x2(a)])
+        be = (C.c_uint64 * (2 * n))(*[int(x) for a in betas for x in _u64x2(a)])
+        wci = (C.c_uint64 * (4 * n))(*[int(x) for w in wc_ins for e in w for x in e])
+        wco = (C.c_uint64 * (4 * n))()
+        gout = (C.c_uint64 * (4 * n * max(1, logw)))()
+        bq = (C.c_uint64 * (2 * n))()
+        self.gpu._ck(self.gpu.L.lfgpu_sumcheck_layer_batch(self.h, B, logv, C.c_void_p(G0.ctypes.data), C.c_void_p(G1.ctypes.data), al, be,
+                                                           logw, nw, C.c_void_p(d_W), ldw, wci, cfn, None, wco, gout, bq))
+        ch = [[[(gout[((b * 2 + h) * logw + r) * 2], gout[((b * 2 + h) * logw + r) * 2 + 1]) for r in range(logw)] for h in range(2)]
+              for b in range(B)]
+        return ([[(wco[4 * b], wco[4 * b + 1]), (wco[4 * b + 2], wco[4 * b + 3])] for b in range(B)], ch,
+                [(bq[2 * b], bq[2 * b + 1]) for b in range(B)])
 
     def close(self):
         if self.h:

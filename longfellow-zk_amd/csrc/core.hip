@@ -285,6 +285,7 @@ int lfgpu_shutdown(lfgpu_ctx* c) {
   if (c->zk_eq) hipFree(c->zk_eq);
   if (c->mailbox_h) hipHostFree(c->mailbox_h);
   if (c->poll_h) hipHostFree((void*)c->poll_h);
+  if (c->sc_batch_h) hipHostFree((void*)c->sc_batch_h);
   for (int i = 0; i < 4; ++i)
     if (c->stage_ev[i]) hipEventDestroy(c->stage_ev[i]);
   if (c->stage_h) hipHostFree(c->stage_h);

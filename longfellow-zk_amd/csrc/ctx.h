@@ -66,6 +66,9 @@ struct lfgpu_ctx {
   volatile u64* poll_h = nullptr;
   u64 poll_seq = 0, poll_next = 0;
   int resident_state = 0;  // 0 untested, 1 the resident sumcheck kernel may be used, -1 it may not
+  // lfgpu_sumcheck_layer_batch: one slot of LF_SC_BATCH_SLOT_WORDS coherent pinned words per statement, each laid out like
+  // poll_h; allocated at the first batched call, sequence numbers from poll_seq
+  volatile u64* sc_batch_h = nullptr;
   // per-context (= per-device) launch configuration: nothing below the C ABI is process-global, so one process may hold
   // contexts on several devices (hipFuncSetAttribute is applied once per context)
   unsigned attr_done = 0;  // bit 0 FFT tile kernels, 1 RS row kernel, 2 bit-sliced butterflies, 3 sumcheck grid tail
@@ -209,6 +212,25 @@ int lf_sc_grid_begin(lfgpu_ctx* c, int field, void* hc_cur, void* vc_cur, void* 
 #define LF_SC_GRID_MAX (256 * 1024)             // largest HQUAD / hand array it takes
 #define LF_SC_GRID_STATE_BYTES (64 + 1024 + 32 * LF_SC_GRID_WGS + 4 * LF_SC_GRID_WGS + 64 + 36 * LF_SC_GRID_MAX)
 #define LF_SC_SMALL_MAX 8192  // largest HQUAD / hand array the single-workgroup step takes
+
+// K14, the batch axis (sumcheck.hip): B statements of one quad per launch.  Statement b's arrays are `base + b * stride`
+// (strides in elements of the array; 0 = shared by all statements), its challenge is r[b].
+#define LF_SC_BATCH_SLOT_WORDS 16
+struct ScBatchChal {
+  elt_t r[LFGPU_SC_BATCH_MAX];
+};
+struct ScSmallBatch {
+  ScSmall a;  // statement 0; a.r is not used
+  size_t s_hc_in, s_vc_in, s_hc_out, s_vc_out, s_W[2], s_Wdst, s_QW /* words */;
+};
+int lf_scb_mailbox(lfgpu_ctx* c);
+int lf_scb_wait(lfgpu_ctx* c, u32 B, u64 seq);
+int lf_scb_eval_large(lfgpu_ctx* c, int field, u32 B, size_t nh, const void* d_hc, const void* d_vc, size_t s_vc, int hand, const void* d_Wo, size_t s_wo,
+                      const void* d_Wh, size_t s_wh, size_t nq, void* d_qw, size_t s_qw_words, void* d_partial, u64 seq);
+int lf_scb_bind_both(lfgpu_ctx* c, int field, u32 B, size_t n0, const ScBatchChal& ch, const void* d_in, size_t s_in, void* d_out, size_t s_out, size_t n,
+                     const void* d_hc, const void* d_vc, size_t s_vc, int hand, const u32* d_off, void* d_hc_out, void* d_vc_out, size_t s_vco);
+int lf_scb_small_step(lfgpu_ctx* c, const ScSmallBatch& sb, const ScBatchChal& ch, u32 B, u64 seq);
+#define LF_SCB_PARTIAL_ELTS (2 * 1024)  // per statement: two sums per block of the partial-sums kernel (SC_MAX_BLOCKS)
 
 int lf_hquad_bind_h_cached(lfgpu_ctx* c, int field, size_t n, const void* d_hc, const void* d_vc, const uint64_t r[2], int hand,
                            void* d_hc_out, void* d_vc_out, const u32* d_off_cached, u32** d_off_keep, size_t* n_out);  // sumcheck.hip

@@ -1141,6 +1141,230 @@ extern "C" int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0
   return sc_layer(q, logv, h_G0, h_G1, alpha, beta, logw, nw, d_W, wc_in, round, user, wc_out, g_out, bound_quad, nullptr);
 }
 
+// ---- K14: ProverLayers::layer (logc = 0) for B statements of one quad in lock-step ("the batch axis").
+// Shared by all statements: the corner indices `hc` (one ping-pong for the large round-hands), the HQUAD size, the recorded bind
+// offsets q->bind_shape.  Per statement: vc, W, QW, the challenge -- arrays of [B] slabs.  A large round-hand is four launches
+// (scatter, partial sums, final sums | bind of both arrays) and a small one a single launch of B workgroups, whatever B; every
+// round-hand has ONE host round trip, through one mailbox slot per statement.  No resident kernel, no CU budget, no LFGPU_SC_*
+// switch: sc_layer and everything it calls are untouched.
+static int sc_layer_batch(lfgpu_quad* q, size_t B, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha, const uint64_t* beta, size_t logw,
+                          size_t nw, void* d_W, size_t ldw, const uint64_t* wc_in, lfgpu_sc_round_batch_fn round, void* user, uint64_t* wc_out,
+                          uint64_t* g_out, uint64_t* bound_quad) {
+  if (!q) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = q->c;
+  const int field = q->field;
+  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "sumcheck_layer_batch: Fp256Base layers run inside the ZK driver (zk256.hip)");
+  if (B == 0 || B > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch: nb must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (!alpha || !beta || !d_W || !wc_in || !round || !wc_out || !g_out || (logv && (!h_G0 || !h_G1)) || nw == 0 || logw > 40 || nw > ((size_t)1 << logw) ||
+      nw <= q->hmax || ldw < nw || logv > 40 || ((size_t)1 << logv) < q->nv)
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch: bad argument (nw must exceed the largest hand index, ldw >= nw, 2^logv >= nv)");
+  const size_t nt = q->n;
+  if ((nt >> 32) || (nw >> 32) || ((ldw * B) >> 40)) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch: more than 2^32 terms or wires");
+  LF_HIP(c, hipSetDevice(c->device));
+  const HostField F(c, field, false);
+  // device state (64-bit sizes): hc once, everything else B times; reserved -- with every scratch the helpers below take -- before
+  // the first launch, so that a request that cannot be met fails here
+  auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  const size_t qwb = nw * (field == LFGPU_FIELD_FP128 ? 32 : 16);  // GF: the accumulator; Fp128: 4 limb words per target
+  const size_t halfe = (nw + 1) / 2;
+  const size_t hs = std::min<size_t>(nt, LF_SC_SMALL_MAX);  // a statement's own corners from the hand-off to the fused steps on
+  const size_t o_hc = 0, o_vc = o_hc + 2 * up(nt * 8), o_qw = o_vc + 2 * up(B * nt * 16), o_wt = o_qw + up(B * qwb), o_hcs = o_wt + 4 * up(B * halfe * 16);
+  const size_t bytes = o_hcs + 2 * up(B * hs * 8) + 256;
+  void* sc = nullptr;
+  void* partial = nullptr;
+  void* sc34 = nullptr;
+  LF_TRY(lf_scratch(c, bytes, &sc));
+  {
+    const u32 lb = (u32)(logv / 2), hb = (u32)logv - lb;
+    const size_t eq_tab = 2 * (((size_t)1 << lb) + ((size_t)1 << hb)) * 16 + 64;                 // lf_raw_eq2_clear
+    const size_t offs = ((nt + 255) / 256) * 4 + 64;                                             // the count + scan of a recorded bind
+    LF_TRY(lf_scratch2(c, std::max(std::max(eq_tab, offs), B * LF_SCB_PARTIAL_ELTS * 16 + 64), &partial));
+    LF_TRY(lf_scratch3(c, q->nv * 16 + 256, &sc34));                                            // lf_quad_bind_g: the EQ vector
+    if (field == LFGPU_FIELD_FP128) LF_TRY(lf_scratch4(c, q->nh0 * 32 + 64, &sc34));            // ... and its limb accumulators
+  }
+  LF_TRY(lf_scb_mailbox(c));
+  volatile u64* const mb = c->sc_batch_h;
+  uint8_t* const base = (uint8_t*)sc;
+  void* hc[2] = {base + o_hc, base + o_hc + up(nt * 8)};
+  void* vc[2] = {base + o_vc, base + o_vc + up(B * nt * 16)};
+  void* qw = base + o_qw;
+  void* wt[4];
+  for (int k = 0; k < 4; ++k) wt[k] = base + o_wt + (size_t)k * up(B * halfe * 16);
+  void* hcs[2] = {base + o_hcs, base + o_hcs + up(B * hs * 8)};
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  auto clk = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double tv0 = verbose ? clk() : 0;
+  // phase 1 -- Quad::bind_g per statement, enqueued back to back, nothing read back.  The corners are the same for every statement:
+  // statement 0 writes them, the others write theirs into the half of the ping-pong that the first bind overwrites
+  size_t nh = 0;
+  const uint8_t* G0 = (const uint8_t*)h_G0;
+  const uint8_t* G1 = (const uint8_t*)h_G1;
+  for (size_t b = 0; b < B; ++b)
+    LF_TRY(lf_quad_bind_g(q, logv, G0 ? G0 + b * logv * 16 : nullptr, G1 ? G1 + b * logv * 16 : nullptr, alpha + 2 * b, beta + 2 * b, b == 0 ? hc[0] : hc[1],
+                          (uint8_t*)vc[0] + b * nt * 16, &nh));
+  const double tv1 = verbose ? clk() : 0;
+  const size_t nh0 = nh;
+  std::vector<elt_t> sum(B);
+  for (size_t b = 0; b < B; ++b) {
+    const uint64_t* w = wc_in + 4 * b;
+    sum[b] = F.add(elt_t{w[0], w[1]}, F.mul(elt_t{alpha[2 * b], alpha[2 * b + 1]}, elt_t{w[2], w[3]}));
+  }
+  struct Arr {
+    void* p;
+    size_t stride;  // elements between two statements
+  };
+  Arr WH[2] = {{d_W, ldw}, {d_W, ldw}};
+  size_t nW[2] = {nw, nw};
+  int cur = 0;                 // half of the vc ping-pong (and, while the corners are shared, of hc) that holds the HQUAD
+  Arr hcp = {hc[0], 0};        // where the corners are: shared until the first bind of a fused step, then per statement
+  int scur = -1;               // ... and then the half of hcs
+  ScBatchChal ch{};
+  bool pending = false;  // the binds of round-hand `phand` with the challenges in `ch` ride in the next fused step
+  int phand = 0;
+  bool qw_clean = false;
+  size_t n_large = 0;
+  double t_large = 0, t_small_first = 0, t_cb = 0;
+  std::vector<uint64_t> evw(B * 6), rr(B * 2);
+  // one fused step for all statements with the current host-side state; the sums (or the read-out) are then in the mailbox
+  auto small_step = [&](int do_eval, int eval_hand) -> int {
+    ScSmallBatch sb{};
+    ScSmall& a = sb.a;
+    a.field = field;
+    a.do_bind = pending ? 1 : 0;
+    a.bind_hand = phand;
+    a.do_eval = do_eval;
+    a.eval_hand = eval_hand;
+    a.hc_in = (uint2*)hcp.p;
+    sb.s_hc_in = hcp.stride;
+    a.vc_in = (elt_t*)vc[cur];
+    a.hc_out = (uint2*)hcs[scur < 0 ? 0 : 1 - scur];
+    a.vc_out = (elt_t*)vc[1 - cur];
+    sb.s_vc_in = sb.s_vc_out = nt;
+    sb.s_hc_out = hs;
+    a.nh = (u32)nh;
+    for (int k = 0; k < 2; ++k) {
+      a.W[k] = (elt_t*)WH[k].p;
+      sb.s_W[k] = WH[k].stride;
+      a.nW[k] = (u32)nW[k];
+    }
+    const Arr dst = (pending && phand == 0 && WH[0].p == d_W) ? Arr{wt[0], halfe} : WH[phand];  // hand 0 detaches from the shared input
+    a.Wdst = (elt_t*)dst.p;
+    sb.s_Wdst = dst.stride;
+    a.QW = (u64*)qw;
+    sb.s_QW = qwb / 8;
+    const u64 seq = ++c->poll_seq;
+    LF_TRY(lf_scb_small_step(c, sb, ch, (u32)B, seq));
+    LF_TRY(lf_scb_wait(c, (u32)B, seq));
+    if (pending) {
+      WH[phand] = dst;
+      nW[phand] = (nW[phand] + 1) / 2;
+      nh = (size_t)mb[4];
+      for (size_t b = 1; b < B; ++b)
+        if (mb[b * LF_SC_BATCH_SLOT_WORDS + 4] != nh) return lf_fail(c, LFGPU_ERR_ASSERT, "sumcheck_layer_batch: the statements' HQUAD sizes differ");
+      cur = 1 - cur;
+      scur = scur < 0 ? 0 : 1 - scur;
+      hcp = Arr{hcs[scur], hs};
+      pending = false;
+    }
+    return LFGPU_OK;
+  };
+  for (size_t rnd = 0; rnd < logw; ++rnd) {
+    for (int hand = 0; hand < 2; ++hand) {
+      const double tr0 = verbose ? clk() : 0;
+      const bool fused = std::max(nh, std::max(nW[0], nW[1])) <= LF_SC_SMALL_MAX;
+      if (fused) {  // phase 3: one launch, workgroup b = statement b
+        if (verbose && t_small_first == 0) t_small_first = clk();
+        LF_TRY(small_step(1, hand));
+      } else {  // phase 2: scatter, partial sums, final sums -> B posts
+        if (!qw_clean) {  // once per layer: the sums leave every accumulator they have read zero
+          LF_HIP(c, hipMemsetAsync(qw, 0, B * qwb, c->stream));
+          qw_clean = true;
+        }
+        const u64 seq = ++c->poll_seq;
+        LF_TRY(lf_scb_eval_large(c, field, (u32)B, nh, hc[cur], vc[cur], nt, hand, WH[1 - hand].p, WH[1 - hand].stride, WH[hand].p, WH[hand].stride, nW[hand], qw,
+                                 qwb / 8, partial, seq));
+        LF_TRY(lf_scb_wait(c, (u32)B, seq));
+      }
+      // per statement, as sc_layer: coef[1] from the running sum (prover_layers.h:390-396), the three evaluations
+      std::vector<elt_t> ev(3 * B);
+      for (size_t b = 0; b < B; ++b) {
+        const volatile u64* m = mb + b * LF_SC_BATCH_SLOT_WORDS;
+        elt_t coef[3];
+        coef[0] = elt_t{m[0], m[1]};
+        coef[2] = elt_t{m[2], m[3]};
+        coef[1] = F.sub(F.sub(F.sub(sum[b], coef[0]), coef[0]), coef[2]);
+        for (int k = 0; k < 3; ++k) {
+          ev[3 * b + k] = F.eval_monomial(coef, F.pts[k]);
+          evw[6 * b + 2 * k] = ev[3 * b + k].lo;
+          evw[6 * b + 2 * k + 1] = ev[3 * b + k].hi;
+        }
+      }
+      const double tcb0 = verbose ? clk() : 0;
+      round(user, (size_t)hand, rnd, B, (const uint64_t(*)[3][2])evw.data(), (uint64_t(*)[2])rr.data());
+      if (verbose) t_cb += clk() - tcb0;
+      for (size_t b = 0; b < B; ++b) {
+        const elt_t r{rr[2 * b], rr[2 * b + 1]};
+        g_out[((b * 2 + hand) * logw + rnd) * 2] = r.lo;
+        g_out[((b * 2 + hand) * logw + rnd) * 2 + 1] = r.hi;
+        sum[b] = F.eval_lagrange(&ev[3 * b], r);
+        ch.r[b] = r;
+      }
+      if (fused) {  // the binds run at the head of the next fused step
+        pending = true;
+        phand = hand;
+        continue;
+      }
+      // Dense::bind (out of place, ping-pong between the hand's two half-size buffers) + HQuad::bind_h of all statements: one launch
+      void* dst = wt[2 * hand];
+      if (dst == WH[hand].p) dst = wt[2 * hand + 1];
+      const size_t rh = 2 * rnd + hand;
+      if (q->bind_shape.size() < 2 * logw) q->bind_shape.resize(2 * logw, lfgpu_quad::BindShape{nullptr, 0, 0});
+      lfgpu_quad::BindShape& bs = q->bind_shape[rh];
+      if (nh > 0 && !(bs.d_off && bs.n_in == nh)) {
+        // no (valid) record of this round-hand's merge structure: taken once through the count + scan path on the shared corners,
+        // as sc_layer records it (statement 0's bind runs here and again, with the same result, in the launch below)
+        if (bs.d_off) (void)hipFree(bs.d_off);
+        bs = lfgpu_quad::BindShape{nullptr, nh, 0};
+        const uint64_t r0[2] = {ch.r[0].lo, ch.r[0].hi};
+        size_t nout = 0;
+        LF_TRY(lf_hquad_bind_h_cached(c, field, nh, hc[cur], vc[cur], r0, hand, hc[1 - cur], vc[1 - cur], nullptr, &bs.d_off, &nout));
+        bs.n_out = nout;
+      }
+      LF_TRY(lf_scb_bind_both(c, field, (u32)B, nW[hand], ch, WH[hand].p, WH[hand].stride, dst, halfe, nh, hc[cur], vc[cur], nt, hand, bs.d_off, hc[1 - cur],
+                              vc[1 - cur], nt));
+      WH[hand] = Arr{dst, halfe};
+      nW[hand] = (nW[hand] + 1) / 2;
+      if (nh) nh = bs.n_out;
+      cur = 1 - cur;
+      hcp = Arr{hc[cur], 0};
+      if (verbose) {
+        t_large += clk() - tr0;
+        ++n_large;
+      }
+    }
+  }
+  // the last binds (if any) and the read-out of W[0][0], W[1][0] and the HQUAD scalar per statement
+  LF_TRY(small_step(0, 0));
+  for (size_t b = 0; b < B; ++b) {
+    const volatile u64* m = mb + b * LF_SC_BATCH_SLOT_WORDS;
+    for (int k = 0; k < 4; ++k) wc_out[4 * b + k] = m[k];
+    if (bound_quad) {
+      bound_quad[2 * b] = m[6];
+      bound_quad[2 * b + 1] = m[7];
+    }
+  }
+  if (verbose)
+    fprintf(stderr, "lfgpu sumcheck_layer_batch: B %zu nterms %zu nh0 %zu nw %zu logw %zu | bind_g %.0f us | %zu large round-hands %.0f us | %zu small %.0f us | caller's round callback %.1f us in all\n",
+            B, nt, nh0, nw, logw, tv1 - tv0, n_large, t_large, 2 * logw - n_large, t_small_first ? clk() - t_small_first : 0.0, t_cb);
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_sumcheck_layer_batch(lfgpu_quad* q, size_t nb, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha,
+                                          const uint64_t* beta, size_t logw, size_t nw, void* d_W, size_t ldw, const uint64_t* wc_in,
+                                          lfgpu_sc_round_batch_fn round, void* user, uint64_t* wc_out, uint64_t* g_out, uint64_t* bound_quad) {
+  return sc_layer_batch(q, nb, logv, h_G0, h_G1, alpha, beta, logw, nw, d_W, ldw, wc_in, round, user, wc_out, g_out, bound_quad);
+}
+
 extern "C" int lfgpu_sumcheck_layer_copies(lfgpu_quad* q, size_t logc, size_t nc, const void* h_Q, size_t logv, const void* h_G0, const void* h_G1,
                                            const uint64_t alpha[2], const uint64_t beta[2], size_t logw, size_t nw, void* d_W,
                                            const uint64_t wc_in[2][2], lfgpu_sc_round_c_fn round_c, lfgpu_sc_round_fn round_h, void* user,

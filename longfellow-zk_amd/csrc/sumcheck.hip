@@ -217,7 +217,9 @@ __global__ __launch_bounds__(1024) void hquad_scan_kernel(u32 nblocks, u32* __re
   }
   if (threadIdx.x == 0) *total = carry;
 }
-template <int F>
+// WRITE_HC = false (the batched kernels, statements b > 0): the halved corners are the same for every statement of a batch, so
+// only statement 0 stores them
+template <int F, bool WRITE_HC = true>
 __device__ __forceinline__ void hquad_emit_body(u32 bx, u32* wave_off /* LDS, SC_THREADS / 64 words */, size_t n, const uint2* __restrict__ hc,
                                                 const elt_t* __restrict__ vc, elt_t r, int hand, const u32* __restrict__ block_off,
                                                 uint2* __restrict__ hc_out, elt_t* __restrict__ vc_out) {
@@ -243,7 +245,7 @@ __device__ __forceinline__ void hquad_emit_body(u32 bx, u32* wave_off /* LDS, SC
     v = Fld<F>::mul(v0, r);  // affine_interpolation_z_nz
   }
   if (hand) h.y = hh >> 1; else h.x = hh >> 1;
-  hc_out[off] = h;
+  if (WRITE_HC) hc_out[off] = h;
   st16(&vc_out[off], v);
 }
 template <int F>
@@ -1794,6 +1796,235 @@ int lf_bind_both_cached(lfgpu_ctx* c, int field, size_t n0, const uint64_t r[2],
   const elt_t rr{r[0], r[1]};
   DISPATCH_FIELD(field, bind_both_kernel, dim3(nbD + nbH), dim3(SC_THREADS), nbD, n0, rr, (const elt_t*)d_in, (elt_t*)d_out, n, (const uint2*)d_hc,
                  (const elt_t*)d_vc, hand ? 1 : 0, d_off_cached, (uint2*)d_hc_out, (elt_t*)d_vc_out);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+// ------------------------------------------------------------------ K14: the batch axis
+// B statements of ONE quad in lock-step (lfgpu_sumcheck_layer_batch, quad.hip: sc_layer_batch).  The corner indices `hc`, the
+// HQUAD size and the merge structure of every HQuad::bind_h are circuit constants, so all statements share one `hc` and one set
+// of recorded offsets; what differs per statement (vc, W, QW, the challenge) is `base + b * stride`.  The per-launch kernels take
+// the statement from blockIdx.y, the fused step from blockIdx.x; the arithmetic bodies are the ones above, so statement b's
+// bytes are those of the single call.  Every launch posts to slot b of the batch mailbox (LF_SC_BATCH_SLOT_WORDS words each,
+// laid out like poll_h: a0, a2, nh, seq, scalar, status).
+__global__ __launch_bounds__(SCAT_THREADS) void qw_scatter_gf_batch_kernel(size_t n, const uint2* __restrict__ hc, const elt_t* __restrict__ vc,
+                                                                           size_t s_vc, int hand, const elt_t* __restrict__ Wo, size_t s_wo,
+                                                                           u64* __restrict__ QW, size_t s_qw /* words */) {
+  const size_t b = blockIdx.y;
+  vc += b * s_vc;
+  Wo += b * s_wo;
+  QW += b * s_qw;
+  const size_t i = (size_t)blockIdx.x * SCAT_THREADS + threadIdx.x;
+  u32 key = 0xffffffffu;
+  elt_t t = elt_zero();
+  if (i < n) {
+    uint2 h = hc[i];
+    key = hand ? h.y : h.x;
+    t = gf_mul(ld16(&vc[i]), ld16(&Wo[hand ? h.x : h.y]));
+  }
+  gf_run_fold_commit<SCAT_THREADS>(key, t, QW);
+}
+__global__ __launch_bounds__(SC_THREADS) void qw_scatter_fp_batch_kernel(size_t n, const uint2* __restrict__ hc, const elt_t* __restrict__ vc,
+                                                                         size_t s_vc, int hand, const elt_t* __restrict__ Wo, size_t s_wo,
+                                                                         u64* __restrict__ acc, size_t s_acc /* words */) {
+  const size_t b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * SC_THREADS + threadIdx.x;
+  if (i >= n) return;
+  uint2 h = hc[i];
+  const u32 p0 = hand ? h.y : h.x, p1 = hand ? h.x : h.y;
+  elt_t t = fp_mul(ld16(&vc[b * s_vc + i]), ld16(&Wo[b * s_wo + p1]));
+  u64* a = acc + b * s_acc + 4 * (size_t)p0;
+  atomicAdd(&a[0], (u64)(u32)t.lo);
+  atomicAdd(&a[1], t.lo >> 32);
+  atomicAdd(&a[2], (u64)(u32)t.hi);
+  atomicAdd(&a[3], t.hi >> 32);
+}
+// accumulator j of one statement, left zero for the next scatter (the self-cleaning read of sumcheck_partials_kernel); Fp128: the
+// four limb sums are recombined here (fp_reduce_limbs, as fp_limb_normalize_kernel does) instead of in a launch of their own
+template <int F>
+__device__ __forceinline__ elt_t scb_take(u64* QW, size_t j) {
+  if (F == FIELD_GF2_128) {
+    elt_t* q = reinterpret_cast<elt_t*>(QW) + j;
+    const elt_t v = ld16(q);
+    st16(q, elt_zero());
+    return v;
+  }
+  elt_t* q = reinterpret_cast<elt_t*>(QW + 4 * j);
+  const elt_t l01 = ld16(q), l23 = ld16(q + 1);
+  st16(q, elt_zero());
+  st16(q + 1, elt_zero());
+  return fp_reduce_limbs(l01.lo, l01.hi, l23.lo, l23.hi);
+}
+template <int F>
+__global__ __launch_bounds__(SC_THREADS) void sumcheck_partials_batch_kernel(size_t n, u64* QW, size_t s_qw /* words */, const elt_t* __restrict__ W,
+                                                                             size_t s_w, elt_t* __restrict__ partial) {
+  __shared__ elt_t sh[SC_THREADS / 64];
+  const size_t b = blockIdx.y;
+  QW += b * s_qw;
+  W += b * s_w;
+  partial += b * 2 * (size_t)gridDim.x;
+  const size_t nodd = n / 2;
+  elt_t a0 = elt_zero(), a2 = elt_zero();
+  for (size_t i = (size_t)blockIdx.x * SC_THREADS + threadIdx.x; i < nodd; i += (size_t)gridDim.x * SC_THREADS) {
+    const elt_t q0 = scb_take<F>(QW, 2 * i), q1 = scb_take<F>(QW, 2 * i + 1);
+    const elt_t w0 = ld16(&W[2 * i]), w1 = ld16(&W[2 * i + 1]);
+    a0 = Fld<F>::add(a0, Fld<F>::mul(q0, w0));
+    a2 = Fld<F>::add(a2, Fld<F>::mul(Fld<F>::sub(q1, q0), Fld<F>::sub(w1, w0)));
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0 && 2 * nodd < n) {  // odd tail (prover_layers.h:381-388)
+    const elt_t t = Fld<F>::mul(scb_take<F>(QW, 2 * nodd), ld16(&W[2 * nodd]));
+    a0 = Fld<F>::add(a0, t);
+    a2 = Fld<F>::add(a2, t);
+  }
+  a0 = block_reduce<F>(a0, sh);
+  a2 = block_reduce<F>(a2, sh);
+  if (threadIdx.x == 0) {
+    st16(&partial[2 * blockIdx.x], a0);
+    st16(&partial[2 * blockIdx.x + 1], a2);
+  }
+}
+template <int F>
+__global__ __launch_bounds__(SC_THREADS) void sumcheck_final_batch_kernel(u32 nblocks, const elt_t* __restrict__ partial, volatile u64* post, u64 seq) {
+  __shared__ elt_t sh[SC_THREADS / 64];
+  const size_t b = blockIdx.y;
+  partial += b * 2 * (size_t)nblocks;
+  elt_t a0 = elt_zero(), a2 = elt_zero();
+  for (u32 k = threadIdx.x; k < nblocks; k += SC_THREADS) {
+    a0 = Fld<F>::add(a0, ld16(&partial[2 * k]));
+    a2 = Fld<F>::add(a2, ld16(&partial[2 * k + 1]));
+  }
+  a0 = block_reduce<F>(a0, sh);
+  a2 = block_reduce<F>(a2, sh);
+  if (threadIdx.x == 0) {
+    u64* po = (u64*)post + b * LF_SC_BATCH_SLOT_WORDS;
+    __hip_atomic_store(&po[0], a0.lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&po[1], a0.hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&po[2], a2.lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&po[3], a2.hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&po[8], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __threadfence_system();
+    __hip_atomic_store(&po[5], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+// bind_both_kernel for all statements, each with its own challenge (a kernel argument: 16 bytes per statement)
+template <int F>
+__global__ __launch_bounds__(SC_THREADS) void bind_both_batch_kernel(u32 nbD, size_t n0, ScBatchChal ch, const elt_t* __restrict__ in, size_t s_in,
+                                                                     elt_t* __restrict__ out, size_t s_out, size_t n, const uint2* __restrict__ hc,
+                                                                     const elt_t* __restrict__ vc, size_t s_vc, int hand,
+                                                                     const u32* __restrict__ block_off, uint2* __restrict__ hc_out,
+                                                                     elt_t* __restrict__ vc_out, size_t s_vco) {
+  __shared__ u32 wave_off[SC_THREADS / 64];
+  const size_t b = blockIdx.y;
+  const elt_t r = ch.r[b];
+  if (blockIdx.x < nbD) dense_bind_body<F>(blockIdx.x, n0, r, in + b * s_in, out + b * s_out);
+  else if (b == 0) hquad_emit_body<F, true>(blockIdx.x - nbD, wave_off, n, hc, vc, r, hand, block_off, hc_out, vc_out);
+  else hquad_emit_body<F, false>(blockIdx.x - nbD, wave_off, n, hc, vc + b * s_vc, r, hand, block_off, hc_out, vc_out + b * s_vco);
+}
+// sc_small_step_kernel on statement blockIdx.x
+template <int F>
+__global__ __launch_bounds__(SM_THREADS) void sc_small_step_batch_kernel(ScSmallBatch sb, ScBatchChal ch, u64 seq, volatile u64* __restrict__ post) {
+  __shared__ ScShared sh;
+  const size_t b = blockIdx.x;
+  const ScSmall& a = sb.a;
+  ScState st;
+  st.hc = a.hc_in + b * sb.s_hc_in;
+  st.vc = a.vc_in + b * sb.s_vc_in;
+  st.hc_other = a.hc_out + b * sb.s_hc_out;
+  st.vc_other = a.vc_out + b * sb.s_vc_out;
+  st.nh = a.nh;
+  st.W[0] = a.W[0] + b * sb.s_W[0];
+  st.W[1] = a.W[1] + b * sb.s_W[1];
+  st.nW[0] = a.nW[0];
+  st.nW[1] = a.nW[1];
+  if (a.do_bind) sc_bind<F>(st, sh, a.bind_hand, ch.r[b], a.Wdst + b * sb.s_Wdst);
+  elt_t a0 = elt_zero(), a2 = elt_zero();
+  if (a.do_eval) sc_eval<F>(st, sh, a.eval_hand, a.QW + b * sb.s_QW, a0, a2);
+  if (threadIdx.x == 0) {
+    if (!a.do_eval) {  // end of the layer: the two bound hand arrays (and the HQUAD scalar)
+      a0 = st.nW[0] ? ld16(&st.W[0][0]) : elt_zero();
+      a2 = st.nW[1] ? ld16(&st.W[1][0]) : elt_zero();
+    }
+    sc_post(st, a0, a2, seq, 0, post + b * LF_SC_BATCH_SLOT_WORDS);
+  }
+}
+
+int lf_scb_mailbox(lfgpu_ctx* c) {
+  if (c->sc_batch_h) return LFGPU_OK;
+  void* p = nullptr;
+  if (hipHostMalloc(&p, (size_t)LFGPU_SC_BATCH_MAX * LF_SC_BATCH_SLOT_WORDS * 8, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+    (void)hipGetLastError();
+    return lf_fail(c, LFGPU_ERR_NOMEM, "sumcheck_layer_batch: the pinned mailbox");
+  }
+  memset(p, 0, (size_t)LFGPU_SC_BATCH_MAX * LF_SC_BATCH_SLOT_WORDS * 8);
+  c->sc_batch_h = (volatile u64*)p;
+  return LFGPU_OK;
+}
+// waits until all B slots carry `seq` (sc_wait_post's dead-kernel watch: the stream is looked at after 50 ms without a post)
+int lf_scb_wait(lfgpu_ctx* c, u32 B, u64 seq) {
+  volatile u64* const mb = c->sc_batch_h;
+  u64 spins = 0;
+  double t_first = 0;
+  for (u32 b = 0; b < B;) {
+    if (__atomic_load_n((const u64*)&mb[(size_t)b * LF_SC_BATCH_SLOT_WORDS + 5], __ATOMIC_ACQUIRE) == seq) {
+      ++b;
+      continue;
+    }
+    if (spins > 0x8000 && (spins & 0xff) == 0) sched_yield();
+    if ((++spins & 0xfff) == 0) {
+      const double t = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+      if (t_first == 0) t_first = t;
+      if (t - t_first < 50.0) continue;
+      const hipError_t q = hipStreamQuery(c->stream);
+      if (q == hipSuccess) {  // the kernel is over: every post must be visible now
+        if (__atomic_load_n((const u64*)&mb[(size_t)b * LF_SC_BATCH_SLOT_WORDS + 5], __ATOMIC_ACQUIRE) == seq) continue;
+        return lf_fail(c, LFGPU_ERR_ASSERT, "sumcheck batch step: kernel finished without posting statement %u", b);
+      }
+      if (q != hipErrorNotReady) return lf_fail(c, LFGPU_ERR_HIP, "sumcheck batch step: %s", hipGetErrorString(q));
+    }
+  }
+  for (u32 b = 0; b < B; ++b)
+    if (mb[(size_t)b * LF_SC_BATCH_SLOT_WORDS + 8] != 0) return lf_fail(c, LFGPU_ERR_ASSERT, "sumcheck batch step: statement %u posted status %llu", b, (unsigned long long)mb[(size_t)b * LF_SC_BATCH_SLOT_WORDS + 8]);
+  return LFGPU_OK;
+}
+// scatter + partial sums + final sums of one large round-hand for all statements: three launches whatever B; the sums are posted
+// under `seq`.  d_qw: per statement 2 (GF) / 4 (Fp128 limb sums) words per target, all zero on entry and again afterwards.
+// d_partial: B * 2 * SC_MAX_BLOCKS elements.
+int lf_scb_eval_large(lfgpu_ctx* c, int field, u32 B, size_t nh, const void* d_hc, const void* d_vc, size_t s_vc, int hand, const void* d_Wo, size_t s_wo,
+                      const void* d_Wh, size_t s_wh, size_t nq, void* d_qw, size_t s_qw_words, void* d_partial, u64 seq) {
+  if ((nh >> 32) || (nq >> 32)) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch: more than 2^32 entries");
+  hand = hand ? 1 : 0;
+  if (nh) {
+    if (field == LFGPU_FIELD_GF2_128)
+      hipLaunchKernelGGL(qw_scatter_gf_batch_kernel, dim3((u32)((nh + SCAT_THREADS - 1) / SCAT_THREADS), B), dim3(SCAT_THREADS), 0, c->stream, nh,
+                         (const uint2*)d_hc, (const elt_t*)d_vc, s_vc, hand, (const elt_t*)d_Wo, s_wo, (u64*)d_qw, s_qw_words);
+    else
+      hipLaunchKernelGGL(qw_scatter_fp_batch_kernel, dim3((u32)((nh + SC_THREADS - 1) / SC_THREADS), B), dim3(SC_THREADS), 0, c->stream, nh,
+                         (const uint2*)d_hc, (const elt_t*)d_vc, s_vc, hand, (const elt_t*)d_Wo, s_wo, (u64*)d_qw, s_qw_words);
+  }
+  u32 nb = (u32)((nq / 2 + SC_THREADS - 1) / SC_THREADS);
+  if (nb == 0) nb = 1;
+  if (nb > SC_MAX_BLOCKS) nb = SC_MAX_BLOCKS;
+  DISPATCH_FIELD(field, sumcheck_partials_batch_kernel, dim3(nb, B), dim3(SC_THREADS), nq, (u64*)d_qw, s_qw_words, (const elt_t*)d_Wh, s_wh, (elt_t*)d_partial);
+  DISPATCH_FIELD(field, sumcheck_final_batch_kernel, dim3(1, B), dim3(SC_THREADS), nb, (const elt_t*)d_partial, c->sc_batch_h, seq);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+// Dense::bind (out of place) + HQuad::bind_h with the recorded offsets for all statements, one launch; n == 0: the dense bind alone
+int lf_scb_bind_both(lfgpu_ctx* c, int field, u32 B, size_t n0, const ScBatchChal& ch, const void* d_in, size_t s_in, void* d_out, size_t s_out, size_t n,
+                     const void* d_hc, const void* d_vc, size_t s_vc, int hand, const u32* d_off, void* d_hc_out, void* d_vc_out, size_t s_vco) {
+  if (n0 == 0 || !d_in || !d_out || d_in == d_out || (n && (!d_hc || !d_vc || !d_hc_out || !d_vc_out || !d_off)))
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch: bind operands");
+  const u32 nbD = (u32)(((n0 + 1) / 2 + SC_THREADS - 1) / SC_THREADS), nbH = (u32)((n + SC_THREADS - 1) / SC_THREADS);
+  DISPATCH_FIELD(field, bind_both_batch_kernel, dim3(nbD + nbH, B), dim3(SC_THREADS), nbD, n0, ch, (const elt_t*)d_in, s_in, (elt_t*)d_out, s_out, n,
+                 (const uint2*)d_hc, (const elt_t*)d_vc, s_vc, hand ? 1 : 0, d_off, (uint2*)d_hc_out, (elt_t*)d_vc_out, s_vco);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+// one fused step for all statements (a grid of B workgroups), posted under `seq`
+int lf_scb_small_step(lfgpu_ctx* c, const ScSmallBatch& sb, const ScBatchChal& ch, u32 B, u64 seq) {
+  if (sb.a.nh > LF_SC_SMALL_MAX || sb.a.nW[0] > LF_SC_SMALL_MAX || sb.a.nW[1] > LF_SC_SMALL_MAX)
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch: operands larger than the single-workgroup bound");
+  DISPATCH_FIELD(sb.a.field, sc_small_step_batch_kernel, dim3(B), dim3(SM_THREADS), sb, ch, seq, c->sc_batch_h);
   LF_HIP(c, hipGetLastError());
   return LFGPU_OK;
 }
