@@ -5,7 +5,8 @@
 //     instead of added to a zeroed one (one v_mov per column instead of two); the REDC never forms m = -U: it computes
 //     T_hi - U + (U >> 20) + cy and adds p when that is negative (a sign from two carry masks merged by one SALU
 //     instruction): 27 -> 19 VALU instructions for the REDC, 71 -> 63 -> 55 per product; the first mad of columns 3, 4 and
-//     5 (a_i b3) cannot carry for w < p and has no capture: 52.
+//     5 (a_i b3) cannot carry for w < p and has no capture: 52; nor can column 2's (a0 b2), for any a and w, and column 1's
+//     first mad reads {acc0.hi, 0} as its addend and writes a fresh pair, which spares column 0 its 64-bit move: 50.
 //   - fpt_add: the carry-out of a + b stays a lane mask and is merged with the borrow of (a + b) - p by one SALU
 //     instruction: 14 -> 12 VALU instructions.
 //   - fpt_sub: the borrow of a - b, kept in an SGPR pair, is the carry-in of the + p chain: 10 -> 9.
@@ -157,23 +158,29 @@ __device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
 // Columns 3, 4 and 5 start with a0 b3, a1 b3 and a2 b3.  The accumulator that enters such a column is {acc.hi, ov} with
 // acc.hi < 2^32 and ov <= 3 (at most three captures in the column before), so it is < 2^34; the first product is at most
 // (2^32 - 1) 0xfffff000 = 2^64 - 2^44 - 2^32 + 2^12; the sum is < 2^64 - 2^44 + 2^34 < 2^64 whatever a is, lazy values
-// included.  That mad cannot carry and is a bare FP_MAD; the column's second mad is the one whose capture writes ov.  Column 2
-// starts with a0 b2, which this bound does not cover (b2 may be 0xffffffff), and keeps its three captures.  13 -> 10 captures,
-// 55 -> 52 VALU instructions per product, same values.  With b3 = 0xffffffff (no field element) column 3's first mad does
-// wrap: tests/test_fp_tile_mul_carries.py has the model, the case and the inputs that reach these carries on the device.
+// included.  That mad cannot carry and is a bare FP_MAD; the column's second mad is the one whose capture writes ov.  13 -> 10
+// captures, 55 -> 52 VALU instructions per product, same values.  With b3 = 0xffffffff (no field element) column 3's first mad
+// does wrap: tests/test_fp_tile_mul_carries.py has the model, the case and the inputs that reach these carries on the device.
+//
+// Column 2 starts with a0 b2, which that bound does not cover (b2 may be 0xffffffff), but another does, for every a and w: column
+// 1's true sum is at most (2^32 - 2) + 2 (2^32 - 1)^2 = 2^65 - 3 2^32, so column 2's accumulator comes in at no more than
+// 2^33 - 3, and a0 b2 <= 2^64 - 2^33 + 1 brings it to 2^64 - 2 at the most.  Its capture is gone too and a1 b1's writes ov: 9
+// captures.  Column 0 has no carry, so column 1's accumulator is {acc0.hi, 0}; its first mad takes that pair as the addend
+// of an out-of-place v_mad_u64_u32 (the pair's high half is a register the compiler keeps at zero, its low half one v_mov_b32)
+// instead of shifting acc0 in place, which cost a v_mov_b32 and a v_mov_b64.  52 -> 50 (tests/test_fp_tile_mul50.py).
 __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   FP_W(a, a0, a1, a2, a3);
   FP_W(b, b0, b1, b2, b3);
   u32 t0, t1, t2, t3, t4, t5, t6, t7, ov;
-  u64 acc;
-  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(acc) : "v"(a0), "v"(b0) : "vcc");
-  t0 = (u32)acc;
-  acc >>= 32;
-  FP_MAD(acc, a0, b1);  // < 2^64: (2^32 - 1)^2 + 2^32 - 1
+  u64 acc0, acc;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(acc0) : "v"(a0), "v"(b0) : "vcc");
+  t0 = (u32)acc0;
+  // out of place, the addend {acc0.hi, 0}; < 2^64: (2^32 - 1)^2 + 2^32 - 1
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(acc) : "v"(a0), "v"(b1), "v"(acc0 >> 32) : "vcc");
   FPT_MADW(acc, ov, a1, b0);
   FPT_COL(t1, acc, ov);
-  FPT_MADW(acc, ov, a0, b2);
-  FP_MADC(acc, ov, a1, b1);
+  FP_MAD(acc, a0, b2);  // < 2^64 for every a and w (see above)
+  FPT_MADW(acc, ov, a1, b1);
   FP_MADC(acc, ov, a2, b0);
   FPT_COL(t2, acc, ov);
   FP_MAD(acc, a0, b3);  // < 2^64 for b3 <= 0xfffff000: no capture (see above), and so in columns 4 and 5
@@ -200,44 +207,47 @@ __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   // + (U >> 20) + cy, W = (d3..d0) + (c - b) 2^128, so W < 0 <=> b and no c.  The cy link needs no s_nop: eight VALU
   // instructions lie between its write and its read.  d0..d3 are outputs of their own, not T_hi's registers, so the
   // allocator can put the result where its user wants it (tied to T_hi, pass A's one-tile kernel needed 23 more VALU).
+  // U and U >> 20 have none: u3 is formed in t3's register, and once T_hi - U has read U the shifts overwrite it (t0..t3
+  // are dead after the reduction).  Five temporaries fewer, which keeps pass A at 71 VGPRs with the 50-instruction product.
   const u32 k = t0 << 12;
   u32 d0, d1, d2, d3;
   {
-    u32 u3, s0, s1, s2, s3, e3;
+    u32 e3;
     u64 cy, b;
-    asm("v_add_co_u32 %4, %10, %12, %16\n\t"  // u3, cy
-        "v_alignbit_b32 %5, %14, %13, 20\n\t"  // U >> 20
-        "v_alignbit_b32 %6, %15, %14, 20\n\t"
-        "v_alignbit_b32 %7, %4, %15, 20\n\t"
-        "v_lshrrev_b32 %8, 20, %4\n\t"
-        "v_sub_co_u32 %0, vcc, %18, %13\n\t"  // T_hi - U
+    asm("v_add_co_u32 %7, %9, %7, %11\n\t"  // u3 (in t3's register), cy
+        "v_sub_co_u32 %0, vcc, %13, %4\n\t"  // T_hi - U
         "s_nop 1\n\t"
-        "v_subb_co_u32 %1, vcc, %19, %14, vcc\n\t"
+        "v_subb_co_u32 %1, vcc, %14, %5, vcc\n\t"
         "s_nop 1\n\t"
-        "v_subb_co_u32 %2, vcc, %20, %15, vcc\n\t"
+        "v_subb_co_u32 %2, vcc, %15, %6, vcc\n\t"
         "s_nop 1\n\t"
-        "v_subb_co_u32 %3, %11, %21, %4, vcc\n\t"  // borrow-out: lane mask b
-        "v_addc_co_u32 %0, vcc, %0, %5, %10\n\t"  // + (U >> 20) + cy, cy the carry-in
+        "v_subb_co_u32 %3, %10, %16, %7, vcc\n\t"  // borrow-out: lane mask b
+        "v_alignbit_b32 %4, %5, %4, 20\n\t"  // U >> 20, in U's registers
+        "v_alignbit_b32 %5, %6, %5, 20\n\t"
+        "v_alignbit_b32 %6, %7, %6, 20\n\t"
+        "v_lshrrev_b32 %7, 20, %7\n\t"
+        "v_addc_co_u32 %0, vcc, %0, %4, %9\n\t"  // + (U >> 20) + cy, cy the carry-in
         "s_nop 1\n\t"
-        "v_addc_co_u32 %1, vcc, %1, %6, vcc\n\t"
+        "v_addc_co_u32 %1, vcc, %1, %5, vcc\n\t"
         "s_nop 1\n\t"
-        "v_addc_co_u32 %2, vcc, %2, %7, vcc\n\t"
+        "v_addc_co_u32 %2, vcc, %2, %6, vcc\n\t"
         "s_nop 1\n\t"
-        "v_addc_co_u32 %3, %10, %3, %8, vcc\n\t"  // carry-out: lane mask c (in cy's SGPR pair)
+        "v_addc_co_u32 %3, %9, %3, %7, vcc\n\t"  // carry-out: lane mask c (in cy's SGPR pair)
         "s_nop 1\n\t"
-        "s_andn2_b64 %10, %11, %10\n\t"  // W < 0 <=> b and no c
+        "s_andn2_b64 %9, %10, %9\n\t"  // W < 0 <=> b and no c
         // W < 0 => + p: + 1 at limb 0 (the mask is the carry-in), + 0xfffff000 at limb 3, as fpt_sub
-        "v_cndmask_b32 %9, 0, %17, %10\n\t"
-        "v_addc_co_u32 %0, vcc, 0, %0, %10\n\t"
+        "v_cndmask_b32 %8, 0, %12, %9\n\t"
+        "v_addc_co_u32 %0, vcc, 0, %0, %9\n\t"
         "s_nop 1\n\t"
         "v_addc_co_u32 %1, vcc, 0, %1, vcc\n\t"
         "s_nop 1\n\t"
         "v_addc_co_u32 %2, vcc, 0, %2, vcc\n\t"
         "s_nop 1\n\t"
-        "v_addc_co_u32 %3, vcc, %9, %3, vcc"
-        : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "=&v"(u3), "=&v"(s0), "=&v"(s1), "=&v"(s2), "=&v"(s3), "=&v"(e3), "=&s"(cy), "=&s"(b)
-        : "v"(t3), "v"(t0), "v"(t1), "v"(t2), "v"(k), "v"(0xfffff000u), "v"(t4), "v"(t5), "v"(t6), "v"(t7)
+        "v_addc_co_u32 %3, vcc, %8, %3, vcc"
+        : "=&v"(d0), "=&v"(d1), "=&v"(d2), "=&v"(d3), "+v"(t0), "+v"(t1), "+v"(t2), "+v"(t3), "=&v"(e3), "=&s"(cy), "=&s"(b)
+        : "v"(k), "v"(0xfffff000u), "v"(t4), "v"(t5), "v"(t6), "v"(t7)
         : "vcc", "scc");
+    // t0..t3 hold U >> 20 from here on, not the column words: do not read them behind the reduction
   }
   return FP_PACK(d0, d1, d2, d3);
 }
