@@ -224,8 +224,8 @@ int lfgpu_sumcheck_layer(lfgpu_quad* q, size_t logv, const void* h_G0, const voi
                          uint64_t bound_quad[2]);
 
 /* ---- the same layer for a batch of statements in lock-step (K14) -------------------------------------
- * nb statements of ONE quad (one circuit layer, nb witnesses) go through the same launches: bind_g per statement, then every
- * round-hand of all statements in a number of launches that does not depend on nb, with ONE host round trip -- one call of
+ * nb statements of ONE quad (one circuit layer, nb witnesses) go through the same launches: bind_g of all statements in at
+ * most three, then every round-hand of all statements in a number of launches that does not depend on nb, with ONE host round trip -- one call of
  * `round` -- per round-hand.  Statement b's evaluations, wc_out, g_out and bound_quad are byte-identical to what
  * lfgpu_sumcheck_layer produces for statement b alone when its callback returns the same challenges.
  * `round` is called 2 * logw times, in the order (round 0, hand 0), (round 0, hand 1), (round 1, hand 0), ...: evals[b] = the
@@ -243,6 +243,12 @@ int lfgpu_sumcheck_layer_batch(lfgpu_quad* q, size_t nb, size_t logv, const void
                                const uint64_t* beta, size_t logw, size_t nw, void* d_W, size_t ldw, const uint64_t* wc_in,
                                lfgpu_sc_round_batch_fn round, void* user, uint64_t* wc_out, uint64_t* g_out,
                                uint64_t* bound_quad);
+/* ProverLayers::eval_quad (nc = 1) for nb statements of ONE quad in one launch: statement b reads its nw wires at
+ * d_W + b * ldw elements (ldw >= nw) and writes its nv outputs at d_V + b * ldv elements (ldv >= nv); ok_out[b] = 0 if an
+ * assert-zero term of statement b is non-zero, the other statements are unaffected.  1 <= nb <= LFGPU_SC_BATCH_MAX.
+ * Fields: GF2_128 and Fp128; LFGPU_ERR_UNSUPPORTED for P256. */
+int lfgpu_eval_quad_batch(lfgpu_quad* q, size_t nb, size_t nw, const void* d_W, size_t ldw, void* d_V, size_t ldv,
+                          int* ok_out /*[nb]*/);
 
 /* ---- circuits with nc > 1 copies: the copy rounds of the sumcheck (K13) ------------------------------
  * The reference's data-parallel axis: every wire array is Dense(n0 = nc, n1 = nw), stored W[wire * nc + c] (copy index

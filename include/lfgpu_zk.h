@@ -124,6 +124,31 @@ int lfgpu_zk_proof_write(const lfgpu_zk_prover* zk, uint8_t* buf, size_t cap, si
 int lfgpu_zk_timings(const lfgpu_zk_prover* zk, double ms[6]);
 int lfgpu_zk_prover_free(lfgpu_zk_prover* zk);
 
+/* ---- ZkProver::prove for a batch of committed provers ----
+ * nb provers of ONE context and ONE circuit, each committed by lfgpu_zk_commit with its own witness, RandomEngine and
+ * transcript, go through ONE chain of dispatches: eval_circuit is one launch per layer for all statements
+ * (lfgpu_eval_quad_batch) and the padded sumcheck one lfgpu_sumcheck_layer_batch call per layer.  The constraints, the Ligero
+ * prove and the opening then run per statement, one after the other, with the code of lfgpu_zk_prove.  Statement b's proof is
+ * byte-identical to what lfgpu_zk_prove(zk[b], h_W[b], ts[b]) produces and ts[b] is left in the same state; afterwards every
+ * prover holds its own proof (lfgpu_zk_proof_write, lfgpu_zk_timings as before).  ok[b] = 0 when witness b does not satisfy the
+ * circuit: that prover holds no proof, the others are unaffected.
+ * lfgpu_zk_timings after a batch: [2] eval_circuit and [3] sumcheck are the BATCH's phase times and [1] the whole call's, the
+ * same values for every member; [4] constraints and [5] Ligero prove are the statement's own; [0] is its commit's.
+ * The batch object owns the device memory the lock-step needs nb_max times (the layers' inputs, the outputs, their pinned
+ * read-back), allocated once in lfgpu_zk_batch_new: lfgpu_zk_prove_batch neither allocates nor frees device memory.  It is
+ * scrubbed when the batch is freed.  The batch may be freed before or after the provers; the context must outlive it.
+ * The library stays single-threaded per call: the host work per statement -- the Fiat-Shamir preamble (SHA-256 over nterms
+ * zero bytes), the constraints, proof_write -- is serial inside one batch.  A caller that wants more throughput runs several
+ * batches in several contexts (lfgpu_own_stream, lfgpu_circuit_share), as examples/zk_throughput.cc does with provers.
+ * 1 <= nb <= nb_max <= LFGPU_SC_BATCH_MAX.  LFGPU_ERR_ARG: a NULL argument, nb out of range, a prover of another context or
+ * circuit, one that has not committed, the same prover twice.  LFGPU_ERR_UNSUPPORTED: an Fp256Base circuit (at _new), a
+ * prover with a communicator set.  LFGPU_ERR_NOMEM from _new when the slabs do not fit. */
+typedef struct lfgpu_zk_batch lfgpu_zk_batch;
+int lfgpu_zk_batch_new(lfgpu_ctx* ctx, const lfgpu_circuit* c, size_t nb_max, lfgpu_zk_batch** out);
+int lfgpu_zk_prove_batch(lfgpu_zk_batch* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                         const lfgpu_transcript_ops* const* ts, int* ok /*[nb]*/);
+int lfgpu_zk_batch_free(lfgpu_zk_batch* batch);
+
 /* ---- ZkVerifier ----
  * ZkVerifier::recv_commitment + verify (lib/zk/zk_verifier.h:68-94) on the wire bytes of ZkProof::write
  * (parsed as ZkProof::read does, lib/zk/zk_proof.h:107-112,218-345).  h_pub: the npub_in public inputs.

@@ -37,13 +37,14 @@ ABI_SYMBOLS = [
     "lfgpu_ligero_quadratic_proof", "lfgpu_ligero_open", "lfgpu_ligero_tableau", "lfgpu_ligero_free",
     "lfgpu_quad_upload", "lfgpu_quad_free", "lfgpu_eval_quad", "lfgpu_quad_bind_g", "lfgpu_sumcheck_layer", "lfgpu_raw_eq2", "lfgpu_quad_bind_gh_all",
     "lfgpu_eval_quad_copies", "lfgpu_sumcheck_evaluations_c", "lfgpu_dense_bind_rows", "lfgpu_eqs", "lfgpu_sumcheck_layer_copies",
-    "lfgpu_sumcheck_layer_batch",
+    "lfgpu_sumcheck_layer_batch", "lfgpu_eval_quad_batch",
     # include/lfgpu_zk.h
     "lfgpu_transcript_new", "lfgpu_transcript_free", "lfgpu_transcript_get_ops", "lfgpu_transcript_write_bytes",
     "lfgpu_transcript_write_elt", "lfgpu_transcript_write_elt_array", "lfgpu_transcript_bytes", "lfgpu_transcript_write_elt_sized", "lfgpu_transcript_write_elt_array_sized", "lfgpu_sha256",
     "lfgpu_aes256_ecb_block", "lfgpu_host_gf2128_mul", "lfgpu_crypto_hw", "lfgpu_circuit_from_lfc1", "lfgpu_circuit_share", "lfgpu_circuit_get_info", "lfgpu_circuit_layer_info",
     "lfgpu_circuit_free", "lfgpu_zk_prover_new", "lfgpu_zk_prover_set_comm", "lfgpu_zk_prover_param", "lfgpu_zk_commit", "lfgpu_zk_prove",
     "lfgpu_zk_proof_write", "lfgpu_zk_timings", "lfgpu_zk_prover_free", "lfgpu_zk_verify", "lfgpu_zk_verify_committed",
+    "lfgpu_zk_batch_new", "lfgpu_zk_prove_batch", "lfgpu_zk_batch_free",
 ]
 
 
@@ -177,6 +178,10 @@ def load_library():
         "lfgpu_zk_verify": [vp, vp, sz, sz, sz, vp, sz, vp, C.POINTER(TranscriptOps), C.POINTER(ci), C.POINTER(C.c_char_p)],
         "lfgpu_zk_verify_committed": [vp, vp, sz, sz, sz, vp, sz, vp, C.POINTER(TranscriptOps), C.POINTER(ci), C.POINTER(C.c_char_p)],
         "lfgpu_crypto_hw": [ci],
+        "lfgpu_eval_quad_batch": [vp, sz, sz, vp, sz, vp, sz, C.POINTER(ci)],
+        "lfgpu_zk_batch_new": [vp, vp, sz, C.POINTER(vp)],
+        "lfgpu_zk_prove_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), C.POINTER(ci)],
+        "lfgpu_zk_batch_free": [vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -552,6 +557,13 @@ class Quad:
         self.gpu._ck(self.gpu.L.lfgpu_eval_quad_copies(self.h, nc, nw, C.c_void_p(d_W), C.c_void_p(d_V), C.byref(ok)))
         return bool(ok.value)
 
+    def eval_batch(self, nb, nw, d_W, ldw, d_V, ldv):
+        """ProverLayers::eval_quad for nb statements in one launch: statement b reads d_W + b * ldw and writes d_V + b * ldv
+        (elements) -> [bool] * nb, False where an assert-zero term of that statement fails"""
+        ok = (C.c_int * max(1, nb))()
+        self.gpu._ck(self.gpu.L.lfgpu_eval_quad_batch(self.h, nb, nw, C.c_void_p(d_W), ldw, C.c_void_p(d_V), ldv, ok))
+        return [bool(ok[b]) for b in range(nb)]
+
     def bind_g(self, logv, G0, G1, alpha, beta, d_hc_out, d_vc_out):
         import numpy as np
         G0, G1 = np.ascontiguousarray(G0), np.ascontiguousarray(G1)
@@ -799,6 +811,39 @@ class ZkProver:
     def close(self):
         if self.h:
             self.gpu.L.lfgpu_zk_prover_free(self.h)
+            self.h = None
+
+
+class ZkBatch:
+    """lfgpu_zk_batch: up to nb_max committed ZkProvers of one context and circuit proved in lock-step through one chain of
+    dispatches (batched eval_circuit and sumcheck; constraints and Ligero prove per statement).  Every proof is
+    byte-identical to ZkProver.prove's.  GF2_128 and Fp128 circuits."""
+
+    def __init__(self, gpu, circuit, nb_max):
+        self.gpu, self.circuit, self.nb_max = gpu, circuit, nb_max
+        h = C.c_void_p()
+        gpu._ck(gpu.L.lfgpu_zk_batch_new(gpu.h, circuit.h, nb_max, C.byref(h)))
+        self.h = h
+
+    def prove(self, provers, Ws, transcripts):
+        """-> [bool] per statement: True = provers[b] holds its proof, False = witness b does not satisfy the circuit"""
+        import numpy as np
+        nb = len(provers)
+        if not (len(Ws) == nb and len(transcripts) == nb):
+            raise ValueError("ZkBatch.prove: one witness and one transcript per prover")
+        Ws = [np.ascontiguousarray(W) for W in Ws]
+        ops = [t.ops() for t in transcripts]
+        n = max(1, nb)
+        zk = (C.c_void_p * n)(*[p.h for p in provers])
+        hw = (C.c_void_p * n)(*[W.ctypes.data for W in Ws])
+        tp = (C.POINTER(TranscriptOps) * n)(*[C.pointer(o) for o in ops])
+        ok = (C.c_int * n)()
+        self.gpu._ck(self.gpu.L.lfgpu_zk_prove_batch(self.h, zk, nb, hw, tp, ok))
+        return [bool(ok[b]) for b in range(nb)]
+
+    def close(self):
+        if self.h:
+            self.gpu.L.lfgpu_zk_batch_free(self.h)
             self.h = None
 
 

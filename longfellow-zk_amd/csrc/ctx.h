@@ -69,6 +69,10 @@ struct lfgpu_ctx {
   // lfgpu_sumcheck_layer_batch: one slot of LF_SC_BATCH_SLOT_WORDS coherent pinned words per statement, each laid out like
   // poll_h; allocated at the first batched call, sequence numbers from poll_seq
   volatile u64* sc_batch_h = nullptr;
+  // ... and the pinned image of the B binding-point sets of its bind_g (quad.hip: lf_quad_bind_g_batch), rewritten per layer once
+  // sc_batch_pts_ev (recorded after its copy) has completed
+  void* sc_batch_pts_h = nullptr;
+  hipEvent_t sc_batch_pts_ev = nullptr;
   // per-context (= per-device) launch configuration: nothing below the C ABI is process-global, so one process may hold
   // contexts on several devices (hipFuncSetAttribute is applied once per context)
   unsigned attr_done = 0;  // bit 0 FFT tile kernels, 1 RS row kernel, 2 bit-sliced butterflies, 3 sumcheck grid tail
@@ -236,6 +240,8 @@ int lf_hquad_bind_h_cached(lfgpu_ctx* c, int field, size_t n, const void* d_hc, 
                            void* d_hc_out, void* d_vc_out, const u32* d_off_cached, u32** d_off_keep, size_t* n_out);  // sumcheck.hip
 struct lfgpu_quad;
 int lf_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail);  // quad.hip
+int lf_eval_quad_batch_async(lfgpu_quad* q, size_t B, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail /*[B]*/);  // quad.hip
+#define LF_EVALB_FAIL_OFF 3584  // lfgpu_eval_quad_batch: LFGPU_SC_BATCH_MAX assert-zero flags in the device mailbox, behind the bind_gh_all sums
 
 // p256.hip (field id 1, 32-byte elements)
 int lf_column_leaves32(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out, size_t out0);

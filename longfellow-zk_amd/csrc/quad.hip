@@ -313,6 +313,163 @@ __global__ __launch_bounds__(QD_THREADS) void fp_limb_normalize4_kernel(const u3
   st16(&out[i], fp_reduce_limbs(acc[4 * i], acc[4 * i + 1], acc[4 * i + 2], acc[4 * i + 3]));
 }
 
+// ---- the batch axis of K11 and K10: B statements of ONE quad per launch, statement = blockIdx.y.  The bodies are those of the
+// single kernels above; a statement's arrays are `base + b * stride`.
+template <int F>
+__global__ __launch_bounds__(QD_THREADS) void eval_quad_batch_kernel(u32 nv, const u32* __restrict__ goff, const corner4* __restrict__ terms,
+                                                                     const elt_t* __restrict__ kvec, const elt_t* __restrict__ W, size_t ldw,
+                                                                     elt_t* __restrict__ V, size_t ldv, int* __restrict__ fail) {
+  const u32 g = blockIdx.x * QD_THREADS + threadIdx.x, b = blockIdx.y;
+  if (g >= nv) return;
+  W += (size_t)b * ldw;
+  elt_t acc = elt_zero();
+  bool bad = false;
+  for (u32 t = goff[g]; t < goff[g + 1]; ++t) {
+    const corner4 cr = terms[t];
+    const elt_t v = ld16(&kvec[cr.vi]);
+    const elt_t p = Fld<F>::mul(ld16(&W[cr.h1]), ld16(&W[cr.h0]));
+    if ((v.lo | v.hi) == 0) {
+      bad |= (p.lo | p.hi) != 0;
+    } else {
+      acc = Fld<F>::add(acc, Fld<F>::mul(v, p));
+    }
+  }
+  st16(&V[(size_t)b * ldv + g], acc);
+  if (bad) atomicOr(&fail[b], 1);
+}
+
+// The B EQ vectors of a layer's bind_g in one launch.  The binding points do not fit the kernel arguments B times (EqPoints is
+// 2.5 KB): statement b's are LF_EQB_STRIDE(logn) elements at pts + b * LF_EQB_STRIDE(logn) in device memory --
+// G0 | G1 | 1-G0 | 1-G1 | alpha | beta (beta is the emit kernel's).  eq: statement b's n entries at eq + b * n.
+// zero + b * zstride (64-bit words): nzero words cleared on the side per statement, as eq_side_clear does for the single call.
+#define LF_EQB_STRIDE(logn) (4 * (size_t)(logn) + 2)
+__device__ __forceinline__ void eq_side_clear_batch(u64* __restrict__ zero, size_t zstride, size_t nzero) {
+  if (!zero) return;
+  u64* z = zero + (size_t)blockIdx.y * zstride;
+  const size_t T = (size_t)gridDim.x * QD_THREADS;
+  for (size_t k = (size_t)blockIdx.x * QD_THREADS + threadIdx.x; k < nzero; k += T) z[k] = 0;
+}
+// logn < 6: the direct product per entry (raw_eq2_kernel)
+template <int F>
+__global__ __launch_bounds__(QD_THREADS) void raw_eq2_batch_kernel(u32 logn, u32 n, const elt_t* __restrict__ pts, elt_t one, elt_t* __restrict__ eq,
+                                                                   u64* __restrict__ zero, size_t zstride, size_t nzero) {
+  const elt_t* G = pts + (size_t)blockIdx.y * LF_EQB_STRIDE(logn);
+  eq_side_clear_batch(zero, zstride, nzero);
+  const u32 i = blockIdx.x * QD_THREADS + threadIdx.x;
+  if (i >= n) return;
+  elt_t e0 = one, e1 = ld16(&G[4 * logn]);
+  for (u32 l = 0; l < logn; ++l) {
+    const u32 bit = (i >> l) & 1;
+    e0 = Fld<F>::mul(e0, ld16(&G[(bit ? 0 : 2 * logn) + l]));
+    e1 = Fld<F>::mul(e1, ld16(&G[(bit ? logn : 3 * logn) + l]));
+  }
+  st16(&eq[(size_t)blockIdx.y * n + i], Fld<F>::add(e0, e1));
+}
+// logn >= 6: raw_eq2_fused_kernel's scheme (64 factor entries per block in LDS, four lanes each) for every size: the high factor
+// of a block's 16 entries is a product of logn - 4 <= 36 points, nine per lane.  One launch whatever B and logn; exact field
+// arithmetic, so the association of the products does not change the bytes.
+template <int F>
+__global__ __launch_bounds__(QD_THREADS) void raw_eq2_fused_batch_kernel(u32 logn, u32 n, const elt_t* __restrict__ pts, elt_t one, elt_t* __restrict__ eq,
+                                                                         u64* __restrict__ zero, size_t zstride, size_t nzero) {
+  static_assert(QD_THREADS == 256, "raw_eq2_fused_batch_kernel: 64 factor entries x 4 lanes");
+  __shared__ elt_t tab[64];  // LO0[16] | LO1[16] | HI0[16] | HI1[16] (alpha folded into HI1)
+  const elt_t* G = pts + (size_t)blockIdx.y * LF_EQB_STRIDE(logn);
+  eq_side_clear_batch(zero, zstride, nzero);
+  constexpr u32 lb = 4;
+  const u32 t = threadIdx.x, e = t >> 2, part = t & 3;
+  const u32 which = e >> 4, j = e & 15, g = which & 1;
+  const bool high = which >= 2;
+  const u32 bits = high ? logn - lb : lb, shift = high ? lb : 0;
+  const u32 idx = high ? blockIdx.x * 16 + j : j;
+  elt_t v = (which == 3 && part == 0) ? ld16(&G[4 * logn]) : one;
+  for (u32 l = part; l < bits; l += 4) {
+    const u32 bit = (idx >> l) & 1;
+    v = Fld<F>::mul(v, ld16(&G[(bit ? g * logn : (2 + g) * logn) + shift + l]));
+  }
+#pragma unroll
+  for (int x = 1; x <= 2; x <<= 1) {
+    elt_t o;
+    o.lo = __shfl_xor(v.lo, x, 64);
+    o.hi = __shfl_xor(v.hi, x, 64);
+    v = Fld<F>::mul(v, o);
+  }
+  if (part == 0) tab[e] = v;
+  __syncthreads();
+  const u32 i = blockIdx.x * QD_THREADS + t;
+  if (i >= n) return;
+  const u32 lo = t & 15, h = t >> 4;
+  const elt_t e0 = Fld<F>::mul(tab[lo], tab[32 + h]);
+  const elt_t e1 = Fld<F>::mul(tab[16 + lo], tab[48 + h]);
+  st16(&eq[(size_t)blockIdx.y * n + i], Fld<F>::add(e0, e1));
+}
+
+// K10 step 3 for B statements: bindg_emit_gf_kernel / bindg_emit_fp_kernel with the statement's beta (pts), EQ vector
+// (eq + b * nv) and sums (vc_out + b * s_vc elements / acc + b * s_acc words).  The corners are the same for every statement:
+// only statement 0 stores them.
+__global__ __launch_bounds__(BG_THREADS) void bindg_emit_gf_batch_kernel(size_t n, const corner4* __restrict__ t, const elt_t* __restrict__ kvec,
+                                                                         const elt_t* __restrict__ eq, size_t nv, const elt_t* __restrict__ pts,
+                                                                         size_t pstride, const u32* __restrict__ block_off, uint2* __restrict__ hc_out,
+                                                                         u64* __restrict__ vc_out, size_t s_vc) {
+  __shared__ u32 wave_off[BG_THREADS / 64];
+  const u32 b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const bool valid = i < n;
+  const bool head = valid && is_head(t, i);
+  const u64 mask = __ballot(head);
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wave_off[wave] = (u32)__popcll(mask);
+  __syncthreads();
+  u32 ri = block_off[blockIdx.x];
+  for (u32 w = 0; w < wave; ++w) ri += wave_off[w];
+  ri += (u32)__popcll(mask & ((2ull << lane) - 1));
+  ri -= 1;
+  elt_t pv = elt_zero();
+  corner4 c0{0, 0, 0, 0};
+  if (valid) {
+    c0 = t[i];
+    elt_t v = ld16(&kvec[c0.vi]);
+    if ((v.lo | v.hi) == 0) v = ld16(&pts[(size_t)b * pstride + pstride - 1]);
+    pv = gf_mul(v, ld16(&eq[(size_t)b * nv + c0.g]));
+  }
+  if (head && b == 0) hc_out[ri] = make_uint2(c0.h0, c0.h1);
+  gf_run_fold_commit<BG_THREADS>(valid ? ri : 0xffffffffu, pv, vc_out + 2 * (size_t)b * s_vc);
+}
+__global__ __launch_bounds__(BG_THREADS) void bindg_emit_fp_batch_kernel(size_t n, const corner4* __restrict__ t, const elt_t* __restrict__ kvec,
+                                                                         const elt_t* __restrict__ eq, size_t nv, const elt_t* __restrict__ pts,
+                                                                         size_t pstride, const u32* __restrict__ block_off, uint2* __restrict__ hc_out,
+                                                                         u64* __restrict__ acc, size_t s_acc) {
+  __shared__ u32 wave_off[BG_THREADS / 64];
+  const u32 b = blockIdx.y;
+  const size_t i = (size_t)blockIdx.x * BG_THREADS + threadIdx.x;
+  const bool valid = i < n;
+  const bool head = valid && is_head(t, i);
+  const u64 mask = __ballot(head);
+  const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) wave_off[wave] = (u32)__popcll(mask);
+  __syncthreads();
+  if (!valid) return;
+  u32 ri = block_off[blockIdx.x];
+  for (u32 w = 0; w < wave; ++w) ri += wave_off[w];
+  ri += (u32)__popcll(mask & ((2ull << lane) - 1)) - 1;
+  const corner4 c0 = t[i];
+  elt_t v = ld16(&kvec[c0.vi]);
+  if ((v.lo | v.hi) == 0) v = ld16(&pts[(size_t)b * pstride + pstride - 1]);
+  const elt_t pv = fp_mul(v, ld16(&eq[(size_t)b * nv + c0.g]));
+  if (head && b == 0) hc_out[ri] = make_uint2(c0.h0, c0.h1);
+  u64* a = acc + (size_t)b * s_acc + 4 * (size_t)ri;
+  atomicAdd(&a[0], (u64)(u32)pv.lo);
+  atomicAdd(&a[1], pv.lo >> 32);
+  atomicAdd(&a[2], (u64)(u32)pv.hi);
+  atomicAdd(&a[3], pv.hi >> 32);
+}
+__global__ __launch_bounds__(QD_THREADS) void fp_limb_normalize4_batch_kernel(size_t total, const u64* __restrict__ acc, size_t s_acc, elt_t* __restrict__ out,
+                                                                              size_t s_out) {
+  const size_t i = (size_t)blockIdx.x * QD_THREADS + threadIdx.x;
+  if (i >= total) return;
+  const u64* a = acc + (size_t)blockIdx.y * s_acc + 4 * i;
+  st16(&out[(size_t)blockIdx.y * s_out + i], fp_reduce_limbs(a[0], a[1], a[2], a[3]));
+}
+
 #define QD_DISPATCH(field, KERNEL, grid, block, ...)                                    \
   do {                                                                                  \
     if ((field) == LFGPU_FIELD_GF2_128)                                                 \
@@ -525,6 +682,36 @@ extern "C" int lfgpu_eval_quad_copies(lfgpu_quad* q, size_t nc, size_t nw, const
   return LFGPU_OK;
 }
 
+// one layer of B statements, asynchronously: statement b reads d_W + b * ldw, writes d_V + b * ldv and ORs its assert-zero
+// failures into d_fail[b] (device; the caller clears and reads the B flags)
+int lf_eval_quad_batch_async(lfgpu_quad* q, size_t B, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail) {
+  lfgpu_ctx* c = q->c;
+  if (q->field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "eval_quad_batch: not built for Fp256Base");
+  if (B == 0 || B > LFGPU_SC_BATCH_MAX || ldw <= q->hmax || ldv < q->nv) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch: nb must be 1..%d, ldw > the largest hand index, ldv >= nv", LFGPU_SC_BATCH_MAX);
+  const u32 nb = (u32)((q->nv + QD_THREADS - 1) / QD_THREADS);
+  QD_DISPATCH(q->field, eval_quad_batch_kernel, dim3(nb, (u32)B), dim3(QD_THREADS), (u32)q->nv, (const u32*)q->d_goff, (const corner4*)q->d_bygate,
+              (const elt_t*)q->d_kvec, (const elt_t*)d_W, ldw, (elt_t*)d_V, ldv, d_fail);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_eval_quad_batch(lfgpu_quad* q, size_t nb, size_t nw, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* ok_out) {
+  if (!q || !d_W || !d_V || !ok_out) return q ? lf_fail(q->c, LFGPU_ERR_ARG, "eval_quad_batch: null argument") : LFGPU_ERR_ARG;
+  lfgpu_ctx* c = q->c;
+  if (q->field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "eval_quad_batch: not built for Fp256Base");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch: nb must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (nw <= q->hmax || ldw < nw || ldv < q->nv || ((ldw * nb) >> 40) || ((ldv * nb) >> 40))
+    return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch: nw = %zu (a corner reads wire %zu), ldw = %zu, ldv = %zu (nv = %zu)", nw, q->hmax, ldw, ldv, q->nv);
+  LF_HIP(c, hipSetDevice(c->device));
+  int* d_fail = (int*)((uint8_t*)c->mailbox_d + LF_EVALB_FAIL_OFF);
+  LF_HIP(c, hipMemsetAsync(d_fail, 0, nb * 4, c->stream));
+  LF_TRY(lf_eval_quad_batch_async(q, nb, d_W, ldw, d_V, ldv, d_fail));
+  LF_HIP(c, hipMemcpyAsync(c->mailbox_h, d_fail, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b < nb; ++b) ok_out[b] = ((const int*)c->mailbox_h)[b] ? 0 : 1;
+  return LFGPU_OK;
+}
+
 // d_zero / zero_bytes (a multiple of 8, < 32 GiB): device words cleared on the side (eq_side_clear), or nullptr
 static int lf_raw_eq2_clear(lfgpu_ctx* c, int field, size_t logn, size_t n, const void* h_G0, const void* h_G1, const uint64_t alpha[2], void* d_eq,
                             void* d_zero, size_t zero_bytes) {
@@ -634,6 +821,74 @@ extern "C" int lfgpu_quad_bind_g(lfgpu_quad* q, size_t logv, const void* h_G0, c
                                  const uint64_t beta[2], void* d_hc_out, void* d_vc_out, size_t* n_out) {
   if (!n_out) return LFGPU_ERR_ARG;
   return lf_quad_bind_g(q, logv, h_G0, h_G1, alpha, beta, d_hc_out, d_vc_out, n_out, nullptr, 0, nullptr, 0);
+}
+
+// Quad::bind_g of B statements of one quad (K14, sc_layer_batch): one copy of the B point sets, one EQ launch, one emit launch and,
+// for Fp128, one normalise launch -- whatever B.  h_G0 / h_G1: [B][logv]; alpha, beta: [B][2]; statement b's sums go to
+// d_vc_out + b * s_vc elements, the corners (the same for every statement) to d_hc_out once.  Enqueue only.  Device temporaries:
+// the point sets in scratch2, the EQ vectors in scratch3, the Fp128 limb accumulators in scratch4.
+static int lf_quad_bind_g_batch(lfgpu_quad* q, size_t B, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha, const uint64_t* beta,
+                                void* d_hc_out, void* d_vc_out, size_t s_vc, size_t* n_out) {
+  lfgpu_ctx* c = q->c;
+  const int field = q->field;
+  const size_t n = q->n, nv = q->nv, nh0 = q->nh0, ps = LF_EQB_STRIDE(logv);
+  if (n >> 32) return lf_fail(c, LFGPU_ERR_ARG, "quad_bind_g: more than 2^32 terms");
+  if (!c->sc_batch_pts_h) {
+    void* p = nullptr;
+    if (hipHostMalloc(&p, (size_t)LFGPU_SC_BATCH_MAX * LF_EQB_STRIDE(40) * 16, hipHostMallocDefault) != hipSuccess ||
+        hipEventCreateWithFlags(&c->sc_batch_pts_ev, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      if (p) (void)hipHostFree(p);
+      return lf_fail(c, LFGPU_ERR_NOMEM, "sumcheck_layer_batch: the pinned binding points");
+    }
+    c->sc_batch_pts_h = p;
+  } else {
+    LF_HIP(c, hipEventSynchronize(c->sc_batch_pts_ev));  // the copy of the previous layer (long done)
+  }
+  const elt_t one = field == LFGPU_FIELD_GF2_128 ? elt_t{1, 0} : h_fp_of_scalar(1);
+  elt_t* const P = (elt_t*)c->sc_batch_pts_h;
+  const elt_t* G0 = (const elt_t*)h_G0;
+  const elt_t* G1 = (const elt_t*)h_G1;
+  for (size_t b = 0; b < B; ++b) {
+    elt_t* Gt = P + b * ps;
+    for (size_t l = 0; l < logv; ++l) {
+      const elt_t g0 = G0[b * logv + l], g1 = G1[b * logv + l];
+      Gt[l] = g0;
+      Gt[logv + l] = g1;
+      Gt[2 * logv + l] = field == LFGPU_FIELD_GF2_128 ? gf_add(one, g0) : fp_sub(one, g0);
+      Gt[3 * logv + l] = field == LFGPU_FIELD_GF2_128 ? gf_add(one, g1) : fp_sub(one, g1);
+    }
+    Gt[4 * logv] = elt_t{alpha[2 * b], alpha[2 * b + 1]};
+    Gt[4 * logv + 1] = elt_t{beta[2 * b], beta[2 * b + 1]};
+  }
+  void *d_ptsv = nullptr, *d_eqv = nullptr, *d_accv = nullptr;
+  LF_TRY(lf_scratch2(c, B * ps * 16 + 64, &d_ptsv));
+  LF_TRY(lf_scratch3(c, B * nv * 16 + 256, &d_eqv));
+  if (field == LFGPU_FIELD_FP128) LF_TRY(lf_scratch4(c, B * nh0 * 32 + 64, &d_accv));
+  LF_HIP(c, hipMemcpyAsync(d_ptsv, P, B * ps * 16, hipMemcpyHostToDevice, c->stream));
+  LF_HIP(c, hipEventRecord(c->sc_batch_pts_ev, c->stream));
+  const elt_t* d_pts = (const elt_t*)d_ptsv;
+  elt_t* d_eq = (elt_t*)d_eqv;
+  // the side clear: GF(2^128) XORs into the sums themselves, Fp128 adds into its limb accumulators
+  u64* const zp = field == LFGPU_FIELD_GF2_128 ? (u64*)d_vc_out : (u64*)d_accv;
+  const size_t zstride = field == LFGPU_FIELD_GF2_128 ? 2 * s_vc : 4 * nh0, nz = field == LFGPU_FIELD_GF2_128 ? 2 * nh0 : 4 * nh0;
+  const dim3 ge((u32)((nv + QD_THREADS - 1) / QD_THREADS), (u32)B);
+  if (logv < 6) QD_DISPATCH(field, raw_eq2_batch_kernel, ge, dim3(QD_THREADS), (u32)logv, (u32)nv, d_pts, one, d_eq, zp, zstride, nz);
+  else QD_DISPATCH(field, raw_eq2_fused_batch_kernel, ge, dim3(QD_THREADS), (u32)logv, (u32)nv, d_pts, one, d_eq, zp, zstride, nz);
+  const dim3 gm((u32)((n + BG_THREADS - 1) / BG_THREADS), (u32)B);
+  if (field == LFGPU_FIELD_GF2_128) {
+    hipLaunchKernelGGL(bindg_emit_gf_batch_kernel, gm, dim3(BG_THREADS), 0, c->stream, n, (const corner4*)q->d_morton, (const elt_t*)q->d_kvec,
+                       (const elt_t*)d_eq, nv, d_pts, ps, (const u32*)q->d_runoff, (uint2*)d_hc_out, (u64*)d_vc_out, s_vc);
+  } else {
+    hipLaunchKernelGGL(bindg_emit_fp_batch_kernel, gm, dim3(BG_THREADS), 0, c->stream, n, (const corner4*)q->d_morton, (const elt_t*)q->d_kvec,
+                       (const elt_t*)d_eq, nv, d_pts, ps, (const u32*)q->d_runoff, (uint2*)d_hc_out, (u64*)d_accv, 4 * nh0);
+    if (nh0)
+      hipLaunchKernelGGL(fp_limb_normalize4_batch_kernel, dim3((u32)((nh0 + QD_THREADS - 1) / QD_THREADS), (u32)B), dim3(QD_THREADS), 0, c->stream, nh0,
+                         (const u64*)d_accv, 4 * nh0, (elt_t*)d_vc_out, s_vc);
+  }
+  LF_HIP(c, hipGetLastError());
+  if (n_out) *n_out = nh0;
+  return LFGPU_OK;
 }
 
 
@@ -1175,12 +1430,11 @@ static int sc_layer_batch(lfgpu_quad* q, size_t B, size_t logv, const void* h_G0
   void* sc34 = nullptr;
   LF_TRY(lf_scratch(c, bytes, &sc));
   {
-    const u32 lb = (u32)(logv / 2), hb = (u32)logv - lb;
-    const size_t eq_tab = 2 * (((size_t)1 << lb) + ((size_t)1 << hb)) * 16 + 64;                 // lf_raw_eq2_clear
     const size_t offs = ((nt + 255) / 256) * 4 + 64;                                             // the count + scan of a recorded bind
-    LF_TRY(lf_scratch2(c, std::max(std::max(eq_tab, offs), B * LF_SCB_PARTIAL_ELTS * 16 + 64), &partial));
-    LF_TRY(lf_scratch3(c, q->nv * 16 + 256, &sc34));                                            // lf_quad_bind_g: the EQ vector
-    if (field == LFGPU_FIELD_FP128) LF_TRY(lf_scratch4(c, q->nh0 * 32 + 64, &sc34));            // ... and its limb accumulators
+    const size_t pts = B * LF_EQB_STRIDE(logv) * 16 + 64;                                        // lf_quad_bind_g_batch: the B point sets
+    LF_TRY(lf_scratch2(c, std::max(std::max(offs, pts), B * LF_SCB_PARTIAL_ELTS * 16 + 64), &partial));
+    LF_TRY(lf_scratch3(c, B * q->nv * 16 + 256, &sc34));                                        // ... the B EQ vectors
+    if (field == LFGPU_FIELD_FP128) LF_TRY(lf_scratch4(c, B * q->nh0 * 32 + 64, &sc34));        // ... and their limb accumulators
   }
   LF_TRY(lf_scb_mailbox(c));
   volatile u64* const mb = c->sc_batch_h;
@@ -1194,14 +1448,10 @@ static int sc_layer_batch(lfgpu_quad* q, size_t B, size_t logv, const void* h_G0
   static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
   auto clk = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double tv0 = verbose ? clk() : 0;
-  // phase 1 -- Quad::bind_g per statement, enqueued back to back, nothing read back.  The corners are the same for every statement:
-  // statement 0 writes them, the others write theirs into the half of the ping-pong that the first bind overwrites
+  // phase 1 -- Quad::bind_g of all statements: at most three launches whatever B, nothing read back.  The corners are the same for
+  // every statement: statement 0 writes them
   size_t nh = 0;
-  const uint8_t* G0 = (const uint8_t*)h_G0;
-  const uint8_t* G1 = (const uint8_t*)h_G1;
-  for (size_t b = 0; b < B; ++b)
-    LF_TRY(lf_quad_bind_g(q, logv, G0 ? G0 + b * logv * 16 : nullptr, G1 ? G1 + b * logv * 16 : nullptr, alpha + 2 * b, beta + 2 * b, b == 0 ? hc[0] : hc[1],
-                          (uint8_t*)vc[0] + b * nt * 16, &nh));
+  LF_TRY(lf_quad_bind_g_batch(q, B, logv, h_G0, h_G1, alpha, beta, hc[0], vc[0], nt, &nh));
   const double tv1 = verbose ? clk() : 0;
   const size_t nh0 = nh;
   std::vector<elt_t> sum(B);

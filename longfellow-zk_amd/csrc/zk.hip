@@ -307,6 +307,49 @@ struct P16 : zkp::Wire16 {
     *bound_quad = E{bq[0], bq[1]};
     return LFGPU_OK;
   }
+  // ---- the batch axis (zkp::prove_batch): B statements of one layer per call
+  typedef void (*round_batch_fn)(void* user, size_t hand, size_t rnd, size_t nb, const E (*ev)[3], E* chal);
+  static constexpr const char* kProveBatchName = "zk_prove_batch";
+  static int eval_layer_batch(lfgpu_quad* q, size_t nb, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail) {
+    return lf_eval_quad_batch_async(q, nb, d_W, ldw, d_V, ldv, d_fail);
+  }
+  struct TrampBatch {
+    round_batch_fn f;
+    void* user;
+    std::vector<E> ev, ch;
+  };
+  static void tramp_batch_cb(void* user, size_t hand, size_t rnd, size_t nb, const uint64_t (*ev)[3][2], uint64_t (*chal)[2]) {
+    TrampBatch* t = (TrampBatch*)user;
+    for (size_t b = 0; b < nb; ++b)
+      for (int k = 0; k < 3; ++k) t->ev[3 * b + k] = E{ev[b][k][0], ev[b][k][1]};
+    t->f(t->user, hand, rnd, nb, (const E(*)[3])t->ev.data(), t->ch.data());
+    for (size_t b = 0; b < nb; ++b) {
+      chal[b][0] = t->ch[b].lo;
+      chal[b][1] = t->ch[b].hi;
+    }
+  }
+  // G0 / G1: [nb][logv]; alpha, beta, bound_quad: [nb]; wc_in, wc_out: [nb][2]; g_out: [nb][2][logw]; d_W: statement b at b * ldw
+  static int sumcheck_layer_batch(lfgpu_quad* q, const HostField&, size_t nb, size_t logv, const E* G0, const E* G1, const E* alpha, const E* beta, size_t logw,
+                                  size_t nw, void* d_W, size_t ldw, const E* wc_in, round_batch_fn round, void* user, E* wc_out, E* g_out, E* bound_quad) {
+    TrampBatch t{round, user, std::vector<E>(3 * nb), std::vector<E>(nb)};
+    std::vector<uint64_t> al(2 * nb), be(2 * nb), wi(4 * nb), wo(4 * nb), bq(2 * nb), g(4 * nb * logw + 2, 0);
+    for (size_t b = 0; b < nb; ++b) {
+      al[2 * b] = alpha[b].lo; al[2 * b + 1] = alpha[b].hi;
+      be[2 * b] = beta[b].lo; be[2 * b + 1] = beta[b].hi;
+      for (int k = 0; k < 2; ++k) {
+        wi[4 * b + 2 * k] = wc_in[2 * b + k].lo;
+        wi[4 * b + 2 * k + 1] = wc_in[2 * b + k].hi;
+      }
+    }
+    LF_TRY(lfgpu_sumcheck_layer_batch(q, nb, logv, G0, G1, al.data(), be.data(), logw, nw, d_W, ldw, wi.data(), tramp_batch_cb, &t, wo.data(), g.data(), bq.data()));
+    for (size_t b = 0; b < nb; ++b) {
+      wc_out[2 * b] = E{wo[4 * b], wo[4 * b + 1]};
+      wc_out[2 * b + 1] = E{wo[4 * b + 2], wo[4 * b + 3]};
+      bound_quad[b] = E{bq[2 * b], bq[2 * b + 1]};
+    }
+    for (size_t i = 0; i < 2 * nb * logw; ++i) g_out[i] = E{g[2 * i], g[2 * i + 1]};
+    return LFGPU_OK;
+  }
   static int bind_gh_all(lfgpu_ctx*, const HostField&, const Layer& L, size_t logv, const E* G0, const E* G1, const E& alpha, const E& beta, const E* H0,
                          const E* H1, E* out) {
     uint64_t bq[2];
@@ -607,6 +650,121 @@ extern "C" int lfgpu_zk_timings(const lfgpu_zk_prover* zk, double ms[6]) {
 extern "C" int lfgpu_zk_prover_free(lfgpu_zk_prover* zk) {
   if (!zk) return LFGPU_ERR_ARG;
   delete zk;
+  return LFGPU_OK;
+}
+
+// ------------------------------------------------------------------ ZkProver::prove for a batch of committed provers
+// The batch owns what the lock-step needs B times: the layers' input slabs (statement b of layer l at d_in[l] + b * ldw[l]
+// elements), the outputs, one assert-zero flag per statement and their pinned read-back.  Everything is allocated in _new:
+// prove_batch neither allocates nor frees device memory (hipFree waits for every stream of the device).
+struct lfgpu_zk_batch {
+  lfgpu_ctx* c = nullptr;
+  const lfgpu_circuit* C = nullptr;
+  size_t nb_max = 0;
+  std::vector<void*> d_in;
+  std::vector<size_t> ldw;
+  // the sizes of the allocations, recorded here: the scrub at destruction does not look at the circuit handle (which the caller
+  // may have freed first)
+  std::vector<size_t> in_bytes;
+  void* d_V = nullptr;
+  size_t ldv = 0, v_bytes = 0;
+  int* d_fail = nullptr;
+  void* h_V = nullptr;
+  size_t h_bytes = 0;
+  ~lfgpu_zk_batch() {
+    // the slabs hold the wire values of every statement -- functions of the witnesses: scrubbed before the memory goes back
+    if (c) {
+      (void)hipSetDevice(c->device);
+      for (size_t l = 0; l < d_in.size(); ++l)
+        if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, in_bytes[l], c->stream);
+      if (d_V) (void)hipMemsetAsync(d_V, 0, v_bytes, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+    }
+    for (void* p : d_in)
+      if (p) (void)hipFree(p);
+    if (d_V) (void)hipFree(d_V);
+    if (d_fail) (void)hipFree(d_fail);
+    if (h_V) {
+      memset(h_V, 0, h_bytes);
+      (void)hipHostFree(h_V);
+    }
+  }
+};
+
+extern "C" int lfgpu_zk_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, lfgpu_zk_batch** out) {
+  if (!c || !C || !out || C->c != c) return LFGPU_ERR_ARG;
+  if (nb_max == 0 || nb_max > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch_new: nb_max must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (C->info.field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_batch_new: Fp256Base circuits are proved one statement at a time");
+  std::unique_ptr<lfgpu_zk_batch> bt(new lfgpu_zk_batch());
+  bt->c = c;
+  bt->C = C;
+  bt->nb_max = nb_max;
+  LF_HIP(c, hipSetDevice(c->device));
+  auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };  // slabs start on 64-byte lines
+  const size_t nl = C->layers.size();
+  bt->d_in.assign(nl, nullptr);
+  bt->ldw.assign(nl, 0);
+  bt->in_bytes.assign(nl, 0);
+  auto alloc = [&](void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return false;
+  };
+  for (size_t l = 0; l < nl; ++l) {
+    bt->ldw[l] = pad4(C->layers[l].nw);
+    bt->in_bytes[l] = nb_max * bt->ldw[l] * 16;
+    if (!alloc(&bt->d_in[l], bt->in_bytes[l])) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: %zu slabs of layer %zu (%zu bytes)", nb_max, l, bt->in_bytes[l]);
+  }
+  bt->ldv = pad4(C->info.nv);
+  bt->v_bytes = nb_max * bt->ldv * 16;
+  bt->h_bytes = bt->v_bytes + nb_max * sizeof(int);
+  if (!alloc(&bt->d_V, bt->v_bytes) || !alloc((void**)&bt->d_fail, nb_max * sizeof(int))) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: outputs");
+  if (hipHostMalloc(&bt->h_V, bt->h_bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    bt->h_V = nullptr;
+    return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: pinned outputs");
+  }
+  LF_TRY(zk_eq_reserve(c, C->info.ninputs));  // (prove_batch then finds the context's EQ table in place)
+  *out = bt.release();
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_zk_prove_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                                    const lfgpu_transcript_ops* const* ts, int* ok) {
+  if (!bt || !zk || !h_W || !ts || !ok) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = bt->c;
+  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!zk[b] || !h_W[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: null argument for statement %zu", b);
+    if (zk[b]->c != c || zk[b]->C != bt->C) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: prover %zu belongs to another context or circuit", b);
+    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_prove_batch: prover %zu has a communicator (the batch runs on one GPU)", b);
+    if (zk[b]->z256 || !zk[b]->lp) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: prover %zu must run commit before prove", b);
+    for (size_t a = 0; a < b; ++a)
+      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: prover %zu appears twice", b);
+  }
+  const lfgpu_circuit* C = bt->C;
+  std::vector<P16> pol;
+  std::vector<zkp::ProverState<P16>*> st(nb);
+  std::vector<lfgpu_ligero_prover*> lp(nb);
+  pol.reserve(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    pol.push_back(policy16(c, C->info.field, &zk[b]->sub));
+    st[b] = &zk[b]->st;
+    lp[b] = zk[b]->lp;
+  }
+  auto eq_table = [&](elt_t** d_eq) {
+    LF_TRY(zk_eq_reserve(c, C->info.ninputs));
+    *d_eq = (elt_t*)c->zk_eq;
+    return (int)LFGPU_OK;
+  };
+  const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max};
+  return zkp::prove_batch<P16>(c, C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
+}
+
+extern "C" int lfgpu_zk_batch_free(lfgpu_zk_batch* bt) {
+  if (!bt) return LFGPU_ERR_ARG;
+  delete bt;
   return LFGPU_OK;
 }
 

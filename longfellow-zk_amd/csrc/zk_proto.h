@@ -18,6 +18,8 @@
 // build_constraints, prove and verify also call the device steps, which the .hip files add as static members:
 //   Lig, kProveName, host_field, kDeferGh, eval_layer, sumcheck_layer, bind_gh_all (+ gh_enqueue / gh_read when kDeferGh),
 //   eq_table, low_degree / dot / quadratic / open, verifier_ext.
+// prove_batch (B statements in lock-step; instantiated for the 16-byte policy only) also wants kProveBatchName, eval_layer_batch
+// and sumcheck_layer_batch.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -712,6 +714,74 @@ void round_cb(void* user, size_t hand, size_t rnd, const typename P::E ev[3], ty
   *chal = r->tst->elt();
 }
 
+// ---- the phases of prove: evaluation + fs_init, padded sumcheck, constraints + Ligero prove.  prove (one statement) and
+// prove_batch (B statements in lock-step) are both written over the pieces below; only the device calls differ.
+struct CloneGuard {  // the copy of the transcript that the sumcheck prover runs on (zk_prover.h:117-124)
+  const lfgpu_transcript_ops* o;
+  void* u;
+  ~CloneGuard() {
+    if (u) o->free_clone(u);
+  }
+};
+// eval_circuit's verdict: no assert-zero term fired and every output is zero (prover_layers.h:52-104, zk_prover.h:104-112)
+template <class P>
+bool witness_ok(const typename P::E* V, size_t nv, int failed) {
+  if (failed) return false;  // an assert-zero term is non-zero: eval_circuit returns nullptr
+  for (size_t i = 0; i < nv; ++i)
+    if (!P::is_zero(V[i])) return false;  // "V->v_[i] != F.zero()"
+  return true;
+}
+template <class P>
+struct ScRun {  // what the padded sumcheck of one statement carries from layer to layer (ProverLayers::prove with pad)
+  using E = typename P::E;
+  std::vector<E> G[2];
+  E WC[2] = {P::zero(), P::zero()};
+  size_t logv = 0;
+};
+template <class P>
+void sc_begin(const Ts<P>& tst, const lfgpu_circuit* C, ProverState<P>& st, ScRun<P>& run) {
+  const size_t nl = C->layers.size();
+  st.proof.sc.assign(nl, {});
+  st.aux.assign(nl, P::zero());
+  for (size_t i = 0; i < kMaxBindings; ++i) (void)tst.elt();  // begin_circuit: Q then G (transcript_sumcheck.h:49-52)
+  run.G[0].resize(kMaxBindings);
+  for (size_t i = 0; i < kMaxBindings; ++i) run.G[0][i] = tst.elt();
+  run.G[1] = run.G[0];
+  run.logv = C->info.logv;
+  run.WC[0] = run.WC[1] = P::zero();
+}
+// a layer's challenges alpha and beta, and the round context of its (hand, round) callbacks
+template <class P>
+RoundCtx<P> sc_layer_open(const typename P::Field& F, const Ts<P>& tst, ProverState<P>& st, size_t ly, size_t logw, typename P::E* alpha,
+                          typename P::E* beta) {
+  *alpha = tst.elt();
+  *beta = tst.elt();
+  auto& S = st.proof.sc[ly];
+  S.hp[0].resize(2 * logw);
+  S.hp[1].resize(2 * logw);
+  return RoundCtx<P>{&F, &tst, &st.pad[ly], &S};
+}
+// end_layer (prover_layers.h:331-344): transmit wc - pad; the claims and the binding of the next layer
+template <class P>
+void sc_layer_close(const typename P::Field& F, const Ts<P>& tst, ProverState<P>& st, size_t ly, size_t logw, const typename P::E wc_out[2],
+                    const typename P::E& bq, const typename P::E* gout /*[2][logw]*/, ScRun<P>& run) {
+  auto& S = st.proof.sc[ly];
+  S.wc[0] = F.sub(wc_out[0], st.pad[ly].wc[0]);
+  S.wc[1] = F.sub(wc_out[1], st.pad[ly].wc[1]);
+  tst.write_array(S.wc, 2);
+  st.aux[ly] = bq;
+  run.WC[0] = wc_out[0];
+  run.WC[1] = wc_out[1];
+  for (int h = 0; h < 2; ++h) {
+    run.G[h].assign(kMaxBindings, P::zero());
+    for (size_t r = 0; r < logw; ++r) run.G[h][r] = gout[h * logw + r];
+  }
+  run.logv = logw;
+}
+template <class P, class EqTable>
+int prove_finish(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const typename P::Field& F, ProverState<P>& st, typename P::Lig* lp, EqTable eq_table,
+                 const typename P::E* W, const Ts<P>& ts);
+
 // d_in: the layers' inputs (eval_circuit leaves them resident for the sumcheck), d_V / h_V: the circuit outputs on the device
 // and pinned (h_V: nv elements, then the assert-zero flag), eq_table(E** d_eq): room for the EQ table over the inputs (valid
 // until lp's dot proof has run), asked for when the constraints are built.  *ok = 0 when the witness does not satisfy the
@@ -755,61 +825,46 @@ int prove(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, ProverState<P>& st
     (void)hipStreamSynchronize(c->stream);
     return lf_fail(c, LFGPU_ERR_NOMEM, "%s: transcript clone", P::kProveName);
   }
-  struct CloneGuard {
-    const lfgpu_transcript_ops* o;
-    void* u;
-    ~CloneGuard() { o->free_clone(u); }
-  } cg{tso, cl};
+  CloneGuard cg{tso, cl};
   const Ts<P> tst{&pol, tso, cl};
 
   t0 = now_ms();
   LF_HIP(c, hipStreamSynchronize(c->stream));
-  if (*failed) return LFGPU_OK;  // an assert-zero term is non-zero: eval_circuit returns nullptr
-  for (size_t i = 0; i < I.nv; ++i)
-    if (!P::is_zero(V[i])) return LFGPU_OK;  // "V->v_[i] != F.zero()"
+  if (!witness_ok<P>(V, I.nv, *failed)) return LFGPU_OK;
   st.ms[2] = t_enq + now_ms() - t0;  // what the evaluation adds to the wall time: enqueue + the wait left after the hashing
 
   // padded sumcheck (ProverLayers::prove with pad, transcript copy tst)
   t0 = now_ms();
-  ProofBody<E>& pr = st.proof;
-  pr.sc.assign(nl, {});
-  st.aux.assign(nl, P::zero());
-  std::vector<E> G[2];
-  {
-    for (size_t i = 0; i < kMaxBindings; ++i) (void)tst.elt();  // begin_circuit: Q then G (transcript_sumcheck.h:49-52)
-    G[0].resize(kMaxBindings);
-    for (size_t i = 0; i < kMaxBindings; ++i) G[0][i] = tst.elt();
-    G[1] = G[0];
-  }
-  size_t logv = I.logv;
-  E WC[2] = {P::zero(), P::zero()};
+  ScRun<P> run;
+  sc_begin<P>(tst, C, st, run);
   std::vector<E> gout;
   for (size_t ly = 0; ly < nl; ++ly) {
     const auto& L = C->layers[ly];
-    const E alpha = tst.elt(), beta = tst.elt();
-    auto& S = pr.sc[ly];
-    S.hp[0].resize(2 * L.logw);
-    S.hp[1].resize(2 * L.logw);
-    RoundCtx<P> rc{&F, &tst, &st.pad[ly], &S};
+    E alpha, beta;
+    RoundCtx<P> rc = sc_layer_open<P>(F, tst, st, ly, L.logw, &alpha, &beta);
     gout.assign(2 * L.logw + 1, P::zero());
     E wc_out[2], bq;
-    LF_TRY(P::sumcheck_layer(L.q, F, logv, G[0].data(), G[1].data(), alpha, beta, L.logw, L.nw, d_in[ly], WC, round_cb<P>, &rc, wc_out, gout.data(), &bq));
-    S.wc[0] = F.sub(wc_out[0], st.pad[ly].wc[0]);  // end_layer (:331-344): transmit wc - pad
-    S.wc[1] = F.sub(wc_out[1], st.pad[ly].wc[1]);
-    tst.write_array(S.wc, 2);
-    st.aux[ly] = bq;
-    WC[0] = wc_out[0];
-    WC[1] = wc_out[1];
-    for (int h = 0; h < 2; ++h) {
-      G[h].assign(kMaxBindings, P::zero());
-      for (size_t r = 0; r < L.logw; ++r) G[h][r] = gout[h * L.logw + r];
-    }
-    logv = L.logw;
+    LF_TRY(P::sumcheck_layer(L.q, F, run.logv, run.G[0].data(), run.G[1].data(), alpha, beta, L.logw, L.nw, d_in[ly], run.WC, round_cb<P>, &rc, wc_out,
+                             gout.data(), &bq));
+    sc_layer_close<P>(F, tst, st, ly, L.logw, wc_out, bq, gout.data(), run);
   }
   st.ms[3] = now_ms() - t0;
 
+  LF_TRY(prove_finish<P>(c, C, pol, F, st, lp, eq_table, W, ts));
+  st.ms[1] = now_ms() - t_start;
+  *ok = 1;
+  return LFGPU_OK;
+}
+
+// verifier_constraints with aux, then LigeroProver::prove, on the ORIGINAL transcript; the proof is then held by st
+template <class P, class EqTable>
+int prove_finish(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const typename P::Field& F, ProverState<P>& st, typename P::Lig* lp, EqTable eq_table,
+                 const typename P::E* W, const Ts<P>& ts) {
+  using E = typename P::E;
+  (void)pol;
+  ProofBody<E>& pr = st.proof;
   // verifier_constraints with aux (zk_common.h:49-136): replay the verifier symbolically on the ORIGINAL transcript
-  t0 = now_ms();
+  double t0 = now_ms();
   E* d_eq = nullptr;
   LF_TRY(eq_table(&d_eq));
   ConstraintSet<E> cs;
@@ -862,9 +917,125 @@ int prove(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, ProverState<P>& st
               tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
   }
   st.ms[5] = now_ms() - t0;
-  st.ms[1] = now_ms() - t_start;
   st.have_proof = true;
-  *ok = 1;
+  return LFGPU_OK;
+}
+
+// ------------------------------------------------------------------ B statements of one circuit in lock-step
+// The device buffers of a batch (the caller's; nothing is allocated here): per layer nb_max input slabs at stride ldw[l]
+// elements, the outputs at stride ldv, one assert-zero flag per statement, and the pinned read-back (nb_max * ldv elements,
+// then nb_max flags).
+struct BatchBufs {
+  void* const* d_in;
+  const size_t* ldw;
+  void* d_V;
+  size_t ldv;
+  int* d_fail;
+  void* h_V;
+  size_t nb_max;
+};
+template <class P>
+void round_batch_cb(void* user, size_t hand, size_t rnd, size_t nb, const typename P::E (*ev)[3], typename P::E* chal) {
+  RoundCtx<P>* r = (RoundCtx<P>*)user;
+  for (size_t b = 0; b < nb; ++b) round_cb<P>(&r[b], hand, rnd, ev[b], &chal[b]);
+}
+// prove for statements 0 .. nb-1: pol[b], st[b], lp[b], h_W[b], tso[b] are statement b's; ok[b] as prove's *ok.  A statement
+// whose witness fails rides along in the sumcheck on its transcript copy -- the launches are the batch's, not its own -- and
+// what it produces is dropped: it holds no proof and its transcript is where the single call leaves it.
+template <class P, class EqTable>
+int prove_batch(lfgpu_ctx* c, const lfgpu_circuit* C, const P* pol, ProverState<P>* const* st, typename P::Lig* const* lp, const BatchBufs& bb, size_t nb,
+                EqTable eq_table, const void* const* h_W, const lfgpu_transcript_ops* const* tso, int* ok) {
+  using E = typename P::E;
+  constexpr size_t B = P::kBytes;
+  const double t_start = now_ms();
+  const typename P::Field F = pol[0].host_field(c);
+  const lfgpu_circuit_info& I = C->info;
+  const size_t nl = C->layers.size();
+  for (size_t b = 0; b < nb; ++b) {
+    ok[b] = 0;
+    st[b]->have_proof = false;
+    st[b]->wire_valid = false;
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+
+  // eval_circuit of all statements: nl launches; the host hashes the nb preambles and clones the transcripts meanwhile
+  double t0 = now_ms();
+  for (size_t b = 0; b < nb; ++b)
+    LF_HIP(c, hipMemcpyAsync((uint8_t*)bb.d_in[nl - 1] + b * bb.ldw[nl - 1] * B, h_W[b], I.ninputs * B, hipMemcpyHostToDevice, c->stream));
+  LF_HIP(c, hipMemsetAsync(bb.d_fail, 0, nb * sizeof(int), c->stream));
+  for (size_t l = nl; l-- > 0;)
+    LF_TRY(P::eval_layer_batch(C->layers[l].q, nb, bb.d_in[l], bb.ldw[l], l ? bb.d_in[l - 1] : bb.d_V, l ? bb.ldw[l - 1] : bb.ldv, bb.d_fail));
+  int* const h_fail = (int*)((uint8_t*)bb.h_V + bb.nb_max * bb.ldv * B);
+  LF_HIP(c, hipMemcpyAsync(bb.h_V, bb.d_V, nb * bb.ldv * B, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipMemcpyAsync(h_fail, bb.d_fail, nb * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  const double t_enq = now_ms() - t0;
+
+  std::vector<Ts<P>> ts, tst;
+  std::vector<CloneGuard> cg(nb, CloneGuard{nullptr, nullptr});
+  ts.reserve(nb);
+  tst.reserve(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    ts.push_back(Ts<P>{&pol[b], tso[b], tso[b]->user});
+    fs_init(ts[b], C, (const E*)h_W[b]);
+    void* cl = tso[b]->clone(tso[b]->user);
+    if (!cl) {
+      (void)hipStreamSynchronize(c->stream);
+      return lf_fail(c, LFGPU_ERR_NOMEM, "%s: transcript clone", P::kProveBatchName);
+    }
+    cg[b].o = tso[b];
+    cg[b].u = cl;
+    tst.push_back(Ts<P>{&pol[b], tso[b], cl});
+  }
+
+  t0 = now_ms();
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  std::vector<char> good(nb, 0);
+  size_t ngood = 0;
+  for (size_t b = 0; b < nb; ++b) {
+    good[b] = witness_ok<P>((const E*)bb.h_V + b * bb.ldv, I.nv, h_fail[b]);
+    ngood += good[b] ? 1 : 0;
+  }
+  const double ms_eval = t_enq + now_ms() - t0;
+  if (!ngood) return LFGPU_OK;
+
+  // padded sumcheck: one batched call per layer; G, alpha, beta, WC and aux are per statement
+  t0 = now_ms();
+  std::vector<ScRun<P>> run(nb);
+  for (size_t b = 0; b < nb; ++b) sc_begin<P>(tst[b], C, *st[b], run[b]);
+  std::vector<E> G0, G1, alpha(nb), beta(nb), wc_in(2 * nb), wc_out(2 * nb), bq(nb), gout;
+  std::vector<RoundCtx<P>> rc;
+  for (size_t ly = 0; ly < nl; ++ly) {
+    const auto& L = C->layers[ly];
+    const size_t logv = run[0].logv;
+    G0.assign(nb * logv + 1, P::zero());
+    G1.assign(nb * logv + 1, P::zero());
+    rc.clear();
+    for (size_t b = 0; b < nb; ++b) {
+      rc.push_back(sc_layer_open<P>(F, tst[b], *st[b], ly, L.logw, &alpha[b], &beta[b]));
+      for (size_t l = 0; l < logv; ++l) {
+        G0[b * logv + l] = run[b].G[0][l];
+        G1[b * logv + l] = run[b].G[1][l];
+      }
+      wc_in[2 * b] = run[b].WC[0];
+      wc_in[2 * b + 1] = run[b].WC[1];
+    }
+    gout.assign(nb * 2 * L.logw + 1, P::zero());
+    LF_TRY(P::sumcheck_layer_batch(L.q, F, nb, logv, G0.data(), G1.data(), alpha.data(), beta.data(), L.logw, L.nw, bb.d_in[ly], bb.ldw[ly], wc_in.data(),
+                                   round_batch_cb<P>, rc.data(), wc_out.data(), gout.data(), bq.data()));
+    for (size_t b = 0; b < nb; ++b) sc_layer_close<P>(F, tst[b], *st[b], ly, L.logw, &wc_out[2 * b], bq[b], &gout[b * 2 * L.logw], run[b]);
+  }
+  const double ms_sc = now_ms() - t0;
+
+  // constraints, Ligero prove and open: per statement, one after the other (the context's EQ table is reused)
+  for (size_t b = 0; b < nb; ++b) {
+    st[b]->ms[2] = ms_eval;
+    st[b]->ms[3] = ms_sc;
+    if (!good[b]) continue;
+    LF_TRY(prove_finish<P>(c, C, pol[b], F, *st[b], lp[b], eq_table, (const E*)h_W[b], ts[b]));
+    ok[b] = 1;
+  }
+  const double ms_all = now_ms() - t_start;
+  for (size_t b = 0; b < nb; ++b) st[b]->ms[1] = ms_all;
   return LFGPU_OK;
 }
 
