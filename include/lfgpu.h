@@ -71,7 +71,8 @@ int lfgpu_own_stream(lfgpu_ctx* ctx);
  * merges consecutive draws into one call of the lfgpu_rng_fn hook -- the same bytes for every engine that is a byte stream
  * (SecureRandomEngine, Transcript, the LCG test engines) and far fewer calls.  exact = 1 keeps the reference's call pattern,
  * for engines whose output depends on the call boundaries (the TestRng of rust/runtime/zk/tests/zk.rs:283-292 returns
- * {2, 0, 0, ...} for EVERY call).  Applies to lfgpu_ligero_commit and lfgpu_zk_commit on this context. */
+ * {2, 0, 0, ...} for EVERY call).  Applies to lfgpu_ligero_commit and lfgpu_zk_commit on this context, and to their _batch
+ * forms. */
 int lfgpu_set_rng_exact_calls(lfgpu_ctx* ctx, int exact);
 int lfgpu_sync(lfgpu_ctx* ctx);
 /* device-memory helpers so that C / ctypes / cgo callers need no HIP runtime */
@@ -141,6 +142,13 @@ int lfgpu_fp256_rs_encode_rows_host(lfgpu_ctx* ctx, size_t nrow, size_t n, size_
  * device for lfgpu_merkle_open.  root_out: 32 host bytes. */
 int lfgpu_column_commit(lfgpu_ctx* ctx, int field, size_t nrow, size_t ld, size_t col0, size_t ncols,
                         const void* d_T, const void* d_nonces, void* d_layers, uint8_t root_out[32]);
+/* lfgpu_column_commit for nb tableaux of one shape: leaf hash + tree of every statement in one launch each,
+ * all roots in one read-back.  d_T[b], d_layers[b]: device pointers per statement (host arrays of nb pointers; the kernels
+ * take them as one by-value argument, nothing is uploaded); d_nonces: [nb][ncols][32] contiguous on the device.
+ * Heap b and root b are byte-identical to lfgpu_column_commit on statement b alone.  1 <= nb <= LFGPU_SC_BATCH_MAX.
+ * Fields: GF2_128 and Fp128; LFGPU_ERR_UNSUPPORTED for P256. */
+int lfgpu_column_commit_batch(lfgpu_ctx* ctx, int field, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb,
+                              const void* const* d_T, const void* d_nonces, void* const* d_layers, uint8_t* roots_out /*[nb][32]*/);
 /* The leaf half of the above alone (enqueue only, nothing read back): d_leaves[j] = leaf digest of column col0 + j,
  * j < ncols, 32 bytes each.  Multi-GPU commit: after the column re-partition a rank hashes the columns it
  * owns, the digests are all-gathered into the leaf level of d_layers and lfgpu_merkle_build_tree finishes on every rank. */
@@ -330,6 +338,26 @@ typedef struct lfgpu_ligero_prover lfgpu_ligero_prover;
 int lfgpu_ligero_commit(lfgpu_ctx* ctx, int field, int subfield_log_bits, const lfgpu_ligero_param* p,
                         const void* h_W, size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng,
                         void* rng_user, uint8_t root_out[32], lfgpu_ligero_prover** out);
+/* nb x lfgpu_ligero_commit of ONE lfgpu_ligero_param and one h_lqc, each statement with its own witness and RandomEngine.
+ * The host layout runs per statement in index order b = 0 .. nb-1, every draw of statement b from rng[b] (user rng_user[b];
+ * rng_user = NULL: every user is NULL) in lfgpu_ligero_commit's order, lfgpu_set_rng_exact_calls honoured.  Handing the SAME
+ * engine to several statements therefore gives the bytes of sequential lfgpu_ligero_commit calls in index order.  The device
+ * half is one chain for all statements: asynchronous uploads from pinned staging memory (kept by the context for the next
+ * call, scrubbed after each), the Reed-Solomon encode with the statement on a grid axis, one leaf-hash launch, the Merkle
+ * levels with the statement on a grid axis, all roots in one read-back and ONE stream synchronise.  GF(2^128) rows longer
+ * than 2^12 (the shapes lfgpu_gf2128_rs_encode_tableau refuses) are encoded per statement with lfgpu_ligero_commit's own
+ * encoder inside the call: correct, merely unbatched.  Fp128: the statements are chunked so that a launch holds at most
+ * 65535 rows and the convolution scratch stays under 256 MiB (LFGPU_CB_CHUNK=<statements per chain> overrides, read once).
+ * Roots, tableaux, Merkle heaps and nonces are byte-identical to nb lfgpu_ligero_commit calls; each out[b] is an ordinary
+ * prover that owns its pooled buffers (every prove / open / free entry point works on it; free in any order).
+ * LFGPU_COMMIT_BATCH=0 (read once) keeps these semantics and runs the single-statement device path per statement.
+ * 1 <= nb <= LFGPU_SC_BATCH_MAX, else LFGPU_ERR_ARG; argument errors are found before the first draw.  An error inside
+ * statement b's layout (LFGPU_ERR_ARG: lqc index out of range; LFGPU_ERR_ASSERT: a quadratic constraint does not hold) fails
+ * the whole call: out[0 .. nb) are NULL and every buffer is back in the pool, scrubbed.  Fields: GF2_128 and Fp128. */
+int lfgpu_ligero_commit_batch(lfgpu_ctx* ctx, int field, int subfield_log_bits, const lfgpu_ligero_param* p, size_t nb,
+                              const void* const* h_W, size_t subfield_boundary, const size_t* h_lqc,
+                              const lfgpu_rng_fn* rng, void* const* rng_user, uint8_t* roots_out /*[nb][32]*/,
+                              lfgpu_ligero_prover** out /*[nb]*/);
 /* LigeroProver::commit split for a row slab [row_lo, row_hi) of the tableau -- the multi-GPU form (rows are independent
  * up to the RandomEngine's draw order, lib/ligero/ligero_prover.h:171-270).
  *  lfgpu_ligero_layout_rows: HOST ONLY (no context, no device).  Performs every RandomEngine draw of commit in the

@@ -148,6 +148,24 @@ int lfgpu_zk_batch_new(lfgpu_ctx* ctx, const lfgpu_circuit* c, size_t nb_max, lf
 int lfgpu_zk_prove_batch(lfgpu_zk_batch* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
                          const lfgpu_transcript_ops* const* ts, int* ok /*[nb]*/);
 int lfgpu_zk_batch_free(lfgpu_zk_batch* batch);
+/* ---- ZkProver::commit for a batch of provers ----
+ * lfgpu_zk_commit (its one-GPU branch) for nb provers of the batch's context and circuit in one chain of dispatches: per
+ * statement, in index order, fill_pad from rng[b] (its draws come before its Ligero draws, as in lfgpu_zk_commit); then ONE
+ * lfgpu_ligero_commit_batch (lfgpu.h) for all statements; then, once every root is back, ts[b]->write_bytes(root b) per
+ * statement.  Afterwards prover b is in exactly the state lfgpu_zk_commit leaves it in (an earlier commitment and proof are
+ * dropped), so lfgpu_zk_prove or lfgpu_zk_prove_batch may follow; roots and proofs are byte-identical to the single path's.
+ * lfgpu_zk_timings()[0] is the whole call's time, the same value for every member.  rng_user = NULL: every user is NULL.
+ * Every statement needs a RandomEngine of its own: the pads of ALL statements are drawn before the first Ligero layout, so an
+ * engine shared between statements would not see the draw order of sequential lfgpu_zk_commit calls.
+ * roots_out: [nb][32] or NULL.  LFGPU_COMMIT_BATCH=0 (read once per process) runs the single-statement device path per
+ * statement instead: the same bytes (the A/B switch).
+ * LFGPU_ERR_ARG (found before the first draw, nothing touched): a NULL entry, nb out of 1 .. nb_max, a prover of another
+ * context or circuit, the same prover twice, provers whose lfgpu_ligero_param differ (another rate, nreq or block_enc).
+ * LFGPU_ERR_UNSUPPORTED: a prover with a communicator set.  On an error after the draws began no transcript has been written
+ * to and every prover of the call holds no commitment. */
+int lfgpu_zk_commit_batch(lfgpu_zk_batch* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                          const lfgpu_rng_fn* rng, void* const* rng_user,
+                          const lfgpu_transcript_ops* const* ts, uint8_t* roots_out /*[nb][32], may be NULL*/);
 
 /* ---- ZkVerifier ----
  * ZkVerifier::recv_commitment + verify (lib/zk/zk_verifier.h:68-94) on the wire bytes of ZkProof::write

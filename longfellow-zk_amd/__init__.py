@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "lfgpu_circuit_free", "lfgpu_zk_prover_new", "lfgpu_zk_prover_set_comm", "lfgpu_zk_prover_param", "lfgpu_zk_commit", "lfgpu_zk_prove",
     "lfgpu_zk_proof_write", "lfgpu_zk_timings", "lfgpu_zk_prover_free", "lfgpu_zk_verify", "lfgpu_zk_verify_committed",
     "lfgpu_zk_batch_new", "lfgpu_zk_prove_batch", "lfgpu_zk_batch_free",
+    "lfgpu_column_commit_batch", "lfgpu_ligero_commit_batch", "lfgpu_zk_commit_batch",
 ]
 
 
@@ -182,6 +183,9 @@ def load_library():
         "lfgpu_zk_batch_new": [vp, vp, sz, C.POINTER(vp)],
         "lfgpu_zk_prove_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), C.POINTER(ci)],
         "lfgpu_zk_batch_free": [vp],
+        "lfgpu_column_commit_batch": [vp, ci, sz, sz, sz, sz, sz, C.POINTER(vp), vp, C.POINTER(vp), vp],
+        "lfgpu_ligero_commit_batch": [vp, ci, ci, C.POINTER(LigeroParam), sz, C.POINTER(vp), sz, vp, C.POINTER(RNG_FN), C.POINTER(vp), vp, C.POINTER(vp)],
+        "lfgpu_zk_commit_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(RNG_FN), C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -330,6 +334,19 @@ class LfGpu:
                                             C.c_void_p(d_nonces), C.c_void_p(d_layers), root))
         return bytes(root)
 
+    def column_commit_batch(self, field, nrow, ld, col0, ncols, d_Ts, d_nonces, d_layers):
+        """lfgpu_column_commit for len(d_Ts) tableaux of one shape in one chain: d_Ts / d_layers are lists of device pointers,
+        d_nonces one contiguous [nb][ncols][32] device array -> [root] per statement"""
+        nb = len(d_Ts)
+        if len(d_layers) != nb:
+            raise ValueError("column_commit_batch: one heap per tableau")
+        n = max(1, nb)
+        roots = (C.c_uint8 * (32 * n))()
+        self._ck(self.L.lfgpu_column_commit_batch(self.h, field, nrow, ld, col0, ncols, nb, (C.c_void_p * n)(*d_Ts), C.c_void_p(d_nonces),
+                                                  (C.c_void_p * n)(*d_layers), roots))
+        raw = bytes(roots)
+        return [raw[32 * b:32 * b + 32] for b in range(nb)]
+
     def merkle_build_tree(self, n, d_layers):
         root = (C.c_uint8 * 32)()
         self._ck(self.L.lfgpu_merkle_build_tree(self.h, n, C.c_void_p(d_layers), root))
@@ -470,6 +487,37 @@ class LigeroProver:
                                            self._cb, None, root, C.byref(h)))
         self.h = h
         return bytes(root)
+
+    @staticmethod
+    def commit_batch(gpu, field, param, Ws, subfield_boundary, lqc, rng_bytes_list, subfield_log_bits=4):
+        """lfgpu_ligero_commit_batch: len(Ws) commits of one LigeroParam and one lqc through one chain of dispatches, statement b
+        with witness Ws[b] and RandomEngine rng_bytes_list[b] (the same callable may appear more than once: the draws then
+        come in index order) -> ([root], [LigeroProver]); the provers are ordinary ones"""
+        import numpy as np
+        nb = len(Ws)
+        if len(rng_bytes_list) != nb:
+            raise ValueError("LigeroProver.commit_batch: one RandomEngine per witness")
+
+        def mk(rng_bytes):
+            def cb(_user, buf, n):
+                C.memmove(buf, rng_bytes(n), n)
+            return RNG_FN(cb)
+
+        cbs = [mk(r) for r in rng_bytes_list]
+        lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
+        Ws = [np.ascontiguousarray(W) for W in Ws]
+        n = max(1, nb)
+        roots = (C.c_uint8 * (32 * n))()
+        hs = (C.c_void_p * n)()
+        gpu._ck(gpu.L.lfgpu_ligero_commit_batch(gpu.h, field, subfield_log_bits, C.byref(param), nb, (C.c_void_p * n)(*[W.ctypes.data for W in Ws]),
+                                                 subfield_boundary, C.c_void_p(lq.ctypes.data) if lq.size else None, (RNG_FN * n)(*cbs), None, roots, hs))
+        raw = bytes(roots)
+        provers = []
+        for b in range(nb):
+            pr = LigeroProver(gpu, field, param, subfield_log_bits)
+            pr.h, pr._cb = C.c_void_p(hs[b]), cbs[b]
+            provers.append(pr)
+        return [raw[32 * b:32 * b + 32] for b in range(nb)], provers
 
     def low_degree_proof(self, u_ldt):
         import numpy as np
@@ -824,6 +872,29 @@ class ZkBatch:
         h = C.c_void_p()
         gpu._ck(gpu.L.lfgpu_zk_batch_new(gpu.h, circuit.h, nb_max, C.byref(h)))
         self.h = h
+
+    def commit(self, provers, Ws, rng_bytes_list, transcripts):
+        """lfgpu_zk_commit_batch: ZkProver.commit for every prover through one chain of dispatches (one batched Ligero commit),
+        statement b with its own witness, RandomEngine `rng_bytes_list[b](n) -> bytes` and transcript -> [root]"""
+        import numpy as np
+        nb = len(provers)
+        if not (len(Ws) == nb and len(rng_bytes_list) == nb and len(transcripts) == nb):
+            raise ValueError("ZkBatch.commit: one witness, one RandomEngine and one transcript per prover")
+
+        def mk(rng_bytes):
+            def cb(_user, buf, n):
+                C.memmove(buf, rng_bytes(n), n)
+            return RNG_FN(cb)
+
+        cbs = [mk(r) for r in rng_bytes_list]
+        Ws = [np.ascontiguousarray(W) for W in Ws]
+        ops = [t.ops() for t in transcripts]
+        n = max(1, nb)
+        roots = (C.c_uint8 * (32 * n))()
+        self.gpu._ck(self.gpu.L.lfgpu_zk_commit_batch(self.h, (C.c_void_p * n)(*[p.h for p in provers]), nb, (C.c_void_p * n)(*[W.ctypes.data for W in Ws]),
+                                                      (RNG_FN * n)(*cbs), None, (C.POINTER(TranscriptOps) * n)(*[C.pointer(o) for o in ops]), roots))
+        raw = bytes(roots)
+        return [raw[32 * b:32 * b + 32] for b in range(nb)]
 
     def prove(self, provers, Ws, transcripts):
         """-> [bool] per statement: True = provers[b] holds its proof, False = witness b does not satisfy the circuit"""

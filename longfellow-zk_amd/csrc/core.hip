@@ -288,6 +288,10 @@ int lfgpu_shutdown(lfgpu_ctx* c) {
   if (c->sc_batch_h) hipHostFree((void*)c->sc_batch_h);
   if (c->sc_batch_pts_ev) hipEventDestroy(c->sc_batch_pts_ev);
   if (c->sc_batch_pts_h) hipHostFree(c->sc_batch_pts_h);
+  if (c->cb_stage_h) {
+    explicit_bzero(c->cb_stage_h, c->cb_stage_bytes);
+    hipHostFree(c->cb_stage_h);
+  }
   for (int i = 0; i < 4; ++i)
     if (c->stage_ev[i]) hipEventDestroy(c->stage_ev[i]);
   if (c->stage_h) hipHostFree(c->stage_h);

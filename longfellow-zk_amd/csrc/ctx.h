@@ -73,9 +73,13 @@ struct lfgpu_ctx {
   // sc_batch_pts_ev (recorded after its copy) has completed
   void* sc_batch_pts_h = nullptr;
   hipEvent_t sc_batch_pts_ev = nullptr;
+  // lfgpu_ligero_commit_batch: pinned staging of the un-encoded images and nonces of a batch of statements, sized for the call
+  // and kept for the next one; it holds witnesses and blinding rows, so it is scrubbed after every call and before it is freed
+  void* cb_stage_h = nullptr;
+  size_t cb_stage_bytes = 0;
   // per-context (= per-device) launch configuration: nothing below the C ABI is process-global, so one process may hold
   // contexts on several devices (hipFuncSetAttribute is applied once per context)
-  unsigned attr_done = 0;  // bit 0 FFT tile kernels, 1 RS row kernel, 2 bit-sliced butterflies, 3 sumcheck grid tail
+  unsigned attr_done = 0;  // bit 0 FFT tile kernels, 1 RS row kernel, 2 bit-sliced butterflies, 3 sumcheck grid tail, 4 batched RS row kernel
   int tile_log = 12;       // FFT tile = 2^tile_log elements (LFGPU_TILE_LOG = 12 | 13)
   unsigned bs_rlog = 5;    // bit-sliced butterfly tile: 2^bs_rlog combos (LFGPU_BS_RLOG = 5..7)
   int sc_tail_ok = -1;     // the shrinking-grid kernel may use its LDS tail (-1 undecided)
@@ -134,7 +138,7 @@ struct LfScrubHost {
 // to the context's pool instead of hipMalloc / hipFree.  A returned buffer may still be in use by work queued on the
 // context's stream (in order: whatever a later user enqueues comes after it).  At most LF_POOL_MAX entries and LF_POOL_MAX_BYTES
 // in all, oldest evicted.
-#define LF_POOL_MAX 8
+#define LF_POOL_MAX (2 * LFGPU_SC_BATCH_MAX)  // a full batch of provers returns its tableaux and Merkle heaps at once (lfgpu_zk_commit_batch)
 #define LF_POOL_MAX_BYTES ((size_t)2 << 30)  // all pooled buffers of a context together; larger single buffers are freed at once
 int lf_pool_get(lfgpu_ctx* c, size_t bytes, void** out);
 void lf_pool_put(lfgpu_ctx* c, void* p, size_t bytes);
@@ -171,6 +175,20 @@ bool h_fp_fits(elt_t raw);      // raw < p
 // Reed-Solomon row extension for either field (GF2_128<k>: LCH14; Fp128: convolution with the 2^32-order root)
 int lf_rs_rows(lfgpu_ctx* c, int field, int k, size_t nrow, size_t n, size_t m, elt_t* d, size_t ld);
 int lf_gf_rs_rows_mixed(lfgpu_ctx* c, int k, size_t nrow, size_t n1, size_t n2, size_t lo2, size_t hi2, size_t m, elt_t* d_T, size_t ld);
+// The batched commit (rs.hip, merkle.hip): the tableaux / Merkle heaps of the statements stay the provers' own buffers, so the
+// kernels take their base pointers as ONE by-value argument indexed by the statement's (wave-uniform) block index -- scalar
+// loads from the kernarg segment, no device-side pointer array that could outlive its batch.
+struct LfBatchPtrs {
+  void* p[LFGPU_SC_BATCH_MAX];
+};
+// lf_gf_rs_rows_mixed for nb tableaux of one shape in one launch (statement on gridDim.y); the same LFGPU_ERR_UNSUPPORTED rule
+int lf_gf_rs_rows_mixed_batch(lfgpu_ctx* c, int k, size_t nb, elt_t* const* d_T, size_t nrow, size_t n1, size_t n2, size_t lo2, size_t hi2, size_t m, size_t ld);
+// Fp128: rows [row0, row0 + nrow) of nb tableaux, each n values long, extended to m through ONE convolution of nb * nrow rows
+int lf_fp_rs_rows_batch(lfgpu_ctx* c, size_t nb, elt_t* const* d_T, size_t row0, size_t nrow, size_t n, size_t m, size_t ld);
+void lf_fp_omega32(uint64_t om[2]);  // the 2^32-order root of Fp128 (lib/algebra/fp_p128.h:48-56), Montgomery image
+// most Fp128 convolution scratch (nb * rows * P * 16 bytes) one launch chain of the batched commit may ask for: the statements
+// are chunked to stay below it (a single statement's row group may exceed it, as it does in lfgpu_ligero_commit)
+#define LF_CB_SCRATCH_CAP ((size_t)256 << 20)
 const GfHostCtx* lf_gf_ctx(lfgpu_ctx* c, int k);
 bool lf_gf_ctx_build(GfHostCtx* g, int k);  // the same constants without a context (host-only entry points)
 elt_t h_lch14_twiddle(const GfHostCtx* g, unsigned i, u64 u);

@@ -309,12 +309,19 @@ extern "C" int lfgpu_ligero_layout_rows(int field, int k, const lfgpu_ligero_par
   return ligero_layout_host(field, k, &g, *pp, (const elt_t*)h_W, subfield_boundary, h_lqc, rng, user, row_lo, row_hi, (elt_t*)h_rows, h_nonces, err);
 }
 
+static int ligero_extend_slab(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, elt_t* d_slab);
 // rows [row_lo, row_hi) of the tableau: upload the un-encoded image and RS-extend every row to block_enc
 // (rows IDOT / IQUAD carry dblock values, every other row block: ligero_prover.h:175,184,203,210,237)
 static int ligero_encode_slab(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, const elt_t* H, elt_t* d_slab) {
   const size_t nr = row_hi - row_lo, ld = p.block_enc, hw = p.dblock;
   if (nr == 0) return LFGPU_OK;
   LF_HIP(c, hipMemcpy2DAsync(d_slab, ld * 16, H, hw * 16, hw * 16, nr, hipMemcpyHostToDevice, c->stream));
+  return ligero_extend_slab(c, field, k, p, row_lo, row_hi, d_slab);
+}
+// ... the RS extension alone, of a slab whose un-encoded image is already on the device
+static int ligero_extend_slab(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, elt_t* d_slab) {
+  const size_t nr = row_hi - row_lo, ld = p.block_enc;
+  if (nr == 0) return LFGPU_OK;
   // the rows with dblock values form one contiguous global range [idot, iquad + 1); clip it to the slab
   const size_t g_lo = std::min(p.idot, p.iquad), g_hi = std::max(p.idot, p.iquad) + 1;
   const bool contiguous = g_hi - g_lo == 2;
@@ -406,6 +413,162 @@ extern "C" int lfgpu_ligero_commit(lfgpu_ctx* c, int field, int k, const lfgpu_l
     fprintf(stderr, "lfgpu ligero_commit: %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
             p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, clk() - tv2);
   *out = pr;
+  return LFGPU_OK;
+}
+
+// ------------------------------------------------------------------ nb commits of one shape in one chain of dispatches
+// statements per launch chain of the batched RS encode: the Fp128 kernels carry the rows of a group on gridDim.y (<= 65535) and
+// the convolution scratch is nb * rows * P * 16 bytes (<= LF_CB_SCRATCH_CAP); LFGPU_CB_CHUNK overrides (read once)
+static size_t commit_batch_chunk(int field, const lfgpu_ligero_param& p, size_t nb) {
+  static const long env = getenv("LFGPU_CB_CHUNK") ? atol(getenv("LFGPU_CB_CHUNK")) : 0;
+  size_t chunk = nb;
+  if (field == LFGPU_FIELD_FP128) {
+    const size_t g_lo = std::min(p.idot, p.iquad), g_hi = std::max(p.idot, p.iquad) + 1;
+    const size_t rows = std::max<size_t>(1, std::max(std::max(g_lo, g_hi - g_lo), p.nrow - g_hi));  // the largest row group
+    size_t P = 1;
+    while (P < p.block_enc) P <<= 1;
+    chunk = std::min(chunk, std::min<size_t>(65535 / rows, LF_CB_SCRATCH_CAP / (rows * P * 16)));
+  }
+  if (env > 0) chunk = std::min(chunk, (size_t)env);
+  return std::max<size_t>(chunk, 1);
+}
+// the RS extension of nb tableaux whose un-encoded images are on the device
+static int ligero_extend_batch(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t nb, elt_t* const* d_T) {
+  const size_t ld = p.block_enc;
+  const size_t lo2 = std::min(p.idot, p.iquad), hi2 = std::max(p.idot, p.iquad) + 1;
+  if (hi2 - lo2 != 2) return lf_fail(c, LFGPU_ERR_ARG, "ligero: IDOT and IQUAD rows must be adjacent");
+  const size_t chunk = commit_batch_chunk(field, p, nb);
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0);
+    if (field == LFGPU_FIELD_GF2_128) {
+      const int rc = lf_gf_rs_rows_mixed_batch(c, k, cb, d_T + b0, p.nrow, p.block, p.dblock, lo2, hi2, p.block_enc, ld);
+      if (rc != LFGPU_ERR_UNSUPPORTED) {
+        LF_TRY(rc);
+        continue;
+      }
+      // rows longer than the LDS-resident kernel: the single path's encoder, statement by statement
+      for (size_t b = b0; b < b0 + cb; ++b) LF_TRY(ligero_extend_slab(c, field, k, p, 0, p.nrow, d_T[b]));
+    } else if (cb * std::max(hi2, p.nrow - hi2) > 65535) {  // (cb = 1) a row group of one statement overflows a launch: the single path's encoder
+      for (size_t b = b0; b < b0 + cb; ++b) LF_TRY(ligero_extend_slab(c, field, k, p, 0, p.nrow, d_T[b]));
+    } else {
+      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, 0, lo2, p.block, p.block_enc, ld));
+      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, lo2, hi2 - lo2, p.dblock, p.block_enc, ld));
+      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, hi2, p.nrow - hi2, p.block, p.block_enc, ld));
+    }
+  }
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_ligero_commit_batch(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, size_t nb, const void* const* h_W,
+                                         size_t subfield_boundary, const size_t* h_lqc, const lfgpu_rng_fn* rng, void* const* rng_user,
+                                         uint8_t* roots_out, lfgpu_ligero_prover** out) {
+  if (!c || !pp || !h_W || !rng || !roots_out || !out) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: null argument");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: nb = %zu, a batch holds 1..%d statements", nb, LFGPU_SC_BATCH_MAX);
+  for (size_t b = 0; b < nb; ++b)
+    if (!ligero_args_ok(field, k, pp, h_W[b], h_lqc, rng[b]))
+      return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: bad argument for statement %zu (null pointer, field or subfield_log_bits)", b);
+  for (size_t b = 0; b < nb; ++b) out[b] = nullptr;
+  auto user = [&](size_t b) { return rng_user ? rng_user[b] : nullptr; };
+  auto drop = [&](int rc) {  // no prover is returned: their buffers go back to the pool scrubbed (lfgpu_ligero_free)
+    for (size_t b = 0; b < nb; ++b) {
+      if (out[b]) lfgpu_ligero_free(out[b]);
+      out[b] = nullptr;
+    }
+    return rc;
+  };
+  static const int batched = getenv("LFGPU_COMMIT_BATCH") ? atoi(getenv("LFGPU_COMMIT_BATCH")) : 1;
+  if (!batched) {  // the A/B switch: the same semantics over the single-statement device path
+    for (size_t b = 0; b < nb; ++b) {
+      const int rc = lfgpu_ligero_commit(c, field, k, pp, h_W[b], subfield_boundary, h_lqc, rng[b], user(b), roots_out + 32 * b, &out[b]);
+      if (rc) {
+        out[b] = nullptr;
+        return drop(rc);
+      }
+    }
+    return LFGPU_OK;
+  }
+  const GfHostCtx* g = field == LFGPU_FIELD_GF2_128 ? lf_gf_ctx(c, k) : nullptr;
+  const lfgpu_ligero_param& p = *pp;
+  const size_t ld = p.block_enc, hw = p.dblock, ncols = p.block_ext;
+  LF_HIP(c, hipSetDevice(c->device));
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  auto clk = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+  const double tv0 = verbose ? clk() : 0;
+  // pinned staging: [nb][nrow][dblock] un-encoded images, then [nb][ncols][32] nonces.  The uploads of the previous call are
+  // over (every call ends with a stream synchronise), so the memory may be rewritten at once.
+  const size_t img = p.nrow * hw * 16, used = nb * (img + ncols * 32);
+  if (c->cb_stage_bytes < used) {
+    if (c->cb_stage_h) (void)hipHostFree(c->cb_stage_h);  // (scrubbed after the call that filled it)
+    c->cb_stage_h = nullptr;
+    c->cb_stage_bytes = 0;
+    if (hipHostMalloc(&c->cb_stage_h, used, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      c->cb_stage_h = nullptr;
+      return lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: %zu bytes of pinned staging", used);
+    }
+    c->cb_stage_bytes = used;
+  }
+  uint8_t* const stage = (uint8_t*)c->cb_stage_h;
+  uint8_t* const h_non = stage + nb * img;
+  struct Scrub {  // the images hold the witnesses, the pads and the blinding rows
+    uint8_t* p;
+    size_t n;
+    ~Scrub() { explicit_bzero(p, n); }
+  } scrub{stage, used};
+  // the host half, statement by statement in index order: all draws of statement b from rng[b]
+  for (size_t b = 0; b < nb; ++b) {
+    char err[256] = {0};
+    const int rc = ligero_layout_host(field, k, g, p, (const elt_t*)h_W[b], subfield_boundary, h_lqc, rng[b], user(b), 0, p.nrow, (elt_t*)(stage + b * img),
+                                      h_non + b * ncols * 32, err, c->rng_exact != 0);
+    if (rc) return lf_fail(c, rc, "%s (statement %zu)", err, b);
+  }
+  const double tv1 = verbose ? clk() : 0;
+  // After a failed enqueue the stream may still read the staging memory: wait before it is scrubbed
+  auto fail = [&](int rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return drop(rc);
+  };
+  const size_t tb = p.nrow * ld * 16, lb = 2 * ncols * 32;
+  elt_t* d_T[LFGPU_SC_BATCH_MAX];
+  void* d_L[LFGPU_SC_BATCH_MAX];
+  for (size_t b = 0; b < nb; ++b) {
+    lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
+    out[b] = pr;
+    pr->c = c;
+    pr->field = field;
+    pr->k = k;
+    pr->p = p;
+    pr->d_T = nullptr;
+    pr->d_layers = nullptr;
+    pr->nonces.assign(h_non + b * ncols * 32, h_non + (b + 1) * ncols * 32);
+    if (lf_pool_get(c, tb, (void**)&pr->d_T) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: tableau alloc (statement %zu)", b));
+    pr->T_bytes = tb;
+    if (lf_pool_get(c, lb, (void**)&pr->d_layers) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: layers alloc (statement %zu)", b));
+    pr->L_bytes = lb;
+    pr->row_lo = 0;
+    pr->row_hi = p.nrow;
+    d_T[b] = pr->d_T;
+    d_L[b] = pr->d_layers;
+  }
+  void* d_non = nullptr;
+  int rc = lf_scratch3(c, nb * ncols * 32, &d_non);
+  if (rc) return fail(rc);
+  if (hipMemcpyAsync(d_non, h_non, nb * ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_batch: nonce upload failed"));
+  for (size_t b = 0; b < nb; ++b)
+    if (hipMemcpy2DAsync(d_T[b], ld * 16, stage + b * img, hw * 16, hw * 16, p.nrow, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+      return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_batch: upload failed (statement %zu)", b));
+  if ((rc = ligero_extend_batch(c, field, k, p, nb, d_T))) return fail(rc);
+  double tv2 = 0;
+  if (verbose) {
+    (void)hipStreamSynchronize(c->stream);
+    tv2 = clk();
+  }
+  // (ends with the one stream synchronise of the call: the uploads above are over when it returns)
+  if ((rc = lfgpu_column_commit_batch(c, field, p.nrow, ld, p.dblock, ncols, nb, (const void* const*)d_T, d_non, d_L, roots_out))) return fail(rc);
+  if (verbose)
+    fprintf(stderr, "lfgpu ligero_commit_batch: %zu x %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
+            nb, p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, clk() - tv2);
   return LFGPU_OK;
 }
 

@@ -14,14 +14,10 @@
 
 // leaf_j = SHA256(nonce_j[32] || canon(T[0][col0+j]) || ... || canon(T[nrow-1][col0+j]))
 // digest j lands at out[out0 + j] (out0 = ncols: the leaf level of the heap; 0: a plain leaf array)
+// (the body of column_leaves_kernel and of its batched twin: column `col`, nonce j, digest to layers[out])
 template <int F>
-__global__ __launch_bounds__(SHA_THREADS) void column_leaves_kernel(u32 nrow, size_t ld, size_t col0, u32 ncols,
-                                                                     const elt_t* __restrict__ T,
-                                                                     const uint4* __restrict__ nonces,
-                                                                     uint4* __restrict__ layers, size_t out0) {
-  u32 j = blockIdx.x * SHA_THREADS + threadIdx.x;
-  if (j >= ncols) return;
-  const elt_t* col = T + col0 + j;
+__device__ __forceinline__ void column_leaf(u32 nrow, size_t ld, const elt_t* __restrict__ col, const uint4* __restrict__ nonces, u32 j,
+                                            uint4* __restrict__ layers, size_t out) {
   sha_state st;
   sha_init(st);
   const u32 nch = 2 + nrow;                       // 16-byte chunks of message
@@ -55,8 +51,26 @@ __global__ __launch_bounds__(SHA_THREADS) void column_leaves_kernel(u32 nrow, si
   }
   uint4 o0 = make_uint4(bswap32(st.h[0]), bswap32(st.h[1]), bswap32(st.h[2]), bswap32(st.h[3]));
   uint4 o1 = make_uint4(bswap32(st.h[4]), bswap32(st.h[5]), bswap32(st.h[6]), bswap32(st.h[7]));
-  layers[2 * (out0 + j)] = o0;
-  layers[2 * (out0 + j) + 1] = o1;
+  layers[2 * out] = o0;
+  layers[2 * out + 1] = o1;
+}
+template <int F>
+__global__ __launch_bounds__(SHA_THREADS) void column_leaves_kernel(u32 nrow, size_t ld, size_t col0, u32 ncols,
+                                                                     const elt_t* __restrict__ T,
+                                                                     const uint4* __restrict__ nonces,
+                                                                     uint4* __restrict__ layers, size_t out0) {
+  u32 j = blockIdx.x * SHA_THREADS + threadIdx.x;
+  if (j >= ncols) return;
+  column_leaf<F>(nrow, ld, T + col0 + j, nonces, j, layers, out0 + j);
+}
+// nb tableaux of one shape: statement blockIdx.y hashes its columns with nonces [b][ncols][32] into leaf level ncols of its own heap
+template <int F>
+__global__ __launch_bounds__(SHA_THREADS) void column_leaves_batch_kernel(u32 nrow, size_t ld, size_t col0, u32 ncols, LfBatchPtrs T,
+                                                                           const uint4* __restrict__ nonces, LfBatchPtrs layers) {
+  const u32 b = blockIdx.y;
+  u32 j = blockIdx.x * SHA_THREADS + threadIdx.x;
+  if (j >= ncols) return;
+  column_leaf<F>(nrow, ld, (const elt_t*)T.p[b] + col0 + j, nonces + 2 * (size_t)b * ncols, j, (uint4*)layers.p[b], (size_t)ncols + j);
 }
 
 // node i = SHA256(node 2i || node 2i+1)
@@ -99,6 +113,28 @@ __global__ __launch_bounds__(1024) void merkle_top_kernel(uint4* layers, size_t 
     __threadfence_block();
     __syncthreads();
   }
+}
+
+// the same two for nb heaps: statement blockIdx.y; the top kernel also leaves root b at roots[b] (one read-back for all)
+__global__ __launch_bounds__(SHA_THREADS) void merkle_level_batch_kernel(LfBatchPtrs layers, size_t lo, size_t hi) {
+  size_t i = lo + (size_t)blockIdx.x * SHA_THREADS + threadIdx.x;
+  if (i < hi) hash2_node((uint4*)layers.p[blockIdx.y], i);
+}
+__global__ __launch_bounds__(1024) void merkle_top_batch_kernel(LfBatchPtrs layers, size_t n, int d_top, uint4* __restrict__ roots) {
+  uint4* L = (uint4*)layers.p[blockIdx.x];
+  for (int d = d_top; d >= 0; --d) {
+    size_t lo = (size_t)1 << d, hi = (size_t)2 << d;
+    if (hi > n) hi = n;
+    size_t i = lo + threadIdx.x;
+    if (i < hi) hash2_node(L, i);
+    __threadfence_block();
+    __syncthreads();
+  }
+  if (threadIdx.x < 2) roots[2 * (size_t)blockIdx.x + threadIdx.x] = L[2 + threadIdx.x];  // node 1, written by thread 0 before the last barrier
+}
+// ncols == 1: the root is the leaf (heap slot 1) and no tree kernel runs
+__global__ void merkle_root_is_leaf_batch_kernel(LfBatchPtrs layers, uint4* __restrict__ roots) {
+  if (threadIdx.x < 2) roots[2 * (size_t)blockIdx.x + threadIdx.x] = ((const uint4*)layers.p[blockIdx.x])[2 + threadIdx.x];
 }
 
 __global__ void gather_digests_kernel(const uint4* __restrict__ layers, const u64* __restrict__ idx, u32 cnt,
@@ -164,6 +200,49 @@ extern "C" int lfgpu_column_commit(lfgpu_ctx* c, int field, size_t nrow, size_t 
   LF_TRY(column_leaves(c, "column_commit", field, nrow, ld, col0, ncols, d_T, d_nonces, d_layers, ncols));
   LF_TRY(build_tree(c, ncols, d_layers));
   return read_root(c, ncols, d_layers, root_out);
+}
+
+extern "C" int lfgpu_column_commit_batch(lfgpu_ctx* c, int field, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb,
+                                         const void* const* d_T, const void* d_nonces, void* const* d_layers, uint8_t* roots_out) {
+  if (!c || !d_T || !d_nonces || !d_layers || !roots_out || ncols == 0) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: bad argument");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: nb = %zu, a batch holds 1..%d statements", nb, LFGPU_SC_BATCH_MAX);
+  if (col0 + ncols > ld) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: col0 + ncols > ld");
+  if (nrow > 0x0fffffffu || ncols > 0x7fffffffu) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: too large");
+  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "column_commit_batch: Fp256Base columns are committed one statement at a time");
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: unknown field %d", field);
+  LfBatchPtrs pt{}, pl{};
+  for (size_t b = 0; b < nb; ++b) {
+    if (!d_T[b] || !d_layers[b]) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: null pointer for statement %zu", b);
+    pt.p[b] = const_cast<void*>(d_T[b]);
+    pl.p[b] = d_layers[b];
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+  void* d_roots = nullptr;
+  LF_TRY(lf_scratch(c, LFGPU_SC_BATCH_MAX * 32, &d_roots));
+  const dim3 gl((u32)((ncols + SHA_THREADS - 1) / SHA_THREADS), (u32)nb);
+  if (field == LFGPU_FIELD_GF2_128)
+    hipLaunchKernelGGL(column_leaves_batch_kernel<FIELD_GF2_128>, gl, dim3(SHA_THREADS), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, pt,
+                       (const uint4*)d_nonces, pl);
+  else
+    hipLaunchKernelGGL(column_leaves_batch_kernel<FIELD_FP128>, gl, dim3(SHA_THREADS), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, pt,
+                       (const uint4*)d_nonces, pl);
+  if (ncols < 2) {
+    hipLaunchKernelGGL(merkle_root_is_leaf_batch_kernel, dim3((u32)nb), dim3(64), 0, c->stream, pl, (uint4*)d_roots);
+  } else {  // build_tree with the statement on a grid axis
+    int d = 0;
+    while (((size_t)2 << d) <= ncols - 1) ++d;
+    for (; d > 10; --d) {
+      size_t lo = (size_t)1 << d, hi = (size_t)2 << d;
+      if (hi > ncols) hi = ncols;
+      hipLaunchKernelGGL(merkle_level_batch_kernel, dim3((u32)((hi - lo + SHA_THREADS - 1) / SHA_THREADS), (u32)nb), dim3(SHA_THREADS), 0, c->stream, pl, lo, hi);
+    }
+    hipLaunchKernelGGL(merkle_top_batch_kernel, dim3((u32)nb), dim3(1024), 0, c->stream, pl, ncols, d, (uint4*)d_roots);
+  }
+  LF_HIP(c, hipGetLastError());
+  LF_HIP(c, hipMemcpyAsync(c->mailbox_h, d_roots, nb * 32, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  memcpy(roots_out, c->mailbox_h, nb * 32);
+  return LFGPU_OK;
 }
 
 // the leaf half alone (multi-GPU commit: a rank hashes the columns it owns); enqueue only

@@ -80,13 +80,18 @@ __device__ __forceinline__ void run_op(elt_t* B, const RsOp op, const elt_t* __r
 
 // rows [lo2, hi2) use plan p2 (another n): the Ligero tableau mixes block- and dblock-long rows (ligero_prover.h:171-270)
 // and one launch for all of them beats three latency-bound ones
-__global__ __launch_bounds__(RS_THREADS) void gf_rs_rows_kernel(RsPlan p1, RsPlan p2, u32 lo2, u32 hi2, elt_t* __restrict__ T, size_t ld) {
-  const RsPlan& p = (blockIdx.x >= lo2 && blockIdx.x < hi2) ? p2 : p1;
+// the plan of a row, picked member by member (all wave-uniform: the plans stay in SGPRs; handing a reference to one of the two
+// kernel arguments to the body below would put both into scratch memory)
+__device__ __forceinline__ RsPlan rs_pick_plan(const RsPlan& p1, const RsPlan& p2, bool two) {
+  return RsPlan{two ? p2.ops : p1.ops, two ? p2.tw : p1.tw, two ? p2.nops_bidir : p1.nops_bidir, two ? p2.l : p1.l,
+                two ? p2.n : p1.n,     two ? p2.m : p1.m,   two ? p2.ncoset : p1.ncoset,         two ? p2.coset_tw_off : p1.coset_tw_off};
+}
+// (the body of gf_rs_rows_kernel and of its batched twin: one workgroup extends the row y by plan p)
+__device__ __forceinline__ void gf_rs_row(const RsPlan& p, elt_t* __restrict__ y) {
   extern __shared__ elt_t lds[];
   const u32 fftn = 1u << p.l, tid = threadIdx.x;
   elt_t* Cc = lds;          // coefficients
   elt_t* Wk = lds + fftn;   // work buffer for the coset FFTs
-  elt_t* y = T + (size_t)blockIdx.x * ld;
   for (u32 i = tid; i < fftn; i += RS_THREADS) st16(&Cc[i], i < p.n ? ld16(&y[i]) : elt_zero());
   __syncthreads();
   for (u32 o = 0; o < p.nops_bidir; ++o) {
@@ -116,6 +121,14 @@ __global__ __launch_bounds__(RS_THREADS) void gf_rs_rows_kernel(RsPlan p1, RsPla
     for (u32 i = tid; i < fftn && b + i < p.m; i += RS_THREADS) st16(&y[b + i], ld16(&Wk[i]));
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(RS_THREADS) void gf_rs_rows_kernel(RsPlan p1, RsPlan p2, u32 lo2, u32 hi2, elt_t* __restrict__ T, size_t ld) {
+  gf_rs_row(rs_pick_plan(p1, p2, blockIdx.x >= lo2 && blockIdx.x < hi2), T + (size_t)blockIdx.x * ld);
+}
+// nb tableaux of one shape in one launch: row blockIdx.x of statement blockIdx.y; the row class comes from the row index
+// inside the statement
+__global__ __launch_bounds__(RS_THREADS) void gf_rs_rows_batch_kernel(RsPlan p1, RsPlan p2, u32 lo2, u32 hi2, LfBatchPtrs T, size_t ld) {
+  gf_rs_row(rs_pick_plan(p1, p2, blockIdx.x >= lo2 && blockIdx.x < hi2), (elt_t*)T.p[blockIdx.y] + (size_t)blockIdx.x * ld);
 }
 
 // ---- rows larger than LDS (2^l > 4096): coefficients in a device work buffer Cc[row][2^l].  The recursion of
@@ -405,6 +418,28 @@ int lf_gf_rs_rows_mixed(lfgpu_ctx* c, int k, size_t nrow, size_t n1, size_t n2, 
   return LFGPU_OK;
 }
 
+int lf_gf_rs_rows_mixed_batch(lfgpu_ctx* c, int k, size_t nb, elt_t* const* d_T, size_t nrow, size_t n1, size_t n2, size_t lo2, size_t hi2, size_t m, size_t ld) {
+  const GfHostCtx* g = lf_gf_ctx(c, k);
+  if (!g || n1 == 0 || n2 == 0 || m <= n1 || m <= n2 || ld < m || lf_log2(n1) > 12 || lf_log2(n2) > 12 ||
+      (g->sub_bits < 64 && m > ((size_t)1 << g->sub_bits)))
+    return LFGPU_ERR_UNSUPPORTED;
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX || nrow == 0) return lf_fail(c, LFGPU_ERR_ARG, "gf_rs_rows_mixed_batch: bad argument");
+  LF_HIP(c, hipSetDevice(c->device));
+  RsPlan p1, p2;
+  LF_TRY(gf_rs_plan(c, g, k, n1, m, &p1));
+  LF_TRY(gf_rs_plan(c, g, k, n2, m, &p2));
+  if (!(c->attr_done & 16u)) {
+    LF_HIP(c, hipFuncSetAttribute((const void*)gf_rs_rows_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 32 << 12));
+    c->attr_done |= 16u;
+  }
+  LfBatchPtrs pt{};
+  for (size_t b = 0; b < nb; ++b) pt.p[b] = d_T[b];
+  const size_t lds = (size_t)32 << (p1.l > p2.l ? p1.l : p2.l);
+  hipLaunchKernelGGL(gf_rs_rows_batch_kernel, dim3((u32)nrow, (u32)nb), dim3(RS_THREADS), lds, c->stream, p1, p2, (u32)lo2, (u32)hi2, pt, ld);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
 extern "C" int lfgpu_gf2128_rs_encode_tableau(lfgpu_ctx* c, int k, size_t nrow, size_t n1, size_t n2, size_t lo2, size_t hi2, size_t m,
                                               void* d_T, size_t ld) {
   if (!c || (!d_T && nrow) || lo2 > hi2 || hi2 > nrow) return lf_fail(c, LFGPU_ERR_ARG, "gf2128_rs_encode_tableau: bad argument");
@@ -429,13 +464,34 @@ extern "C" int lfgpu_gf2128_rs_encode_rows_host(lfgpu_ctx* c, int k, size_t nrow
 
 // ------------------------------------------------------------------ K4: Fp128
 // x_i = binom_i * y_i (i < n), zero-padded to P;  z = fftb(fftf(x) . yhat);  y_k = lead_{k-d} * z_k (k >= n)
-__global__ void fp_rs_pre_kernel(u32 n, u32 P, const elt_t* __restrict__ binom, const elt_t* __restrict__ T, size_t ld,
-                                 elt_t* __restrict__ X) {
+// (the bodies of fp_rs_pre_kernel / fp_rs_post_kernel and of their batched twins: tableau row t, scratch row x)
+__device__ __forceinline__ void fp_rs_pre_row(u32 n, u32 P, const elt_t* __restrict__ binom, const elt_t* __restrict__ t, elt_t* __restrict__ x) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
   elt_t v = elt_zero();
-  if (i < n) v = fp_mul(ld16(&binom[i]), ld16(&T[(size_t)blockIdx.y * ld + i]));
-  st16(&X[(size_t)blockIdx.y * P + i], v);
+  if (i < n) v = fp_mul(ld16(&binom[i]), ld16(&t[i]));
+  st16(&x[i], v);
+}
+__device__ __forceinline__ void fp_rs_post_row(u32 n, u32 m, const elt_t* __restrict__ lead, const elt_t* __restrict__ x, elt_t* __restrict__ t) {
+  u32 i = n + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  st16(&t[i], fp_mul(ld16(&lead[i - (n - 1)]), ld16(&x[i])));
+}
+__global__ void fp_rs_pre_kernel(u32 n, u32 P, const elt_t* __restrict__ binom, const elt_t* __restrict__ T, size_t ld,
+                                 elt_t* __restrict__ X) {
+  fp_rs_pre_row(n, P, binom, T + (size_t)blockIdx.y * ld, X + (size_t)blockIdx.y * P);
+}
+// one row group of nb tableaux: row r = blockIdx.y of the launch is local row row0 + r % rows of statement r / rows; X stays
+// the contiguous [nb * rows][P] array of the single kernels, so the FFTs and the pointwise product run on it unchanged
+__global__ void fp_rs_pre_batch_kernel(u32 n, u32 P, const elt_t* __restrict__ binom, LfBatchPtrs T, u32 rows, u32 row0, size_t ld,
+                                       elt_t* __restrict__ X) {
+  const u32 b = blockIdx.y / rows, lr = row0 + blockIdx.y % rows;
+  fp_rs_pre_row(n, P, binom, (const elt_t*)T.p[b] + (size_t)lr * ld, X + (size_t)blockIdx.y * P);
+}
+__global__ void fp_rs_post_batch_kernel(u32 n, u32 m, u32 P, const elt_t* __restrict__ lead, const elt_t* __restrict__ X, LfBatchPtrs T,
+                                        u32 rows, u32 row0, size_t ld) {
+  const u32 b = blockIdx.y / rows, lr = row0 + blockIdx.y % rows;
+  fp_rs_post_row(n, m, lead, X + (size_t)blockIdx.y * P, (elt_t*)T.p[b] + (size_t)lr * ld);
 }
 __global__ void fp_rs_pointwise_kernel(u32 P, const elt_t* __restrict__ yhat, elt_t* __restrict__ X) {
   u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -445,16 +501,13 @@ __global__ void fp_rs_pointwise_kernel(u32 P, const elt_t* __restrict__ yhat, el
 }
 __global__ void fp_rs_post_kernel(u32 n, u32 m, u32 P, const elt_t* __restrict__ lead, const elt_t* __restrict__ X,
                                   elt_t* __restrict__ T, size_t ld) {
-  u32 i = n + blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  st16(&T[(size_t)blockIdx.y * ld + i], fp_mul(ld16(&lead[i - (n - 1)]), ld16(&X[(size_t)blockIdx.y * P + i])));
+  fp_rs_post_row(n, m, lead, X + (size_t)blockIdx.y * P, T + (size_t)blockIdx.y * ld);
 }
 
-extern "C" int lfgpu_fp128_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, const uint64_t omega[2],
-                                          uint64_t omega_order, void* d_T, size_t ld) {
-  if (!c || !omega || (!d_T && nrow)) return lf_fail(c, LFGPU_ERR_ARG, "fp128_rs_encode_rows: null argument");
+// the checks and the cached constants of one (n, m): the padded size P and the device tables binom, lead, yhat
+static int fp_rs_tables(lfgpu_ctx* c, size_t n, size_t m, size_t ld, const uint64_t omega[2], uint64_t omega_order, size_t* P_out, void** binom_out,
+                        void** lead_out, void** yhat_out) {
   if (n == 0 || m < n || ld < m) return lf_fail(c, LFGPU_ERR_ARG, "fp128_rs_encode_rows: need 0 < n <= m <= ld");
-  if (nrow == 0 || m == n) return LFGPU_OK;
   size_t P = 1;
   while (P < m) P <<= 1;
   if (P > omega_order) return lf_fail(c, LFGPU_ERR_ARG, "fp128_rs_encode_rows: omega_order < padding");
@@ -509,6 +562,21 @@ extern "C" int lfgpu_fp128_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, s
     lf_table_lookup(c, key + ":binom", &dbinom);
     lf_table_lookup(c, key + ":lead", &dlead);
   }
+  *P_out = P;
+  *binom_out = dbinom;
+  *lead_out = dlead;
+  *yhat_out = dyhat;
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_fp128_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, const uint64_t omega[2],
+                                          uint64_t omega_order, void* d_T, size_t ld) {
+  if (!c || !omega || (!d_T && nrow)) return lf_fail(c, LFGPU_ERR_ARG, "fp128_rs_encode_rows: null argument");
+  if (n == 0 || m < n || ld < m) return lf_fail(c, LFGPU_ERR_ARG, "fp128_rs_encode_rows: need 0 < n <= m <= ld");
+  if (nrow == 0 || m == n) return LFGPU_OK;
+  size_t P = 0;
+  void *dbinom = nullptr, *dlead = nullptr, *dyhat = nullptr;
+  LF_TRY(fp_rs_tables(c, n, m, ld, omega, omega_order, &P, &dbinom, &dlead, &dyhat));
   void* X = nullptr;
   LF_TRY(lf_scratch2(c, nrow * P * 16, &X));
   dim3 gp((u32)((P + 255) / 256), (u32)nrow);
@@ -520,6 +588,42 @@ extern "C" int lfgpu_fp128_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, s
   dim3 go((u32)((m - n + 255) / 256), (u32)nrow);
   hipLaunchKernelGGL(fp_rs_post_kernel, go, dim3(256), 0, c->stream, (u32)n, (u32)m, (u32)P, (const elt_t*)dlead,
                      (const elt_t*)X, (elt_t*)d_T, ld);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+void lf_fp_omega32(uint64_t om[2]) {
+  static const char* kOmega = "164956748514267535023998284330560247862";
+  unsigned __int128 v = 0;
+  for (const char* s = kOmega; *s; ++s) v = v * 10 + (unsigned)(*s - '0');
+  const elt_t w = h_fp_to_mont(elt_t{(u64)v, (u64)(v >> 64)});
+  om[0] = w.lo;
+  om[1] = w.hi;
+}
+
+// lfgpu_fp128_rs_encode_rows on rows [row0, row0 + nrow) of nb tableaux at once (the caller keeps nb * nrow <= 65535)
+int lf_fp_rs_rows_batch(lfgpu_ctx* c, size_t nb, elt_t* const* d_T, size_t row0, size_t nrow, size_t n, size_t m, size_t ld) {
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX || nb * nrow > 65535) return lf_fail(c, LFGPU_ERR_ARG, "fp_rs_rows_batch: bad argument");
+  if (nrow == 0 || m == n) return LFGPU_OK;
+  uint64_t omega[2];
+  lf_fp_omega32(omega);
+  const uint64_t omega_order = (uint64_t)1 << 32;
+  size_t P = 0;
+  void *dbinom = nullptr, *dlead = nullptr, *dyhat = nullptr;
+  LF_TRY(fp_rs_tables(c, n, m, ld, omega, omega_order, &P, &dbinom, &dlead, &dyhat));
+  const size_t rows = nb * nrow;
+  LfBatchPtrs pt{};
+  for (size_t b = 0; b < nb; ++b) pt.p[b] = d_T[b];
+  void* X = nullptr;
+  LF_TRY(lf_scratch2(c, rows * P * 16, &X));
+  dim3 gp((u32)((P + 255) / 256), (u32)rows);
+  hipLaunchKernelGGL(fp_rs_pre_batch_kernel, gp, dim3(256), 0, c->stream, (u32)n, (u32)P, (const elt_t*)dbinom, pt, (u32)nrow, (u32)row0, ld, (elt_t*)X);
+  LF_TRY(lfgpu_fp128_fft(c, 1, rows, P, omega, omega_order, X, P));
+  hipLaunchKernelGGL(fp_rs_pointwise_kernel, gp, dim3(256), 0, c->stream, (u32)P, (const elt_t*)dyhat, (elt_t*)X);
+  LF_TRY(lfgpu_fp128_fft(c, 0, rows, P, omega, omega_order, X, P));
+  dim3 go((u32)((m - n + 255) / 256), (u32)rows);
+  hipLaunchKernelGGL(fp_rs_post_batch_kernel, go, dim3(256), 0, c->stream, (u32)n, (u32)m, (u32)P, (const elt_t*)dlead, (const elt_t*)X, pt, (u32)nrow,
+                     (u32)row0, ld);
   LF_HIP(c, hipGetLastError());
   return LFGPU_OK;
 }

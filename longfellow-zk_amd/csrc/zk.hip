@@ -762,6 +762,71 @@ extern "C" int lfgpu_zk_prove_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* 
   return zkp::prove_batch<P16>(c, C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
 }
 
+// ZkProver::commit for nb provers: lfgpu_zk_commit's one-GPU branch per statement around ONE lfgpu_ligero_commit_batch
+extern "C" int lfgpu_zk_commit_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng,
+                                     void* const* rng_user, const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
+  if (!bt || !zk || !h_W || !rng || !ts) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = bt->c;
+  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!zk[b] || !h_W[b] || !rng[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: null argument for statement %zu", b);
+    if (zk[b]->c != c || zk[b]->C != bt->C || zk[b]->z256) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: prover %zu belongs to another context or circuit", b);
+    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_commit_batch: prover %zu has a communicator (the batch runs on one GPU)", b);
+    if (memcmp(&zk[b]->st.param, &zk[0]->st.param, sizeof(lfgpu_ligero_param)) != 0)
+      return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: prover %zu has another LigeroParam (rate, nreq or block_enc) than prover 0", b);
+    for (size_t a = 0; a < b; ++a)
+      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: prover %zu appears twice", b);
+  }
+  const double t0 = now_ms();
+  const lfgpu_circuit* C = bt->C;
+  const int field = C->info.field;
+  const HostField F(c, field);
+  const lfgpu_ligero_param& p = zk[0]->st.param;
+  // whatever happens from here on, no prover of the call keeps an earlier commitment or proof
+  for (size_t b = 0; b < nb; ++b) {
+    if (zk[b]->lp) {
+      lfgpu_ligero_free(zk[b]->lp);
+      zk[b]->lp = nullptr;
+    }
+    zk[b]->st.have_proof = false;
+    zk[b]->st.wire_valid = false;
+  }
+  // witness || pads of every statement; fill_pad's draws of statement b come from rng[b], before its Ligero draws
+  std::vector<elt_t> Wv(nb * p.nw);
+  LF_SCRUB_ON_EXIT(Wv);
+  // (the pads of ALL statements are drawn before the first Ligero layout: a statement's own order -- pads, then layout -- is
+  // the single path's as long as its engine is its own, which the header asks for)
+  std::vector<const void*> Wp(nb);
+  std::vector<void*> users(nb);
+  std::vector<uint8_t> roots(nb * 32);
+  std::vector<lfgpu_ligero_prover*> lps(nb, nullptr);
+  const size_t sfb = C->info.subfield_boundary >= zk[0]->st.npub ? C->info.subfield_boundary - zk[0]->st.npub : 0;
+  auto pads = [&](size_t b) {
+    lfgpu_rng_fn r = rng[b];
+    void* u = rng_user ? rng_user[b] : nullptr;
+    auto draw = [&]() { return zkp::elt_sample(field, [&](uint8_t* buf, size_t n) { r(u, buf, n); }); };
+    elt_t* W = Wv.data() + b * p.nw;
+    memcpy(W, (const elt_t*)h_W[b] + zk[b]->st.npub, zk[b]->st.n_witness * 16);
+    const size_t pi = zkp::pad_layout<P16>(F, C, zk[b]->st.n_witness, zk[b]->st.lqc, draw, &zk[b]->st.pad, W);
+    Wp[b] = W;
+    users[b] = u;
+    return pi == p.nw;
+  };
+  for (size_t b = 0; b < nb; ++b)
+    if (!pads(b)) return lf_fail(c, LFGPU_ERR_ASSERT, "zk_commit_batch: witness layout (statement %zu)", b);
+  // (the lqc triples are the circuit's: the same for every prover)
+  LF_TRY(lfgpu_ligero_commit_batch(c, field, 4, &p, nb, Wp.data(), sfb, zk[0]->st.lqc.data(), rng, users.data(), roots.data(), lps.data()));
+  for (size_t b = 0; b < nb; ++b) {
+    zk[b]->lp = lps[b];
+    memcpy(zk[b]->st.proof.root, &roots[32 * b], 32);
+    ts[b]->write_bytes(ts[b]->user, zk[b]->st.proof.root, 32);  // LigeroTranscript::write_commitment
+  }
+  if (roots_out) memcpy(roots_out, roots.data(), nb * 32);
+  const double dt = now_ms() - t0;
+  for (size_t b = 0; b < nb; ++b) zk[b]->st.ms[0] = dt;
+  return LFGPU_OK;
+}
+
 extern "C" int lfgpu_zk_batch_free(lfgpu_zk_batch* bt) {
   if (!bt) return LFGPU_ERR_ARG;
   delete bt;
