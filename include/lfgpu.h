@@ -334,7 +334,10 @@ typedef void (*lfgpu_rng_fn)(void* user, uint8_t* buf, size_t n);
 typedef struct lfgpu_ligero_prover lfgpu_ligero_prover;
 /* LigeroProver::commit (lib/ligero/ligero_prover.h:58-79) minus the transcript write:
  * layout (blinding / witness / quadratic rows), RS-encode every row, Merkle-commit the
- * columns [dblock, block_enc).  h_W: nw host elements; h_lqc: nq x {x,y,z}. */
+ * columns [dblock, block_enc).  h_W: nw host elements; h_lqc: nq x {x,y,z}.  GF2_128: every h_W[i], i < subfield_boundary,
+ * must lie in the subfield (the reference's check, :63-66; such rows are blinded with subfield randomness): LFGPU_ERR_ARG with
+ * the index in the message otherwise, before anything is drawn from rng.  The same holds for every entry point below that
+ * lays out witness rows (commit_batch, layout_rows, layout_rows_sharded, commit_sharded). */
 int lfgpu_ligero_commit(lfgpu_ctx* ctx, int field, int subfield_log_bits, const lfgpu_ligero_param* p,
                         const void* h_W, size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng,
                         void* rng_user, uint8_t root_out[32], lfgpu_ligero_prover** out);
@@ -352,7 +355,7 @@ int lfgpu_ligero_commit(lfgpu_ctx* ctx, int field, int subfield_log_bits, const 
  * prover that owns its pooled buffers (every prove / open / free entry point works on it; free in any order).
  * LFGPU_COMMIT_BATCH=0 (read once) keeps these semantics and runs the single-statement device path per statement.
  * 1 <= nb <= LFGPU_SC_BATCH_MAX, else LFGPU_ERR_ARG; argument errors are found before the first draw.  An error inside
- * statement b's layout (LFGPU_ERR_ARG: lqc index out of range; LFGPU_ERR_ASSERT: a quadratic constraint does not hold) fails
+ * statement b's layout (LFGPU_ERR_ARG: lqc index out of range, or a witness below subfield_boundary outside the subfield; LFGPU_ERR_ASSERT: a quadratic constraint does not hold) fails
  * the whole call: out[0 .. nb) are NULL and every buffer is back in the pool, scrubbed.  Fields: GF2_128 and Fp128. */
 int lfgpu_ligero_commit_batch(lfgpu_ctx* ctx, int field, int subfield_log_bits, const lfgpu_ligero_param* p, size_t nb,
                               const void* const* h_W, size_t subfield_boundary, const size_t* h_lqc,

@@ -210,6 +210,31 @@ int lf_rs_rows(lfgpu_ctx* c, int field, int k, size_t nrow, size_t n, size_t m, 
   return lfgpu_fp128_rs_encode_rows(c, nrow, n, m, om, (uint64_t)1 << 32, d, ld);
 }
 
+// GF2_128::in_subfield (gf2_128.h:201-204) for the witness check of LigeroProver::commit: beta in reduced echelon form, an
+// element lies in the subfield iff cancelling its pivot bits leaves nothing
+struct SubfieldTest {
+  elt_t v[32];
+  int pivot[32];
+  unsigned n = 0;
+  static int top_bit(elt_t e) { return e.hi ? 64 + (63 - __builtin_clzll(e.hi)) : e.lo ? 63 - __builtin_clzll(e.lo) : -1; }
+  static bool bit_of(elt_t e, int j) { return j >= 64 ? (e.hi >> (j - 64)) & 1 : (e.lo >> j) & 1; }
+  explicit SubfieldTest(const GfHostCtx* g) {
+    for (unsigned i = 0; i < g->sub_bits && i < 32; ++i) {
+      elt_t e = g->beta[i];
+      for (unsigned r = 0; r < n; ++r)
+        if (bit_of(e, pivot[r])) e = gf_add(e, v[r]);
+      v[n] = e;  // beta is a basis: e != 0
+      pivot[n++] = top_bit(e);
+    }
+  }
+  bool in_subfield(elt_t e) const {
+    if (e.hi == 0 && e.lo <= 1) return true;  // 0 and 1, nearly every input of a bit circuit
+    for (unsigned r = 0; r < n; ++r)  // a row's pivot bit is clear in every LATER row: one pass in order
+      if (bit_of(e, pivot[r])) e = gf_add(e, v[r]);
+    return (e.lo | e.hi) == 0;
+  }
+};
+
 // The host half of LigeroProver::commit (ligero_prover.h:171-270 + merkle_commitment.h:52-54): every RandomEngine draw in
 // the reference's order; the un-encoded image (first dblock columns) of rows [row_lo, row_hi) goes to H
 // ([(row_hi - row_lo)][dblock]); rows outside the slab are drawn into a spare row and dropped, so that ranks which replay
@@ -218,6 +243,16 @@ int lf_rs_rows(lfgpu_ctx* c, int field, int k, size_t nrow, size_t n, size_t m, 
 static int ligero_layout_host(int field, int k, const GfHostCtx* g, const lfgpu_ligero_param& p, const elt_t* W, size_t subfield_boundary,
                               const size_t* h_lqc, lfgpu_rng_fn rng, void* user, size_t row_lo, size_t row_hi, elt_t* H, uint8_t* nonces,
                               char* err, bool exact = false) {
+  // the check that opens LigeroProver::commit (ligero_prover.h:63-66), before any draw: a row below the boundary is blinded
+  // with subfield randomness, which hides nothing of a full-field value in it.  in_subfield is identically true for Fp128.
+  if (field == LFGPU_FIELD_GF2_128 && subfield_boundary) {
+    const SubfieldTest sub(g);
+    for (size_t i = 0; i < std::min(subfield_boundary, p.nw); ++i)
+      if (!sub.in_subfield(W[i])) {
+        snprintf(err, 256, "ligero_commit: element not in subfield: W[%zu], below subfield_boundary %zu (ligero_prover.h:63-66)", i, subfield_boundary);
+        return LFGPU_ERR_ARG;
+      }
+  }
   Sampler S{field, k, g, rng, user, exact};
   const elt_t zero{0, 0};
   const size_t hw = p.dblock;

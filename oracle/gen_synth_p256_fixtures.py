@@ -6,8 +6,9 @@ real reference) for every case and stores the fixtures of tests/test_zk_p256_syn
   synth_p256.json            one record per case: shapes as compiled, LigeroParam, commitment root, SHA-256 of the proof
                              bytes and of every section of ZkProof::write, the reference verifier's verdict
 With the argument fp128 the same for oracle/_ref/gen_synth_fp128 (ref_synth_fp128.cc, tests/test_zk_fp128_synth.py):
-synth_fp128_<case>.{lfc1,w}.xz with 16-byte Elt images, synth_fp128.json.
-Data only -- no source text.  Usage: python oracle/gen_synth_p256_fixtures.py [p256|fp128] [outdir]"""
+synth_fp128_<case>.{lfc1,w}.xz with 16-byte Elt images, synth_fp128.json; with the argument gf for oracle/_ref/gen_synth_gf
+(ref_synth_gf.cc, tests/test_zk_gf_synth.py): synth_gf_<case>.{lfc1,w}.xz with 16-byte Elt images, synth_gf.json.
+Data only -- no source text.  Usage: python oracle/gen_synth_p256_fixtures.py [p256|fp128|gf] [outdir]"""
 import json
 import lzma
 import os
@@ -16,7 +17,7 @@ import sys
 import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-FIELDS = ("p256", "fp128")
+FIELDS = ("p256", "fp128", "gf")
 
 
 def case_names(gen):

@@ -13,7 +13,9 @@
 // oracle/gen_synth_p256_fixtures.py compresses the two binary files and collects the records in tests/golden/synth_p256.json.
 //
 // ref_synth_fp128.cc compiles this same text over Fp128 (REF_SYNTH_FP128: 16-byte elements, the file stem synth_fp128_, the
-// FFT Reed-Solomon factory of ref_flatsha.cc under REF_FP128, a case table of its own) into gen_synth_fp128.
+// FFT Reed-Solomon factory of ref_flatsha.cc under REF_FP128, a case table of its own) into gen_synth_fp128, and
+// ref_synth_gf.cc over GF2_128<> (REF_SYNTH_GF2_128: the stem synth_gf_, the LCH14 Reed-Solomon factory of ref_flatsha.cc, a
+// case table of its own) into gen_synth_gf.  What differs in characteristic 2 stands under "GF(2^128)" below.
 //
 // A layer of B gates over the A wires below it: gate j is a sum of T products P[a] * P[b], the pairs taken in order from
 // pair(m) = (2m mod A, 2m + 1 + 2 floor(2m / A) mod A), m = jT .. jT + T - 1, T >= ceil(A / 2B) so that every wire below is
@@ -22,6 +24,17 @@
 // evaluates every gate in the field as it builds it, feeds each output's value in as one more input and asserts
 // gate - input == 0, so the circuit is satisfied by construction.  The only constants are 1 and -1; input values come from a
 // pool of 61 LCG-drawn elements, with 0, 1 and p - 1 on the data inputs 1, 2, 3.
+//
+// GF(2^128).  LigeroProver::commit refuses a witness below subfield_boundary that is not in the 16-bit subfield, so in a case
+// that calls begin_full_field() every data input created before the call comes from a second pool of 61 values drawn with
+// RandomEngine::subfield_elt; the inputs after it come from the full-field pool.  -1 == 1, so the data input 3 holds
+// of_scalar(0xffff), the element whose subfield coordinates are all ones (legal on either side of the boundary; the record
+// names it input_ones).  1 + 1 == 0: a product that occurs twice in one gate vanishes from the compiled circuit.  The
+// descriptions of the table avoid that (pair(m) repeats only after A^2 / 4 pairs; the hub and common products never
+// equal a pair product of their gate at these sizes), and tests/test_zk_gf_synth.py recounts terms, hand pairs, fan-in and
+// fan-out from the LFC1 bytes.  The record also holds the run structure of the opened columns, parsed from the wire bytes
+// (run lengths, number of 16-byte and of 2-byte elements) and subfield_boundary - npub_in, the boundary LigeroProver gets.
+// CPU time of the whole table: 14 s, 13 of them in wide (compile and prove of two layers of 263006 wires).
 #include <cstdio>
 #include <cstring>
 #include <map>
@@ -37,6 +50,8 @@
 #include "circuits/logic/compiler_backend.h"
 #include "circuits/logic/logic.h"
 #include "ec/p256.h"
+#include "gf2k/gf2_128.h"
+#include "gf2k/lch14_reed_solomon.h"
 #include "proto/circuit_io.h"
 #include "proto/circuit_writer.h"
 #include "random/random.h"
@@ -65,11 +80,24 @@ class LcgRng : public RandomEngine {
   uint64_t s_;
 };
 
-#ifdef REF_SYNTH_FP128
+#if defined(REF_SYNTH_GF2_128)
+using Field = GF2_128<>;
+static const Field kField;
+static const FieldID kFieldId = GF2_128_ID;
+#define SYNTH_STEM "synth_gf_"
+#define SYNTH_THIRD_KEY "input_ones"
+// the LCH14 Reed-Solomon factory as ref_flatsha.cc sets it up for GF(2^128)
+using RSFactory_b = LCH14ReedSolomonFactory<Field>;
+struct RSSetup {
+  const RSFactory_b rsf;
+  explicit RSSetup(const Field& F) : rsf(F) {}
+};
+#elif defined(REF_SYNTH_FP128)
 using Field = Fp128<>;
 static const Field kField;
 static const FieldID kFieldId = FP128_ID;
 #define SYNTH_STEM "synth_fp128_"
+#define SYNTH_THIRD_KEY "input_mone"
 // the FFT Reed-Solomon factory as lib/zk/zk_test.cc sets it up for Fp128 (ref_flatsha.cc under REF_FP128)
 using FftConv = FFTConvolutionFactory<Field>;
 using RSFactory_b = ReedSolomonFactory<Field, FftConv>;
@@ -83,6 +111,7 @@ using Field = Fp256Base;
 static const Field& kField = p256_base;
 static const FieldID kFieldId = P256_ID;
 #define SYNTH_STEM "synth_p256_"
+#define SYNTH_THIRD_KEY "input_mone"
 using f2_p256 = Fp2<Fp256Base>;
 using FftExtConvolutionFactory = FFTExtConvolutionFactory<Fp256Base, f2_p256>;
 using RSFactory_b = ReedSolomonFactory<Fp256Base, FftExtConvolutionFactory>;
@@ -121,7 +150,29 @@ struct CaseSpec {
 
 static const std::vector<CaseSpec>& cases() {
   static const std::vector<CaseSpec> c = {
-#ifdef REF_SYNTH_FP128
+#if defined(REF_SYNTH_GF2_128)
+      // wide: as over Fp128 -- two layers beyond 2^18 wires and beyond 262144 hand pairs, a wire read by every gate of such a
+      // layer and (here) one hand pair in every gate of it, gates of more than 1024 terms; rate 5, 40 queries, block_enc by
+      // the reference's search
+      {"wide", 31, 5, 40, 0, 0, false, 0, 2000, {{263000, 2, false, false}, {263000, 1, true, true}, {30, 4384, false, false}, {5, 3, false, false}}},
+      // odd: 2^12 + 1 inputs, then 3 * 2^10, 5000 and 2^10 + 1 wires; begin_full_field() after exactly three witness
+      // rows of the recorded LigeroParam (w = 323, which does not depend on where the boundary lies): the last subfield-only
+      // row ends ON the boundary, and the input right after it holds a full-field pool value
+      {"odd", 32, 7, 132, 0, 0, false, 3 * 323, 4093, {{3068, 1, false, false}, {4996, 1, false, true}, {1021, 3, false, false}, {100, 6, false, false}, {3, 17, false, false}}},
+      // funnel: 9 down to 2 output variables and 0; rate 4 and 6 queries, so that the search settles on a small block_enc
+      // (block <= 128: LCH14 plans of fewer than 7 levels)
+      {"funnel", 33, 4, 6, 0, 0, false, 0, 300, {{398, 1, false, false}, {198, 1, false, false}, {98, 1, false, false}, {48, 1, false, false}, {22, 1, false, false},
+                                                  {10, 1, false, false}, {4, 1, false, false}, {2, 1, false, false}, {1, 1, false, false}}},
+      // tall: block_enc 24581 at rate 4 is the least with block > 4096 (4097; dblock 8193): every row takes the general
+      // encoder, and 120000 private inputs make 30 witness rows, so that the rows after IQUAD -- one call of 33 rows -- take
+      // its bit-sliced tower variant.  Public inputs (data and outputs); begin_full_field() 9000 inputs in: two
+      // subfield-only rows, a mixed one, full rows
+      {"tall", 34, 4, 30, 24581, 5, true, 9000, 120000, {{2000, 10, false, false}, {100, 10, false, false}, {4, 13, false, false}}},
+      // long: a small circuit in the widest tableau the field admits (evaluation points must exist in the 16-bit subfield):
+      // 7 rows through the plain variant of the general encoder, the last LCH14 coset partial for block and for dblock; two
+      // outputs (one output variable)
+      {"long", 35, 4, 20, 65535, 0, false, 0, 3000, {{500, 3, false, false}, {40, 7, false, false}, {2, 10, false, false}}},
+#elif defined(REF_SYNTH_FP128)
       // wide: two layers beyond 2^18 wires and beyond 262144 hand pairs (two round-hands on the per-launch kernels before the
       // resident grid's hand-off point of 131072), a wire read by every gate of such a layer, gates of more than 1024 terms;
       // rate and query count other than the flatsha fixture's (7, 132), block_enc by the reference's search
@@ -203,12 +254,20 @@ int main(int argc, char** argv) {
   using Elt = Field::Elt;
   const Field& F = kField;
 
-  // the value pool
+  // the value pool(s)
   Elt pool[61];
   {
     LcgRng vr(cs->seed);
     for (auto& e : pool) e = vr.elt(F);
   }
+#ifdef REF_SYNTH_GF2_128
+  Elt subpool[61];
+  {
+    LcgRng vr(cs->seed + 1000);
+    for (auto& e : subpool) e = vr.subfield_elt(F);
+  }
+  bool full_field = cs->nsub == 0;  // no begin_full_field(): subfield_boundary stays 0 and nothing is promised
+#endif
   const size_t nout = cs->layers.back().gates;
   std::vector<Elt> wit;  // by input index
   std::vector<size_t> out_input(nout);
@@ -225,9 +284,15 @@ int main(int argc, char** argv) {
     auto data_input = [&]() {
       const size_t i = P.size();
       Elt v = pool[(i * 7 + i / 61) % 61];
+#ifdef REF_SYNTH_GF2_128
+      if (!full_field) v = subpool[(i * 7 + i / 61) % 61];
+      const Elt third = F.of_scalar(0xffff);
+#else
+      const Elt third = F.mone();
+#endif
       if (i == 1) v = F.zero();
       if (i == 2) v = F.one();
-      if (i == 3) v = F.mone();
+      if (i == 3) v = third;
       if (i >= 1 && i <= 3) special[i - 1] = wit.size();
       P.push_back(LC.eltw_input());
       PV.push_back(v);
@@ -244,7 +309,12 @@ int main(int argc, char** argv) {
     if (cs->pub_outputs) out_inputs();
     Q.private_input();
     for (size_t i = 0; i < cs->npriv; ++i) {
-      if (cs->nsub && i == cs->nsub) Q.begin_full_field();
+      if (cs->nsub && i == cs->nsub) {
+        Q.begin_full_field();
+#ifdef REF_SYNTH_GF2_128
+        full_field = true;
+#endif
+      }
       data_input();
     }
     if (!cs->pub_outputs) out_inputs();
@@ -338,7 +408,7 @@ int main(int argc, char** argv) {
   }
   fprintf(js, "\"lfc1_bytes\": %zu, \"lfc1_sha256\": \"%s\", \"witness_sha256\": \"%s\", ", cb.size(), sha_hex(cb.data(), cb.size()).c_str(),
           sha_hex((const uint8_t*)W.v_.data(), kEltBytes * c.ninputs).c_str());
-  fprintf(js, "\"input_zero\": %zu, \"input_one\": %zu, \"input_mone\": %zu, \"first_output_input\": %zu, \"noutput_inputs\": %zu, ", special[0], special[1], special[2],
+  fprintf(js, "\"input_zero\": %zu, \"input_one\": %zu, \"" SYNTH_THIRD_KEY "\": %zu, \"first_output_input\": %zu, \"noutput_inputs\": %zu, ", special[0], special[1], special[2],
           out_input[0], nout);
   fprintf(js, "\"layers\": [");
   for (size_t i = 0; i < c.nl; ++i) {
@@ -383,12 +453,40 @@ int main(int argc, char** argv) {
           sha_hex(wire.data(), wire.size()).c_str());
   size_t off = 0;
   for (size_t i = 0; i < sec.size(); ++i) {
-    fprintf(js, "%s{\"name\": \"%s\", \"offset\": %zu, \"bytes\": %zu, \"sha256\": \"%s\"}", i ? ", " : "", sec[i].first.c_str(), off, sec[i].second,
+    fprintf(js, "%s{\"name\": \"%s\", \"offset\": %zu, \"bytes\": %zu, \"sha256\": \"%s\"", i ? ", " : "", sec[i].first.c_str(), off, sec[i].second,
             sha_hex(wire.data() + off, sec[i].second).c_str());
+#ifdef REF_SYNTH_GF2_128
+    if (sec[i].first == "opened_columns") {
+      // the run structure of ZkProof::write (zk_proof.h:156-178), read back from the wire bytes: 4-byte run lengths in front
+      // of alternating runs of 16-byte and 2-byte elements, the first run full-field
+      std::vector<size_t> runs;
+      size_t at = off, left = p.nreq * p.nrow, nelt[2] = {0, 0};
+      const size_t end = off + sec[i].second;
+      while (left) {
+        if (at + 4 > end) return 9;
+        const size_t n = (size_t)wire[at] | (size_t)wire[at + 1] << 8 | (size_t)wire[at + 2] << 16 | (size_t)wire[at + 3] << 24;
+        const bool sub = runs.size() & 1;
+        at += 4 + n * (sub ? Field::kSubFieldBytes : Field::kBytes);
+        if (n > left || at > end) return 9;
+        nelt[sub] += n;
+        left -= n;
+        runs.push_back(n);
+      }
+      if (at != end) return 9;
+      fprintf(js, ", \"runs\": [");
+      for (size_t k = 0; k < runs.size(); ++k) fprintf(js, "%s%zu", k ? ", " : "", runs[k]);
+      fprintf(js, "], \"full\": %zu, \"sub\": %zu", nelt[0], nelt[1]);
+    }
+#endif
+    fprintf(js, "}");
     off += sec[i].second;
   }
   if (off != wire.size()) return 8;
-  fprintf(js, "], \"reference_verifier_accepts\": %s}\n", vok ? "true" : "false");
+  fprintf(js, "], ");
+#ifdef REF_SYNTH_GF2_128
+  fprintf(js, "\"ligero_subfield_boundary\": %zu, ", c.subfield_boundary >= c.npub_in ? c.subfield_boundary - c.npub_in : 0);  // zk_prover.h:83-88
+#endif
+  fprintf(js, "\"reference_verifier_accepts\": %s}\n", vok ? "true" : "false");
   if (fclose(js) != 0) return 7;
 
   // the shapes as compiled, for tuning the descriptions

@@ -113,6 +113,21 @@ def _witness(field, nw, lqc, seed):
     return W
 
 
+def _subfield_prefix(W, n, lqc, seed):
+    """GF(2^128): W[:n] replaced by elements of the 16-bit subfield -- what a commit with subfield_boundary = n demands of its
+    witness (LigeroProver::commit, ligero_prover.h:63-66) -- and the products of the triples recomputed"""
+    from synth_fixture import GfSubfield
+    o, sub = ol.oracle(), GfSubfield()
+    W = W.copy()
+    for i, u in enumerate(np.random.default_rng(seed).integers(1, 1 << 16, size=n)):
+        e = sub.of_scalar(int(u))
+        W[i] = (e & (2**64 - 1), e >> 64)
+    for x, y, z in lqc:
+        assert z >= n
+        W[z] = arr(o.lfo_mul(GF, elt(W[x]), elt(W[y])))
+    return W
+
+
 def _open_idx(p):
     return sorted(int(i) for i in np.random.default_rng(p.block_ext).choice(p.block_ext, size=p.nreq, replace=False))
 
@@ -266,6 +281,8 @@ def test_exact_rng_calls_with_an_engine_that_answers_every_call_alike():
             p = pkg.ligero_param(field, 40, 7, 4, 3, 64)
             lqc = _lqc(40, 7, 31)
             Ws = [_witness(field, 40, lqc, 300 + b) for b in range(2)]
+            if field == GF:  # below the boundary of 17 (two subfield-only rows of w = 7 and a mixed one) the witness is subfield-valued
+                Ws = [_subfield_prefix(W, 17, lqc, 310 + b) for b, W in enumerate(Ws)]
             want = [_single(gpu, pkg, field, p, W, 17, lqc, two) for W in Ws]
             roots, provers = pkg.LigeroProver.commit_batch(gpu, field, p, Ws, 17, lqc, [two, two])
             for b in range(2):

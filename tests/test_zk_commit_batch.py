@@ -50,7 +50,7 @@ def teardown(circ, provers, batch, tss=()):
 
 
 # ---------------------------------------------------------------- commit by batch, prove by batch
-CASES = [("flatsha_nb1", 3), ("flatsha_nb1_pub9_sfb777", 2), ("funnel", 64), ("odd", 3), ("tall", 2), ("long", 2)]
+CASES = [("flatsha_nb1", 3), ("flatsha_nb1_pub9_sfb777", 2), ("funnel", 64), ("odd", 3), ("tall", 2), ("long", 2), ("gf long", 2)]
 
 
 @pytest.mark.parametrize("case,B", CASES, ids=["%s-B%d" % c for c in CASES])

@@ -1,5 +1,6 @@
 """The Fp128 prover and verifier (csrc/zk.hip and the kernels under it, compiled for LFC1 field id 6) at the shapes the one
-reference circuit of that field, flatsha_fp_nb1, never reaches.
+reference circuit of that field, flatsha_fp_nb1, never reaches.  (test_zk_p256_synth.py does the same for Fp256Base,
+test_zk_gf_synth.py for GF(2^128).)
 
 That circuit has 684 .. 24546 wires per layer, at least 684 hand pairs everywhere, no public input and one tableau shape
 (block_enc 4096, rate 7, 132 queries).  The fixtures here are synthetic layered circuits compiled, proved and verified by
@@ -34,6 +35,7 @@ import numpy as np
 import pytest
 
 from oracle_lib import SC_GRID_MAX as GRID_MAX
+from synth_fixture import elt_int, read_lfc1_16 as read_lfc1_fp128
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, "tests", "golden")
@@ -56,37 +58,6 @@ def load_case(name):
     raw = lzma.decompress(open(os.path.join(GOLD, "synth_fp128_%s.lfc1.xz" % name), "rb").read())
     wb = lzma.decompress(open(os.path.join(GOLD, "synth_fp128_%s.w.xz" % name), "rb").read())
     return rec, raw, np.frombuffer(wb, dtype=np.uint64).reshape(-1, 2).copy()
-
-
-def read_lfc1_fp128(raw):
-    """the reference's LFC1 wire format (lib/proto/circuit_writer.h:39-85) with 16-byte constants ->
-    dict(fid, nv, nc, npub_in, subfield_boundary, ninputs, nl, nconst, layers=[{logw, nw, g, h0, h1, vi}])"""
-    b = np.frombuffer(raw, dtype=np.uint8)
-    assert b[0] == 1
-    pos = 1
-
-    def num():
-        nonlocal pos
-        v = int(b[pos]) | int(b[pos + 1]) << 8 | int(b[pos + 2]) << 16
-        pos += 3
-        return v
-
-    fid, nv, nc, npub, sfb, nin, nl, nk = (num() for _ in range(8))
-    pos += 16 * nk
-    layers = []
-    for _ in range(nl):
-        logw, nw, nq = num(), num(), num()
-        t = b[pos:pos + 12 * nq].reshape(nq, 4, 3).astype(np.int64)
-        pos += 12 * nq
-        v = t[:, :, 0] | (t[:, :, 1] << 8) | (t[:, :, 2] << 16)
-        idx = np.cumsum((v[:, :3] >> 1) * (1 - 2 * (v[:, :3] & 1)), axis=0)  # deltas, LSB = sign
-        layers.append(dict(logw=logw, nw=nw, g=idx[:, 0], h0=idx[:, 1], h1=idx[:, 2], vi=v[:, 3]))
-    assert pos + 32 == len(b)
-    return dict(fid=fid, nv=nv, nc=nc, npub_in=npub, subfield_boundary=sfb, ninputs=nin, nl=nl, nconst=nk, layers=layers)
-
-
-def elt_int(row):
-    return int(row[0]) | int(row[1]) << 64
 
 
 def test_fixtures_cover_the_shapes():

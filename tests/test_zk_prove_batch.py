@@ -45,7 +45,12 @@ def _flatsha(variant):
 
 
 def _synth(name):
-    rec, raw, W = load_case(name)
+    """an Fp128 case of test_zk_fp128_synth.py, or with the prefix "gf " a GF(2^128) case of test_zk_gf_synth.py"""
+    if name.startswith("gf "):
+        from test_zk_gf_synth import load_case as load_gf
+        rec, raw, W = load_gf(name[3:])
+    else:
+        rec, raw, W = load_case(name)
     return raw, W, dict(rate=rec["rate"], nreq=rec["nreq"], block_enc=rec["block_enc_arg"], rng_seed=rec["rng_seed"], sha=rec["zk_wire_sha256"])
 
 
@@ -120,7 +125,7 @@ def check_batch(case, B, nb_max=None):
 
 
 # ---------------------------------------------------------------- the prover
-CASES = [("flatsha_nb1", 3), ("flatsha_nb1_pub9_sfb777", 2), ("funnel", 3), ("funnel", 64), ("odd", 3), ("wide", 2)]
+CASES = [("flatsha_nb1", 3), ("flatsha_nb1_pub9_sfb777", 2), ("funnel", 3), ("funnel", 64), ("odd", 3), ("wide", 2), ("gf funnel", 64), ("gf odd", 3)]
 
 
 @pytest.mark.gpu
