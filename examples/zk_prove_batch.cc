@@ -5,7 +5,7 @@
 // provers are then committed again with the same seeds and proved by ONE lfgpu_zk_prove_batch.  The B wire images must agree
 // byte for byte, and every batched proof must pass lfgpu_zk_verify.  Prints one JSON line; exits non-zero on any difference.
 // --bench N: N passes alternating "B sequential proves" and "one batched prove" (commits untimed), medians and ranges per
-// statement in the JSON line.
+// statement in the JSON line, with the constraints and Ligero-prove phase times of the last batched pass.
 //
 //   g++ -std=c++17 -O2 -Iinclude examples/zk_prove_batch.cc -Llongfellow-zk_amd -llfgpu -Wl,-rpath,$PWD/longfellow-zk_amd -o zk_prove_batch
 //   ./zk_prove_batch circuit.lfc1 witness.bin B [--bench N]
@@ -186,14 +186,21 @@ int main(int argc, char** argv) {
     std::sort(v.begin(), v.end());
     return v[v.size() / 2];
   };
+  // the constraints and Ligero-prove phases of the last batched pass: with the batched Ligero prove (the default) they are the
+  // batch's phase times, the same for every member; with LFGPU_LIGERO_PROVE_BATCH=0 statement 0's own
+  double pl[6], pz[6];
+  CK(ctx, lfgpu_zk_timings(st[0].zk, pl));
+  CK(ctx, lfgpu_zk_timings(st[B - 1].zk, pz));
+  const bool shared = B > 1 && pl[4] == pz[4] && pl[5] == pz[5];
   auto lo = [](const std::vector<double>& v) { return v.empty() ? 0.0 : *std::min_element(v.begin(), v.end()); };
   auto hi = [](const std::vector<double>& v) { return v.empty() ? 0.0 : *std::max_element(v.begin(), v.end()); };
   printf("{\"B\": %zu, \"field\": %d, \"layers\": %zu, \"terms\": %zu, \"proof_bytes\": %zu, \"batch_equals_sequential\": %s, \"bench_passes\": %d, "
          "\"sequential_ms_per_statement\": {\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}, "
          "\"batched_ms_per_statement\": {\"median\": %.3f, \"min\": %.3f, \"max\": %.3f}, "
-         "\"batch_phases_ms\": {\"prove\": %.3f, \"eval_circuit\": %.3f, \"sumcheck\": %.3f, \"constraints_0\": %.3f, \"ligero_prove_0\": %.3f}}\n",
+         "\"batch_phases_ms\": {\"prove\": %.3f, \"eval_circuit\": %.3f, \"sumcheck\": %.3f, \"constraints_0\": %.3f, \"ligero_prove_0\": %.3f}, "
+         "\"last_batched_pass_ms\": {\"constraints\": %.3f, \"ligero_prove\": %.3f, \"shared_by_all_members\": %s}}\n",
          B, info.field, info.nl, info.nterms, proof_bytes, same ? "true" : "false", bench, med(tseq), lo(tseq), hi(tseq), med(tbat), lo(tbat), hi(tbat), ph[1], ph[2],
-         ph[3], ph[4], ph[5]);
+         ph[3], ph[4], ph[5], pl[4], pl[5], shared ? "true" : "false");
   for (size_t b = 0; b < B; ++b) {
     lfgpu_transcript_free(st[b].ts);
     lfgpu_zk_prover_free(st[b].zk);

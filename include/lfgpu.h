@@ -75,6 +75,11 @@ int lfgpu_own_stream(lfgpu_ctx* ctx);
  * forms. */
 int lfgpu_set_rng_exact_calls(lfgpu_ctx* ctx, int exact);
 int lfgpu_sync(lfgpu_ctx* ctx);
+/* Diagnostic, NOT part of the stable ABI: the context's pooled scratch buffer `which` (0..3; today 2 holds the Ligero-level
+ * temporaries of the prove entry points): its current device address (NULL before first use) and size.  For memory accounting
+ * and for the tests of the "dense block aliases the call's scratch" argument error.  The numbering, the number of buffers and
+ * which entry point uses which may change in any release, and a buffer moves when it grows: nothing may be built on them. */
+int lfgpu_scratch_info(const lfgpu_ctx* ctx, int which, void** d_out, size_t* bytes_out);
 /* device-memory helpers so that C / ctypes / cgo callers need no HIP runtime */
 int lfgpu_malloc(lfgpu_ctx* ctx, size_t bytes, void** d_out);
 int lfgpu_free(lfgpu_ctx* ctx, void* d_ptr);
@@ -444,6 +449,34 @@ int lfgpu_ligero_quadratic_proof(lfgpu_ligero_prover* pr, const void* h_u_quad, 
 /* compute_req (:346-351) + MerkleCommitment::open (merkle_commitment.h:66-73) */
 int lfgpu_ligero_open(lfgpu_ligero_prover* pr, const size_t* idx, void* h_req, uint8_t* h_nonces,
                       uint8_t* h_path, size_t path_cap, size_t* npath);
+/* ---- LigeroProver::prove for nb committed provers of ONE context, field (GF2_128 or Fp128) and lfgpu_ligero_param ----
+ * lfgpu_ligero_prove_batch: the low-degree, dot (sparse form) and quadratic proofs of all statements in one chain of
+ * dispatches with the statement on a grid axis -- one memset, one dense and one sparse launch for the A rows of all
+ * statements, their Reed-Solomon extension, the dot-proof, low-degree and quadratic combinations (one launch each) -- and one
+ * read-back.  Statement b's arguments are what the three single calls
+ * take: h_u_ldt [nb][nwqrow], d_dense[b] (device; ndense elements, the same count for every statement; may hold NULLs when
+ * ndense == 0) with scale [nb][2], the sparse list h_idx[b] / h_val[b] of nsparse[b] entries (0 allowed; strictly
+ * increasing flat indices below nwqrow * w), h_u_quad [nb][nqtriples] (NULL when nqtriples == 0).  Outputs: h_y_ldt
+ * [nb][block], h_y_dot [nb][dblock], h_y_q0 [nb][r], h_y_q2 [nb][dblock - block], byte-identical to
+ * lfgpu_ligero_low_degree_proof, lfgpu_ligero_dot_proof_sparse and lfgpu_ligero_quadratic_proof on pr[b] alone.
+ * lfgpu_ligero_open_batch: lfgpu_ligero_open for all statements -- one column gather, one digest gather, one read-back.
+ * idx: [nb][nreq]; h_req [nb][nrow][nreq]; h_nonces [nb][nreq][32]; statement b's npath[b] path digests at
+ * h_path + b * path_cap * 32 (the lengths differ with the opened positions).
+ * Working memory comes from the context's pooled scratch (it grows on the first call at a shape; later calls allocate
+ * nothing).  It holds the A rows (public), the y vectors and the opened columns (proof bytes) and challenge vectors: nothing
+ * of it is scrubbed.  Statements are chunked so that a chain's working set and its Fp128 convolution scratch stay under
+ * 256 MiB and the rows of a chain's Fp128 extension fit one launch; LFGPU_LP_CHUNK=<statements per chain> overrides (read once).
+ * 1 <= nb <= LFGPU_SC_BATCH_MAX.  LFGPU_ERR_ARG, found before anything is enqueued or written: a NULL entry, a prover of
+ * another context, field or lfgpu_ligero_param, the same prover twice, a sparse list that is not strictly increasing or out of
+ * range, an opened index out of range or given twice within a statement, a dense block inside the call's scratch.
+ * LFGPU_ERR_UNSUPPORTED: a sharded prover or a slab prover (row_lo != 0 || row_hi != nrow), Fp256Base.  LFGPU_ERR_ASSERT: the
+ * W part of a statement's y_quad is non-zero (as lfgpu_ligero_quadratic_proof). */
+int lfgpu_ligero_prove_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const void* h_u_ldt,
+                             const void* const* d_dense, size_t ndense, const uint64_t* scale /*[nb][2]*/,
+                             const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse /*[nb]*/,
+                             const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2);
+int lfgpu_ligero_open_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx /*[nb][nreq]*/,
+                            void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath /*[nb]*/);
 /* device pointer of the resident tableau (nrow x block_enc elements) */
 int lfgpu_ligero_tableau(lfgpu_ligero_prover* pr, void** d_T);
 int lfgpu_ligero_free(lfgpu_ligero_prover* pr);

@@ -127,16 +127,29 @@ int lfgpu_zk_prover_free(lfgpu_zk_prover* zk);
 /* ---- ZkProver::prove for a batch of committed provers ----
  * nb provers of ONE context and ONE circuit, each committed by lfgpu_zk_commit with its own witness, RandomEngine and
  * transcript, go through ONE chain of dispatches: eval_circuit is one launch per layer for all statements
- * (lfgpu_eval_quad_batch) and the padded sumcheck one lfgpu_sumcheck_layer_batch call per layer.  The constraints, the Ligero
- * prove and the opening then run per statement, one after the other, with the code of lfgpu_zk_prove.  Statement b's proof is
+ * (lfgpu_eval_quad_batch) and the padded sumcheck one lfgpu_sumcheck_layer_batch call per layer.  Then, for the statements
+ * with a good witness: the constraints per statement on the host, ONE launch for the EQ tables of their input constraints, ONE
+ * lfgpu_ligero_prove_batch and ONE lfgpu_ligero_open_batch (lfgpu.h) -- three synchronising read-backs per chunk of
+ * statements (lfgpu.h: LFGPU_LP_CHUNK), normally one chunk.
+ * LFGPU_LIGERO_PROVE_BATCH=0 (read once per process; the A/B switch, the same bytes) runs constraints, Ligero prove and
+ * opening per statement, one after the other, with the code of lfgpu_zk_prove; so does a batch whose good statements do not all
+ * hold the same lfgpu_ligero_param -- provers of one circuit made with different rate, nreq or block_enc: a valid batch, the
+ * sumcheck does not depend on them, but their tableaux differ in shape.  Statement b's proof is
  * byte-identical to what lfgpu_zk_prove(zk[b], h_W[b], ts[b]) produces and ts[b] is left in the same state; afterwards every
  * prover holds its own proof (lfgpu_zk_proof_write, lfgpu_zk_timings as before).  ok[b] = 0 when witness b does not satisfy the
  * circuit: that prover holds no proof, the others are unaffected.
  * lfgpu_zk_timings after a batch: [2] eval_circuit and [3] sumcheck are the BATCH's phase times and [1] the whole call's, the
- * same values for every member; [4] constraints and [5] Ligero prove are the statement's own; [0] is its commit's.
+ * same values for every member; so are [4] constraints and [5] Ligero prove on the batched path (the batch's phase times: the
+ * statements' device work is one chain); with LFGPU_LIGERO_PROVE_BATCH=0, or in a batch of mixed Ligero parameters, those two
+ * stay the statement's own.  [0] is its commit's.
+ * An error code from the call (not ok[b] = 0, which is a result) leaves the batch without a usable outcome: on the batched path
+ * an error in the tail -- for example LFGPU_ERR_ASSERT for one statement's y_quad -- leaves EVERY statement without a proof and
+ * with ok[b] = 0, where the per-statement loop has already completed the statements in front of the failing one.
  * The batch object owns the device memory the lock-step needs nb_max times (the layers' inputs, the outputs, their pinned
- * read-back), allocated once in lfgpu_zk_batch_new: lfgpu_zk_prove_batch neither allocates nor frees device memory.  It is
- * scrubbed when the batch is freed.  The batch may be freed before or after the provers; the context must outlive it.
+ * read-back, the EQ tables over the inputs), allocated once in lfgpu_zk_batch_new.  lfgpu_zk_prove_batch frees no device
+ * memory; what it may allocate is the context's pooled scratch, which grows on the first call at a shape and is kept.  The
+ * slabs that hold functions of the witnesses are scrubbed when the batch is freed (the EQ tables depend on challenges only).
+ * The batch may be freed before or after the provers; the context must outlive it.
  * The library stays single-threaded per call: the host work per statement -- the Fiat-Shamir preamble (SHA-256 over nterms
  * zero bytes), the constraints, proof_write -- is serial inside one batch.  A caller that wants more throughput runs several
  * batches in several contexts (lfgpu_own_stream, lfgpu_circuit_share), as examples/zk_throughput.cc does with provers.

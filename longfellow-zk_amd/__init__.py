@@ -106,7 +106,7 @@ def load_library():
     pu64 = C.POINTER(C.c_uint64)
     sig = {
         "lfgpu_init": [ci, C.POINTER(vp)], "lfgpu_shutdown": [vp], "lfgpu_set_stream": [vp, vp], "lfgpu_own_stream": [vp], "lfgpu_set_rng_exact_calls": [vp, ci], "lfgpu_sync": [vp],
-        "lfgpu_malloc": [vp, sz, C.POINTER(vp)], "lfgpu_free": [vp, vp],
+        "lfgpu_malloc": [vp, sz, C.POINTER(vp)], "lfgpu_free": [vp, vp], "lfgpu_scratch_info": [vp, ci, C.POINTER(vp), C.POINTER(sz)],
         "lfgpu_memcpy_h2d": [vp, vp, vp, sz], "lfgpu_memcpy_d2h": [vp, vp, vp, sz],
         "lfgpu_fp128_fft": [vp, ci, sz, sz, pu64, u64, vp, sz],
         "lfgpu_f64_2_fft": [vp, ci, sz, sz, pu64, u64, vp, sz],
@@ -185,6 +185,8 @@ def load_library():
         "lfgpu_zk_batch_free": [vp],
         "lfgpu_column_commit_batch": [vp, ci, sz, sz, sz, sz, sz, C.POINTER(vp), vp, C.POINTER(vp), vp],
         "lfgpu_ligero_commit_batch": [vp, ci, ci, C.POINTER(LigeroParam), sz, C.POINTER(vp), sz, vp, C.POINTER(RNG_FN), C.POINTER(vp), vp, C.POINTER(vp)],
+        "lfgpu_ligero_prove_batch": [vp, C.POINTER(vp), sz, vp, C.POINTER(vp), sz, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), vp, vp, vp, vp, vp],
+        "lfgpu_ligero_open_batch": [vp, C.POINTER(vp), sz, C.POINTER(sz), vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_zk_commit_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(RNG_FN), C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), vp],
     }
     for name, args in sig.items():
@@ -518,6 +520,57 @@ class LigeroProver:
             pr.h, pr._cb = C.c_void_p(hs[b]), cbs[b]
             provers.append(pr)
         return [raw[32 * b:32 * b + 32] for b in range(nb)], provers
+
+    @staticmethod
+    def prove_batch(gpu, provers, u_ldt, d_dense, ndense, scales, idxs, vals, u_quad):
+        """lfgpu_ligero_prove_batch: the low-degree, dot (sparse form) and quadratic proofs of len(provers) committed provers of
+        one LigeroParam in one chain of dispatches.  u_ldt: [nb][nwqrow] elements; d_dense: one device pointer per statement (or
+        None when ndense == 0); scales: [nb] elements; idxs[b] / vals[b]: statement b's sparse list (may be empty); u_quad:
+        [nb][nqtriples] elements -> (y_ldt [nb][block], y_dot [nb][dblock], y_q0 [nb][r], y_q2 [nb][dblock - block])"""
+        import numpy as np
+        nb = len(provers)
+        p = provers[0].p if nb else LigeroParam()
+        n = max(1, nb)
+        u = np.ascontiguousarray(u_ldt, dtype=np.uint64)
+        uq = np.ascontiguousarray(u_quad, dtype=np.uint64)
+        sc = np.ascontiguousarray(scales, dtype=np.uint64)
+        ix = [np.ascontiguousarray(i, dtype=np.uint64) for i in idxs]
+        vl = [np.ascontiguousarray(v, dtype=np.uint64) for v in vals]
+        if len(ix) != nb or len(vl) != nb:
+            raise ValueError("LigeroProver.prove_batch: one sparse list per prover")
+        y_ldt = np.zeros((n, p.block, 2), dtype=np.uint64)
+        y_dot = np.zeros((n, p.dblock, 2), dtype=np.uint64)
+        y_q0 = np.zeros((n, p.r, 2), dtype=np.uint64)
+        y_q2 = np.zeros((n, p.dblock - p.block, 2), dtype=np.uint64)
+        dd = (C.c_void_p * n)(*(d_dense if d_dense is not None else [None] * nb))
+        gpu._ck(gpu.L.lfgpu_ligero_prove_batch(
+            gpu.h, (C.c_void_p * n)(*[pr.h.value if pr.h else None for pr in provers]), nb, C.c_void_p(u.ctypes.data), dd, ndense,
+            C.c_void_p(sc.ctypes.data), (C.c_void_p * n)(*[i.ctypes.data if i.size else None for i in ix]),
+            (C.c_void_p * n)(*[v.ctypes.data if v.size else None for v in vl]), (C.c_size_t * n)(*[len(i) for i in ix]),
+            C.c_void_p(uq.ctypes.data) if uq.size else None, C.c_void_p(y_ldt.ctypes.data), C.c_void_p(y_dot.ctypes.data), C.c_void_p(y_q0.ctypes.data),
+            C.c_void_p(y_q2.ctypes.data)))
+        return y_ldt[:nb], y_dot[:nb], y_q0[:nb], y_q2[:nb]
+
+    @staticmethod
+    def open_batch(gpu, provers, idxs):
+        """lfgpu_ligero_open_batch: open() of every prover with its own nreq indices idxs[b] in one column gather, one digest gather
+        and one read-back -> [(req[nrow][nreq], nonces[nreq], path digests)] per statement"""
+        import numpy as np
+        nb = len(provers)
+        p = provers[0].p if nb else LigeroParam()
+        n = max(1, nb)
+        flat = [int(j) for i in idxs for j in i]
+        if len(flat) != nb * p.nreq:
+            raise ValueError("LigeroProver.open_batch: nreq indices per prover")
+        req = np.zeros((n, p.nrow, p.nreq, 2), dtype=np.uint64)
+        nonces = np.zeros((n, p.nreq, 32), dtype=np.uint8)
+        cap = p.nreq * p.mc_pathlen + 1
+        path = np.zeros((n, cap, 32), dtype=np.uint8)
+        npath = (C.c_size_t * n)()
+        gpu._ck(gpu.L.lfgpu_ligero_open_batch(gpu.h, (C.c_void_p * n)(*[pr.h.value if pr.h else None for pr in provers]), nb,
+                                               (C.c_size_t * max(1, len(flat)))(*flat), C.c_void_p(req.ctypes.data), C.c_void_p(nonces.ctypes.data),
+                                               C.c_void_p(path.ctypes.data), cap, npath))
+        return [(req[b], nonces[b], [bytes(path[b, i]) for i in range(npath[b])]) for b in range(nb)]
 
     def low_degree_proof(self, u_ldt):
         import numpy as np
@@ -864,8 +917,9 @@ class ZkProver:
 
 class ZkBatch:
     """lfgpu_zk_batch: up to nb_max committed ZkProvers of one context and circuit proved in lock-step through one chain of
-    dispatches (batched eval_circuit and sumcheck; constraints and Ligero prove per statement).  Every proof is
-    byte-identical to ZkProver.prove's.  GF2_128 and Fp128 circuits."""
+    dispatches (batched eval_circuit and sumcheck; one EQ launch, one lfgpu_ligero_prove_batch and one
+    lfgpu_ligero_open_batch for the Ligero proofs of all statements; LFGPU_LIGERO_PROVE_BATCH=0 runs that tail per statement).
+    Every proof is byte-identical to ZkProver.prove's.  GF2_128 and Fp128 circuits."""
 
     def __init__(self, gpu, circuit, nb_max):
         self.gpu, self.circuit, self.nb_max = gpu, circuit, nb_max

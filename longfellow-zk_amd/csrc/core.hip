@@ -337,6 +337,14 @@ int lfgpu_sync(lfgpu_ctx* c) {
   LF_HIP(c, hipStreamSynchronize(c->stream));
   return LFGPU_OK;
 }
+int lfgpu_scratch_info(const lfgpu_ctx* c, int which, void** d_out, size_t* bytes_out) {
+  if (!c || which < 0 || which > 3 || !d_out || !bytes_out) return LFGPU_ERR_ARG;
+  void* const d[4] = {c->scratch, c->scratch2, c->scratch3, c->scratch4};
+  const size_t n[4] = {c->scratch_bytes, c->scratch2_bytes, c->scratch3_bytes, c->scratch4_bytes};
+  *d_out = d[which];
+  *bytes_out = n[which];
+  return LFGPU_OK;
+}
 int lfgpu_malloc(lfgpu_ctx* c, size_t bytes, void** d_out) {
   if (!c || !d_out) return LFGPU_ERR_ARG;
   hipError_t e = hipMalloc(d_out, bytes ? bytes : 16);

@@ -185,6 +185,14 @@ struct LfBatchPtrs {
 int lf_gf_rs_rows_mixed_batch(lfgpu_ctx* c, int k, size_t nb, elt_t* const* d_T, size_t nrow, size_t n1, size_t n2, size_t lo2, size_t hi2, size_t m, size_t ld);
 // Fp128: rows [row0, row0 + nrow) of nb tableaux, each n values long, extended to m through ONE convolution of nb * nrow rows
 int lf_fp_rs_rows_batch(lfgpu_ctx* c, size_t nb, elt_t* const* d_T, size_t row0, size_t nrow, size_t n, size_t m, size_t ld);
+// The batched Ligero prove (ligero.hip): the gathers of the opening for nb tableaux / Merkle heaps in one launch each (sumcheck.hip,
+// merkle.hip; enqueue only, index lists already on the device) and the host walk of MerkleTree::generate_compressed_proof
+int lf_gather_columns_batch(lfgpu_ctx* c, size_t nb, size_t nrow, size_t ld, size_t col0, const LfBatchPtrs& T, const u64* d_idx, size_t nreq, void* d_req);
+int lf_merkle_path_nodes(lfgpu_ctx* c, size_t n, const size_t* pos, size_t np, std::vector<u64>& idx);
+int lf_merkle_gather_batch(lfgpu_ctx* c, size_t nb, size_t n, const LfBatchPtrs& layers, const u64* d_idx, const u64* d_off, size_t maxcnt, void* d_out);
+// Eqs::raw_eq2 for nb statements in one launch (quad.hip): h_G0 / h_G1: [nb][logn], alpha: [nb][2]; statement b's n entries at
+// d_eq + b * n.  Enqueue only (the binding points go through the pinned image of the batched bind_g).
+int lf_raw_eq2_batch(lfgpu_ctx* c, int field, size_t nb, size_t logn, size_t n, const void* h_G0, const void* h_G1, const uint64_t* alpha, void* d_eq);
 void lf_fp_omega32(uint64_t om[2]);  // the 2^32-order root of Fp128 (lib/algebra/fp_p128.h:48-56), Montgomery image
 // most Fp128 convolution scratch (nb * rows * P * 16 bytes) one launch chain of the batched commit may ask for: the statements
 // are chunked to stay below it (a single statement's row group may exceed it, as it does in lfgpu_ligero_commit)

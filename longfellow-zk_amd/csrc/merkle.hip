@@ -137,10 +137,25 @@ __global__ void merkle_root_is_leaf_batch_kernel(LfBatchPtrs layers, uint4* __re
   if (threadIdx.x < 2) roots[2 * (size_t)blockIdx.x + threadIdx.x] = ((const uint4*)layers.p[blockIdx.x])[2 + threadIdx.x];
 }
 
-__global__ void gather_digests_kernel(const uint4* __restrict__ layers, const u64* __restrict__ idx, u32 cnt,
-                                      uint4* __restrict__ out) {
+// out[k] = heap node idx[k], k < cnt (two 16-byte halves per node; the body of gather_digests_kernel and of its batched twin;
+// a node index beyond the heap's nnodes reads nothing)
+__device__ __forceinline__ void gather_digests_body(const uint4* __restrict__ layers, size_t nnodes, const u64* __restrict__ idx, u32 cnt,
+                                                    uint4* __restrict__ out) {
   u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t < 2 * cnt) out[t] = layers[2 * idx[t >> 1] + (t & 1)];
+  if (t >= 2 * cnt) return;
+  const u64 node = idx[t >> 1];
+  if (node < nnodes) out[t] = layers[2 * node + (t & 1)];
+}
+__global__ void gather_digests_kernel(const uint4* __restrict__ layers, size_t nnodes, const u64* __restrict__ idx, u32 cnt,
+                                      uint4* __restrict__ out) {
+  gather_digests_body(layers, nnodes, idx, cnt, out);
+}
+// the sibling lists of nb heaps, one after the other: statement blockIdx.y's are entries [off[b], off[b + 1]) of idx and of out
+__global__ void gather_digests_batch_kernel(LfBatchPtrs layers, size_t nnodes, const u64* __restrict__ idx, const u64* __restrict__ off,
+                                            uint4* __restrict__ out) {
+  const u32 b = blockIdx.y;
+  const u64 o = off[b];
+  gather_digests_body((const uint4*)layers.p[b], nnodes, idx + o, (u32)(off[b + 1] - o), out + 2 * o);
 }
 
 static int build_tree(lfgpu_ctx* c, size_t n, void* d_layers) {
@@ -253,10 +268,8 @@ extern "C" int lfgpu_column_leaves(lfgpu_ctx* c, int field, size_t nrow, size_t 
 
 // MerkleTree::generate_compressed_proof (merkle_tree.h:63-84,122-143): the index walk is
 // host logic on positions only; the digests are gathered on the device.
-extern "C" int lfgpu_merkle_open(lfgpu_ctx* c, size_t n, const void* d_layers, const size_t* pos, size_t np,
-                                 uint8_t* h_path, size_t path_cap, size_t* npath) {
-  if (!c || !d_layers || !pos || !npath || np == 0 || n == 0)
-    return lf_fail(c, LFGPU_ERR_ARG, "merkle_open: bad argument (a proof with 0 leaves is not defined)");
+// the heap nodes of a compressed proof for the leaves pos[0 .. np) of a tree with n leaves, appended to idx in proof order
+int lf_merkle_path_nodes(lfgpu_ctx* c, size_t n, const size_t* pos, size_t np, std::vector<u64>& idx) {
   std::vector<bool> tree(2 * n, false);
   for (size_t ip = 0; ip < np; ++ip) {
     if (pos[ip] >= n) return lf_fail(c, LFGPU_ERR_ARG, "merkle_open: invalid leaf position");
@@ -264,7 +277,6 @@ extern "C" int lfgpu_merkle_open(lfgpu_ctx* c, size_t n, const void* d_layers, c
     tree[pos[ip] + n] = true;
   }
   for (size_t i = n; i-- > 1;) tree[i] = tree[2 * i] || tree[2 * i + 1];
-  std::vector<u64> idx;
   for (size_t i = n; i-- > 1;) {
     if (tree[i]) {
       size_t child = 2 * i;
@@ -272,6 +284,25 @@ extern "C" int lfgpu_merkle_open(lfgpu_ctx* c, size_t n, const void* d_layers, c
       if (!tree[child]) idx.push_back(child);
     }
   }
+  return LFGPU_OK;
+}
+// the digest gather of nb heaps with n leaves each in one launch: d_idx / d_off as gather_digests_batch_kernel takes them (on the
+// device, node indices below 2 n), maxcnt = the longest list, d_out: 32 bytes per entry in list order.  Enqueue only.
+int lf_merkle_gather_batch(lfgpu_ctx* c, size_t nb, size_t n, const LfBatchPtrs& layers, const u64* d_idx, const u64* d_off, size_t maxcnt, void* d_out) {
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX || !d_idx || !d_off || !d_out || (maxcnt >> 30)) return lf_fail(c, LFGPU_ERR_ARG, "merkle_gather_batch: bad argument");
+  if (maxcnt == 0) return LFGPU_OK;
+  hipLaunchKernelGGL(gather_digests_batch_kernel, dim3((u32)((2 * maxcnt + 255) / 256), (u32)nb), dim3(256), 0, c->stream, layers, 2 * n, d_idx, d_off,
+                     (uint4*)d_out);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_merkle_open(lfgpu_ctx* c, size_t n, const void* d_layers, const size_t* pos, size_t np,
+                                 uint8_t* h_path, size_t path_cap, size_t* npath) {
+  if (!c || !d_layers || !pos || !npath || np == 0 || n == 0)
+    return lf_fail(c, LFGPU_ERR_ARG, "merkle_open: bad argument (a proof with 0 leaves is not defined)");
+  std::vector<u64> idx;
+  LF_TRY(lf_merkle_path_nodes(c, n, pos, np, idx));
   *npath = idx.size();
   if (idx.empty()) return LFGPU_OK;
   if (!h_path || idx.size() > path_cap) return lf_fail(c, LFGPU_ERR_ARG, "merkle_open: path buffer too small");
@@ -283,7 +314,7 @@ extern "C" int lfgpu_merkle_open(lfgpu_ctx* c, size_t n, const void* d_layers, c
   LF_HIP(c, hipMemcpyAsync(d_idx, idx.data(), idx.size() * 8, hipMemcpyHostToDevice, c->stream));
   u32 cnt = (u32)idx.size();
   hipLaunchKernelGGL(gather_digests_kernel, dim3((2 * cnt + 255) / 256), dim3(256), 0, c->stream,
-                     (const uint4*)d_layers, (const u64*)d_idx, cnt, d_out);
+                     (const uint4*)d_layers, 2 * n, (const u64*)d_idx, cnt, d_out);
   LF_HIP(c, hipGetLastError());
   LF_HIP(c, hipMemcpyAsync(h_path, d_out, idx.size() * 32, hipMemcpyDeviceToHost, c->stream));
   LF_HIP(c, hipStreamSynchronize(c->stream));

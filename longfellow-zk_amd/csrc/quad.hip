@@ -823,16 +823,10 @@ extern "C" int lfgpu_quad_bind_g(lfgpu_quad* q, size_t logv, const void* h_G0, c
   return lf_quad_bind_g(q, logv, h_G0, h_G1, alpha, beta, d_hc_out, d_vc_out, n_out, nullptr, 0, nullptr, 0);
 }
 
-// Quad::bind_g of B statements of one quad (K14, sc_layer_batch): one copy of the B point sets, one EQ launch, one emit launch and,
-// for Fp128, one normalise launch -- whatever B.  h_G0 / h_G1: [B][logv]; alpha, beta: [B][2]; statement b's sums go to
-// d_vc_out + b * s_vc elements, the corners (the same for every statement) to d_hc_out once.  Enqueue only.  Device temporaries:
-// the point sets in scratch2, the EQ vectors in scratch3, the Fp128 limb accumulators in scratch4.
-static int lf_quad_bind_g_batch(lfgpu_quad* q, size_t B, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha, const uint64_t* beta,
-                                void* d_hc_out, void* d_vc_out, size_t s_vc, size_t* n_out) {
-  lfgpu_ctx* c = q->c;
-  const int field = q->field;
-  const size_t n = q->n, nv = q->nv, nh0 = q->nh0, ps = LF_EQB_STRIDE(logv);
-  if (n >> 32) return lf_fail(c, LFGPU_ERR_ARG, "quad_bind_g: more than 2^32 terms");
+// the pinned image of B binding-point sets (LF_EQB_STRIDE(logv) elements each; beta may be null: zero), ready for one copy
+static int eqb_points_fill(lfgpu_ctx* c, int field, size_t B, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha, const uint64_t* beta,
+                           elt_t one) {
+  const size_t ps = LF_EQB_STRIDE(logv);
   if (!c->sc_batch_pts_h) {
     void* p = nullptr;
     if (hipHostMalloc(&p, (size_t)LFGPU_SC_BATCH_MAX * LF_EQB_STRIDE(40) * 16, hipHostMallocDefault) != hipSuccess ||
@@ -845,7 +839,6 @@ static int lf_quad_bind_g_batch(lfgpu_quad* q, size_t B, size_t logv, const void
   } else {
     LF_HIP(c, hipEventSynchronize(c->sc_batch_pts_ev));  // the copy of the previous layer (long done)
   }
-  const elt_t one = field == LFGPU_FIELD_GF2_128 ? elt_t{1, 0} : h_fp_of_scalar(1);
   elt_t* const P = (elt_t*)c->sc_batch_pts_h;
   const elt_t* G0 = (const elt_t*)h_G0;
   const elt_t* G1 = (const elt_t*)h_G1;
@@ -859,8 +852,23 @@ static int lf_quad_bind_g_batch(lfgpu_quad* q, size_t B, size_t logv, const void
       Gt[3 * logv + l] = field == LFGPU_FIELD_GF2_128 ? gf_add(one, g1) : fp_sub(one, g1);
     }
     Gt[4 * logv] = elt_t{alpha[2 * b], alpha[2 * b + 1]};
-    Gt[4 * logv + 1] = elt_t{beta[2 * b], beta[2 * b + 1]};
+    Gt[4 * logv + 1] = beta ? elt_t{beta[2 * b], beta[2 * b + 1]} : elt_t{0, 0};
   }
+  return LFGPU_OK;
+}
+// Quad::bind_g of B statements of one quad (K14, sc_layer_batch): one copy of the B point sets, one EQ launch, one emit launch and,
+// for Fp128, one normalise launch -- whatever B.  h_G0 / h_G1: [B][logv]; alpha, beta: [B][2]; statement b's sums go to
+// d_vc_out + b * s_vc elements, the corners (the same for every statement) to d_hc_out once.  Enqueue only.  Device temporaries:
+// the point sets in scratch2, the EQ vectors in scratch3, the Fp128 limb accumulators in scratch4.
+static int lf_quad_bind_g_batch(lfgpu_quad* q, size_t B, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha, const uint64_t* beta,
+                                void* d_hc_out, void* d_vc_out, size_t s_vc, size_t* n_out) {
+  lfgpu_ctx* c = q->c;
+  const int field = q->field;
+  const size_t n = q->n, nv = q->nv, nh0 = q->nh0, ps = LF_EQB_STRIDE(logv);
+  if (n >> 32) return lf_fail(c, LFGPU_ERR_ARG, "quad_bind_g: more than 2^32 terms");
+  const elt_t one = field == LFGPU_FIELD_GF2_128 ? elt_t{1, 0} : h_fp_of_scalar(1);
+  LF_TRY(eqb_points_fill(c, field, B, logv, h_G0, h_G1, alpha, beta, one));
+  elt_t* const P = (elt_t*)c->sc_batch_pts_h;
   void *d_ptsv = nullptr, *d_eqv = nullptr, *d_accv = nullptr;
   LF_TRY(lf_scratch2(c, B * ps * 16 + 64, &d_ptsv));
   LF_TRY(lf_scratch3(c, B * nv * 16 + 256, &d_eqv));
@@ -891,6 +899,27 @@ static int lf_quad_bind_g_batch(lfgpu_quad* q, size_t B, size_t logv, const void
   return LFGPU_OK;
 }
 
+
+// Eqs::raw_eq2 of nb statements in one launch (ctx.h): the EQ kernels of the batched bind_g without its side clear
+int lf_raw_eq2_batch(lfgpu_ctx* c, int field, size_t nb, size_t logn, size_t n, const void* h_G0, const void* h_G1, const uint64_t* alpha, void* d_eq) {
+  if (!c || !alpha || !d_eq || (logn && (!h_G0 || !h_G1)) || (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128)) return LFGPU_ERR_ARG;
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "raw_eq2_batch: nb must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (logn > 40 || ((size_t)1 << logn) < n || (n >> 32)) return lf_fail(c, LFGPU_ERR_ARG, "raw_eq2: n out of range");
+  if (n == 0) return LFGPU_OK;
+  LF_HIP(c, hipSetDevice(c->device));
+  const size_t ps = LF_EQB_STRIDE(logn);
+  const elt_t one = field == LFGPU_FIELD_GF2_128 ? elt_t{1, 0} : h_fp_of_scalar(1);
+  LF_TRY(eqb_points_fill(c, field, nb, logn, h_G0, h_G1, alpha, nullptr, one));
+  void* d_ptsv = nullptr;
+  LF_TRY(lf_scratch2(c, nb * ps * 16 + 64, &d_ptsv));
+  LF_HIP(c, hipMemcpyAsync(d_ptsv, c->sc_batch_pts_h, nb * ps * 16, hipMemcpyHostToDevice, c->stream));
+  LF_HIP(c, hipEventRecord(c->sc_batch_pts_ev, c->stream));
+  const dim3 ge((u32)((n + QD_THREADS - 1) / QD_THREADS), (u32)nb);
+  if (logn < 6) QD_DISPATCH(field, raw_eq2_batch_kernel, ge, dim3(QD_THREADS), (u32)logn, (u32)n, (const elt_t*)d_ptsv, one, (elt_t*)d_eq, (u64*)nullptr, (size_t)0, (size_t)0);
+  else QD_DISPATCH(field, raw_eq2_fused_batch_kernel, ge, dim3(QD_THREADS), (u32)logn, (u32)n, (const elt_t*)d_ptsv, one, (elt_t*)d_eq, (u64*)nullptr, (size_t)0, (size_t)0);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
 
 // ---- Quad::bind_gh_all (lib/sumcheck/quad.h:188-210): the verifier's combined bind, no expansion:
 //   sum over the corners of prep_v(v, beta) * (EQ(G0,g) + alpha EQ(G1,g)) * EQ(H0,h0) * EQ(H1,h1)

@@ -565,12 +565,23 @@ __global__ __launch_bounds__(1024) void rows_axpy_kernel(u32 nrows, size_t n, el
     st16(&y[j], acc);
   }
 }
-__global__ void gather_columns_kernel(u32 nrow, size_t ld, size_t col0, const elt_t* __restrict__ T,
-                                      const u64* __restrict__ idx, u32 nreq, elt_t* __restrict__ req) {
+// req[i][j] = T[i][col0 + idx[j]] (the body of gather_columns_kernel and of its batched twin; an index beyond the row reads nothing)
+__device__ __forceinline__ void gather_columns_body(u32 nrow, size_t ld, size_t col0, const elt_t* __restrict__ T, const u64* __restrict__ idx, u32 nreq,
+                                                    elt_t* __restrict__ req) {
   u32 t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nrow * nreq) return;
   u32 i = t / nreq, j = t % nreq;
-  st16(&req[t], ld16(&T[(size_t)i * ld + col0 + idx[j]]));
+  const u64 col = col0 + idx[j];
+  if (col < ld) st16(&req[t], ld16(&T[(size_t)i * ld + col]));
+}
+__global__ void gather_columns_kernel(u32 nrow, size_t ld, size_t col0, const elt_t* __restrict__ T,
+                                      const u64* __restrict__ idx, u32 nreq, elt_t* __restrict__ req) {
+  gather_columns_body(nrow, ld, col0, T, idx, nreq, req);
+}
+// statement blockIdx.y gathers from its own tableau with its own index list: req[b][i][j] = T_b[i][col0 + idx[b][j]]
+__global__ void gather_columns_batch_kernel(u32 nrow, size_t ld, size_t col0, LfBatchPtrs T, const u64* __restrict__ idx, u32 nreq, elt_t* __restrict__ req) {
+  const u32 b = blockIdx.y;
+  gather_columns_body(nrow, ld, col0, (const elt_t*)T.p[b], idx + (size_t)b * nreq, nreq, req + (size_t)b * nrow * nreq);
 }
 
 // out[i] = a[i] (op) b[i]: op 0 add, 1 sub, 2 mul   (Field::addf/subf/mulf element-wise)
@@ -2060,6 +2071,18 @@ extern "C" int lfgpu_gather_columns(lfgpu_ctx* c, size_t nrow, size_t ld, size_t
                      (const elt_t*)d_T, (const u64*)di, (u32)nreq, (elt_t*)d_req);
   LF_HIP(c, hipGetLastError());
   LF_HIP(c, hipStreamSynchronize(c->stream));
+  return LFGPU_OK;
+}
+
+// lfgpu_gather_columns for nb tableaux of one shape in one launch; d_idx: [nb][nreq] on the device (range-checked by the caller),
+// d_req: [nb][nrow][nreq].  Enqueue only.
+int lf_gather_columns_batch(lfgpu_ctx* c, size_t nb, size_t nrow, size_t ld, size_t col0, const LfBatchPtrs& T, const u64* d_idx, size_t nreq, void* d_req) {
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX || !d_idx || !d_req || ((nrow * nreq) >> 31)) return lf_fail(c, LFGPU_ERR_ARG, "gather_columns_batch: bad argument");
+  if (nrow == 0 || nreq == 0) return LFGPU_OK;
+  const u32 tot = (u32)(nrow * nreq);
+  hipLaunchKernelGGL(gather_columns_batch_kernel, dim3((tot + 255) / 256, (u32)nb), dim3(256), 0, c->stream, (u32)nrow, ld, col0, T, d_idx, (u32)nreq,
+                     (elt_t*)d_req);
+  LF_HIP(c, hipGetLastError());
   return LFGPU_OK;
 }
 

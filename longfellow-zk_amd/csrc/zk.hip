@@ -380,6 +380,22 @@ struct P16 : zkp::Wire16 {
     LF_HIP(c, hipStreamSynchronize(c->stream));
     return LFGPU_OK;
   }
+  // ... for nb statements in one launch: H0 / H1 [nb][logn], statement b's table at d_eq + b * n, its first npub entries to
+  // eq_in + b * npub in one read-back
+  static int eq_table_batch(lfgpu_ctx* c, const HostField& F, size_t nb, size_t logn, size_t n, const E* H0, const E* H1, const E* alpha, E* d_eq,
+                            size_t npub, E* eq_in) {
+    std::vector<uint64_t> al(2 * nb);
+    for (size_t b = 0; b < nb; ++b) {
+      al[2 * b] = alpha[b].lo;
+      al[2 * b + 1] = alpha[b].hi;
+    }
+    LF_TRY(lf_raw_eq2_batch(c, F.field, nb, logn, n, H0, H1, al.data(), d_eq));
+    if (npub) {  // (without public inputs nothing is read: the tables are consumed in stream order by the dot proofs)
+      LF_HIP(c, hipMemcpy2DAsync(eq_in, npub * 16, d_eq, n * 16, npub * 16, nb, hipMemcpyDeviceToHost, c->stream));
+      LF_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return LFGPU_OK;
+  }
   static int low_degree(Lig* lp, const E* u, E* y) { return lfgpu_ligero_low_degree_proof(lp, u, y); }
   static int dot(Lig* lp, const E* d_dense, size_t ndense, const E& scale, const uint64_t* idx, const E* val, size_t nsparse, E* y) {
     return lfgpu_ligero_dot_proof_sparse(lp, d_dense, ndense, W2(scale).v, idx, val, nsparse, y);
@@ -387,6 +403,15 @@ struct P16 : zkp::Wire16 {
   static int quadratic(Lig* lp, const E* u, E* y0, E* y2) { return lfgpu_ligero_quadratic_proof(lp, u, y0, y2); }
   static int open(Lig* lp, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t cap, size_t* npath) {
     return lfgpu_ligero_open(lp, idx, req, nonces, path, cap, npath);
+  }
+  static int ligero_prove_batch(lfgpu_ctx* c, Lig* const* lp, size_t nb, const E* u_ldt, const E* const* d_dense, size_t ndense, const E* scale,
+                                const uint64_t* const* idx, const E* const* val, const size_t* nsparse, const E* u_quad, E* y_ldt, E* y_dot, E* y_q0, E* y_q2) {
+    static_assert(sizeof(E) == 16, "E is the uint64_t[2] image the C ABI takes");
+    return lfgpu_ligero_prove_batch(c, lp, nb, u_ldt, (const void* const*)d_dense, ndense, (const uint64_t*)scale, idx, (const void* const*)val, nsparse, u_quad,
+                                    y_ldt, y_dot, y_q0, y_q2);
+  }
+  static int ligero_open_batch(lfgpu_ctx* c, Lig* const* lp, size_t nb, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t cap, size_t* npath) {
+    return lfgpu_ligero_open_batch(c, lp, nb, idx, req, nonces, path, cap, npath);
   }
   // LigeroVerifier: rows [0, nwqrow) = [0^r | A_i] extended block -> block_enc, rows nwqrow.. = y_ldt, y_dot, y_quad;
   // ext = those rows at the opened columns
@@ -655,8 +680,10 @@ extern "C" int lfgpu_zk_prover_free(lfgpu_zk_prover* zk) {
 
 // ------------------------------------------------------------------ ZkProver::prove for a batch of committed provers
 // The batch owns what the lock-step needs B times: the layers' input slabs (statement b of layer l at d_in[l] + b * ldw[l]
-// elements), the outputs, one assert-zero flag per statement and their pinned read-back.  Everything is allocated in _new:
-// prove_batch neither allocates nor frees device memory (hipFree waits for every stream of the device).
+// elements), the outputs, one assert-zero flag per statement, their pinned read-back and nb_max EQ tables over the inputs (the
+// dense blocks of the batched dot proofs).  All of it is allocated in _new and nothing is freed inside prove_batch (hipFree waits
+// for every stream of the device); the only device memory a call may allocate is the context's pooled scratch, which grows on the
+// first call at a shape.
 struct lfgpu_zk_batch {
   lfgpu_ctx* c = nullptr;
   const lfgpu_circuit* C = nullptr;
@@ -671,6 +698,7 @@ struct lfgpu_zk_batch {
   int* d_fail = nullptr;
   void* h_V = nullptr;
   size_t h_bytes = 0;
+  void* d_eq = nullptr;  // [nb_max][ninputs]: functions of the challenges only, not scrubbed
   ~lfgpu_zk_batch() {
     // the slabs hold the wire values of every statement -- functions of the witnesses: scrubbed before the memory goes back
     if (c) {
@@ -684,6 +712,7 @@ struct lfgpu_zk_batch {
       if (p) (void)hipFree(p);
     if (d_V) (void)hipFree(d_V);
     if (d_fail) (void)hipFree(d_fail);
+    if (d_eq) (void)hipFree(d_eq);
     if (h_V) {
       memset(h_V, 0, h_bytes);
       (void)hipHostFree(h_V);
@@ -725,7 +754,8 @@ extern "C" int lfgpu_zk_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t n
     bt->h_V = nullptr;
     return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: pinned outputs");
   }
-  LF_TRY(zk_eq_reserve(c, C->info.ninputs));  // (prove_batch then finds the context's EQ table in place)
+  if (!alloc(&bt->d_eq, std::max<size_t>(nb_max * C->info.ninputs, 1) * 16)) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: %zu EQ tables over the inputs", nb_max);
+  LF_TRY(zk_eq_reserve(c, C->info.ninputs));  // (the per-statement path of prove_batch then finds the context's EQ table in place)
   *out = bt.release();
   return LFGPU_OK;
 }
@@ -758,7 +788,7 @@ extern "C" int lfgpu_zk_prove_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* 
     *d_eq = (elt_t*)c->zk_eq;
     return (int)LFGPU_OK;
   };
-  const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max};
+  const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max, bt->d_eq};
   return zkp::prove_batch<P16>(c, C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
 }
 

@@ -529,9 +529,25 @@ struct ConstraintSet {
   std::vector<E> b;  // one entry per constraint
   size_t n = 0;      // number of constraints; the dense one is n - 1
 };
+// What the EQ table of the input constraint is built from, for a caller that launches the tables of several statements at once
+// (prove_finish_batch): build_constraints then stops in front of its EQ step, and input_constraint_b finishes the last entry of b
+// once the public part of the table is back.
+template <class E>
+struct EqPending {
+  std::vector<E> g0, g1;  // the last layer's challenges, logw each
+  E alpha, wc0, wc1;
+};
+template <class P>
+void input_constraint_b(const typename P::Field& F, const typename P::E& alpha, const typename P::E& wc0, const typename P::E& wc1, const typename P::E* eq_in,
+                        const typename P::E* pub, size_t npub, ConstraintSet<typename P::E>& out) {
+  typename P::E pub_binding = P::zero();
+  for (size_t i = 0; i < npub; ++i) pub_binding = F.add(pub_binding, F.mul(eq_in[i], pub[i]));
+  out.b.push_back(F.sub(F.add(wc0, F.mul(alpha, wc1)), pub_binding));
+}
 template <class P>
 int build_constraints(lfgpu_ctx* c, const lfgpu_circuit* C, const typename P::Field& F, const Ts<P>& ts, const std::vector<LayerPad<typename P::E>>& proof,
-                      const std::vector<typename P::E>* aux, const typename P::E* pub, typename P::E* d_eq, ConstraintSet<typename P::E>& out) {
+                      const std::vector<typename P::E>* aux, const typename P::E* pub, typename P::E* d_eq, ConstraintSet<typename P::E>& out,
+                      EqPending<typename P::E>* pend = nullptr) {
   using E = typename P::E;
   const lfgpu_circuit_info& I = C->info;
   const size_t nl = C->layers.size(), npub = I.npub_in;
@@ -643,12 +659,18 @@ int build_constraints(lfgpu_ctx* c, const lfgpu_circuit* C, const typename P::Fi
   out.n = ci + 1;
   // EQ(g0, i) + alpha EQ(g1, i) over the inputs on the device: the public part is folded into b, the private part is the
   // dense block of A
+  const auto& L_p = proof[nl - 1];
+  if (pend) {  // the caller builds the table (and nothing of this statement has been launched)
+    pend->g0 = gh[0];
+    pend->g1 = gh[1];
+    pend->alpha = alpha;
+    pend->wc0 = L_p.wc[0];
+    pend->wc1 = L_p.wc[1];
+    return LFGPU_OK;
+  }
   std::vector<E> eq_in(npub ? npub : 1, P::zero());
   LF_TRY(P::eq_table(c, F, C->layers[nl - 1].logw, I.ninputs, gh[0].data(), gh[1].data(), alpha, d_eq, npub, eq_in.data()));
-  const auto& L_p = proof[nl - 1];
-  E pub_binding = P::zero();
-  for (size_t i = 0; i < npub; ++i) pub_binding = F.add(pub_binding, F.mul(eq_in[i], pub[i]));
-  out.b.push_back(F.sub(F.add(L_p.wc[0], F.mul(alpha, L_p.wc[1])), pub_binding));
+  input_constraint_b<P>(F, alpha, L_p.wc[0], L_p.wc[1], eq_in.data(), pub, npub, out);
   return LFGPU_OK;
 }
 
@@ -923,8 +945,8 @@ int prove_finish(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const typen
 
 // ------------------------------------------------------------------ B statements of one circuit in lock-step
 // The device buffers of a batch (the caller's; nothing is allocated here): per layer nb_max input slabs at stride ldw[l]
-// elements, the outputs at stride ldv, one assert-zero flag per statement, and the pinned read-back (nb_max * ldv elements,
-// then nb_max flags).
+// elements, the outputs at stride ldv, one assert-zero flag per statement, the pinned read-back (nb_max * ldv elements,
+// then nb_max flags), and nb_max EQ tables over the inputs at a stride of ninputs elements (prove_finish_batch).
 struct BatchBufs {
   void* const* d_in;
   const size_t* ldw;
@@ -933,12 +955,111 @@ struct BatchBufs {
   int* d_fail;
   void* h_V;
   size_t nb_max;
+  void* d_eq;
 };
 template <class P>
 void round_batch_cb(void* user, size_t hand, size_t rnd, size_t nb, const typename P::E (*ev)[3], typename P::E* chal) {
   RoundCtx<P>* r = (RoundCtx<P>*)user;
   for (size_t b = 0; b < nb; ++b) round_cb<P>(&r[b], hand, rnd, ev[b], &chal[b]);
 }
+// prove_finish for the statements sel[0 .. m) of a batch (those with a good witness) with the device work of all of them in
+// three chains: ONE EQ table launch (statement g's table at bb.d_eq + g * ninputs, its public part read back once), ONE
+// lfgpu_ligero_prove_batch, ONE lfgpu_ligero_open_batch.  Per statement the transcript sees exactly what prove_finish shows
+// it, in the same order: the device calls of the single path lie between draws and never touch the transcript.
+// ms: {constraints, Ligero prove} of the whole batch.
+template <class P>
+int prove_finish_batch(lfgpu_ctx* c, const lfgpu_circuit* C, const typename P::Field& F, ProverState<P>* const* st, typename P::Lig* const* lp,
+                       const BatchBufs& bb, const std::vector<size_t>& sel, const void* const* h_W, const std::vector<Ts<P>>& ts, double ms[2]) {
+  using E = typename P::E;
+  const lfgpu_circuit_info& I = C->info;
+  const size_t m = sel.size(), nl = C->layers.size(), npub = I.npub_in, logn = C->layers[nl - 1].logw;
+  const lfgpu_ligero_param& p = st[sel[0]]->param;
+  // verifier_constraints with aux per statement on its ORIGINAL transcript (host only), then the EQ tables of all statements
+  double t0 = now_ms();
+  std::vector<ConstraintSet<E>> cs(m);
+  std::vector<EqPending<E>> pend(m);
+  for (size_t g = 0; g < m; ++g) {
+    const size_t b = sel[g];
+    LF_TRY(build_constraints<P>(c, C, F, ts[b], st[b]->proof.sc, &st[b]->aux, (const E*)h_W[b], nullptr, cs[g], &pend[g]));
+  }
+  E* const d_eq = (E*)bb.d_eq;
+  {
+    std::vector<E> G0(m * logn + 1, P::zero()), G1(m * logn + 1, P::zero()), al(m), eq_in(m * npub + 1, P::zero());
+    for (size_t g = 0; g < m; ++g) {
+      for (size_t l = 0; l < logn; ++l) {
+        G0[g * logn + l] = pend[g].g0[l];
+        G1[g * logn + l] = pend[g].g1[l];
+      }
+      al[g] = pend[g].alpha;
+    }
+    LF_TRY(P::eq_table_batch(c, F, m, logn, I.ninputs, G0.data(), G1.data(), al.data(), d_eq, npub, eq_in.data()));
+    for (size_t g = 0; g < m; ++g)
+      input_constraint_b<P>(F, pend[g].alpha, pend[g].wc0, pend[g].wc1, eq_in.data() + g * npub, (const E*)h_W[sel[g]], npub, cs[g]);
+  }
+  ms[0] = now_ms() - t0;
+
+  // LigeroProver::prove (ligero_prover.h:84-146): the draws of every statement, then the device work of all of them
+  t0 = now_ms();
+  const size_t nqt = p.nqtriples, ymid = p.dblock - p.block;
+  std::vector<E> u_ldt(m * p.nwqrow + 1, P::zero()), u_quad(m * nqt + 1, P::zero()), scale(m);
+  std::vector<std::vector<uint64_t>> a_idx(m);
+  std::vector<std::vector<E>> a_val(m);
+  std::vector<const uint64_t*> pi(m);
+  std::vector<const E*> pv(m), pdense(m);
+  std::vector<size_t> nsp(m);
+  std::vector<typename P::Lig*> lps(m);
+  for (size_t g = 0; g < m; ++g) {
+    const size_t b = sel[g];
+    const uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};  // zk_prover.h:143
+    ts[b].write_bytes(hash_of_A, 32);
+    for (size_t i = 0; i < p.nwqrow; ++i) u_ldt[g * p.nwqrow + i] = ts[b].elt();
+    std::vector<E> alphal(cs[g].n), alphaq(3 * p.nq);
+    for (auto& e : alphal) e = ts[b].elt();
+    for (auto& e : alphaq) e = ts[b].elt();
+    inner_product_sparse<P>(F, p, cs[g].a, alphal, st[b]->lqc, alphaq, a_idx[g], a_val[g]);
+    scale[g] = alphal[cs[g].n - 1];
+    for (size_t i = 0; i < nqt; ++i) u_quad[g * nqt + i] = ts[b].elt();
+    pi[g] = a_idx[g].data();
+    pv[g] = a_val[g].data();
+    nsp[g] = a_idx[g].size();
+    pdense[g] = d_eq + g * I.ninputs + st[b]->npub;
+    lps[g] = lp[b];
+  }
+  std::vector<E> y_ldt(m * p.block), y_dot(m * p.dblock), y_q0(m * p.r + 1), y_q2(m * ymid + 1);
+  LF_TRY(P::ligero_prove_batch(c, lps.data(), m, u_ldt.data(), pdense.data(), st[sel[0]]->n_witness, scale.data(), pi.data(), pv.data(), nsp.data(),
+                               nqt ? u_quad.data() : nullptr, y_ldt.data(), y_dot.data(), y_q0.data(), y_q2.data()));
+  std::vector<size_t> idx(m * p.nreq);
+  for (size_t g = 0; g < m; ++g) {
+    const size_t b = sel[g];
+    ProofBody<E>& pr = st[b]->proof;
+    pr.y_ldt.assign(y_ldt.begin() + g * p.block, y_ldt.begin() + (g + 1) * p.block);
+    pr.y_dot.assign(y_dot.begin() + g * p.dblock, y_dot.begin() + (g + 1) * p.dblock);
+    pr.y_q0.assign(y_q0.begin() + g * p.r, y_q0.begin() + (g + 1) * p.r);
+    pr.y_q2.assign(y_q2.begin() + g * ymid, y_q2.begin() + (g + 1) * ymid);
+    ts[b].write_array(pr.y_ldt.data(), pr.y_ldt.size());
+    ts[b].write_array(pr.y_dot.data(), pr.y_dot.size());
+    ts[b].write_array(pr.y_q0.data(), pr.y_q0.size());
+    ts[b].write_array(pr.y_q2.data(), pr.y_q2.size());
+    ts[b].choose(p.block_ext, p.nreq, idx.data() + g * p.nreq);
+  }
+  const size_t cap = p.nreq * p.mc_pathlen + 1;
+  std::vector<E> req(m * p.nrow * p.nreq);
+  std::vector<uint8_t> nonces(m * p.nreq * 32), path(m * cap * 32);
+  std::vector<size_t> npath(m, 0);
+  LF_TRY(P::ligero_open_batch(c, lps.data(), m, idx.data(), req.data(), nonces.data(), path.data(), cap, npath.data()));
+  for (size_t g = 0; g < m; ++g) {
+    ProofBody<E>& pr = st[sel[g]]->proof;
+    pr.req.assign(req.begin() + g * p.nrow * p.nreq, req.begin() + (g + 1) * p.nrow * p.nreq);
+    pr.nonces.assign(nonces.begin() + g * p.nreq * 32, nonces.begin() + (g + 1) * p.nreq * 32);
+    pr.path.assign(cap * 32, 0);
+    memcpy(pr.path.data(), path.data() + g * cap * 32, npath[g] * 32);
+    pr.npath = npath[g];
+    st[sel[g]]->have_proof = true;
+  }
+  ms[1] = now_ms() - t0;
+  return LFGPU_OK;
+}
+
 // prove for statements 0 .. nb-1: pol[b], st[b], lp[b], h_W[b], tso[b] are statement b's; ok[b] as prove's *ok.  A statement
 // whose witness fails rides along in the sumcheck on its transcript copy -- the launches are the batch's, not its own -- and
 // what it produces is dropped: it holds no proof and its transcript is where the single call leaves it.
@@ -1026,13 +1147,36 @@ int prove_batch(lfgpu_ctx* c, const lfgpu_circuit* C, const P* pol, ProverState<
   }
   const double ms_sc = now_ms() - t0;
 
-  // constraints, Ligero prove and open: per statement, one after the other (the context's EQ table is reused)
+  // constraints, Ligero prove and open of the statements with a good witness: in three chains for all of them
+  // (prove_finish_batch), or with LFGPU_LIGERO_PROVE_BATCH=0 (read once per process; the A/B switch, the same bytes) per
+  // statement, one after the other, with the context's EQ table reused
+  static const int lig_batched = getenv("LFGPU_LIGERO_PROVE_BATCH") ? atoi(getenv("LFGPU_LIGERO_PROVE_BATCH")) : 1;
   for (size_t b = 0; b < nb; ++b) {
     st[b]->ms[2] = ms_eval;
     st[b]->ms[3] = ms_sc;
-    if (!good[b]) continue;
-    LF_TRY(prove_finish<P>(c, C, pol[b], F, *st[b], lp[b], eq_table, (const E*)h_W[b], ts[b]));
-    ok[b] = 1;
+  }
+  // The sumcheck does not look at the Ligero parameters, so provers of one circuit with different rate, nreq or block_enc are a
+  // valid batch; their tableaux have different shapes, which the batched tail cannot take: such a batch keeps the per-statement loop.
+  std::vector<size_t> sel;
+  for (size_t b = 0; b < nb; ++b)
+    if (good[b]) sel.push_back(b);
+  bool one_shape = true;
+  for (size_t g = 1; g < sel.size(); ++g)
+    if (memcmp(&st[sel[g]]->param, &st[sel[0]]->param, sizeof(lfgpu_ligero_param)) != 0) one_shape = false;
+  if (lig_batched && one_shape) {
+    double ms_fin[2] = {0, 0};
+    LF_TRY(prove_finish_batch<P>(c, C, F, st, lp, bb, sel, h_W, ts, ms_fin));
+    for (size_t b = 0; b < nb; ++b) {
+      st[b]->ms[4] = ms_fin[0];
+      st[b]->ms[5] = ms_fin[1];
+      if (good[b]) ok[b] = 1;
+    }
+  } else {
+    for (size_t b = 0; b < nb; ++b) {
+      if (!good[b]) continue;
+      LF_TRY(prove_finish<P>(c, C, pol[b], F, *st[b], lp[b], eq_table, (const E*)h_W[b], ts[b]));
+      ok[b] = 1;
+    }
   }
   const double ms_all = now_ms() - t_start;
   for (size_t b = 0; b < nb; ++b) st[b]->ms[1] = ms_all;
