@@ -14,25 +14,11 @@
 #include <new>
 
 #include "ctx.h"
+#include "ligero_slab.h"
 
-struct lfgpu_ligero_prover {
-  lfgpu_ctx* c;
-  int field, k;
-  lfgpu_ligero_param p;
-  elt_t* d_T;             // [nrow][block_enc]
-  uint8_t* d_layers;      // [2*block_ext][32]
-  size_t T_bytes = 0, L_bytes = 0;
-  std::vector<uint8_t> nonces;  // block_ext * 32 (host copy for open)
-  // rows [row_lo, row_hi) of the tableau live in d_T (a slab of a multi-GPU commit; [0, nrow) on one GPU).  The prove
-  // functions then return this slab's PARTIAL sums (rows it does not hold contribute zero); the caller folds the ranks.
-  size_t row_lo = 0, row_hi = 0;
-  bool owns = true;  // d_T / d_layers are freed (stashed) by lfgpu_ligero_free
-  // a prover made by lfgpu_ligero_commit_sharded: the prove entry points fold the ranks' partial results through these hooks
-  bool sharded = false;
-  lfgpu_comm_ops comm{};
-  std::vector<std::pair<size_t, size_t>> spans;  // row slab of every rank
-  bool has(size_t i) const { return i >= row_lo && i < row_hi; }
-  elt_t* row(size_t i) const { return d_T + (i - row_lo) * p.block_enc; }
+// the C ABI's opaque prover: the shared record (ligero_slab.h) over 16-byte elements, plus which of the two fields it serves
+struct lfgpu_ligero_prover : lig::Slab<elt_t> {
+  int field = 0, k = 0;
 };
 
 static size_t ceildiv(size_t a, size_t b) { return (a + b - 1) / b; }
@@ -608,15 +594,10 @@ extern "C" int lfgpu_ligero_commit_batch(lfgpu_ctx* c, int field, int k, const l
 }
 
 // ------------------------------------------------------------------ rows sharded over the GPUs of a node
-static void shard_split(size_t n, int rank, int world, size_t* start, size_t* count) {  // contiguous, sizes differ by at most 1
-  const size_t base = n / (size_t)world, rem = n % (size_t)world, r = (size_t)rank;
-  *start = r * base + std::min(r, rem);
-  *count = base + (r < rem ? 1 : 0);
-}
 extern "C" int lfgpu_ligero_row_shard(const lfgpu_ligero_param* p, int rank, int world, size_t* row_lo, size_t* row_hi) {
   if (!p || !row_lo || !row_hi || world < 1 || rank < 0 || rank >= world) return LFGPU_ERR_ARG;
   size_t lo, cnt;
-  shard_split(p->nrow, rank, world, &lo, &cnt);
+  lig::shard_split(p->nrow, rank, world, &lo, &cnt);
   *row_lo = std::min(lo, p->iq);
   *row_hi = rank == world - 1 ? p->nrow : std::min(lo + cnt, p->iq);
   return LFGPU_OK;
@@ -668,23 +649,6 @@ void lf_record_rng(lfgpu_rng_fn rng, void* rng_user, std::vector<uint8_t>* rec, 
   *fn = record_fn;
   *user = r;
 }
-// field sum over the ranks of a host vector every rank holds a partial of (RCCL has no XOR / mod-p reduction: all_gather + fold)
-static int comm_fold(const lfgpu_ligero_prover* pr, elt_t* y, size_t n) {
-  const lfgpu_comm_ops& cm = pr->comm;
-  if (cm.world == 1) return LFGPU_OK;
-  std::vector<elt_t> all((size_t)cm.world * n);
-  if (cm.all_gather(cm.user, y, all.data(), n * 16, 0, nullptr)) return lf_fail(pr->c, LFGPU_ERR_HIP, "ligero (sharded): all_gather hook failed");
-  for (size_t j = 0; j < n; ++j) y[j] = all[j];
-  for (int q = 1; q < cm.world; ++q) {
-    const elt_t* v = all.data() + (size_t)q * n;
-    if (pr->field == LFGPU_FIELD_GF2_128)
-      for (size_t j = 0; j < n; ++j) y[j] = gf_add(y[j], v[j]);
-    else
-      for (size_t j = 0; j < n; ++j) y[j] = fp_add(y[j], v[j]);
-  }
-  return LFGPU_OK;
-}
-
 static int layout_sharded_host(int field, int k, const GfHostCtx* g, const lfgpu_ligero_param& p, const void* h_W, size_t subfield_boundary,
                                const size_t* h_lqc, lfgpu_rng_fn rng, void* user, const lfgpu_comm_ops* cm, bool exact, size_t row_lo, size_t row_hi,
                                elt_t* H, uint8_t* nonces, char* err) {
@@ -728,133 +692,6 @@ extern "C" int lfgpu_ligero_layout_rows_sharded(int field, int k, const lfgpu_li
   if (hi > lo && !h_rows) return LFGPU_ERR_ARG;
   char err[256] = {0};
   return layout_sharded_host(field, k, &g, *pp, h_W, subfield_boundary, h_lqc, rng, user, cm, false, lo, hi, (elt_t*)h_rows, h_nonces, err);
-}
-
-extern "C" int lfgpu_ligero_commit_sharded(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const void* h_W, size_t subfield_boundary,
-                                           const size_t* h_lqc, lfgpu_rng_fn rng, void* user, const lfgpu_comm_ops* cm, uint8_t root_out[32],
-                                           lfgpu_ligero_prover** out) {
-  if (!c || !pp || !root_out || !out || !comm_ok(cm) || (cm->rank == 0 && !rng) || (pp->nw && !h_W) || (pp->nq && !h_lqc))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: null argument / incomplete communicator");
-  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: field");
-  const lfgpu_ligero_param& p = *pp;
-  if (p.ildt != 0 || p.idot != 1 || p.iquad != 2 || p.iw != 3) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: row order");
-  LF_HIP(c, hipSetDevice(c->device));
-  const GfHostCtx* g = field == LFGPU_FIELD_GF2_128 ? lf_gf_ctx(c, k) : nullptr;
-  if (field == LFGPU_FIELD_GF2_128 && !g) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: k");
-  const int world = cm->world, rank = cm->rank;
-  lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
-  pr->c = c;
-  pr->field = field;
-  pr->k = k;
-  pr->p = p;
-  pr->d_T = nullptr;
-  pr->d_layers = nullptr;
-  pr->nonces.resize(p.block_ext * 32);
-  pr->sharded = true;
-  pr->comm = *cm;
-  pr->spans.resize(world);
-  for (int q = 0; q < world; ++q) (void)lfgpu_ligero_row_shard(&p, q, world, &pr->spans[q].first, &pr->spans[q].second);
-  pr->row_lo = pr->spans[rank].first;
-  pr->row_hi = pr->spans[rank].second;
-  void* d_send = nullptr;
-  void* d_cols = nullptr;
-  size_t send_bytes_tot = 0, cols_bytes = 0;
-  // the exchange buffers hold encoded rows of the tableau (witness, pads, blinding rows): scrubbed like the tableau itself
-  // (lfgpu_ligero_free) before they go back to the pool, in stream order behind their last use
-  auto retire = [&](void*& d, size_t bytes) {
-    if (!d) return;
-    (void)hipMemsetAsync(d, 0, bytes, c->stream);
-    lf_pool_put(c, d, bytes);
-    d = nullptr;
-  };
-  auto fail = [&](int rc) {
-    retire(d_send, send_bytes_tot);
-    retire(d_cols, cols_bytes);
-    lfgpu_ligero_free(pr);
-    return rc;
-  };
-  const size_t nr = pr->row_hi - pr->row_lo, ld = p.block_enc, ncols = p.block_ext;
-  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-  auto clk = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tv0 = clk();
-  double tv1 = tv0, tv2 = tv0, tv3 = tv0, tv4 = tv0;
-  // 1. host layout of this rank's slab from the one random stream
-  std::vector<elt_t> H(std::max<size_t>(nr, 1) * p.dblock);
-  LF_SCRUB_ON_EXIT(H);
-  {
-    char err[256] = {0};
-    const int rc = layout_sharded_host(field, k, g, p, h_W, subfield_boundary, h_lqc, rng, user, cm, c->rng_exact != 0, pr->row_lo, pr->row_hi, H.data(),
-                                       pr->nonces.data(), err);
-    if (rc) return fail(lf_fail(c, rc, "%s", err));
-  }
-  tv1 = clk();
-  // 2. RS-extend the slab: rows are independent, no collective
-  const size_t tb = std::max<size_t>(nr, 1) * ld * 16, lb = 2 * ncols * 32;
-  if (lf_pool_get(c, tb, (void**)&pr->d_T) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: slab alloc"));
-  pr->T_bytes = tb;
-  if (lf_pool_get(c, lb, (void**)&pr->d_layers) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: layers alloc"));
-  pr->L_bytes = lb;
-  int rc = nr ? ligero_encode_slab(c, field, k, p, pr->row_lo, pr->row_hi, H.data(), pr->d_T) : LFGPU_OK;
-  if (rc) return fail(rc);
-  // 3. a leaf hashes ALL rows of one column: one all_to_all re-partitions the encoded columns [dblock, block_enc) so that
-  //    this rank owns columns [mc0, mc0 + mcn) of every row.  Send block for rank q: my rows x its columns, contiguous.
-  std::vector<size_t> soff(world), sbytes(world), roff(world), rbytes(world);
-  size_t mc0 = 0, mcn = 0;
-  shard_split(ncols, rank, world, &mc0, &mcn);
-  for (int q = 0; q < world; ++q) {
-    size_t c0, cn;
-    shard_split(ncols, q, world, &c0, &cn);
-    soff[q] = send_bytes_tot;
-    sbytes[q] = nr * cn * 16;
-    send_bytes_tot += sbytes[q];
-    roff[q] = pr->spans[q].first * mcn * 16;  // slabs are contiguous and ascending: the received blocks ARE the column matrix
-    rbytes[q] = (pr->spans[q].second - pr->spans[q].first) * mcn * 16;
-  }
-  cols_bytes = std::max<size_t>(p.nrow * mcn * 16, 16);
-  send_bytes_tot = std::max<size_t>(send_bytes_tot, 16);
-  if (lf_pool_get(c, send_bytes_tot, &d_send) != LFGPU_OK || lf_pool_get(c, cols_bytes, &d_cols) != LFGPU_OK)
-    return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: exchange buffers"));
-  for (int q = 0; q < world && nr; ++q) {
-    size_t c0, cn;
-    shard_split(ncols, q, world, &c0, &cn);
-    if (cn && hipMemcpy2DAsync((uint8_t*)d_send + soff[q], cn * 16, pr->d_T + p.dblock + c0, ld * 16, cn * 16, nr, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_sharded: pack"));
-  }
-  if (verbose) {
-    (void)hipStreamSynchronize(c->stream);
-    tv2 = clk();
-  }
-  if (cm->all_to_all(cm->user, d_send, soff.data(), sbytes.data(), d_cols, roff.data(), rbytes.data(), 1, c->stream))
-    return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_sharded: all_to_all hook failed"));
-  tv3 = clk();
-  // 4. local leaves of my columns, all_gather of the digests (ragged: padded to the largest share), the tree on every rank
-  size_t maxn = 0, dummy = 0;
-  shard_split(ncols, 0, world, &dummy, &maxn);
-  void* d_non = nullptr;
-  if ((rc = lf_scratch3(c, ncols * 32 + (size_t)(world + 1) * maxn * 32 + 64, &d_non))) return fail(rc);
-  uint8_t* d_mine = (uint8_t*)d_non + ncols * 32;
-  uint8_t* d_all = d_mine + maxn * 32;
-  if (hipMemcpyAsync(d_non, pr->nonces.data(), ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-      hipMemsetAsync(d_mine, 0, maxn * 32, c->stream) != hipSuccess)
-    return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_sharded: nonce upload"));
-  if (mcn && (rc = lfgpu_column_leaves(c, field, p.nrow, mcn, 0, mcn, d_cols, (const uint8_t*)d_non + mc0 * 32, d_mine))) return fail(rc);
-  if (cm->all_gather(cm->user, d_mine, d_all, maxn * 32, 1, c->stream)) return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_sharded: all_gather hook failed"));
-  if (hipMemsetAsync(pr->d_layers, 0, ncols * 32, c->stream) != hipSuccess) return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_sharded: layers"));
-  for (int q = 0; q < world; ++q) {
-    size_t c0, cn;
-    shard_split(ncols, q, world, &c0, &cn);
-    if (cn && hipMemcpyAsync(pr->d_layers + (ncols + c0) * 32, d_all + (size_t)q * maxn * 32, cn * 32, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_sharded: leaves"));
-  }
-  if ((rc = lfgpu_merkle_build_tree(c, ncols, pr->d_layers, root_out))) return fail(rc);
-  tv4 = clk();
-  if (verbose)
-    fprintf(stderr, "lfgpu ligero_commit_sharded rank %d/%d: rows [%zu, %zu): layout + stream %.2f ms | upload + RS encode + pack %.2f | all_to_all %.2f | leaves + all_gather + tree %.2f\n",
-            rank, world, pr->row_lo, pr->row_hi, tv1 - tv0, tv2 - tv1, tv3 - tv2, tv4 - tv3);
-  retire(d_send, send_bytes_tot);
-  retire(d_cols, cols_bytes);
-  *out = pr;
-  return LFGPU_OK;
 }
 
 // host-only check of a caller's hooks
@@ -902,22 +739,7 @@ extern "C" int lfgpu_comm_selftest(const lfgpu_comm_ops* cm) {
 
 extern "C" int lfgpu_ligero_free(lfgpu_ligero_prover* pr) {
   if (!pr) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = pr->c;
-  // keep the buffers for the next commit of the same shape (the context's pool); the stream is in order, so work still
-  // queued on them finishes before anything a later commit enqueues
-  auto stash = [&](void* p, size_t bytes) {
-    if (!p) return;
-    // the tableau holds the witness, the pads and the blinding rows: scrub it before it outlives its prover (enqueued on the
-    // stream, in order behind the prover's last kernels)
-    if (bytes) (void)hipMemsetAsync(p, 0, bytes, c ? c->stream : nullptr);
-    if (c && bytes) lf_pool_put(c, p, bytes);
-    else (void)hipFree(p);
-  };
-  if (pr->owns) {
-    stash(pr->d_T, pr->T_bytes);
-    stash(pr->d_layers, pr->L_bytes);
-  }
-  delete pr;
+  delete pr;  // ~Slab scrubs the buffers it owns and returns them to the context's pool
   return LFGPU_OK;
 }
 extern "C" int lfgpu_ligero_tableau(lfgpu_ligero_prover* pr, void** d_T) {
@@ -1030,36 +852,7 @@ __global__ void layout_aext_kernel(u32 r, u32 w, size_t lda, const elt_t* __rest
       hipLaunchKernelGGL(KERNEL<FIELD_FP128>, grid, block, 0, c->stream, __VA_ARGS__);   \
   } while (0)
 
-// witness / quadratic rows [a_lo, a_hi) (indices relative to iw) that this prover's slab holds
-static void owned_wq_rows(const lfgpu_ligero_prover* pr, size_t* a_lo, size_t* a_hi) {
-  const lfgpu_ligero_param& p = pr->p;
-  const size_t lo = std::min(std::max(pr->row_lo, p.iw), p.iw + p.nwqrow), hi = std::min(std::max(pr->row_hi, p.iw), p.iw + p.nwqrow);
-  *a_lo = lo - p.iw;
-  *a_hi = std::max(hi, lo) - p.iw;
-}
-
-extern "C" int lfgpu_ligero_low_degree_proof(lfgpu_ligero_prover* pr, const void* h_u, void* h_y) {
-  if (!pr || !h_u || !h_y) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = pr->c;
-  const lfgpu_ligero_param& p = pr->p;
-  LF_HIP(c, hipSetDevice(c->device));
-  void* dy = nullptr;
-  LF_TRY(lf_scratch3(c, p.block * 16, &dy));
-  if (pr->has(p.ildt))
-    LF_HIP(c, hipMemcpyAsync(dy, pr->row(p.ildt), p.block * 16, hipMemcpyDeviceToDevice, c->stream));
-  else
-    LF_HIP(c, hipMemsetAsync(dy, 0, p.block * 16, c->stream));
-  size_t a_lo, a_hi;
-  owned_wq_rows(pr, &a_lo, &a_hi);
-  if (a_hi > a_lo)
-    LF_TRY(lfgpu_rows_axpy(c, pr->field, a_hi - a_lo, p.block, dy, (const uint64_t*)h_u + 2 * a_lo, pr->row(p.iw + a_lo), p.block_enc));
-  LF_TRY(lfgpu_memcpy_d2h(c, h_y, dy, p.block * 16));
-  return pr->sharded ? comm_fold(pr, (elt_t*)h_y, p.block) : LFGPU_OK;
-}
-
-// ---- the inner-product matrix built on the device (inner_product_vector + layout_Aext, ligero_param.h:382-430)
-// rows[i][r + j] = scale * dense[i*w + j] over the first ndense flat positions (the private-input block of the last
-// constraint), then rows[pos(idx)] += val for the caller's sparse terms (duplicates already folded by the caller)
+// ---- the kernels of the inner-product matrix (lig::a_rows, ligero_slab.h)
 // (the bodies of the two kernels and of their batched twins: flat position t of n; nflat = nrows * w bounds the sparse indices)
 template <int F>
 __device__ __forceinline__ void a_rows_dense_body(u32 r, u32 w, size_t ld, elt_t scale, const elt_t* __restrict__ dense, size_t n, elt_t* __restrict__ rows) {
@@ -1105,66 +898,140 @@ __global__ void a_rows_sparse_batch_kernel(u32 r, u32 w, size_t ld, const u64* _
   a_rows_sparse_body<F>(r, w, ld, idx + o, val + o, (size_t)(off[b + 1] - o), nflat, rows + (size_t)b * srows);
 }
 
+// ---- the width policy of ligero_slab.h for the two 16-byte fields: it wraps the entry points and kernels that exist and carries
+// the field.  These steps upload their host vectors themselves: lfgpu_rows_axpy and lfgpu_gather_columns end with a synchronise,
+// a short sparse list goes through the pinned staging ring without one.
+struct L16 {
+  using E = elt_t;
+  int field, k;
+  E add(E a, E b) const { return h_add(field, a, b); }
+  static bool is_zero(E a) { return (a.lo | a.hi) == 0; }
+  int rows_axpy(lfgpu_ctx* c, size_t nrows, size_t n, E* d_y, const E* h_u, const E* d_T, size_t ld) const {
+    return lfgpu_rows_axpy(c, field, nrows, n, d_y, (const uint64_t*)h_u, d_T, ld);
+  }
+  int rows_vaxpy(lfgpu_ctx* c, size_t nrows, size_t n, const E* T0, const E* A, size_t lda, const E* T, size_t ld, E* y) const {
+    LIG_DISPATCH(field, rows_vaxpy_kernel, dim3((u32)((n + 63) / 64)), dim3(1024), (u32)nrows, n, T0, A, lda, T, ld, y);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  int quad_combo(lfgpu_ctx* c, size_t nt, size_t n, const E* Tq, const E* u, const E* X, const E* Y, const E* Z, size_t ld, E* y) const {
+    LIG_DISPATCH(field, quad_combo_kernel, dim3((u32)((n + 255) / 256)), dim3(256), (u32)nt, n, Tq, u, X, Y, Z, ld, y);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  // lfgpu_ligero_inner_product_rows promises its callers, who bring their own buffer, that the first r + w columns are cleared
+  int a_rows_clear(lfgpu_ctx* c, E* d_rows, size_t ld, size_t ncols, size_t nrows) const {
+    LF_HIP(c, hipMemset2DAsync(d_rows, ld * 16, 0, ncols * 16, nrows, c->stream));
+    return LFGPU_OK;
+  }
+  int a_rows_dense(lfgpu_ctx* c, size_t r, size_t w, size_t ld, const E& scale, const E* d_dense, size_t n, E* d_rows) const {
+    LIG_DISPATCH(field, a_rows_dense_kernel, dim3((u32)((n + 255) / 256)), dim3(256), (u32)r, (u32)w, ld, scale, d_dense, n, d_rows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  int a_rows_sparse(lfgpu_ctx* c, size_t r, size_t w, size_t ld, const uint64_t* h_idx, const E* h_val, size_t n, size_t nflat, E* d_rows) const {
+    void* d_sp = nullptr;
+    LF_TRY(lf_scratch2(c, n * 24 + 64, &d_sp));
+    E* d_val = (E*)d_sp;
+    u64* d_idx = (u64*)(d_val + n);
+    if (n * 24 <= LF_STAGE_SLOT) {  // one staged copy: values then indices
+      std::vector<uint8_t> pack(n * 24);
+      memcpy(pack.data(), h_val, n * 16);
+      memcpy(pack.data() + n * 16, h_idx, n * 8);
+      LF_TRY(lf_stage_upload(c, d_sp, pack.data(), pack.size()));
+    } else {
+      LF_HIP(c, hipMemcpyAsync(d_val, h_val, n * 16, hipMemcpyHostToDevice, c->stream));
+      LF_HIP(c, hipMemcpyAsync(d_idx, h_idx, n * 8, hipMemcpyHostToDevice, c->stream));
+      LF_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    LIG_DISPATCH(field, a_rows_sparse_kernel, dim3((u32)((n + 255) / 256)), dim3(256), (u32)r, (u32)w, ld, (const u64*)d_idx, (const E*)d_val, n, nflat, d_rows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  int gather_columns(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, const E* d_T, const size_t* h_idx, size_t nreq, E* d_req) const {
+    return lfgpu_gather_columns(c, nrow, ld, col0, d_T, h_idx, nreq, d_req);
+  }
+  int rs_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, E* d, size_t ld) const { return lf_rs_rows(c, field, k, nrow, n, m, d, ld); }
+  int column_leaves(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out) const {
+    return lfgpu_column_leaves(c, field, nrow, ld, col0, ncols, d_T, d_nonces, d_out);
+  }
+};
+static L16 policy16(const lfgpu_ligero_prover* pr) { return L16{pr->field, pr->k}; }
+
+// (the sharded commit stands below the policy: its steps 3 and 4 are lig::column_commit_sharded over L16)
+extern "C" int lfgpu_ligero_commit_sharded(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const void* h_W, size_t subfield_boundary,
+                                           const size_t* h_lqc, lfgpu_rng_fn rng, void* user, const lfgpu_comm_ops* cm, uint8_t root_out[32],
+                                           lfgpu_ligero_prover** out) {
+  if (!c || !pp || !root_out || !out || !comm_ok(cm) || (cm->rank == 0 && !rng) || (pp->nw && !h_W) || (pp->nq && !h_lqc))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: null argument / incomplete communicator");
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: field");
+  const lfgpu_ligero_param& p = *pp;
+  if (p.ildt != 0 || p.idot != 1 || p.iquad != 2 || p.iw != 3) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: row order");
+  LF_HIP(c, hipSetDevice(c->device));
+  const GfHostCtx* g = field == LFGPU_FIELD_GF2_128 ? lf_gf_ctx(c, k) : nullptr;
+  if (field == LFGPU_FIELD_GF2_128 && !g) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: k");
+  const int world = cm->world, rank = cm->rank;
+  lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
+  pr->c = c;
+  pr->field = field;
+  pr->k = k;
+  pr->p = p;
+  pr->d_T = nullptr;
+  pr->d_layers = nullptr;
+  pr->nonces.resize(p.block_ext * 32);
+  pr->sharded = true;
+  pr->comm = *cm;
+  pr->spans.resize(world);
+  for (int q = 0; q < world; ++q) (void)lfgpu_ligero_row_shard(&p, q, world, &pr->spans[q].first, &pr->spans[q].second);
+  pr->row_lo = pr->spans[rank].first;
+  pr->row_hi = pr->spans[rank].second;
+  auto fail = [&](int rc) {
+    lfgpu_ligero_free(pr);
+    return rc;
+  };
+  const size_t nr = pr->row_hi - pr->row_lo, ld = p.block_enc, ncols = p.block_ext;
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  const double tv0 = lig::clock_ms();
+  // 1. host layout of this rank's slab from the one random stream
+  std::vector<elt_t> H(std::max<size_t>(nr, 1) * p.dblock);
+  LF_SCRUB_ON_EXIT(H);
+  {
+    char err[256] = {0};
+    const int rc = layout_sharded_host(field, k, g, p, h_W, subfield_boundary, h_lqc, rng, user, cm, c->rng_exact != 0, pr->row_lo, pr->row_hi, H.data(),
+                                       pr->nonces.data(), err);
+    if (rc) return fail(lf_fail(c, rc, "%s", err));
+  }
+  const double tv1 = lig::clock_ms();
+  if (verbose) fprintf(stderr, "lfgpu ligero_commit_sharded rank %d/%d: rows [%zu, %zu): layout + stream %.2f ms\n", rank, world, pr->row_lo, pr->row_hi, tv1 - tv0);
+  // 2. RS-extend the slab: rows are independent, no collective
+  const size_t tb = std::max<size_t>(nr, 1) * ld * 16, lb = 2 * ncols * 32;
+  if (lf_pool_get(c, tb, (void**)&pr->d_T) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: slab alloc"));
+  pr->T_bytes = tb;
+  if (lf_pool_get(c, lb, (void**)&pr->d_layers) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: layers alloc"));
+  pr->L_bytes = lb;
+  int rc = nr ? ligero_encode_slab(c, field, k, p, pr->row_lo, pr->row_hi, H.data(), pr->d_T) : LFGPU_OK;
+  if (rc) return fail(rc);
+  // 3. + 4. the columns: all_to_all, local leaves, all_gather of the digests, the tree on every rank (it prints its own phases)
+  if ((rc = lig::column_commit_sharded(pr, policy16(pr), cm, tv1, root_out))) return fail(rc);
+  *out = pr;
+  return LFGPU_OK;
+}
+
 extern "C" int lfgpu_ligero_inner_product_rows(lfgpu_ctx* c, int field, size_t w, size_t r, size_t ld, size_t nrows, const void* d_dense,
                                                size_t ndense, const uint64_t scale[2], const uint64_t* h_idx, const void* h_val,
                                                size_t nsparse, void* d_rows) {
   if (!c || !d_rows || w == 0 || r + w > ld || (ndense && (!d_dense || !scale)) || (nsparse && (!h_idx || !h_val)) || ndense > nrows * w)
     return lf_fail(c, LFGPU_ERR_ARG, "ligero_inner_product_rows: bad argument");
   if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "ligero_inner_product_rows: field");
-  for (size_t t = 0; t < nsparse; ++t) {
-    if (h_idx[t] >= nrows * w) return lf_fail(c, LFGPU_ERR_ARG, "ligero_inner_product_rows: sparse index out of range");
-    if (t && h_idx[t] <= h_idx[t - 1]) return lf_fail(c, LFGPU_ERR_ARG, "ligero_inner_product_rows: sparse indices must be strictly increasing");
-  }
   LF_HIP(c, hipSetDevice(c->device));
-  LF_HIP(c, hipMemset2DAsync(d_rows, ld * 16, 0, (r + w) * 16, nrows, c->stream));
-  if (ndense) {
-    const elt_t sc{scale[0], scale[1]};
-    LIG_DISPATCH(field, a_rows_dense_kernel, dim3((u32)((ndense + 255) / 256)), dim3(256), (u32)r, (u32)w, ld, sc, (const elt_t*)d_dense, ndense,
-                 (elt_t*)d_rows);
-  }
-  if (nsparse) {
-    void* d_sp = nullptr;
-    LF_TRY(lf_scratch2(c, nsparse * 24 + 64, &d_sp));
-    elt_t* d_val = (elt_t*)d_sp;
-    u64* d_idx = (u64*)(d_val + nsparse);
-    if (nsparse * 24 <= LF_STAGE_SLOT) {  // one staged copy: values then indices
-      std::vector<uint8_t> pack(nsparse * 24);
-      memcpy(pack.data(), h_val, nsparse * 16);
-      memcpy(pack.data() + nsparse * 16, h_idx, nsparse * 8);
-      LF_TRY(lf_stage_upload(c, d_sp, pack.data(), pack.size()));
-    } else {
-      LF_HIP(c, hipMemcpyAsync(d_val, h_val, nsparse * 16, hipMemcpyHostToDevice, c->stream));
-      LF_HIP(c, hipMemcpyAsync(d_idx, h_idx, nsparse * 8, hipMemcpyHostToDevice, c->stream));
-      LF_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    LIG_DISPATCH(field, a_rows_sparse_kernel, dim3((u32)((nsparse + 255) / 256)), dim3(256), (u32)r, (u32)w, ld, (const u64*)d_idx,
-                 (const elt_t*)d_val, nsparse, nrows * w, (elt_t*)d_rows);
-  }
-  LF_HIP(c, hipGetLastError());
-  return LFGPU_OK;
+  const elt_t sc = scale ? elt_t{scale[0], scale[1]} : elt_t{0, 0};
+  return lig::a_rows(c, L16{field, 0}, w, r, ld, nrows, (const elt_t*)d_dense, ndense, sc, h_idx, (const elt_t*)h_val, nsparse, (elt_t*)d_rows);
 }
 
-// dot_proof once the rows [0^r | A_i | 0...] stand in dAext (lda = dblock; all nwqrow rows, of which the slab's are
-// used): extend, combine, read back
-static int dot_proof_finish(lfgpu_ligero_prover* pr, elt_t* dAext, elt_t* dy, void* h_y) {
-  lfgpu_ctx* c = pr->c;
-  const lfgpu_ligero_param& p = pr->p;
-  const size_t lda = p.dblock;
-  size_t a_lo, a_hi;
-  owned_wq_rows(pr, &a_lo, &a_hi);
-  const elt_t* T0 = nullptr;
-  if (pr->has(p.idot)) {
-    T0 = pr->row(p.idot);
-  } else {  // a zero row behind dy (the callers reserve 2 * dblock)
-    LF_HIP(c, hipMemsetAsync(dy + p.dblock, 0, p.dblock * 16, c->stream));
-    T0 = dy + p.dblock;
-  }
-  if (a_hi > a_lo) LF_TRY(lf_rs_rows(c, pr->field, pr->k, a_hi - a_lo, p.block, p.dblock, dAext + a_lo * lda, lda));
-  LIG_DISPATCH(pr->field, rows_vaxpy_kernel, dim3((u32)((p.dblock + 63) / 64)), dim3(1024), (u32)(a_hi - a_lo), p.dblock, T0,
-               (const elt_t*)(dAext + a_lo * lda), lda, (const elt_t*)(a_hi > a_lo ? pr->row(p.iw + a_lo) : pr->d_T), p.block_enc, dy);
-  LF_HIP(c, hipGetLastError());
-  LF_TRY(lfgpu_memcpy_d2h(c, h_y, dy, p.dblock * 16));
-  return pr->sharded ? comm_fold(pr, (elt_t*)h_y, p.dblock) : LFGPU_OK;
+extern "C" int lfgpu_ligero_low_degree_proof(lfgpu_ligero_prover* pr, const void* h_u, void* h_y) {
+  if (!pr || !h_u || !h_y) return LFGPU_ERR_ARG;
+  LF_HIP(pr->c, hipSetDevice(pr->c->device));
+  return lig::low_degree(pr, policy16(pr), (const elt_t*)h_u, (elt_t*)h_y);
 }
 
 extern "C" int lfgpu_ligero_dot_proof(lfgpu_ligero_prover* pr, const void* h_A, void* h_y) {
@@ -1182,69 +1049,22 @@ extern "C" int lfgpu_ligero_dot_proof(lfgpu_ligero_prover* pr, const void* h_A, 
   LF_HIP(c, hipMemsetAsync(dAext, 0, p.nwqrow * lda * 16, c->stream));
   hipLaunchKernelGGL(layout_aext_kernel, dim3((u32)((p.block + 255) / 256), (u32)p.nwqrow), dim3(256), 0, c->stream,
                      (u32)p.r, (u32)p.w, lda, (const elt_t*)dA, dAext);
-  return dot_proof_finish(pr, dAext, dy, h_y);
+  return lig::dot_finish(pr, policy16(pr), dAext, dy, (elt_t*)h_y);
 }
 
 extern "C" int lfgpu_ligero_dot_proof_sparse(lfgpu_ligero_prover* pr, const void* d_dense, size_t ndense, const uint64_t scale[2],
                                              const uint64_t* h_idx, const void* h_val, size_t nsparse, void* h_y) {
   if (!pr || !h_y) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = pr->c;
-  const lfgpu_ligero_param& p = pr->p;
-  LF_HIP(c, hipSetDevice(c->device));
-  const size_t lda = p.dblock;
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, (p.nwqrow * lda + 2 * p.dblock) * 16 + 64, &sc));
-  if (d_dense && ndense) {  // the dense block must not live in the scratch this call is about to overwrite
-    const uint8_t* lo = (const uint8_t*)sc;
-    const uint8_t* d = (const uint8_t*)d_dense;
-    if (d + ndense * 16 > lo && d < lo + (p.nwqrow * lda + 2 * p.dblock) * 16) return lf_fail(c, LFGPU_ERR_ARG, "ligero_dot_proof_sparse: dense block aliases scratch");
-  }
-  elt_t* dAext = (elt_t*)sc;
-  elt_t* dy = dAext + p.nwqrow * lda;
-  LF_HIP(c, hipMemsetAsync(dAext, 0, p.nwqrow * lda * 16, c->stream));
-  LF_TRY(lfgpu_ligero_inner_product_rows(c, pr->field, p.w, p.r, lda, p.nwqrow, d_dense, ndense, scale, h_idx, h_val, nsparse, dAext));
-  return dot_proof_finish(pr, dAext, dy, h_y);
+  if (ndense && !scale) return lf_fail(pr->c, LFGPU_ERR_ARG, "ligero_dot_proof_sparse: a dense block needs its scale");
+  LF_HIP(pr->c, hipSetDevice(pr->c->device));
+  const elt_t sc = scale ? elt_t{scale[0], scale[1]} : elt_t{0, 0};
+  return lig::dot(pr, policy16(pr), (const elt_t*)d_dense, ndense, sc, h_idx, (const elt_t*)h_val, nsparse, (elt_t*)h_y);
 }
 
 extern "C" int lfgpu_ligero_quadratic_proof(lfgpu_ligero_prover* pr, const void* h_u_quad, void* h_y0, void* h_y2) {
   if (!pr || !h_y0 || !h_y2 || (pr->p.nqtriples && !h_u_quad)) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = pr->c;
-  const lfgpu_ligero_param& p = pr->p;
-  LF_HIP(c, hipSetDevice(c->device));
-  // a triple (x_i, y_i, z_i) is multiplied element-wise, so a slab must hold all quadratic rows or none of them
-  const size_t q_lo = p.iq, q_hi = p.iq + 3 * p.nqtriples;
-  const bool all_q = p.nqtriples == 0 || (pr->row_lo <= q_lo && q_hi <= pr->row_hi);
-  const bool no_q = pr->row_hi <= q_lo || pr->row_lo >= q_hi;
-  if (!all_q && !no_q) return lf_fail(c, LFGPU_ERR_ARG, "quadratic_proof: the slab splits the quadratic rows (shard so that one rank holds [iq, nrow))");
-  const size_t nt = all_q ? p.nqtriples : 0;
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, (p.nqtriples + 2 * p.dblock) * 16 + 64, &sc));
-  elt_t* du = (elt_t*)sc;
-  elt_t* dy = du + p.nqtriples + 1;
-  elt_t* dz = dy + p.dblock;
-  if (nt) LF_HIP(c, hipMemcpyAsync(du, h_u_quad, p.nqtriples * 16, hipMemcpyHostToDevice, c->stream));
-  const size_t ld = p.block_enc;
-  const elt_t* Tq = nullptr;
-  if (pr->has(p.iquad)) {
-    Tq = pr->row(p.iquad);
-  } else {
-    LF_HIP(c, hipMemsetAsync(dz, 0, p.dblock * 16, c->stream));
-    Tq = dz;
-  }
-  const elt_t* X = nt ? pr->row(p.iq) : pr->d_T;
-  const elt_t* Y = X + p.nqtriples * ld;
-  const elt_t* Z = Y + p.nqtriples * ld;
-  LIG_DISPATCH(pr->field, quad_combo_kernel, dim3((u32)((p.dblock + 255) / 256)), dim3(256), (u32)nt, p.dblock, Tq, (const elt_t*)du, X, Y, Z, ld, dy);
-  LF_HIP(c, hipGetLastError());
-  std::vector<elt_t> y(p.dblock);
-  LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, p.dblock * 16));
-  if (pr->sharded) LF_TRY(comm_fold(pr, y.data(), p.dblock));
-  if (pr->sharded || (pr->row_lo == 0 && pr->row_hi == p.nrow))  // sanity check of the reference (:335-337); a bare slab's partial sums are checked by its caller after the fold
-    for (size_t j = 0; j < p.w; ++j)
-      if (y[p.r + j].lo | y[p.r + j].hi) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero");
-  memcpy(h_y0, y.data(), p.r * 16);
-  memcpy(h_y2, y.data() + p.block, (p.dblock - p.block) * 16);
-  return LFGPU_OK;
+  LF_HIP(pr->c, hipSetDevice(pr->c->device));
+  return lig::quadratic(pr, policy16(pr), (const elt_t*)h_u_quad, (elt_t*)h_y0, (elt_t*)h_y2);
 }
 
 // a prover over rows [row_lo, row_hi) that the caller has laid out and encoded (lfgpu_ligero_encode_rows) in d_slab;
@@ -1272,35 +1092,7 @@ extern "C" int lfgpu_ligero_prover_from_slab(lfgpu_ctx* c, int field, int k, con
 extern "C" int lfgpu_ligero_open(lfgpu_ligero_prover* pr, const size_t* idx, void* h_req, uint8_t* h_nonces,
                                  uint8_t* h_path, size_t path_cap, size_t* npath) {
   if (!pr || !idx || !h_req || !h_nonces || !npath) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = pr->c;
-  const lfgpu_ligero_param& p = pr->p;
-  for (size_t i = 0; i < p.nreq; ++i)
-    if (idx[i] >= p.block_ext) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open: index out of range");
-  if (pr->nonces.size() != 32 * p.block_ext || !pr->d_layers) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open: this prover holds no commitment");
-  // a slab returns its own rows of req ((row_hi - row_lo) x nreq, in row order); a sharded prover gathers every rank's rows
-  const size_t nr = pr->row_hi - pr->row_lo;
-  std::vector<uint8_t> mine;
-  size_t maxr = nr;
-  if (pr->sharded) {
-    for (const auto& sp : pr->spans) maxr = std::max(maxr, sp.second - sp.first);
-    mine.assign(maxr * p.nreq * 16, 0);
-  }
-  void* h_dst = pr->sharded ? (void*)mine.data() : h_req;
-  if (nr) {
-    void* dreq = nullptr;
-    LF_TRY(lf_scratch3(c, nr * p.nreq * 16, &dreq));
-    LF_TRY(lfgpu_gather_columns(c, nr, p.block_enc, p.dblock, pr->d_T, idx, p.nreq, dreq));
-    LF_TRY(lfgpu_memcpy_d2h(c, h_dst, dreq, nr * p.nreq * 16));
-  }
-  if (pr->sharded) {
-    const lfgpu_comm_ops& cm = pr->comm;
-    std::vector<uint8_t> all((size_t)cm.world * mine.size());
-    if (cm.all_gather(cm.user, mine.data(), all.data(), mine.size(), 0, nullptr)) return lf_fail(c, LFGPU_ERR_HIP, "ligero_open (sharded): all_gather hook failed");
-    for (int q = 0; q < cm.world; ++q)
-      memcpy((uint8_t*)h_req + pr->spans[q].first * p.nreq * 16, all.data() + (size_t)q * mine.size(), (pr->spans[q].second - pr->spans[q].first) * p.nreq * 16);
-  }
-  for (size_t i = 0; i < p.nreq; ++i) memcpy(h_nonces + 32 * i, &pr->nonces[32 * idx[i]], 32);
-  return lfgpu_merkle_open(c, p.block_ext, pr->d_layers, idx, p.nreq, h_path, path_cap, npath);
+  return lig::open(pr, policy16(pr), idx, (elt_t*)h_req, h_nonces, h_path, path_cap, npath);
 }
 
 // ------------------------------------------------------------------ LigeroProver::prove for nb committed provers of one shape

@@ -1,0 +1,349 @@
+// ligero_slab.h -- the prover that holds a slab of a Ligero tableau, and its prove-side calls, written once over a width policy L.
+//
+// ligero.hip (GF(2^128) and Fp128, 16-byte elements) and zk256.hip (Fp256Base, 32-byte elements) each supply a policy and
+// instantiate what is here.  Reference: LigeroProver::low_degree_proof / dot_proof / quadratic_proof / compute_req
+// (lib/ligero/ligero_prover.h:281-351), inner_product_vector + layout_Aext (lib/ligero/ligero_param.h:382-430), MerkleCommitment
+// (lib/merkle/merkle_commitment.h:50-73).
+//
+// A policy is a plain struct with no virtual calls.  It supplies the element type E, the host add / is_zero, and
+// the device steps the bodies call; each step uploads its own host vectors the way its width always has (and synchronises where
+// it always has), so nothing below tests which width it serves:
+//   rows_axpy      y[j] += sum_i u[i] T[i][j], u on the host
+//   rows_vaxpy     y[j] = T0[j] + sum_i A[i][j] T[i][j]
+//   quad_combo     y[j] = Tq[j] + sum_i u[i] (Z_i[j] - X_i[j] Y_i[j])
+//   a_rows_clear / a_rows_dense / a_rows_sparse   the pieces of a_rows below; the sparse lists are on the host
+//   gather_columns req[i][j] = T[i][col0 + idx[j]], idx on the host
+//   rs_rows        nrow rows of n values extended to m, in place
+//   column_leaves  the leaf digests of ncols columns
+// What differs by design stays in the two files: the host layouts (the order and batching of the RandomEngine draws), the
+// one-GPU commit bodies, the Reed-Solomon encoding of a fresh tableau, the batched entry points (16-byte only) and every kernel.
+#pragma once
+#include <algorithm>
+#include <chrono>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <utility>
+#include <vector>
+
+#include "ctx.h"
+
+// Everything below has internal linkage (as in zk_proto.h): each file that includes this header wants its own copy.
+namespace lig {
+namespace {
+template <class E>
+struct Slab {
+  lfgpu_ctx* c = nullptr;
+  lfgpu_ligero_param p{};
+  E* d_T = nullptr;             // [row_hi - row_lo][block_enc]
+  uint8_t* d_layers = nullptr;  // [2*block_ext][32]
+  size_t T_bytes = 0, L_bytes = 0;
+  std::vector<uint8_t> nonces;  // block_ext * 32 (host copy for open)
+  // rows [row_lo, row_hi) of the tableau live in d_T (a slab of a multi-GPU commit; [0, nrow) on one GPU).  The prove
+  // functions then return this slab's PARTIAL sums (rows it does not hold contribute zero); the caller folds the ranks.
+  size_t row_lo = 0, row_hi = 0;
+  bool owns = true;  // d_T / d_layers go back to the pool with the prover
+  // a prover of a sharded commit: the prove functions fold the ranks' partial results through these hooks
+  bool sharded = false;
+  lfgpu_comm_ops comm{};
+  std::vector<std::pair<size_t, size_t>> spans;  // row slab of every rank
+  bool has(size_t i) const { return i >= row_lo && i < row_hi; }
+  E* row(size_t i) const { return d_T + (i - row_lo) * p.block_enc; }
+  Slab() = default;
+  Slab(const Slab&) = delete;
+  Slab& operator=(const Slab&) = delete;
+  ~Slab() {
+    // keep the buffers for the next commit of the same shape (the context's pool: a hipFree per proof would wait for every
+    // stream of the device); the stream is in order, so work still queued on them finishes before anything a later commit enqueues
+    auto stash = [&](void* d, size_t bytes) {
+      if (!d) return;
+      // the tableau holds the witness, the pads and the blinding rows: scrub it before it outlives its prover (enqueued on the
+      // stream, in order behind the prover's last kernels)
+      if (bytes) (void)hipMemsetAsync(d, 0, bytes, c ? c->stream : nullptr);
+      if (c && bytes) lf_pool_put(c, d, bytes);
+      else (void)hipFree(d);
+    };
+    if (!owns) return;
+    stash(d_T, T_bytes);
+    stash(d_layers, L_bytes);
+  }
+};
+
+inline double clock_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+
+inline void shard_split(size_t n, int rank, int world, size_t* start, size_t* count) {  // contiguous, sizes differ by at most 1
+  const size_t base = n / (size_t)world, rem = n % (size_t)world, r = (size_t)rank;
+  *start = r * base + std::min(r, rem);
+  *count = base + (r < rem ? 1 : 0);
+}
+
+// field sum over the ranks of a host vector every rank holds a partial of (RCCL has no XOR / mod-p reduction: all_gather + fold);
+// nothing to do for a prover that is not sharded
+template <class L>
+int comm_fold(const Slab<typename L::E>* pr, const L& pol, typename L::E* y, size_t n) {
+  using E = typename L::E;
+  const lfgpu_comm_ops& cm = pr->comm;
+  if (!pr->sharded || cm.world == 1) return LFGPU_OK;
+  std::vector<E> all((size_t)cm.world * n);
+  LF_SCRUB_ON_EXIT(all);  // the ranks' partial sums are not part of the proof; only their fold is
+  if (cm.all_gather(cm.user, y, all.data(), n * sizeof(E), 0, nullptr)) return lf_fail(pr->c, LFGPU_ERR_HIP, "ligero (sharded): all_gather hook failed");
+  for (size_t j = 0; j < n; ++j) y[j] = all[j];
+  for (int q = 1; q < cm.world; ++q)
+    for (size_t j = 0; j < n; ++j) y[j] = pol.add(y[j], all[(size_t)q * n + j]);
+  return LFGPU_OK;
+}
+
+// witness / quadratic rows [a_lo, a_hi) (indices relative to iw) that this prover's slab holds
+template <class E>
+void owned_wq_rows(const Slab<E>* pr, size_t* a_lo, size_t* a_hi) {
+  const lfgpu_ligero_param& p = pr->p;
+  const size_t lo = std::min(std::max(pr->row_lo, p.iw), p.iw + p.nwqrow), hi = std::min(std::max(pr->row_hi, p.iw), p.iw + p.nwqrow);
+  *a_lo = lo - p.iw;
+  *a_hi = std::max(hi, lo) - p.iw;
+}
+
+// low_degree_proof (:281-291)
+template <class L>
+int low_degree(Slab<typename L::E>* pr, const L& pol, const typename L::E* u, typename L::E* y) {
+  using E = typename L::E;
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  void* dy = nullptr;
+  LF_TRY(lf_scratch3(c, p.block * sizeof(E), &dy));
+  if (pr->has(p.ildt))
+    LF_HIP(c, hipMemcpyAsync(dy, pr->row(p.ildt), p.block * sizeof(E), hipMemcpyDeviceToDevice, c->stream));
+  else
+    LF_HIP(c, hipMemsetAsync(dy, 0, p.block * sizeof(E), c->stream));
+  size_t a_lo, a_hi;
+  owned_wq_rows(pr, &a_lo, &a_hi);
+  if (a_hi > a_lo) LF_TRY(pol.rows_axpy(c, a_hi - a_lo, p.block, (E*)dy, u + a_lo, pr->row(p.iw + a_lo), p.block_enc));
+  LF_TRY(lfgpu_memcpy_d2h(c, y, dy, p.block * sizeof(E)));
+  return comm_fold(pr, pol, y, p.block);
+}
+
+// ---- the inner-product matrix built on the device (inner_product_vector + layout_Aext, ligero_param.h:382-430)
+// rows[i][r + j] = scale * dense[i*w + j] over the first ndense flat positions (the private-input block of the last
+// constraint), then rows[pos(idx)] += val for the caller's sparse terms.  The sparse kernels read, add and write without
+// atomics, so the indices must be strictly increasing (duplicates already folded by the caller) and in range.
+template <class L>
+int a_rows(lfgpu_ctx* c, const L& pol, size_t w, size_t r, size_t ld, size_t nrows, const typename L::E* d_dense, size_t ndense,
+           const typename L::E& scale, const uint64_t* h_idx, const typename L::E* h_val, size_t nsparse, typename L::E* d_rows) {
+  if (ndense > nrows * w || (ndense && !d_dense) || (nsparse && (!h_idx || !h_val))) return lf_fail(c, LFGPU_ERR_ARG, "ligero inner-product rows: bad argument");
+  for (size_t t = 0; t < nsparse; ++t) {
+    if (h_idx[t] >= nrows * w) return lf_fail(c, LFGPU_ERR_ARG, "ligero inner-product rows: sparse index out of range");
+    if (t && h_idx[t] <= h_idx[t - 1]) return lf_fail(c, LFGPU_ERR_ARG, "ligero inner-product rows: sparse indices must be strictly increasing");
+  }
+  LF_TRY(pol.a_rows_clear(c, d_rows, ld, r + w, nrows));
+  if (ndense) LF_TRY(pol.a_rows_dense(c, r, w, ld, scale, d_dense, ndense, d_rows));
+  if (nsparse) LF_TRY(pol.a_rows_sparse(c, r, w, ld, h_idx, h_val, nsparse, nrows * w, d_rows));
+  return LFGPU_OK;
+}
+
+// dot_proof (:293-309) once the rows [0^r | A_i | 0...] stand in dAext (lda = dblock; all nwqrow rows, of which the slab's are
+// used; a spare row of dblock elements behind dy): extend, combine, read back
+template <class L>
+int dot_finish(Slab<typename L::E>* pr, const L& pol, typename L::E* dAext, typename L::E* dy, typename L::E* y) {
+  using E = typename L::E;
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  const size_t lda = p.dblock;
+  size_t a_lo, a_hi;
+  owned_wq_rows(pr, &a_lo, &a_hi);
+  const E* T0 = nullptr;
+  if (pr->has(p.idot)) {
+    T0 = pr->row(p.idot);
+  } else {  // a zero row behind dy
+    LF_HIP(c, hipMemsetAsync(dy + p.dblock, 0, p.dblock * sizeof(E), c->stream));
+    T0 = dy + p.dblock;
+  }
+  if (a_hi > a_lo) LF_TRY(pol.rs_rows(c, a_hi - a_lo, p.block, p.dblock, dAext + a_lo * lda, lda));
+  LF_TRY(pol.rows_vaxpy(c, a_hi - a_lo, p.dblock, T0, dAext + a_lo * lda, lda, a_hi > a_lo ? pr->row(p.iw + a_lo) : pr->d_T, p.block_enc, dy));
+  LF_TRY(lfgpu_memcpy_d2h(c, y, dy, p.dblock * sizeof(E)));
+  return comm_fold(pr, pol, y, p.dblock);
+}
+// ... with A given as inner_product_vector builds it: scale * dense[0..ndense) over the first flat positions plus the sparse terms
+template <class L>
+int dot(Slab<typename L::E>* pr, const L& pol, const typename L::E* d_dense, size_t ndense, const typename L::E& scale, const uint64_t* h_idx,
+        const typename L::E* h_val, size_t nsparse, typename L::E* y) {
+  using E = typename L::E;
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  const size_t lda = p.dblock, bytes = (p.nwqrow * lda + 2 * p.dblock) * sizeof(E);
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, bytes + 64, &sc));
+  if (d_dense && ndense) {  // the dense block must not live in the scratch this call is about to overwrite
+    const uint8_t* lo = (const uint8_t*)sc;
+    const uint8_t* d = (const uint8_t*)d_dense;
+    if (d + ndense * sizeof(E) > lo && d < lo + bytes) return lf_fail(c, LFGPU_ERR_ARG, "ligero dot proof: dense block aliases scratch");
+  }
+  E* dAext = (E*)sc;
+  LF_HIP(c, hipMemsetAsync(dAext, 0, p.nwqrow * lda * sizeof(E), c->stream));
+  LF_TRY(a_rows(c, pol, p.w, p.r, lda, p.nwqrow, d_dense, ndense, scale, h_idx, h_val, nsparse, dAext));
+  return dot_finish(pr, pol, dAext, dAext + p.nwqrow * lda, y);
+}
+
+// quadratic_proof (:311-344)
+template <class L>
+int quadratic(Slab<typename L::E>* pr, const L& pol, const typename L::E* u, typename L::E* y0, typename L::E* y2) {
+  using E = typename L::E;
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  // a triple (x_i, y_i, z_i) is multiplied element-wise, so a slab must hold all quadratic rows or none of them
+  const size_t q_lo = p.iq, q_hi = p.iq + 3 * p.nqtriples;
+  const bool all_q = p.nqtriples == 0 || (pr->row_lo <= q_lo && q_hi <= pr->row_hi);
+  const bool no_q = pr->row_hi <= q_lo || pr->row_lo >= q_hi;
+  if (!all_q && !no_q) return lf_fail(c, LFGPU_ERR_ARG, "quadratic_proof: the slab splits the quadratic rows (shard so that one rank holds [iq, nrow))");
+  const size_t nt = all_q ? p.nqtriples : 0;
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, (p.nqtriples + 1 + 2 * p.dblock) * sizeof(E) + 64, &sc));
+  E* du = (E*)sc;
+  E* dy = du + p.nqtriples + 1;
+  E* dz = dy + p.dblock;
+  if (nt) LF_HIP(c, hipMemcpyAsync(du, u, p.nqtriples * sizeof(E), hipMemcpyHostToDevice, c->stream));
+  const size_t ld = p.block_enc;
+  const E* Tq = nullptr;
+  if (pr->has(p.iquad)) {
+    Tq = pr->row(p.iquad);
+  } else {
+    LF_HIP(c, hipMemsetAsync(dz, 0, p.dblock * sizeof(E), c->stream));
+    Tq = dz;
+  }
+  const E* X = nt ? pr->row(p.iq) : pr->d_T;
+  const E* Y = X + p.nqtriples * ld;
+  const E* Z = Y + p.nqtriples * ld;
+  LF_TRY(pol.quad_combo(c, nt, p.dblock, Tq, du, X, Y, Z, ld, dy));
+  std::vector<E> y(p.dblock);
+  LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, p.dblock * sizeof(E)));
+  LF_TRY(comm_fold(pr, pol, y.data(), p.dblock));
+  if (pr->sharded || (pr->row_lo == 0 && pr->row_hi == p.nrow))  // sanity check of the reference (:335-337); a bare slab's partial sums are checked by its caller after the fold
+    for (size_t j = 0; j < p.w; ++j)
+      if (!pol.is_zero(y[p.r + j])) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero");
+  memcpy(y0, y.data(), p.r * sizeof(E));
+  memcpy(y2, y.data() + p.block, (p.dblock - p.block) * sizeof(E));
+  return LFGPU_OK;
+}
+
+// compute_req + MerkleCommitment::open
+template <class L>
+int open(Slab<typename L::E>* pr, const L& pol, const size_t* idx, typename L::E* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath) {
+  using E = typename L::E;
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  for (size_t i = 0; i < p.nreq; ++i)
+    if (idx[i] >= p.block_ext) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open: index out of range");
+  if (pr->nonces.size() != 32 * p.block_ext || !pr->d_layers) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open: this prover holds no commitment");
+  // a slab returns its own rows of req ((row_hi - row_lo) x nreq, in row order); a sharded prover gathers every rank's rows
+  const size_t nr = pr->row_hi - pr->row_lo;
+  std::vector<uint8_t> mine;  // padded to the largest slab for the all_gather
+  size_t maxr = nr;
+  if (pr->sharded) {
+    for (const auto& sp : pr->spans) maxr = std::max(maxr, sp.second - sp.first);
+    mine.assign(maxr * p.nreq * sizeof(E), 0);
+  }
+  void* h_dst = pr->sharded ? (void*)mine.data() : (void*)h_req;
+  if (nr) {
+    void* dreq = nullptr;
+    LF_TRY(lf_scratch3(c, nr * p.nreq * sizeof(E), &dreq));
+    LF_TRY(pol.gather_columns(c, nr, p.block_enc, p.dblock, pr->d_T, idx, p.nreq, (E*)dreq));
+    LF_TRY(lfgpu_memcpy_d2h(c, h_dst, dreq, nr * p.nreq * sizeof(E)));
+  }
+  if (pr->sharded) {
+    const lfgpu_comm_ops& cm = pr->comm;
+    std::vector<uint8_t> all((size_t)cm.world * mine.size());
+    if (cm.all_gather(cm.user, mine.data(), all.data(), mine.size(), 0, nullptr)) return lf_fail(c, LFGPU_ERR_HIP, "ligero_open (sharded): all_gather hook failed");
+    for (int q = 0; q < cm.world; ++q)
+      memcpy((uint8_t*)h_req + pr->spans[q].first * p.nreq * sizeof(E), all.data() + (size_t)q * mine.size(),
+             (pr->spans[q].second - pr->spans[q].first) * p.nreq * sizeof(E));
+  }
+  for (size_t i = 0; i < p.nreq; ++i) memcpy(h_nonces + 32 * i, &pr->nonces[32 * idx[i]], 32);
+  return lfgpu_merkle_open(c, p.block_ext, pr->d_layers, idx, p.nreq, h_path, path_cap, npath);
+}
+
+// The column commitment of a sharded prover whose slab stands encoded in d_T (spans, row_lo / row_hi, nonces and d_layers set).
+// A leaf hashes ALL rows of one column: one all_to_all re-partitions the encoded columns [dblock, block_enc) so that this rank
+// owns columns [mc0, mc0 + mcn) of every row; then local leaves, an all_gather of the digests and the tree on every rank
+// (lfgpu_merkle_build_tree ends with a stream synchronise).  Byte-oriented: only the element size and the leaf hash are the policy's.
+// t_begin: clock_ms() when the caller began to upload and encode the slab, for the LFGPU_VERBOSE phase line.
+template <class L>
+int column_commit_sharded(Slab<typename L::E>* pr, const L& pol, const lfgpu_comm_ops* cm, double t_begin, uint8_t root_out[32]) {
+  constexpr size_t esz = sizeof(typename L::E);
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  const int world = cm->world, rank = cm->rank;
+  const size_t nr = pr->row_hi - pr->row_lo, ld = p.block_enc, ncols = p.block_ext;
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  double tv2 = t_begin;
+  void* d_send = nullptr;
+  void* d_cols = nullptr;
+  size_t send_bytes_tot = 0, cols_bytes = 0;
+  // the exchange buffers hold encoded rows of the tableau (witness, pads, blinding rows): scrubbed like the tableau itself
+  // (~Slab) before they go back to the pool, in stream order behind their last use
+  auto retire = [&](void*& d, size_t bytes) {
+    if (!d) return;
+    (void)hipMemsetAsync(d, 0, bytes, c->stream);
+    lf_pool_put(c, d, bytes);
+    d = nullptr;
+  };
+  auto done = [&](int rc) {
+    retire(d_send, send_bytes_tot);
+    retire(d_cols, cols_bytes);
+    return rc;
+  };
+  // Send block for rank q: my rows x its columns, contiguous.
+  std::vector<size_t> soff(world), sbytes(world), roff(world), rbytes(world);
+  size_t mc0 = 0, mcn = 0;
+  shard_split(ncols, rank, world, &mc0, &mcn);
+  for (int q = 0; q < world; ++q) {
+    size_t c0, cn;
+    shard_split(ncols, q, world, &c0, &cn);
+    soff[q] = send_bytes_tot;
+    sbytes[q] = nr * cn * esz;
+    send_bytes_tot += sbytes[q];
+    roff[q] = pr->spans[q].first * mcn * esz;  // slabs are contiguous and ascending: the received blocks ARE the column matrix
+    rbytes[q] = (pr->spans[q].second - pr->spans[q].first) * mcn * esz;
+  }
+  cols_bytes = std::max<size_t>(p.nrow * mcn * esz, esz);
+  send_bytes_tot = std::max<size_t>(send_bytes_tot, esz);
+  if (lf_pool_get(c, send_bytes_tot, &d_send) != LFGPU_OK || lf_pool_get(c, cols_bytes, &d_cols) != LFGPU_OK)
+    return done(lf_fail(c, LFGPU_ERR_NOMEM, "ligero (sharded): exchange buffers"));
+  for (int q = 0; q < world && nr; ++q) {
+    size_t c0, cn;
+    shard_split(ncols, q, world, &c0, &cn);
+    if (cn && hipMemcpy2DAsync((uint8_t*)d_send + soff[q], cn * esz, pr->d_T + p.dblock + c0, ld * esz, cn * esz, nr, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+      return done(lf_fail(c, LFGPU_ERR_HIP, "ligero (sharded): pack"));
+  }
+  if (verbose) {
+    (void)hipStreamSynchronize(c->stream);
+    tv2 = clock_ms();
+  }
+  if (cm->all_to_all(cm->user, d_send, soff.data(), sbytes.data(), d_cols, roff.data(), rbytes.data(), 1, c->stream))
+    return done(lf_fail(c, LFGPU_ERR_HIP, "ligero (sharded): all_to_all hook failed"));
+  const double tv3 = clock_ms();
+  // local leaves of my columns, all_gather of the digests (ragged: padded to the largest share), the tree on every rank
+  size_t maxn = 0, dummy = 0;
+  shard_split(ncols, 0, world, &dummy, &maxn);
+  void* d_non = nullptr;
+  int rc = lf_scratch3(c, ncols * 32 + (size_t)(world + 1) * maxn * 32 + 64, &d_non);
+  if (rc) return done(rc);
+  uint8_t* d_mine = (uint8_t*)d_non + ncols * 32;
+  uint8_t* d_all = d_mine + maxn * 32;
+  if (hipMemcpyAsync(d_non, pr->nonces.data(), ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess ||
+      hipMemsetAsync(d_mine, 0, maxn * 32, c->stream) != hipSuccess)
+    return done(lf_fail(c, LFGPU_ERR_HIP, "ligero (sharded): nonce upload"));
+  if (mcn && (rc = pol.column_leaves(c, p.nrow, mcn, 0, mcn, d_cols, (const uint8_t*)d_non + mc0 * 32, d_mine))) return done(rc);
+  if (cm->all_gather(cm->user, d_mine, d_all, maxn * 32, 1, c->stream)) return done(lf_fail(c, LFGPU_ERR_HIP, "ligero (sharded): all_gather hook failed"));
+  if (hipMemsetAsync(pr->d_layers, 0, ncols * 32, c->stream) != hipSuccess) return done(lf_fail(c, LFGPU_ERR_HIP, "ligero (sharded): layers"));
+  for (int q = 0; q < world; ++q) {
+    size_t c0, cn;
+    shard_split(ncols, q, world, &c0, &cn);
+    if (cn && hipMemcpyAsync(pr->d_layers + (ncols + c0) * 32, d_all + (size_t)q * maxn * 32, cn * 32, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+      return done(lf_fail(c, LFGPU_ERR_HIP, "ligero (sharded): leaves"));
+  }
+  if ((rc = lfgpu_merkle_build_tree(c, ncols, pr->d_layers, root_out))) return done(rc);
+  if (verbose)
+    fprintf(stderr, "lfgpu ligero column commit (sharded) rank %d/%d: rows [%zu, %zu) of %zu-byte elements: upload + RS encode + pack %.2f ms | all_to_all %.2f | leaves + all_gather + tree %.2f\n",
+            rank, world, pr->row_lo, pr->row_hi, esz, tv2 - t_begin, tv3 - tv2, clock_ms() - tv3);
+  return done(LFGPU_OK);
+}
+}  // namespace
+}  // namespace lig

@@ -21,6 +21,7 @@
 #include <memory>
 #include <string>
 
+#include "ligero_slab.h"  // the Ligero prover record and its prove side, over the policy L32 below
 #include "zk_proto.h"  // F256 (the host field), the protocol layer and Wire32
 
 typedef elt32_t E;
@@ -1422,31 +1423,66 @@ int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail
 
 // ------------------------------------------------------------------ Ligero over 32-byte elements (one GPU holds all rows)
 namespace {
-struct Lig256 {
-  lfgpu_ctx* c = nullptr;
-  lfgpu_ligero_param p{};
-  E* d_T = nullptr;  // [nrow][block_enc]
-  uint8_t* d_layers = nullptr;
-  std::vector<uint8_t> nonces;
-  // rows [row_lo, row_hi) live in d_T: all of them on one GPU, a slab with a communicator (lfgpu_zk_prover_set_comm above the
-  // size threshold): the prove functions then fold the ranks' partial vectors with the field's addition, as ligero.hip does
-  size_t row_lo = 0, row_hi = 0;
-  bool sharded = false;
-  lfgpu_comm_ops comm{};
-  std::vector<std::pair<size_t, size_t>> spans;
-  bool has(size_t i) const { return i >= row_lo && i < row_hi; }
-  E* row(size_t i) const { return d_T + (i - row_lo) * p.block_enc; }
-  size_t slab_bytes() const { return std::max<size_t>(row_hi - row_lo, 1) * p.block_enc * 32; }
-  ~Lig256() {
-    if (d_T) {  // the tableau holds the witness, the pads and the blinding rows: scrub it (enqueued in order behind the prover's
-                // last kernels), then keep the buffer for the next commit of this shape: a hipFree per proof would wait for every
-                // stream of the device (ctx.h, lf_pool_put)
-      (void)hipMemsetAsync(d_T, 0, slab_bytes(), c->stream);
-      lf_pool_put(c, d_T, slab_bytes());
-    }
-    if (d_layers) lf_pool_put(c, d_layers, 2 * p.block_ext * 32);
+// The width policy of ligero_slab.h for Fp256Base: the row kernels above, lfgpu_fp256_rs_encode_rows and lf_column_leaves32.  The
+// prover is bound by a latency chain of short launches, so these steps only enqueue: host vectors go to lf_scratch2
+// by plain asynchronous copies, and whoever reads the result back synchronises.  The one exception is a_rows_sparse.
+struct L32 {
+  using E = elt32_t;
+  static E add(const E& a, const E& b) { return fp256_add(a, b); }
+  static bool is_zero(const E& a) { return e32_is_zero(a); }
+  static int rows_axpy(lfgpu_ctx* c, size_t nrows, size_t n, E* d_y, const E* h_u, const E* d_T, size_t ld) {
+    void* du = nullptr;
+    LF_TRY(lf_scratch2(c, nrows * 32 + 64, &du));
+    LF_HIP(c, hipMemcpyAsync(du, h_u, nrows * 32, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(rows_axpy256_kernel, dim3(nblk(n, 64)), dim3(256), 0, c->stream, (u32)nrows, n, d_y, (const E*)du, d_T, ld);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  static int rows_vaxpy(lfgpu_ctx* c, size_t nrows, size_t n, const E* T0, const E* A, size_t lda, const E* T, size_t ld, E* y) {
+    hipLaunchKernelGGL(rows_vaxpy256_kernel, dim3(nblk(n, 64)), dim3(256), 0, c->stream, (u32)nrows, n, T0, A, lda, T, ld, y);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  static int quad_combo(lfgpu_ctx* c, size_t nt, size_t n, const E* Tq, const E* u, const E* X, const E* Y, const E* Zr, size_t ld, E* y) {
+    hipLaunchKernelGGL(quad_combo256_kernel, dim3(nblk(n)), dim3(Z_THREADS), 0, c->stream, (u32)nt, n, Tq, u, X, Y, Zr, ld, y);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  static int a_rows_clear(lfgpu_ctx*, E*, size_t, size_t, size_t) { return LFGPU_OK; }  // both callers clear the whole matrix themselves
+  static int a_rows_dense(lfgpu_ctx* c, size_t r, size_t w, size_t ld, const E& scale, const E* d_dense, size_t n, E* d_rows) {
+    hipLaunchKernelGGL(a_rows_dense256_kernel, dim3(nblk(n)), dim3(Z_THREADS), 0, c->stream, (u32)r, (u32)w, ld, scale, d_dense, n, d_rows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  // (a_rows_sparse256_kernel has no bound on idx: lig::a_rows has checked the list against nflat on the host)
+  static int a_rows_sparse(lfgpu_ctx* c, size_t r, size_t w, size_t ld, const uint64_t* h_idx, const E* h_val, size_t n, size_t /*nflat*/, E* d_rows) {
+    void* d_sp = nullptr;
+    LF_TRY(lf_scratch2(c, n * 40 + 64, &d_sp));
+    E* d_val = (E*)d_sp;
+    u64* d_idx = (u64*)(d_val + n);
+    LF_HIP(c, hipMemcpyAsync(d_val, h_val, n * 32, hipMemcpyHostToDevice, c->stream));
+    LF_HIP(c, hipMemcpyAsync(d_idx, h_idx, n * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(a_rows_sparse256_kernel, dim3(nblk(n)), dim3(Z_THREADS), 0, c->stream, (u32)r, (u32)w, ld, (const u64*)d_idx, (const E*)d_val, n, d_rows);
+    LF_HIP(c, hipGetLastError());
+    LF_HIP(c, hipStreamSynchronize(c->stream));  // the staging area is the Reed-Solomon encoder's work space next
+    return LFGPU_OK;
+  }
+  // h_idx is the caller's array and outlives the read-back that follows
+  static int gather_columns(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, const E* d_T, const size_t* h_idx, size_t nreq, E* d_req) {
+    static_assert(sizeof(size_t) == sizeof(u64), "the kernel reads the indices as u64");
+    void* di = nullptr;
+    LF_TRY(lf_scratch2(c, nreq * 8 + 64, &di));
+    LF_HIP(c, hipMemcpyAsync(di, h_idx, nreq * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(gather_columns256_kernel, dim3(nblk(nrow * nreq)), dim3(Z_THREADS), 0, c->stream, (u32)nrow, ld, col0, d_T, (const u64*)di, (u32)nreq, d_req);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  static int rs_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, E* d, size_t ld) { return lfgpu_fp256_rs_encode_rows(c, nrow, n, m, d, ld); }
+  static int column_leaves(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out) {
+    return lf_column_leaves32(c, nrow, ld, col0, ncols, d_T, d_nonces, d_out, 0);
   }
 };
+using Lig32 = lig::Slab<E>;  // the prover record: all rows on one GPU, or a slab with a communicator (lfgpu_zk_prover_set_comm above the size threshold)
 
 // the host half of LigeroProver::commit (ligero_prover.h:171-270 + merkle_commitment.h:52-54): every RandomEngine draw in the
 // reference's order (FpGeneric::sample and sample_subfield are the same function, fp_generic.h:360-376)
@@ -1505,33 +1541,14 @@ int lig256_layout(const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lf
   return LFGPU_OK;
 }
 
-// field sum over the ranks of a host vector every rank holds a partial of (all_gather + fold: RCCL has no mod-p reduction)
-static int comm_fold256(const Lig256* L, E* y, size_t n) {
-  const lfgpu_comm_ops& cm = L->comm;
-  if (!L->sharded || cm.world == 1) return LFGPU_OK;
-  std::vector<E> all((size_t)cm.world * n);
-  if (cm.all_gather(cm.user, y, all.data(), n * 32, 0, nullptr)) return lf_fail(L->c, LFGPU_ERR_HIP, "ligero256 (sharded): all_gather hook failed");
-  for (size_t j = 0; j < n; ++j) y[j] = all[j];
-  for (int q = 1; q < cm.world; ++q)
-    for (size_t j = 0; j < n; ++j) y[j] = fp256_add(y[j], all[(size_t)q * n + j]);
-  return LFGPU_OK;
-}
-// witness / quadratic rows [a_lo, a_hi) (relative to iw) that the slab holds
-static void owned_wq256(const Lig256* L, size_t* a_lo, size_t* a_hi) {
-  const lfgpu_ligero_param& p = L->p;
-  const size_t lo = std::min(std::max(L->row_lo, p.iw), p.iw + p.nwqrow), hi = std::min(std::max(L->row_hi, p.iw), p.iw + p.nwqrow);
-  *a_lo = lo - p.iw;
-  *a_hi = std::max(hi, lo) - p.iw;
-}
-
 // cm != nullptr (more than one rank; the caller has made every rank's `rng` yield the same bytes): every rank lays out the whole
 // host image (it is small next to the encoded tableau), keeps and encodes its row slab, and the columns are committed as in
-// lfgpu_ligero_commit_sharded (ligero.hip): one all_to_all of the encoded columns, local leaves, all_gather of the digests, the
-// tree on every rank
-int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user, uint8_t root[32], Lig256** out,
+// lfgpu_ligero_commit_sharded (lig::column_commit_sharded): one all_to_all of the encoded columns, local leaves, all_gather of
+// the digests, the tree on every rank
+int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user, uint8_t root[32], Lig32** out,
                   const lfgpu_comm_ops* cm = nullptr) {
   if (p.ildt != 0 || p.idot != 1 || p.iquad != 2 || p.iw != 3) return lf_fail(c, LFGPU_ERR_ARG, "ligero256: row order");
-  std::unique_ptr<Lig256> L(new Lig256());
+  std::unique_ptr<Lig32> L(new Lig32());
   L->c = c;
   L->p = p;
   L->nonces.resize(32 * p.block_ext);
@@ -1552,7 +1569,10 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
   const int rc = lig256_layout(p, W, lqc, rng, user, H.data(), L->nonces.data(), err, c->rng_exact != 0);
   if (rc) return lf_fail(c, rc, "%s", err);
   const size_t ld = p.block_enc, nr = L->row_hi - L->row_lo, ncols = p.block_ext;
-  if (lf_pool_get(c, L->slab_bytes(), (void**)&L->d_T) != LFGPU_OK || lf_pool_get(c, 2 * p.block_ext * 32, (void**)&L->d_layers) != LFGPU_OK)
+  const double t_enc = lig::clock_ms();  // (the sharded column commit's LFGPU_VERBOSE line counts upload + encode from here)
+  L->T_bytes = std::max<size_t>(nr, 1) * ld * 32;
+  L->L_bytes = 2 * ncols * 32;
+  if (lf_pool_get(c, L->T_bytes, (void**)&L->d_T) != LFGPU_OK || lf_pool_get(c, L->L_bytes, (void**)&L->d_layers) != LFGPU_OK)
     return lf_fail(c, LFGPU_ERR_NOMEM, "ligero256: tableau alloc");
   if (nr) LF_HIP(c, hipMemcpy2DAsync(L->d_T, ld * 32, H.data() + L->row_lo * p.dblock, p.dblock * 32, p.dblock * 32, nr, hipMemcpyHostToDevice, c->stream));
   // rows IDOT / IQUAD carry dblock values, every other row block (ligero_prover.h:175,184,203,210,237): the slab's share of each group
@@ -1563,8 +1583,8 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
   LF_TRY(encode(0, 1, p.block));
   LF_TRY(encode(1, 3, p.dblock));
   LF_TRY(encode(3, p.nrow, p.block));
-  void* d_non = nullptr;
   if (!L->sharded) {
+    void* d_non = nullptr;
     LF_TRY(lf_scratch3(c, p.block_ext * 32, &d_non));
     LF_HIP(c, hipMemcpyAsync(d_non, L->nonces.data(), p.block_ext * 32, hipMemcpyHostToDevice, c->stream));
     LF_TRY(lfgpu_column_commit(c, LFGPU_FIELD_P256, p.nrow, ld, p.dblock, p.block_ext, L->d_T, d_non, L->d_layers, root));
@@ -1572,200 +1592,9 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
     *out = L.release();
     return LFGPU_OK;
   }
-  // ---- sharded column commit
-  auto split = [&](size_t n, int q, size_t* start, size_t* count) {
-    const size_t base = n / (size_t)world, rem = n % (size_t)world, r = (size_t)q;
-    *start = r * base + std::min(r, rem);
-    *count = base + (r < rem ? 1 : 0);
-  };
-  std::vector<size_t> soff(world), sbytes(world), roff(world), rbytes(world);
-  size_t mc0 = 0, mcn = 0, send_tot = 0, maxn = 0, dummy = 0;
-  split(ncols, rank, &mc0, &mcn);
-  split(ncols, 0, &dummy, &maxn);
-  for (int q = 0; q < world; ++q) {
-    size_t c0, cn;
-    split(ncols, q, &c0, &cn);
-    soff[q] = send_tot;
-    sbytes[q] = nr * cn * 32;
-    send_tot += sbytes[q];
-    roff[q] = L->spans[q].first * mcn * 32;
-    rbytes[q] = (L->spans[q].second - L->spans[q].first) * mcn * 32;
-  }
-  const size_t send_bytes = std::max<size_t>(send_tot, 32), cols_bytes = std::max<size_t>(p.nrow * mcn * 32, 32);
-  void *d_send = nullptr, *d_cols = nullptr;
-  if (lf_pool_get(c, send_bytes, &d_send) != LFGPU_OK) return lf_fail(c, LFGPU_ERR_NOMEM, "ligero256 (sharded): exchange buffers");
-  if (lf_pool_get(c, cols_bytes, &d_cols) != LFGPU_OK) {
-    lf_pool_put(c, d_send, send_bytes);
-    return lf_fail(c, LFGPU_ERR_NOMEM, "ligero256 (sharded): exchange buffers");
-  }
-  auto done = [&](int code) {  // encoded rows of the tableau: scrubbed like the tableau before they go back to the pool
-    (void)hipMemsetAsync(d_send, 0, send_bytes, c->stream);
-    (void)hipMemsetAsync(d_cols, 0, cols_bytes, c->stream);
-    lf_pool_put(c, d_send, send_bytes);
-    lf_pool_put(c, d_cols, cols_bytes);
-    return code;
-  };
-  for (int q = 0; q < world && nr; ++q) {
-    size_t c0, cn;
-    split(ncols, q, &c0, &cn);
-    if (cn && hipMemcpy2DAsync((uint8_t*)d_send + soff[q], cn * 32, L->d_T + p.dblock + c0, ld * 32, cn * 32, nr, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return done(lf_fail(c, LFGPU_ERR_HIP, "ligero256 (sharded): pack"));
-  }
-  if (cm->all_to_all(cm->user, d_send, soff.data(), sbytes.data(), d_cols, roff.data(), rbytes.data(), 1, c->stream))
-    return done(lf_fail(c, LFGPU_ERR_HIP, "ligero256 (sharded): all_to_all hook failed"));
-  int rc2 = lf_scratch3(c, ncols * 32 + (size_t)(world + 1) * maxn * 32 + 64, &d_non);
-  if (rc2) return done(rc2);
-  uint8_t* d_mine = (uint8_t*)d_non + ncols * 32;
-  uint8_t* d_all = d_mine + maxn * 32;
-  if (hipMemcpyAsync(d_non, L->nonces.data(), ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess || hipMemsetAsync(d_mine, 0, maxn * 32, c->stream) != hipSuccess)
-    return done(lf_fail(c, LFGPU_ERR_HIP, "ligero256 (sharded): nonce upload"));
-  if (mcn && (rc2 = lf_column_leaves32(c, p.nrow, mcn, 0, mcn, d_cols, (const uint8_t*)d_non + mc0 * 32, d_mine, 0))) return done(rc2);
-  if (cm->all_gather(cm->user, d_mine, d_all, maxn * 32, 1, c->stream)) return done(lf_fail(c, LFGPU_ERR_HIP, "ligero256 (sharded): all_gather hook failed"));
-  if (hipMemsetAsync(L->d_layers, 0, ncols * 32, c->stream) != hipSuccess) return done(lf_fail(c, LFGPU_ERR_HIP, "ligero256 (sharded): layers"));
-  for (int q = 0; q < world; ++q) {
-    size_t c0, cn;
-    split(ncols, q, &c0, &cn);
-    if (cn && hipMemcpyAsync(L->d_layers + (ncols + c0) * 32, d_all + (size_t)q * maxn * 32, cn * 32, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return done(lf_fail(c, LFGPU_ERR_HIP, "ligero256 (sharded): leaves"));
-  }
-  if ((rc2 = lfgpu_merkle_build_tree(c, ncols, L->d_layers, root))) return done(rc2);  // synchronises: H may go
-  done(LFGPU_OK);
+  LF_TRY(lig::column_commit_sharded(L.get(), L32(), cm, t_enc, root));  // ends with a synchronise: H may go
   *out = L.release();
   return LFGPU_OK;
-}
-
-int lig256_low_degree(Lig256* L, const E* u, E* y) {  // low_degree_proof (:281-291)
-  lfgpu_ctx* c = L->c;
-  const lfgpu_ligero_param& p = L->p;
-  void *dy = nullptr, *du = nullptr;
-  LF_TRY(lf_scratch3(c, p.block * 32, &dy));
-  LF_TRY(lf_scratch2(c, p.nwqrow * 32 + 64, &du));
-  if (L->has(p.ildt)) LF_HIP(c, hipMemcpyAsync(dy, L->row(p.ildt), p.block * 32, hipMemcpyDeviceToDevice, c->stream));
-  else LF_HIP(c, hipMemsetAsync(dy, 0, p.block * 32, c->stream));
-  LF_HIP(c, hipMemcpyAsync(du, u, p.nwqrow * 32, hipMemcpyHostToDevice, c->stream));
-  size_t a_lo, a_hi;
-  owned_wq256(L, &a_lo, &a_hi);
-  if (a_hi > a_lo)
-    hipLaunchKernelGGL(rows_axpy256_kernel, dim3(nblk(p.block, 64)), dim3(256), 0, c->stream, (u32)(a_hi - a_lo), p.block, (E*)dy, (const E*)du + a_lo,
-                       (const E*)L->row(p.iw + a_lo), p.block_enc);
-  LF_HIP(c, hipGetLastError());
-  LF_TRY(lfgpu_memcpy_d2h(c, y, dy, p.block * 32));
-  return comm_fold256(L, y, p.block);
-}
-
-// dot_proof (:293-309) with A given as inner_product_vector builds it: a dense block scale * dense[0..ndense) over the first
-// flat positions plus sparse (index, value) terms (strictly increasing indices)
-int lig256_dot(Lig256* L, const E* d_dense, size_t ndense, const E& scale, const uint64_t* idx, const E* val, size_t nsparse, E* y) {
-  lfgpu_ctx* c = L->c;
-  const lfgpu_ligero_param& p = L->p;
-  const size_t lda = p.dblock;
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, (p.nwqrow * lda + 2 * p.dblock) * 32 + 64, &sc));
-  E* dA = (E*)sc;
-  E* dy = dA + p.nwqrow * lda;
-  LF_HIP(c, hipMemsetAsync(dA, 0, p.nwqrow * lda * 32, c->stream));
-  if (ndense) hipLaunchKernelGGL(a_rows_dense256_kernel, dim3(nblk(ndense)), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, lda, scale, d_dense, ndense, dA);
-  if (nsparse) {
-    void* d_sp = nullptr;
-    LF_TRY(lf_scratch2(c, nsparse * 40 + 64, &d_sp));
-    E* d_val = (E*)d_sp;
-    u64* d_idx = (u64*)(d_val + nsparse);
-    LF_HIP(c, hipMemcpyAsync(d_val, val, nsparse * 32, hipMemcpyHostToDevice, c->stream));
-    LF_HIP(c, hipMemcpyAsync(d_idx, idx, nsparse * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(a_rows_sparse256_kernel, dim3(nblk(nsparse)), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, lda, (const u64*)d_idx, (const E*)d_val,
-                       nsparse, dA);
-    LF_HIP(c, hipGetLastError());
-    LF_HIP(c, hipStreamSynchronize(c->stream));  // the staging area is the Reed-Solomon encoder's work space next
-  }
-  size_t a_lo, a_hi;
-  owned_wq256(L, &a_lo, &a_hi);
-  if (a_hi > a_lo) LF_TRY(lfgpu_fp256_rs_encode_rows(c, a_hi - a_lo, p.block, p.dblock, dA + a_lo * lda, lda));
-  const E* T0 = nullptr;
-  if (L->has(p.idot)) {
-    T0 = L->row(p.idot);
-  } else {  // a zero row behind dy
-    LF_HIP(c, hipMemsetAsync(dy + p.dblock, 0, p.dblock * 32, c->stream));
-    T0 = dy + p.dblock;
-  }
-  hipLaunchKernelGGL(rows_vaxpy256_kernel, dim3(nblk(p.dblock, 64)), dim3(256), 0, c->stream, (u32)(a_hi - a_lo), p.dblock, T0, (const E*)(dA + a_lo * lda), lda,
-                     (const E*)(a_hi > a_lo ? L->row(p.iw + a_lo) : L->d_T), p.block_enc, dy);
-  LF_HIP(c, hipGetLastError());
-  LF_TRY(lfgpu_memcpy_d2h(c, y, dy, p.dblock * 32));
-  return comm_fold256(L, y, p.dblock);
-}
-
-int lig256_quadratic(Lig256* L, const E* u, E* y0, E* y2) {  // quadratic_proof (:311-344)
-  lfgpu_ctx* c = L->c;
-  const lfgpu_ligero_param& p = L->p;
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, (p.nqtriples + 1 + 2 * p.dblock) * 32 + 64, &sc));
-  E* du = (E*)sc;
-  E* dy = du + p.nqtriples + 1;
-  if (p.nqtriples) LF_HIP(c, hipMemcpyAsync(du, u, p.nqtriples * 32, hipMemcpyHostToDevice, c->stream));
-  const size_t ld = p.block_enc;
-  // a triple is multiplied element-wise: the slab holds all quadratic rows (the last rank) or none
-  const size_t q_lo = p.iq, q_hi = p.iq + 3 * p.nqtriples;
-  const bool all_q = p.nqtriples == 0 || (L->row_lo <= q_lo && q_hi <= L->row_hi);
-  if (!all_q && !(L->row_hi <= q_lo || L->row_lo >= q_hi)) return lf_fail(c, LFGPU_ERR_ARG, "quadratic_proof256: the slab splits the quadratic rows");
-  const size_t nt = all_q ? p.nqtriples : 0;
-  const E* Tq = nullptr;
-  if (L->has(p.iquad)) {
-    Tq = L->row(p.iquad);
-  } else {
-    LF_HIP(c, hipMemsetAsync(dy + p.dblock, 0, p.dblock * 32, c->stream));
-    Tq = dy + p.dblock;
-  }
-  const E* X = nt ? L->row(p.iq) : L->d_T;
-  const E* Y = X + p.nqtriples * ld;
-  const E* Zr = Y + p.nqtriples * ld;
-  hipLaunchKernelGGL(quad_combo256_kernel, dim3(nblk(p.dblock)), dim3(Z_THREADS), 0, c->stream, (u32)nt, p.dblock, Tq, (const E*)du, X, Y, Zr, ld, dy);
-  LF_HIP(c, hipGetLastError());
-  std::vector<E> y(p.dblock);
-  LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, p.dblock * 32));
-  LF_TRY(comm_fold256(L, y.data(), p.dblock));
-  for (size_t j = 0; j < p.w; ++j)
-    if (!e32_is_zero(y[p.r + j])) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero");
-  memcpy(y0, y.data(), p.r * 32);
-  memcpy(y2, y.data() + p.block, (p.dblock - p.block) * 32);
-  return LFGPU_OK;
-}
-
-int lig256_open(Lig256* L, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t path_cap, size_t* npath) {  // compute_req + MerkleCommitment::open
-  lfgpu_ctx* c = L->c;
-  const lfgpu_ligero_param& p = L->p;
-  for (size_t i = 0; i < p.nreq; ++i)
-    if (idx[i] >= p.block_ext) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open: index out of range");
-  void *dreq = nullptr, *di = nullptr;
-  const size_t nr = L->row_hi - L->row_lo;
-  size_t maxr = nr;
-  for (const auto& sp : L->spans) maxr = std::max(maxr, sp.second - sp.first);
-  LF_TRY(lf_scratch3(c, std::max<size_t>(nr, 1) * p.nreq * 32, &dreq));
-  LF_TRY(lf_scratch2(c, p.nreq * 8 + 64, &di));
-  std::vector<u64> ix(idx, idx + p.nreq);
-  LF_HIP(c, hipMemcpyAsync(di, ix.data(), p.nreq * 8, hipMemcpyHostToDevice, c->stream));
-  std::vector<uint8_t> mine;  // a slab's rows of req, padded to the largest slab for the all_gather
-  void* h_dst = req;
-  if (L->sharded) {
-    mine.assign(maxr * p.nreq * 32, 0);
-    h_dst = mine.data();
-  }
-  if (nr) {
-    hipLaunchKernelGGL(gather_columns256_kernel, dim3(nblk(nr * p.nreq)), dim3(Z_THREADS), 0, c->stream, (u32)nr, p.block_enc, p.dblock, (const E*)L->d_T,
-                       (const u64*)di, (u32)p.nreq, (E*)dreq);
-    LF_HIP(c, hipGetLastError());
-    LF_TRY(lfgpu_memcpy_d2h(c, h_dst, dreq, nr * p.nreq * 32));
-  } else {
-    LF_HIP(c, hipStreamSynchronize(c->stream));  // ix is a local
-  }
-  if (L->sharded) {
-    const lfgpu_comm_ops& cm = L->comm;
-    std::vector<uint8_t> all((size_t)cm.world * mine.size());
-    if (cm.all_gather(cm.user, mine.data(), all.data(), mine.size(), 0, nullptr)) return lf_fail(c, LFGPU_ERR_HIP, "ligero256_open (sharded): all_gather hook failed");
-    for (int q = 0; q < cm.world; ++q)
-      memcpy((uint8_t*)req + L->spans[q].first * p.nreq * 32, all.data() + (size_t)q * mine.size(), (L->spans[q].second - L->spans[q].first) * p.nreq * 32);
-  }
-  for (size_t i = 0; i < p.nreq; ++i) memcpy(nonces + 32 * i, &L->nonces[32 * idx[i]], 32);
-  return lfgpu_merkle_open(c, p.block_ext, L->d_layers, idx, p.nreq, path, path_cap, npath);
 }
 }  // namespace
 
@@ -1797,7 +1626,7 @@ int bind_gh_all256(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, const
 
 // Wire32 (zk_proto.h) plus the device steps of this file
 struct P32 : zkp::Wire32 {
-  using Lig = Lig256;
+  using Lig = Lig32;
   using Layer = lfgpu_circuit::Layer;
   static constexpr const char* kProveName = "zk256_prove";
   static F256 host_field(lfgpu_ctx*) { return F256(); }
@@ -1817,13 +1646,13 @@ struct P32 : zkp::Wire32 {
     if (npub) LF_TRY(lfgpu_memcpy_d2h(c, eq_in, d_eq, npub * 32));
     return LFGPU_OK;
   }
-  static int low_degree(Lig* lp, const E* u, E* y) { return lig256_low_degree(lp, u, y); }
+  static int low_degree(Lig* lp, const E* u, E* y) { return lig::low_degree(lp, L32(), u, y); }
   static int dot(Lig* lp, const E* d_dense, size_t ndense, const E& scale, const uint64_t* idx, const E* val, size_t nsparse, E* y) {
-    return lig256_dot(lp, d_dense, ndense, scale, idx, val, nsparse, y);
+    return lig::dot(lp, L32(), d_dense, ndense, scale, idx, val, nsparse, y);
   }
-  static int quadratic(Lig* lp, const E* u, E* y0, E* y2) { return lig256_quadratic(lp, u, y0, y2); }
+  static int quadratic(Lig* lp, const E* u, E* y0, E* y2) { return lig::quadratic(lp, L32(), u, y0, y2); }
   static int open(Lig* lp, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t cap, size_t* npath) {
-    return lig256_open(lp, idx, req, nonces, path, cap, npath);
+    return lig::open(lp, L32(), idx, req, nonces, path, cap, npath);
   }
   static size_t verifier_bytes(const lfgpu_circuit_info& I, const lfgpu_ligero_param& p) {
     return (I.ninputs + (p.nwqrow + 3) * p.block_enc + (p.nwqrow + 3) * p.nreq) * 32 + 256;
@@ -1837,18 +1666,7 @@ struct P32 : zkp::Wire32 {
     E* d_T = (E*)d_eq + I.ninputs;
     E* d_req = d_T + nrows_dev * ld;
     LF_HIP(c, hipMemset2DAsync(d_T, ld * 32, 0, p.dblock * 32, nrows_dev, c->stream));
-    hipLaunchKernelGGL(a_rows_dense256_kernel, dim3(nblk(n_witness)), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, scale, d_eq + I.npub_in, n_witness, d_T);
-    if (!a_idx.empty()) {
-      void* d_sp = nullptr;
-      LF_TRY(lf_scratch2(c, a_idx.size() * 40 + 64, &d_sp));
-      E* d_val = (E*)d_sp;
-      u64* d_idx = (u64*)(d_val + a_idx.size());
-      LF_HIP(c, hipMemcpyAsync(d_val, a_val.data(), a_idx.size() * 32, hipMemcpyHostToDevice, c->stream));
-      LF_HIP(c, hipMemcpyAsync(d_idx, a_idx.data(), a_idx.size() * 8, hipMemcpyHostToDevice, c->stream));
-      hipLaunchKernelGGL(a_rows_sparse256_kernel, dim3(nblk(a_idx.size())), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, (const u64*)d_idx, (const E*)d_val,
-                         a_idx.size(), d_T);
-    }
-    LF_HIP(c, hipGetLastError());
+    LF_TRY(lig::a_rows(c, L32(), p.w, p.r, ld, p.nwqrow, d_eq + I.npub_in, n_witness, scale, a_idx.data(), a_val.data(), a_idx.size(), d_T));
     LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 0) * ld, pr.y_ldt.data(), p.block * 32, hipMemcpyHostToDevice, c->stream));
     LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 1) * ld, pr.y_dot.data(), p.dblock * 32, hipMemcpyHostToDevice, c->stream));
     E* yq = d_T + (p.nwqrow + 2) * ld;  // y_quad = y_quad_0 | 0^w | y_quad_2
@@ -1876,7 +1694,7 @@ struct Zk256 {
   lfgpu_ctx* c = nullptr;
   const lfgpu_circuit* C = nullptr;
   zkp::ProverState<P32> st;  // pads, the held proof, its wire bytes, timings
-  Lig256* lp = nullptr;
+  Lig32* lp = nullptr;
   std::vector<void*> d_in;  // the layers' inputs (eval_circuit), resident for the sumcheck
   void* d_V = nullptr;
   void* h_V = nullptr;  // pinned: outputs then the assert-zero flag
@@ -1888,7 +1706,7 @@ struct Zk256 {
   ~Zk256() {
     delete lp;
     // the layers' wire values are functions of the witness: scrubbed before the memory goes back to the allocator (as the
-    // tableau is, Lig256; the host copies of the pads: ~ProverState)
+    // tableau is, ~Slab of ligero_slab.h; the host copies of the pads: ~ProverState)
     for (size_t l = 0; l < d_in.size(); ++l)
       if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, C->layers[l].nw * 32, c->stream);
     if (d_V) (void)hipMemsetAsync(d_V, 0, C->info.nv * 32, c->stream);
