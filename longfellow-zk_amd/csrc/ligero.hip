@@ -10,7 +10,7 @@
 // uploaded once; the GPU then RS-encodes every row (K3/K4) and commits the columns
 // (K5/K6).  The tableau stays in HBM for the prove-side row combinations (K12).
 #include <algorithm>
-#include <chrono>
+#include <memory>
 #include <new>
 
 #include "ctx.h"
@@ -97,90 +97,6 @@ extern "C" int lfgpu_ligero_param_init(lfgpu_ligero_param* p, int field, int k, 
   return LFGPU_OK;
 }
 
-// ---- field sampling on the host (RandomEngine::elt / subfield_elt, lib/random/random.h:38-48)
-struct Sampler {
-  int field, k;
-  const GfHostCtx* g;
-  lfgpu_rng_fn rng;
-  void* user;
-  bool exact = false;  // lfgpu_set_rng_exact_calls: one call per element, as the reference draws
-  // n consecutive full-field elements.  GF2_128::sample consumes exactly 16 bytes per element
-  // (gf2_128.h:182-190), so n draws of 16 bytes equal one draw of 16n bytes for every byte-stream
-  // RandomEngine of the reference (LCG test engines, Transcript/FSPRF, SecureRandomEngine); Fp128 uses
-  // rejection sampling and is drawn element by element.
-  void elts(elt_t* out, size_t n) {
-    if (field == LFGPU_FIELD_GF2_128 && !exact) {
-      rng(user, reinterpret_cast<uint8_t*>(out), 16 * n);  // little-endian host: bytes are the Elt image
-    } else {
-      for (size_t i = 0; i < n; ++i) out[i] = elt();
-    }
-  }
-  elt_t elt() {
-    if (field == LFGPU_FIELD_GF2_128) {  // GF2_128::sample gf2_128.h:182-190: 16 bytes LE
-      uint8_t b[16];
-      rng(user, b, 16);
-      elt_t e;
-      memcpy(&e.lo, b, 8);
-      memcpy(&e.hi, b + 8, 8);
-      return e;
-    }
-    // FpGeneric::sample fp_generic.h:360-371: 16 bytes, reject >= p, to Montgomery
-    for (;;) {
-      uint8_t b[16];
-      rng(user, b, 16);
-      elt_t e;
-      memcpy(&e.lo, b, 8);
-      memcpy(&e.hi, b + 8, 8);
-      if (e.hi < FP_P_HI || (e.hi == FP_P_HI && e.lo < FP_P_LO)) {
-        // to_montgomery = mul by R^2 (fp_generic.h:278-282); C++11 initialises a function-local static once, thread-safely
-        static const elt_t rsq = [] {
-          elt_t r{1, 0};
-          for (int i = 0; i < 256; ++i) r = fp_add(r, r);
-          return r;
-        }();
-        return fp_mul(e, rsq);
-      }
-    }
-  }
-  // n consecutive subfield elements: kSubFieldBytes each, so for a byte-stream engine one draw of n * kSubFieldBytes bytes;
-  // of_scalar through the byte tables (the mdoc hash circuit draws 34 000 of them per commit: 2.0 -> 0.2 ms of host time)
-  void subfield_elts(elt_t* out, size_t n) {
-    if (field != LFGPU_FIELD_GF2_128 || exact) {
-      for (size_t i = 0; i < n; ++i) out[i] = subfield_elt();
-      return;
-    }
-    const size_t nb = g->sub_bits / 8;
-    uint8_t buf[1024];
-    for (size_t done = 0; done < n;) {
-      const size_t m = std::min(n - done, sizeof(buf) / nb);
-      rng(user, buf, m * nb);
-      for (size_t i = 0; i < m; ++i) {
-        elt_t t = g->sub_tab[0][buf[i * nb]];
-        for (size_t b = 1; b < nb; ++b) t = gf_add(t, g->sub_tab[b][buf[i * nb + b]]);
-        out[done + i] = t;
-      }
-      done += m;
-    }
-  }
-  elt_t subfield_elt() {
-    if (field != LFGPU_FIELD_GF2_128) return elt();  // FpGeneric::sample_subfield = sample
-    // GF2_128::sample_subfield gf2_128.h:192-214: kSubFieldBytes LE -> of_scalar
-    uint8_t b[8] = {0};
-    size_t nb = g->sub_bits / 8;
-    rng(user, b, nb);
-    u64 u = 0;
-    for (size_t i = nb; i-- > 0;) u = (u << 8) | b[i];
-    elt_t t{0, 0};
-    for (unsigned bit = 0; bit < g->sub_bits; ++bit, u >>= 1)
-      if (u & 1) t = gf_add(t, g->beta[bit]);
-    return t;
-  }
-};
-
-static inline elt_t h_add(int field, elt_t a, elt_t b) { return field == LFGPU_FIELD_GF2_128 ? gf_add(a, b) : fp_add(a, b); }
-static inline elt_t h_sub(int field, elt_t a, elt_t b) { return field == LFGPU_FIELD_GF2_128 ? gf_add(a, b) : fp_sub(a, b); }
-static inline elt_t h_mul(int field, elt_t a, elt_t b) { return field == LFGPU_FIELD_GF2_128 ? gf_mul(a, b) : fp_mul(a, b); }
-
 int lf_rs_rows(lfgpu_ctx* c, int field, int k, size_t nrow, size_t n, size_t m, elt_t* d, size_t ld) {
   if (nrow == 0) return LFGPU_OK;
   if (field == LFGPU_FIELD_GF2_128) return lfgpu_gf2128_rs_encode_rows(c, k, nrow, n, m, d, ld);
@@ -194,122 +110,6 @@ int lf_rs_rows(lfgpu_ctx* c, int field, int k, size_t nrow, size_t n, size_t m, 
   elt_t w = fp_mul(raw, rsq);
   uint64_t om[2] = {w.lo, w.hi};
   return lfgpu_fp128_rs_encode_rows(c, nrow, n, m, om, (uint64_t)1 << 32, d, ld);
-}
-
-// GF2_128::in_subfield (gf2_128.h:201-204) for the witness check of LigeroProver::commit: beta in reduced echelon form, an
-// element lies in the subfield iff cancelling its pivot bits leaves nothing
-struct SubfieldTest {
-  elt_t v[32];
-  int pivot[32];
-  unsigned n = 0;
-  static int top_bit(elt_t e) { return e.hi ? 64 + (63 - __builtin_clzll(e.hi)) : e.lo ? 63 - __builtin_clzll(e.lo) : -1; }
-  static bool bit_of(elt_t e, int j) { return j >= 64 ? (e.hi >> (j - 64)) & 1 : (e.lo >> j) & 1; }
-  explicit SubfieldTest(const GfHostCtx* g) {
-    for (unsigned i = 0; i < g->sub_bits && i < 32; ++i) {
-      elt_t e = g->beta[i];
-      for (unsigned r = 0; r < n; ++r)
-        if (bit_of(e, pivot[r])) e = gf_add(e, v[r]);
-      v[n] = e;  // beta is a basis: e != 0
-      pivot[n++] = top_bit(e);
-    }
-  }
-  bool in_subfield(elt_t e) const {
-    if (e.hi == 0 && e.lo <= 1) return true;  // 0 and 1, nearly every input of a bit circuit
-    for (unsigned r = 0; r < n; ++r)  // a row's pivot bit is clear in every LATER row: one pass in order
-      if (bit_of(e, pivot[r])) e = gf_add(e, v[r]);
-    return (e.lo | e.hi) == 0;
-  }
-};
-
-// The host half of LigeroProver::commit (ligero_prover.h:171-270 + merkle_commitment.h:52-54): every RandomEngine draw in
-// the reference's order; the un-encoded image (first dblock columns) of rows [row_lo, row_hi) goes to H
-// ([(row_hi - row_lo)][dblock]); rows outside the slab are drawn into a spare row and dropped, so that ranks which replay
-// the same byte stream hold consistent slabs of ONE tableau.  nonces (block_ext * 32 bytes) may be null: the draw still
-// happens.  Returns LFGPU_OK / LFGPU_ERR_ARG / LFGPU_ERR_ASSERT with a message in err (256 bytes).
-static int ligero_layout_host(int field, int k, const GfHostCtx* g, const lfgpu_ligero_param& p, const elt_t* W, size_t subfield_boundary,
-                              const size_t* h_lqc, lfgpu_rng_fn rng, void* user, size_t row_lo, size_t row_hi, elt_t* H, uint8_t* nonces,
-                              char* err, bool exact = false) {
-  // the check that opens LigeroProver::commit (ligero_prover.h:63-66), before any draw: a row below the boundary is blinded
-  // with subfield randomness, which hides nothing of a full-field value in it.  in_subfield is identically true for Fp128.
-  if (field == LFGPU_FIELD_GF2_128 && subfield_boundary) {
-    const SubfieldTest sub(g);
-    for (size_t i = 0; i < std::min(subfield_boundary, p.nw); ++i)
-      if (!sub.in_subfield(W[i])) {
-        snprintf(err, 256, "ligero_commit: element not in subfield: W[%zu], below subfield_boundary %zu (ligero_prover.h:63-66)", i, subfield_boundary);
-        return LFGPU_ERR_ARG;
-      }
-  }
-  Sampler S{field, k, g, rng, user, exact};
-  const elt_t zero{0, 0};
-  const size_t hw = p.dblock;
-  std::vector<elt_t> spare(hw);
-  auto row = [&](size_t i) -> elt_t* {
-    if (i >= row_lo && i < row_hi) return H + (i - row_lo) * hw;
-    return spare.data();
-  };
-  auto own = [&](size_t i) { return i >= row_lo && i < row_hi; };
-  for (size_t i = row_lo; i < row_hi; ++i) std::fill(row(i), row(i) + hw, zero);
-  // layout_blinding_rows (ligero_prover.h:171-205)
-  S.elts(row(p.ildt), p.block);
-  {
-    elt_t* d = row(p.idot);
-    S.elts(d, p.dblock);
-    elt_t sum = zero;
-    for (size_t j = 0; j < p.w; ++j) sum = h_add(field, sum, d[p.r + j]);
-    d[p.r] = h_sub(field, d[p.r], sum);
-  }
-  {
-    elt_t* q = row(p.iquad);
-    S.elts(q, p.dblock);
-    for (size_t j = 0; j < p.w; ++j) q[p.r + j] = zero;
-  }
-  // layout_witness_rows (:207-231)
-  for (size_t i = 0; i < p.nwrow; ++i) {
-    elt_t* t = row(i + p.iw);
-    const bool subfield_only = ((i + 1) * p.w <= subfield_boundary);
-    if (subfield_only) {
-      S.subfield_elts(t, p.r);
-    } else {
-      S.elts(t, p.r);
-    }
-    if (!own(i + p.iw)) continue;
-    const size_t max_col = std::min(p.w, p.nw - i * p.w);
-    for (size_t j = 0; j < max_col; ++j) t[p.r + j] = W[i * p.w + j];
-  }
-  // layout_quadratic_rows (:233-270)
-  const size_t iqx = p.iq, iqy = iqx + p.nqtriples, iqz = iqy + p.nqtriples;
-  for (size_t i = 0; i < p.nqtriples; ++i) {
-    S.elts(row(iqx + i), p.r);
-    S.elts(row(iqy + i), p.r);
-    S.elts(row(iqz + i), p.r);
-    for (size_t j = 0; j < p.w && j + i * p.w < p.nq; ++j) {
-      const size_t* l = &h_lqc[3 * (j + i * p.w)];
-      if (l[0] >= p.nw || l[1] >= p.nw || l[2] >= p.nw) {
-        snprintf(err, 256, "ligero_commit: lqc index >= nw");
-        return LFGPU_ERR_ARG;
-      }
-      const elt_t prod = h_mul(field, W[l[0]], W[l[1]]);
-      if (!(prod.lo == W[l[2]].lo && prod.hi == W[l[2]].hi)) {
-        snprintf(err, 256, "ligero_commit: invalid quadratic constraints (ligero_prover.h:259-260)");
-        return LFGPU_ERR_ASSERT;
-      }
-      if (own(iqx + i)) row(iqx + i)[j + p.r] = W[l[0]];
-      if (own(iqy + i)) row(iqy + i)[j + p.r] = W[l[1]];
-      if (own(iqz + i)) row(iqz + i)[j + p.r] = W[l[2]];
-    }
-  }
-  // MerkleCommitment::commit draws one 32-byte nonce per leaf, after the layout (merkle_commitment.h:52-54): one draw of
-  // 32 * block_ext bytes is the same stream for every byte-stream engine
-  if (nonces && exact) {
-    for (size_t j = 0; j < p.block_ext; ++j) rng(user, nonces + 32 * j, 32);
-  } else if (nonces) {
-    rng(user, nonces, 32 * p.block_ext);
-  } else {
-    std::vector<uint8_t> drop(32 * p.block_ext);
-    if (exact) for (size_t j = 0; j < p.block_ext; ++j) rng(user, drop.data() + 32 * j, 32);
-    else rng(user, drop.data(), drop.size());
-  }
-  return LFGPU_OK;
 }
 
 static bool ligero_args_ok(int field, int k, const lfgpu_ligero_param* pp, const void* h_W, const size_t* h_lqc, lfgpu_rng_fn rng) {
@@ -327,270 +127,7 @@ extern "C" int lfgpu_ligero_layout_rows(int field, int k, const lfgpu_ligero_par
   GfHostCtx g;
   if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx_build(&g, k)) return LFGPU_ERR_ARG;
   char err[256];
-  return ligero_layout_host(field, k, &g, *pp, (const elt_t*)h_W, subfield_boundary, h_lqc, rng, user, row_lo, row_hi, (elt_t*)h_rows, h_nonces, err);
-}
-
-static int ligero_extend_slab(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, elt_t* d_slab);
-// rows [row_lo, row_hi) of the tableau: upload the un-encoded image and RS-extend every row to block_enc
-// (rows IDOT / IQUAD carry dblock values, every other row block: ligero_prover.h:175,184,203,210,237)
-static int ligero_encode_slab(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, const elt_t* H, elt_t* d_slab) {
-  const size_t nr = row_hi - row_lo, ld = p.block_enc, hw = p.dblock;
-  if (nr == 0) return LFGPU_OK;
-  LF_HIP(c, hipMemcpy2DAsync(d_slab, ld * 16, H, hw * 16, hw * 16, nr, hipMemcpyHostToDevice, c->stream));
-  return ligero_extend_slab(c, field, k, p, row_lo, row_hi, d_slab);
-}
-// ... the RS extension alone, of a slab whose un-encoded image is already on the device
-static int ligero_extend_slab(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, elt_t* d_slab) {
-  const size_t nr = row_hi - row_lo, ld = p.block_enc;
-  if (nr == 0) return LFGPU_OK;
-  // the rows with dblock values form one contiguous global range [idot, iquad + 1); clip it to the slab
-  const size_t g_lo = std::min(p.idot, p.iquad), g_hi = std::max(p.idot, p.iquad) + 1;
-  const bool contiguous = g_hi - g_lo == 2;
-  const size_t lo2 = std::min(std::max(g_lo, row_lo), row_hi) - row_lo, hi2 = std::min(std::max(g_hi, row_lo), row_hi) - row_lo;
-  int rc = field == LFGPU_FIELD_GF2_128 && contiguous
-               ? lf_gf_rs_rows_mixed(c, k, nr, p.block, p.dblock, lo2, hi2, p.block_enc, d_slab, ld)
-               : LFGPU_ERR_UNSUPPORTED;
-  if (rc == LFGPU_ERR_UNSUPPORTED) {  // rows larger than the LDS-resident kernel / Fp128: group by group
-    if (!contiguous) return lf_fail(c, LFGPU_ERR_ARG, "ligero: IDOT and IQUAD rows must be adjacent");
-    LF_TRY(lf_rs_rows(c, field, k, lo2, p.block, p.block_enc, d_slab, ld));
-    LF_TRY(lf_rs_rows(c, field, k, hi2 - lo2, p.dblock, p.block_enc, d_slab + lo2 * ld, ld));
-    LF_TRY(lf_rs_rows(c, field, k, nr - hi2, p.block, p.block_enc, d_slab + hi2 * ld, ld));
-    rc = LFGPU_OK;
-  }
-  return rc;
-}
-
-extern "C" int lfgpu_ligero_encode_rows(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, size_t row_lo, size_t row_hi,
-                                        const void* h_rows, void* d_slab) {
-  if (!c || !pp || row_lo > row_hi || row_hi > pp->nrow || (row_hi > row_lo && (!h_rows || !d_slab)))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_encode_rows: bad argument");
-  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_encode_rows: field");
-  if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, k)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_encode_rows: subfield_log_bits must be 4 or 5");
-  LF_HIP(c, hipSetDevice(c->device));
-  LF_TRY(ligero_encode_slab(c, field, k, *pp, row_lo, row_hi, (const elt_t*)h_rows, (elt_t*)d_slab));
-  LF_HIP(c, hipStreamSynchronize(c->stream));  // h_rows is the caller's: the upload must be over before we return
-  return LFGPU_OK;
-}
-
-extern "C" int lfgpu_ligero_commit(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const void* h_W,
-                                   size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng, void* user,
-                                   uint8_t root_out[32], lfgpu_ligero_prover** out) {
-  if (!c || !root_out || !out || !ligero_args_ok(field, k, pp, h_W, h_lqc, rng))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit: bad argument (null pointer, field or subfield_log_bits)");
-  const GfHostCtx* g = nullptr;
-  if (field == LFGPU_FIELD_GF2_128) g = lf_gf_ctx(c, k);
-  const lfgpu_ligero_param& p = *pp;
-  const size_t ld = p.block_enc;
-  LF_HIP(c, hipSetDevice(c->device));
-
-  lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
-  pr->c = c;
-  pr->field = field;
-  pr->k = k;
-  pr->p = p;
-  pr->d_T = nullptr;
-  pr->d_layers = nullptr;
-  pr->nonces.resize(p.block_ext * 32);
-  auto fail = [&](int rc) {
-    lfgpu_ligero_free(pr);
-    return rc;
-  };
-  // host image of the un-encoded rows (only the first dblock columns are ever non-trivial) + the nonces: the single-GPU
-  // commit is the slab [0, nrow) of the sharded one
-  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-  auto clk = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tv0 = verbose ? clk() : 0;
-  std::vector<elt_t> H(p.nrow * p.dblock);
-  LF_SCRUB_ON_EXIT(H);
-  {
-    char err[256] = {0};
-    const int rc = ligero_layout_host(field, k, g, p, (const elt_t*)h_W, subfield_boundary, h_lqc, rng, user, 0, p.nrow, H.data(),
-                                      pr->nonces.data(), err, c->rng_exact != 0);
-    if (rc) return fail(lf_fail(c, rc, "%s", err));
-  }
-  const double tv1 = verbose ? clk() : 0;
-  const size_t tb = p.nrow * ld * 16, lb = 2 * p.block_ext * 32;
-  // buffers of an earlier prover with the same shape where there is one (the context's pool)
-  if (lf_pool_get(c, tb, (void**)&pr->d_T) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit: tableau alloc"));
-  if (lf_pool_get(c, lb, (void**)&pr->d_layers) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit: layers alloc"));
-  pr->T_bytes = tb;
-  pr->L_bytes = lb;
-  pr->row_lo = 0;
-  pr->row_hi = p.nrow;
-  void* d_non = nullptr;
-  int rc = lf_scratch3(c, p.block_ext * 32, &d_non);
-  if (rc) return fail(rc);
-  if (hipMemcpyAsync(d_non, pr->nonces.data(), p.block_ext * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit: upload failed"));
-  if ((rc = ligero_encode_slab(c, field, k, p, 0, p.nrow, H.data(), pr->d_T))) return fail(rc);
-  double tv2 = 0;
-  if (verbose) {
-    (void)hipStreamSynchronize(c->stream);
-    tv2 = clk();
-  }
-  if ((rc = lfgpu_column_commit(c, field, p.nrow, ld, p.dblock, p.block_ext, pr->d_T, d_non, pr->d_layers, root_out)))
-    return fail(rc);
-  if (verbose)
-    fprintf(stderr, "lfgpu ligero_commit: %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
-            p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, clk() - tv2);
-  *out = pr;
-  return LFGPU_OK;
-}
-
-// ------------------------------------------------------------------ nb commits of one shape in one chain of dispatches
-// statements per launch chain of the batched RS encode: the Fp128 kernels carry the rows of a group on gridDim.y (<= 65535) and
-// the convolution scratch is nb * rows * P * 16 bytes (<= LF_CB_SCRATCH_CAP); LFGPU_CB_CHUNK overrides (read once)
-static size_t commit_batch_chunk(int field, const lfgpu_ligero_param& p, size_t nb) {
-  static const long env = getenv("LFGPU_CB_CHUNK") ? atol(getenv("LFGPU_CB_CHUNK")) : 0;
-  size_t chunk = nb;
-  if (field == LFGPU_FIELD_FP128) {
-    const size_t g_lo = std::min(p.idot, p.iquad), g_hi = std::max(p.idot, p.iquad) + 1;
-    const size_t rows = std::max<size_t>(1, std::max(std::max(g_lo, g_hi - g_lo), p.nrow - g_hi));  // the largest row group
-    size_t P = 1;
-    while (P < p.block_enc) P <<= 1;
-    chunk = std::min(chunk, std::min<size_t>(65535 / rows, LF_CB_SCRATCH_CAP / (rows * P * 16)));
-  }
-  if (env > 0) chunk = std::min(chunk, (size_t)env);
-  return std::max<size_t>(chunk, 1);
-}
-// the RS extension of nb tableaux whose un-encoded images are on the device
-static int ligero_extend_batch(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, size_t nb, elt_t* const* d_T) {
-  const size_t ld = p.block_enc;
-  const size_t lo2 = std::min(p.idot, p.iquad), hi2 = std::max(p.idot, p.iquad) + 1;
-  if (hi2 - lo2 != 2) return lf_fail(c, LFGPU_ERR_ARG, "ligero: IDOT and IQUAD rows must be adjacent");
-  const size_t chunk = commit_batch_chunk(field, p, nb);
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0);
-    if (field == LFGPU_FIELD_GF2_128) {
-      const int rc = lf_gf_rs_rows_mixed_batch(c, k, cb, d_T + b0, p.nrow, p.block, p.dblock, lo2, hi2, p.block_enc, ld);
-      if (rc != LFGPU_ERR_UNSUPPORTED) {
-        LF_TRY(rc);
-        continue;
-      }
-      // rows longer than the LDS-resident kernel: the single path's encoder, statement by statement
-      for (size_t b = b0; b < b0 + cb; ++b) LF_TRY(ligero_extend_slab(c, field, k, p, 0, p.nrow, d_T[b]));
-    } else if (cb * std::max(hi2, p.nrow - hi2) > 65535) {  // (cb = 1) a row group of one statement overflows a launch: the single path's encoder
-      for (size_t b = b0; b < b0 + cb; ++b) LF_TRY(ligero_extend_slab(c, field, k, p, 0, p.nrow, d_T[b]));
-    } else {
-      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, 0, lo2, p.block, p.block_enc, ld));
-      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, lo2, hi2 - lo2, p.dblock, p.block_enc, ld));
-      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, hi2, p.nrow - hi2, p.block, p.block_enc, ld));
-    }
-  }
-  return LFGPU_OK;
-}
-
-extern "C" int lfgpu_ligero_commit_batch(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, size_t nb, const void* const* h_W,
-                                         size_t subfield_boundary, const size_t* h_lqc, const lfgpu_rng_fn* rng, void* const* rng_user,
-                                         uint8_t* roots_out, lfgpu_ligero_prover** out) {
-  if (!c || !pp || !h_W || !rng || !roots_out || !out) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: null argument");
-  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: nb = %zu, a batch holds 1..%d statements", nb, LFGPU_SC_BATCH_MAX);
-  for (size_t b = 0; b < nb; ++b)
-    if (!ligero_args_ok(field, k, pp, h_W[b], h_lqc, rng[b]))
-      return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: bad argument for statement %zu (null pointer, field or subfield_log_bits)", b);
-  for (size_t b = 0; b < nb; ++b) out[b] = nullptr;
-  auto user = [&](size_t b) { return rng_user ? rng_user[b] : nullptr; };
-  auto drop = [&](int rc) {  // no prover is returned: their buffers go back to the pool scrubbed (lfgpu_ligero_free)
-    for (size_t b = 0; b < nb; ++b) {
-      if (out[b]) lfgpu_ligero_free(out[b]);
-      out[b] = nullptr;
-    }
-    return rc;
-  };
-  static const int batched = getenv("LFGPU_COMMIT_BATCH") ? atoi(getenv("LFGPU_COMMIT_BATCH")) : 1;
-  if (!batched) {  // the A/B switch: the same semantics over the single-statement device path
-    for (size_t b = 0; b < nb; ++b) {
-      const int rc = lfgpu_ligero_commit(c, field, k, pp, h_W[b], subfield_boundary, h_lqc, rng[b], user(b), roots_out + 32 * b, &out[b]);
-      if (rc) {
-        out[b] = nullptr;
-        return drop(rc);
-      }
-    }
-    return LFGPU_OK;
-  }
-  const GfHostCtx* g = field == LFGPU_FIELD_GF2_128 ? lf_gf_ctx(c, k) : nullptr;
-  const lfgpu_ligero_param& p = *pp;
-  const size_t ld = p.block_enc, hw = p.dblock, ncols = p.block_ext;
-  LF_HIP(c, hipSetDevice(c->device));
-  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-  auto clk = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-  const double tv0 = verbose ? clk() : 0;
-  // pinned staging: [nb][nrow][dblock] un-encoded images, then [nb][ncols][32] nonces.  The uploads of the previous call are
-  // over (every call ends with a stream synchronise), so the memory may be rewritten at once.
-  const size_t img = p.nrow * hw * 16, used = nb * (img + ncols * 32);
-  if (c->cb_stage_bytes < used) {
-    if (c->cb_stage_h) (void)hipHostFree(c->cb_stage_h);  // (scrubbed after the call that filled it)
-    c->cb_stage_h = nullptr;
-    c->cb_stage_bytes = 0;
-    if (hipHostMalloc(&c->cb_stage_h, used, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      c->cb_stage_h = nullptr;
-      return lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: %zu bytes of pinned staging", used);
-    }
-    c->cb_stage_bytes = used;
-  }
-  uint8_t* const stage = (uint8_t*)c->cb_stage_h;
-  uint8_t* const h_non = stage + nb * img;
-  struct Scrub {  // the images hold the witnesses, the pads and the blinding rows
-    uint8_t* p;
-    size_t n;
-    ~Scrub() { explicit_bzero(p, n); }
-  } scrub{stage, used};
-  // the host half, statement by statement in index order: all draws of statement b from rng[b]
-  for (size_t b = 0; b < nb; ++b) {
-    char err[256] = {0};
-    const int rc = ligero_layout_host(field, k, g, p, (const elt_t*)h_W[b], subfield_boundary, h_lqc, rng[b], user(b), 0, p.nrow, (elt_t*)(stage + b * img),
-                                      h_non + b * ncols * 32, err, c->rng_exact != 0);
-    if (rc) return lf_fail(c, rc, "%s (statement %zu)", err, b);
-  }
-  const double tv1 = verbose ? clk() : 0;
-  // After a failed enqueue the stream may still read the staging memory: wait before it is scrubbed
-  auto fail = [&](int rc) {
-    (void)hipStreamSynchronize(c->stream);
-    return drop(rc);
-  };
-  const size_t tb = p.nrow * ld * 16, lb = 2 * ncols * 32;
-  elt_t* d_T[LFGPU_SC_BATCH_MAX];
-  void* d_L[LFGPU_SC_BATCH_MAX];
-  for (size_t b = 0; b < nb; ++b) {
-    lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
-    out[b] = pr;
-    pr->c = c;
-    pr->field = field;
-    pr->k = k;
-    pr->p = p;
-    pr->d_T = nullptr;
-    pr->d_layers = nullptr;
-    pr->nonces.assign(h_non + b * ncols * 32, h_non + (b + 1) * ncols * 32);
-    if (lf_pool_get(c, tb, (void**)&pr->d_T) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: tableau alloc (statement %zu)", b));
-    pr->T_bytes = tb;
-    if (lf_pool_get(c, lb, (void**)&pr->d_layers) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: layers alloc (statement %zu)", b));
-    pr->L_bytes = lb;
-    pr->row_lo = 0;
-    pr->row_hi = p.nrow;
-    d_T[b] = pr->d_T;
-    d_L[b] = pr->d_layers;
-  }
-  void* d_non = nullptr;
-  int rc = lf_scratch3(c, nb * ncols * 32, &d_non);
-  if (rc) return fail(rc);
-  if (hipMemcpyAsync(d_non, h_non, nb * ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-    return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_batch: nonce upload failed"));
-  for (size_t b = 0; b < nb; ++b)
-    if (hipMemcpy2DAsync(d_T[b], ld * 16, stage + b * img, hw * 16, hw * 16, p.nrow, hipMemcpyHostToDevice, c->stream) != hipSuccess)
-      return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_batch: upload failed (statement %zu)", b));
-  if ((rc = ligero_extend_batch(c, field, k, p, nb, d_T))) return fail(rc);
-  double tv2 = 0;
-  if (verbose) {
-    (void)hipStreamSynchronize(c->stream);
-    tv2 = clk();
-  }
-  // (ends with the one stream synchronise of the call: the uploads above are over when it returns)
-  if ((rc = lfgpu_column_commit_batch(c, field, p.nrow, ld, p.dblock, ncols, nb, (const void* const*)d_T, d_non, d_L, roots_out))) return fail(rc);
-  if (verbose)
-    fprintf(stderr, "lfgpu ligero_commit_batch: %zu x %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
-            nb, p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, clk() - tv2);
-  return LFGPU_OK;
+  return lig::layout(lig::Host16{field, k, &g}, *pp, (const elt_t*)h_W, subfield_boundary, h_lqc, rng, user, false, row_lo, row_hi, (elt_t*)h_rows, h_nonces, err);
 }
 
 // ------------------------------------------------------------------ rows sharded over the GPUs of a node
@@ -649,16 +186,16 @@ void lf_record_rng(lfgpu_rng_fn rng, void* rng_user, std::vector<uint8_t>* rec, 
   *fn = record_fn;
   *user = r;
 }
-static int layout_sharded_host(int field, int k, const GfHostCtx* g, const lfgpu_ligero_param& p, const void* h_W, size_t subfield_boundary,
-                               const size_t* h_lqc, lfgpu_rng_fn rng, void* user, const lfgpu_comm_ops* cm, bool exact, size_t row_lo, size_t row_hi,
-                               elt_t* H, uint8_t* nonces, char* err) {
+static int layout_sharded_host(const lig::Host16& hp, const lfgpu_ligero_param& p, const void* h_W, size_t subfield_boundary, const size_t* h_lqc,
+                               lfgpu_rng_fn rng, void* user, const lfgpu_comm_ops* cm, bool exact, size_t row_lo, size_t row_hi, elt_t* H, uint8_t* nonces,
+                               char* err) {
   // the RandomEngine is ONE sequential stream (ligero_prover.h:171-270, merkle_commitment.h:52-54): rank 0 draws all of it
   // (recorded while it lays out its own slab), the other ranks replay it and keep their rows
   std::vector<uint8_t> stream;
   LF_SCRUB_ON_EXIT(stream);
   if (cm->rank == 0) {  // rank 0 lays out its own slab while it draws: one pass, and the others wait for nothing else
     RecordRng rec{rng, user, &stream};
-    const int rc = ligero_layout_host(field, k, g, p, (const elt_t*)h_W, subfield_boundary, h_lqc, record_fn, &rec, row_lo, row_hi, H, nonces, err, exact);
+    const int rc = lig::layout(hp, p, (const elt_t*)h_W, subfield_boundary, h_lqc, record_fn, &rec, exact, row_lo, row_hi, H, nonces, err);
     const bool sent = lf_comm_bcast_blob(cm, stream) == LFGPU_OK;  // even after a failed layout: the others are waiting in the broadcast
     if (rc) return rc;
     if (!sent) {
@@ -672,7 +209,7 @@ static int layout_sharded_host(int field, int k, const GfHostCtx* g, const lfgpu
     return LFGPU_ERR_HIP;
   }
   ReplayRng rep{&stream, 0, false};
-  const int rc = ligero_layout_host(field, k, g, p, (const elt_t*)h_W, subfield_boundary, h_lqc, replay_fn, &rep, row_lo, row_hi, H, nonces, err, exact);
+  const int rc = lig::layout(hp, p, (const elt_t*)h_W, subfield_boundary, h_lqc, replay_fn, &rep, exact, row_lo, row_hi, H, nonces, err);
   if (rc) return rc;
   if (rep.dry || rep.pos != stream.size()) {
     snprintf(err, 256, "ligero (sharded): the replayed random stream does not match the layout (%zu of %zu bytes)", rep.pos, stream.size());
@@ -691,7 +228,7 @@ extern "C" int lfgpu_ligero_layout_rows_sharded(int field, int k, const lfgpu_li
   LF_TRY(lfgpu_ligero_row_shard(pp, cm->rank, cm->world, &lo, &hi));
   if (hi > lo && !h_rows) return LFGPU_ERR_ARG;
   char err[256] = {0};
-  return layout_sharded_host(field, k, &g, *pp, h_W, subfield_boundary, h_lqc, rng, user, cm, false, lo, hi, (elt_t*)h_rows, h_nonces, err);
+  return layout_sharded_host(lig::Host16{field, k, &g}, *pp, h_W, subfield_boundary, h_lqc, rng, user, cm, false, lo, hi, (elt_t*)h_rows, h_nonces, err);
 }
 
 // host-only check of a caller's hooks
@@ -901,11 +438,7 @@ __global__ void a_rows_sparse_batch_kernel(u32 r, u32 w, size_t ld, const u64* _
 // ---- the width policy of ligero_slab.h for the two 16-byte fields: it wraps the entry points and kernels that exist and carries
 // the field.  These steps upload their host vectors themselves: lfgpu_rows_axpy and lfgpu_gather_columns end with a synchronise,
 // a short sparse list goes through the pinned staging ring without one.
-struct L16 {
-  using E = elt_t;
-  int field, k;
-  E add(E a, E b) const { return h_add(field, a, b); }
-  static bool is_zero(E a) { return (a.lo | a.hi) == 0; }
+struct L16 : lig::Host16 {
   int rows_axpy(lfgpu_ctx* c, size_t nrows, size_t n, E* d_y, const E* h_u, const E* d_T, size_t ld) const {
     return lfgpu_rows_axpy(c, field, nrows, n, d_y, (const uint64_t*)h_u, d_T, ld);
   }
@@ -952,13 +485,203 @@ struct L16 {
     return lfgpu_gather_columns(c, nrow, ld, col0, d_T, h_idx, nreq, d_req);
   }
   int rs_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, E* d, size_t ld) const { return lf_rs_rows(c, field, k, nrow, n, m, d, ld); }
+  // GF(2^128) has the one-launch kernel (rows up to the LDS-resident size); Fp128 goes group by group
+  int rs_rows_mixed(lfgpu_ctx* c, size_t nrow, size_t n1, size_t n2, size_t lo2, size_t hi2, size_t m, E* d, size_t ld) const {
+    return field == LFGPU_FIELD_GF2_128 ? lf_gf_rs_rows_mixed(c, k, nrow, n1, n2, lo2, hi2, m, d, ld) : (int)LFGPU_ERR_UNSUPPORTED;
+  }
   int column_leaves(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out) const {
     return lfgpu_column_leaves(c, field, nrow, ld, col0, ncols, d_T, d_nonces, d_out);
   }
 };
-static L16 policy16(const lfgpu_ligero_prover* pr) { return L16{pr->field, pr->k}; }
+static L16 policy16(const lfgpu_ligero_prover* pr) { return L16{{pr->field, pr->k, nullptr}}; }
+// ... for a commit: with the subfield tables of the host layout (null for an unknown k)
+static L16 policy16(lfgpu_ctx* c, int field, int k) { return L16{{field, k, field == LFGPU_FIELD_GF2_128 ? lf_gf_ctx(c, k) : nullptr}}; }
+static lfgpu_ligero_prover* new_prover16(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, const lfgpu_comm_ops* cm) {
+  lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
+  pr->init(c, p, cm);
+  pr->field = field;
+  pr->k = k;
+  return pr;
+}
 
-// (the sharded commit stands below the policy: its steps 3 and 4 are lig::column_commit_sharded over L16)
+extern "C" int lfgpu_ligero_encode_rows(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, size_t row_lo, size_t row_hi,
+                                        const void* h_rows, void* d_slab) {
+  if (!c || !pp || row_lo > row_hi || row_hi > pp->nrow || (row_hi > row_lo && (!h_rows || !d_slab)))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_encode_rows: bad argument");
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_encode_rows: field");
+  if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, k)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_encode_rows: subfield_log_bits must be 4 or 5");
+  LF_HIP(c, hipSetDevice(c->device));
+  if (row_hi > row_lo)
+    LF_HIP(c, hipMemcpy2DAsync(d_slab, pp->block_enc * 16, h_rows, pp->dblock * 16, pp->dblock * 16, row_hi - row_lo, hipMemcpyHostToDevice, c->stream));
+  const int rc = lig::extend_slab(c, policy16(c, field, k), *pp, row_lo, row_hi, (elt_t*)d_slab);
+  LF_HIP(c, hipStreamSynchronize(c->stream));  // h_rows is the caller's: the upload must be over before we return
+  return rc;
+}
+
+// the single-GPU commit is the slab [0, nrow) of the sharded one
+extern "C" int lfgpu_ligero_commit(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const void* h_W,
+                                   size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng, void* user,
+                                   uint8_t root_out[32], lfgpu_ligero_prover** out) {
+  if (!c || !root_out || !out || !ligero_args_ok(field, k, pp, h_W, h_lqc, rng))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit: bad argument (null pointer, field or subfield_log_bits)");
+  const lfgpu_ligero_param& p = *pp;
+  LF_HIP(c, hipSetDevice(c->device));
+  const L16 pol = policy16(c, field, k);
+  const double t0 = lig::clock_ms();
+  std::unique_ptr<lfgpu_ligero_prover> pr(new_prover16(c, field, k, p, nullptr));
+  std::vector<elt_t> H(p.nrow * p.dblock);
+  LF_SCRUB_ON_EXIT(H);
+  char err[256] = {0};
+  const int rc = lig::layout(pol, p, (const elt_t*)h_W, subfield_boundary, h_lqc, rng, user, c->rng_exact != 0, 0, p.nrow, H.data(), pr->nonces.data(), err);
+  if (rc) return lf_fail(c, rc, "%s", err);
+  LF_TRY(lig::commit_rows(pr.get(), pol, H.data(), t0, root_out));
+  *out = pr.release();
+  return LFGPU_OK;
+}
+
+// ------------------------------------------------------------------ nb commits of one shape in one chain of dispatches
+// statements per launch chain of the batched RS encode: the Fp128 kernels carry the rows of a group on gridDim.y (<= 65535) and
+// the convolution scratch is nb * rows * P * 16 bytes (<= LF_CB_SCRATCH_CAP); LFGPU_CB_CHUNK overrides (read once)
+static size_t commit_batch_chunk(int field, const lfgpu_ligero_param& p, size_t nb) {
+  static const long env = getenv("LFGPU_CB_CHUNK") ? atol(getenv("LFGPU_CB_CHUNK")) : 0;
+  size_t chunk = nb;
+  if (field == LFGPU_FIELD_FP128) {
+    const size_t g_lo = std::min(p.idot, p.iquad), g_hi = std::max(p.idot, p.iquad) + 1;
+    const size_t rows = std::max<size_t>(1, std::max(std::max(g_lo, g_hi - g_lo), p.nrow - g_hi));  // the largest row group
+    size_t P = 1;
+    while (P < p.block_enc) P <<= 1;
+    chunk = std::min(chunk, std::min<size_t>(65535 / rows, LF_CB_SCRATCH_CAP / (rows * P * 16)));
+  }
+  if (env > 0) chunk = std::min(chunk, (size_t)env);
+  return std::max<size_t>(chunk, 1);
+}
+// the RS extension of nb tableaux whose un-encoded images are on the device
+static int ligero_extend_batch(lfgpu_ctx* c, const L16& pol, const lfgpu_ligero_param& p, size_t nb, elt_t* const* d_T) {
+  const int field = pol.field, k = pol.k;
+  const size_t ld = p.block_enc;
+  const size_t lo2 = std::min(p.idot, p.iquad), hi2 = std::max(p.idot, p.iquad) + 1;
+  if (hi2 - lo2 != 2) return lf_fail(c, LFGPU_ERR_ARG, "ligero: IDOT and IQUAD rows must be adjacent");
+  const size_t chunk = commit_batch_chunk(field, p, nb);
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0);
+    if (field == LFGPU_FIELD_GF2_128) {
+      const int rc = lf_gf_rs_rows_mixed_batch(c, k, cb, d_T + b0, p.nrow, p.block, p.dblock, lo2, hi2, p.block_enc, ld);
+      if (rc != LFGPU_ERR_UNSUPPORTED) {
+        LF_TRY(rc);
+        continue;
+      }
+      // rows longer than the LDS-resident kernel: the single path's encoder, statement by statement
+      for (size_t b = b0; b < b0 + cb; ++b) LF_TRY(lig::extend_slab(c, pol, p, 0, p.nrow, d_T[b]));
+    } else if (cb * std::max(hi2, p.nrow - hi2) > 65535) {  // (cb = 1) a row group of one statement overflows a launch: the single path's encoder
+      for (size_t b = b0; b < b0 + cb; ++b) LF_TRY(lig::extend_slab(c, pol, p, 0, p.nrow, d_T[b]));
+    } else {
+      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, 0, lo2, p.block, p.block_enc, ld));
+      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, lo2, hi2 - lo2, p.dblock, p.block_enc, ld));
+      LF_TRY(lf_fp_rs_rows_batch(c, cb, d_T + b0, hi2, p.nrow - hi2, p.block, p.block_enc, ld));
+    }
+  }
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_ligero_commit_batch(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, size_t nb, const void* const* h_W,
+                                         size_t subfield_boundary, const size_t* h_lqc, const lfgpu_rng_fn* rng, void* const* rng_user,
+                                         uint8_t* roots_out, lfgpu_ligero_prover** out) {
+  if (!c || !pp || !h_W || !rng || !roots_out || !out) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: null argument");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: nb = %zu, a batch holds 1..%d statements", nb, LFGPU_SC_BATCH_MAX);
+  for (size_t b = 0; b < nb; ++b)
+    if (!ligero_args_ok(field, k, pp, h_W[b], h_lqc, rng[b]))
+      return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch: bad argument for statement %zu (null pointer, field or subfield_log_bits)", b);
+  for (size_t b = 0; b < nb; ++b) out[b] = nullptr;
+  auto user = [&](size_t b) { return rng_user ? rng_user[b] : nullptr; };
+  auto drop = [&](int rc) {  // no prover is returned: their buffers go back to the pool scrubbed (lfgpu_ligero_free)
+    for (size_t b = 0; b < nb; ++b) {
+      if (out[b]) lfgpu_ligero_free(out[b]);
+      out[b] = nullptr;
+    }
+    return rc;
+  };
+  static const int batched = getenv("LFGPU_COMMIT_BATCH") ? atoi(getenv("LFGPU_COMMIT_BATCH")) : 1;
+  if (!batched) {  // the A/B switch: the same semantics over the single-statement device path
+    for (size_t b = 0; b < nb; ++b) {
+      const int rc = lfgpu_ligero_commit(c, field, k, pp, h_W[b], subfield_boundary, h_lqc, rng[b], user(b), roots_out + 32 * b, &out[b]);
+      if (rc) {
+        out[b] = nullptr;
+        return drop(rc);
+      }
+    }
+    return LFGPU_OK;
+  }
+  const L16 pol = policy16(c, field, k);
+  const lfgpu_ligero_param& p = *pp;
+  const size_t ld = p.block_enc, hw = p.dblock, ncols = p.block_ext;
+  LF_HIP(c, hipSetDevice(c->device));
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  const double tv0 = lig::clock_ms();
+  // pinned staging: [nb][nrow][dblock] un-encoded images, then [nb][ncols][32] nonces.  The uploads of the previous call are
+  // over (every call ends with a stream synchronise), so the memory may be rewritten at once.
+  const size_t img = p.nrow * hw * 16, used = nb * (img + ncols * 32);
+  if (c->cb_stage_bytes < used) {
+    if (c->cb_stage_h) (void)hipHostFree(c->cb_stage_h);  // (scrubbed after the call that filled it)
+    c->cb_stage_h = nullptr;
+    c->cb_stage_bytes = 0;
+    if (hipHostMalloc(&c->cb_stage_h, used, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      c->cb_stage_h = nullptr;
+      return lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: %zu bytes of pinned staging", used);
+    }
+    c->cb_stage_bytes = used;
+  }
+  uint8_t* const stage = (uint8_t*)c->cb_stage_h;
+  uint8_t* const h_non = stage + nb * img;
+  struct Scrub {  // the images hold the witnesses, the pads and the blinding rows
+    uint8_t* p;
+    size_t n;
+    ~Scrub() { explicit_bzero(p, n); }
+  } scrub{stage, used};
+  // the host half, statement by statement in index order: all draws of statement b from rng[b]
+  for (size_t b = 0; b < nb; ++b) {
+    char err[256] = {0};
+    const int rc = lig::layout(pol, p, (const elt_t*)h_W[b], subfield_boundary, h_lqc, rng[b], user(b), c->rng_exact != 0, 0, p.nrow, (elt_t*)(stage + b * img),
+                               h_non + b * ncols * 32, err);
+    if (rc) return lf_fail(c, rc, "%s (statement %zu)", err, b);
+  }
+  const double tv1 = lig::clock_ms();
+  // After a failed enqueue the stream may still read the staging memory: wait before it is scrubbed
+  auto fail = [&](int rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return drop(rc);
+  };
+  elt_t* d_T[LFGPU_SC_BATCH_MAX];
+  void* d_L[LFGPU_SC_BATCH_MAX];
+  int rc = LFGPU_OK;
+  for (size_t b = 0; b < nb; ++b) {
+    lfgpu_ligero_prover* pr = out[b] = new_prover16(c, field, k, p, nullptr);
+    pr->nonces.assign(h_non + b * ncols * 32, h_non + (b + 1) * ncols * 32);
+    if ((rc = pr->alloc())) return fail(rc);
+    d_T[b] = pr->d_T;
+    d_L[b] = pr->d_layers;
+  }
+  void* d_non = nullptr;
+  if ((rc = lf_scratch3(c, nb * ncols * 32, &d_non))) return fail(rc);
+  if (hipMemcpyAsync(d_non, h_non, nb * ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_batch: nonce upload failed"));
+  for (size_t b = 0; b < nb; ++b)
+    if (hipMemcpy2DAsync(d_T[b], ld * 16, stage + b * img, hw * 16, hw * 16, p.nrow, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+      return fail(lf_fail(c, LFGPU_ERR_HIP, "ligero_commit_batch: upload failed (statement %zu)", b));
+  if ((rc = ligero_extend_batch(c, pol, p, nb, d_T))) return fail(rc);
+  double tv2 = 0;
+  if (verbose) {
+    (void)hipStreamSynchronize(c->stream);
+    tv2 = lig::clock_ms();
+  }
+  // (ends with the one stream synchronise of the call: the uploads above are over when it returns)
+  if ((rc = lfgpu_column_commit_batch(c, field, p.nrow, ld, p.dblock, ncols, nb, (const void* const*)d_T, d_non, d_L, roots_out))) return fail(rc);
+  if (verbose)
+    fprintf(stderr, "lfgpu ligero_commit_batch: %zu x %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
+            nb, p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, lig::clock_ms() - tv2);
+  return LFGPU_OK;
+}
+
 extern "C" int lfgpu_ligero_commit_sharded(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const void* h_W, size_t subfield_boundary,
                                            const size_t* h_lqc, lfgpu_rng_fn rng, void* user, const lfgpu_comm_ops* cm, uint8_t root_out[32],
                                            lfgpu_ligero_prover** out) {
@@ -968,52 +691,19 @@ extern "C" int lfgpu_ligero_commit_sharded(lfgpu_ctx* c, int field, int k, const
   const lfgpu_ligero_param& p = *pp;
   if (p.ildt != 0 || p.idot != 1 || p.iquad != 2 || p.iw != 3) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: row order");
   LF_HIP(c, hipSetDevice(c->device));
-  const GfHostCtx* g = field == LFGPU_FIELD_GF2_128 ? lf_gf_ctx(c, k) : nullptr;
-  if (field == LFGPU_FIELD_GF2_128 && !g) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: k");
-  const int world = cm->world, rank = cm->rank;
-  lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
-  pr->c = c;
-  pr->field = field;
-  pr->k = k;
-  pr->p = p;
-  pr->d_T = nullptr;
-  pr->d_layers = nullptr;
-  pr->nonces.resize(p.block_ext * 32);
-  pr->sharded = true;
-  pr->comm = *cm;
-  pr->spans.resize(world);
-  for (int q = 0; q < world; ++q) (void)lfgpu_ligero_row_shard(&p, q, world, &pr->spans[q].first, &pr->spans[q].second);
-  pr->row_lo = pr->spans[rank].first;
-  pr->row_hi = pr->spans[rank].second;
-  auto fail = [&](int rc) {
-    lfgpu_ligero_free(pr);
-    return rc;
-  };
-  const size_t nr = pr->row_hi - pr->row_lo, ld = p.block_enc, ncols = p.block_ext;
-  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-  const double tv0 = lig::clock_ms();
-  // 1. host layout of this rank's slab from the one random stream
-  std::vector<elt_t> H(std::max<size_t>(nr, 1) * p.dblock);
+  const L16 pol = policy16(c, field, k);
+  if (field == LFGPU_FIELD_GF2_128 && !pol.g) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_sharded: k");
+  const double t0 = lig::clock_ms();
+  std::unique_ptr<lfgpu_ligero_prover> pr(new_prover16(c, field, k, p, cm));
+  // host layout of this rank's slab from the one random stream; then the slab is encoded (rows are independent) and the columns go
+  // through all_to_all, local leaves, all_gather of the digests and the tree on every rank
+  std::vector<elt_t> H(std::max<size_t>(pr->row_hi - pr->row_lo, 1) * p.dblock);
   LF_SCRUB_ON_EXIT(H);
-  {
-    char err[256] = {0};
-    const int rc = layout_sharded_host(field, k, g, p, h_W, subfield_boundary, h_lqc, rng, user, cm, c->rng_exact != 0, pr->row_lo, pr->row_hi, H.data(),
-                                       pr->nonces.data(), err);
-    if (rc) return fail(lf_fail(c, rc, "%s", err));
-  }
-  const double tv1 = lig::clock_ms();
-  if (verbose) fprintf(stderr, "lfgpu ligero_commit_sharded rank %d/%d: rows [%zu, %zu): layout + stream %.2f ms\n", rank, world, pr->row_lo, pr->row_hi, tv1 - tv0);
-  // 2. RS-extend the slab: rows are independent, no collective
-  const size_t tb = std::max<size_t>(nr, 1) * ld * 16, lb = 2 * ncols * 32;
-  if (lf_pool_get(c, tb, (void**)&pr->d_T) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: slab alloc"));
-  pr->T_bytes = tb;
-  if (lf_pool_get(c, lb, (void**)&pr->d_layers) != LFGPU_OK) return fail(lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_sharded: layers alloc"));
-  pr->L_bytes = lb;
-  int rc = nr ? ligero_encode_slab(c, field, k, p, pr->row_lo, pr->row_hi, H.data(), pr->d_T) : LFGPU_OK;
-  if (rc) return fail(rc);
-  // 3. + 4. the columns: all_to_all, local leaves, all_gather of the digests, the tree on every rank (it prints its own phases)
-  if ((rc = lig::column_commit_sharded(pr, policy16(pr), cm, tv1, root_out))) return fail(rc);
-  *out = pr;
+  char err[256] = {0};
+  const int rc = layout_sharded_host(pol, p, h_W, subfield_boundary, h_lqc, rng, user, cm, c->rng_exact != 0, pr->row_lo, pr->row_hi, H.data(), pr->nonces.data(), err);
+  if (rc) return lf_fail(c, rc, "%s", err);
+  LF_TRY(lig::commit_rows(pr.get(), pol, H.data(), t0, root_out));
+  *out = pr.release();
   return LFGPU_OK;
 }
 
@@ -1025,7 +715,7 @@ extern "C" int lfgpu_ligero_inner_product_rows(lfgpu_ctx* c, int field, size_t w
   if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "ligero_inner_product_rows: field");
   LF_HIP(c, hipSetDevice(c->device));
   const elt_t sc = scale ? elt_t{scale[0], scale[1]} : elt_t{0, 0};
-  return lig::a_rows(c, L16{field, 0}, w, r, ld, nrows, (const elt_t*)d_dense, ndense, sc, h_idx, (const elt_t*)h_val, nsparse, (elt_t*)d_rows);
+  return lig::a_rows(c, L16{{field, 0, nullptr}}, w, r, ld, nrows, (const elt_t*)d_dense, ndense, sc, h_idx, (const elt_t*)h_val, nsparse, (elt_t*)d_rows);
 }
 
 extern "C" int lfgpu_ligero_low_degree_proof(lfgpu_ligero_prover* pr, const void* h_u, void* h_y) {
@@ -1074,17 +764,8 @@ extern "C" int lfgpu_ligero_prover_from_slab(lfgpu_ctx* c, int field, int k, con
   if (!c || !pp || !out || row_lo > row_hi || row_hi > pp->nrow || (row_hi > row_lo && !d_slab))
     return lf_fail(c, LFGPU_ERR_ARG, "ligero_prover_from_slab: bad argument");
   if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prover_from_slab: field");
-  lfgpu_ligero_prover* pr = new lfgpu_ligero_prover();
-  pr->c = c;
-  pr->field = field;
-  pr->k = k;
-  pr->p = *pp;
-  pr->d_T = (elt_t*)d_slab;
-  pr->d_layers = (uint8_t*)d_layers;
-  pr->row_lo = row_lo;
-  pr->row_hi = row_hi;
-  pr->owns = false;
-  if (h_nonces) pr->nonces.assign(h_nonces, h_nonces + 32 * pp->block_ext);
+  lfgpu_ligero_prover* pr = new_prover16(c, field, k, *pp, nullptr);
+  pr->borrow(row_lo, row_hi, (elt_t*)d_slab, (uint8_t*)d_layers, h_nonces);
   *out = pr;
   return LFGPU_OK;
 }

@@ -1,22 +1,27 @@
-// ligero_slab.h -- the prover that holds a slab of a Ligero tableau, and its prove-side calls, written once over a width policy L.
+// ligero_slab.h -- the prover that holds a slab of a Ligero tableau: its record, its commit side and its prove-side calls, written
+// once over a width policy L.
 //
 // ligero.hip (GF(2^128) and Fp128, 16-byte elements) and zk256.hip (Fp256Base, 32-byte elements) each supply a policy and
-// instantiate what is here.  Reference: LigeroProver::low_degree_proof / dot_proof / quadratic_proof / compute_req
-// (lib/ligero/ligero_prover.h:281-351), inner_product_vector + layout_Aext (lib/ligero/ligero_param.h:382-430), MerkleCommitment
-// (lib/merkle/merkle_commitment.h:50-73).
+// instantiate what is here.  Reference: LigeroProver::commit / low_degree_proof / dot_proof / quadratic_proof / compute_req
+// (lib/ligero/ligero_prover.h:58-79,281-351), inner_product_vector + layout_Aext (lib/ligero/ligero_param.h:382-430),
+// MerkleCommitment (lib/merkle/merkle_commitment.h:50-73).
 //
-// A policy is a plain struct with no virtual calls.  It supplies the element type E, the host add / is_zero, and
-// the device steps the bodies call; each step uploads its own host vectors the way its width always has (and synchronises where
-// it always has), so nothing below tests which width it serves:
+// A policy is a plain struct with no virtual calls.  It derives from its host policy (ligero_layout.h: the element
+// type E, the field id, host add / is_zero, the RandomEngine draws) and adds the device steps the bodies call; each step uploads
+// its own host vectors the way its width always has (and synchronises where it always has), so nothing below tests which width
+// it serves:
 //   rows_axpy      y[j] += sum_i u[i] T[i][j], u on the host
 //   rows_vaxpy     y[j] = T0[j] + sum_i A[i][j] T[i][j]
 //   quad_combo     y[j] = Tq[j] + sum_i u[i] (Z_i[j] - X_i[j] Y_i[j])
 //   a_rows_clear / a_rows_dense / a_rows_sparse   the pieces of a_rows below; the sparse lists are on the host
 //   gather_columns req[i][j] = T[i][col0 + idx[j]], idx on the host
 //   rs_rows        nrow rows of n values extended to m, in place
+//   rs_rows_mixed  a slab's three row groups in one launch where the width has such a kernel, else LFGPU_ERR_UNSUPPORTED
 //   column_leaves  the leaf digests of ncols columns
-// What differs by design stays in the two files: the host layouts (the order and batching of the RandomEngine draws), the
-// one-GPU commit bodies, the Reed-Solomon encoding of a fresh tableau, the batched entry points (16-byte only) and every kernel.
+// The commit side: Slab::init / alloc build the record, extend_slab Reed-Solomon-encodes a fresh slab, commit_rows uploads a
+// slab's host image, encodes it and commits the columns (one GPU, or the sharded exchange).  What stays in the two files: the
+// entry points with their argument checks and their own layout call (ligero_layout.h; the sharded record / replay of the engine),
+// the batched entry points (16-byte only) and every kernel.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -27,6 +32,7 @@
 #include <vector>
 
 #include "ctx.h"
+#include "ligero_layout.h"
 
 // Everything below has internal linkage (as in zk_proto.h): each file that includes this header wants its own copy.
 namespace lig {
@@ -50,6 +56,41 @@ struct Slab {
   bool has(size_t i) const { return i >= row_lo && i < row_hi; }
   E* row(size_t i) const { return d_T + (i - row_lo) * p.block_enc; }
   Slab() = default;
+  // the record of a commit: parameters, room for the nonces and the slab -- [0, nrow), or with a communicator this rank's rows
+  // of lfgpu_ligero_row_shard next to every rank's span
+  void init(lfgpu_ctx* ctx, const lfgpu_ligero_param& param, const lfgpu_comm_ops* cm) {
+    c = ctx;
+    p = param;
+    nonces.resize(32 * p.block_ext);
+    row_lo = 0;
+    row_hi = p.nrow;
+    if (!cm) return;
+    sharded = true;
+    comm = *cm;
+    spans.resize(cm->world);
+    for (int q = 0; q < cm->world; ++q) (void)lfgpu_ligero_row_shard(&p, q, cm->world, &spans[q].first, &spans[q].second);
+    row_lo = spans[cm->rank].first;
+    row_hi = spans[cm->rank].second;
+  }
+  // tableau and Merkle heap: buffers of an earlier prover with the same shape where there is one (the context's pool)
+  int alloc() {
+    T_bytes = std::max<size_t>(row_hi - row_lo, 1) * p.block_enc * sizeof(E);
+    L_bytes = 2 * p.block_ext * 32;
+    if (lf_pool_get(c, T_bytes, (void**)&d_T) != LFGPU_OK || lf_pool_get(c, L_bytes, (void**)&d_layers) != LFGPU_OK)
+      return lf_fail(c, LFGPU_ERR_NOMEM, "ligero commit: tableau / Merkle heap alloc (rows [%zu, %zu))", row_lo, row_hi);
+    return LFGPU_OK;
+  }
+  // ... or rows [lo, hi) that the caller has encoded in a buffer of its own; layers / h_nonces: the Merkle heap and the nonces of
+  // the whole commitment, may be null (then `open` answers that the prover holds no commitment)
+  void borrow(size_t lo, size_t hi, E* T, uint8_t* layers, const uint8_t* h_nonces) {
+    row_lo = lo;
+    row_hi = hi;
+    d_T = T;
+    d_layers = layers;
+    owns = false;
+    if (h_nonces) nonces.assign(h_nonces, h_nonces + 32 * p.block_ext);
+    else nonces.clear();
+  }
   Slab(const Slab&) = delete;
   Slab& operator=(const Slab&) = delete;
   ~Slab() {
@@ -265,10 +306,11 @@ int open(Slab<typename L::E>* pr, const L& pol, const size_t* idx, typename L::E
 // (lfgpu_merkle_build_tree ends with a stream synchronise).  Byte-oriented: only the element size and the leaf hash are the policy's.
 // t_begin: clock_ms() when the caller began to upload and encode the slab, for the LFGPU_VERBOSE phase line.
 template <class L>
-int column_commit_sharded(Slab<typename L::E>* pr, const L& pol, const lfgpu_comm_ops* cm, double t_begin, uint8_t root_out[32]) {
+int column_commit_sharded(Slab<typename L::E>* pr, const L& pol, double t_begin, uint8_t root_out[32]) {
   constexpr size_t esz = sizeof(typename L::E);
   lfgpu_ctx* c = pr->c;
   const lfgpu_ligero_param& p = pr->p;
+  const lfgpu_comm_ops* cm = &pr->comm;
   const int world = cm->world, rank = cm->rank;
   const size_t nr = pr->row_hi - pr->row_lo, ld = p.block_enc, ncols = p.block_ext;
   static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
@@ -344,6 +386,64 @@ int column_commit_sharded(Slab<typename L::E>* pr, const L& pol, const lfgpu_com
     fprintf(stderr, "lfgpu ligero column commit (sharded) rank %d/%d: rows [%zu, %zu) of %zu-byte elements: upload + RS encode + pack %.2f ms | all_to_all %.2f | leaves + all_gather + tree %.2f\n",
             rank, world, pr->row_lo, pr->row_hi, esz, tv2 - t_begin, tv3 - tv2, clock_ms() - tv3);
   return done(LFGPU_OK);
+}
+// The Reed-Solomon extension of rows [row_lo, row_hi) of a fresh tableau whose un-encoded image stands in d_slab: rows IDOT /
+// IQUAD carry dblock values, every other row block (ligero_prover.h:175,184,203,210,237).  The dblock rows form one contiguous
+// global range [idot, iquad + 1), clipped to the slab: one mixed launch where the policy has one, else group by group.
+template <class L>
+int extend_slab(lfgpu_ctx* c, const L& pol, const lfgpu_ligero_param& p, size_t row_lo, size_t row_hi, typename L::E* d_slab) {
+  const size_t nr = row_hi - row_lo, ld = p.block_enc;
+  if (nr == 0) return LFGPU_OK;
+  const size_t g_lo = std::min(p.idot, p.iquad), g_hi = std::max(p.idot, p.iquad) + 1;
+  if (g_hi - g_lo != 2) return lf_fail(c, LFGPU_ERR_ARG, "ligero: IDOT and IQUAD rows must be adjacent");
+  const size_t lo2 = std::min(std::max(g_lo, row_lo), row_hi) - row_lo, hi2 = std::min(std::max(g_hi, row_lo), row_hi) - row_lo;
+  const int rc = pol.rs_rows_mixed(c, nr, p.block, p.dblock, lo2, hi2, p.block_enc, d_slab, ld);
+  if (rc != LFGPU_ERR_UNSUPPORTED) return rc;
+  auto group = [&](size_t a, size_t b, size_t n) { return b > a ? pol.rs_rows(c, b - a, n, p.block_enc, d_slab + a * ld, ld) : (int)LFGPU_OK; };
+  LF_TRY(group(0, lo2, p.block));
+  LF_TRY(group(lo2, hi2, p.dblock));
+  return group(hi2, nr, p.block);
+}
+
+// The device half of a commit: pr initialised (Slab::init, nonces drawn), H the un-encoded host image of its slab
+// ([row_hi - row_lo][dblock], only the first dblock columns are ever non-trivial).  Allocates, uploads, encodes (K3/K4) and
+// commits the columns (K5/K6): one GPU hashes its own columns, a sharded prover goes through the exchange above.  t_call:
+// clock_ms() when the caller began its layout, for the LFGPU_VERBOSE phase lines.  Both column commits end with a stream
+// synchronise, and so does every failure here: H is the caller's to scrub and free as soon as this returns.
+template <class L>
+int commit_rows(Slab<typename L::E>* pr, const L& pol, const typename L::E* H, double t_call, uint8_t root_out[32]) {
+  constexpr size_t esz = sizeof(typename L::E);
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  const size_t nr = pr->row_hi - pr->row_lo, ld = p.block_enc;
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  const double tv1 = clock_ms();
+  if (verbose && pr->sharded)
+    fprintf(stderr, "lfgpu ligero_commit_sharded rank %d/%d: rows [%zu, %zu): layout + stream %.2f ms\n", pr->comm.rank, pr->comm.world, pr->row_lo, pr->row_hi, tv1 - t_call);
+  auto run = [&]() -> int {
+    LF_TRY(pr->alloc());
+    if (nr) LF_HIP(c, hipMemcpy2DAsync(pr->d_T, ld * esz, H, p.dblock * esz, p.dblock * esz, nr, hipMemcpyHostToDevice, c->stream));
+    LF_TRY(extend_slab(c, pol, p, pr->row_lo, pr->row_hi, pr->d_T));  // rows are independent: no collective
+    if (pr->sharded) return column_commit_sharded(pr, pol, tv1, root_out);  // (it prints its own phases)
+    // the nonces go up behind the encode: in front of it, the encoder's first-use table uploads of a new shape take other copy
+    // paths in the runtime (4 more copy dispatches in the first Fp256Base commit of a context, profiles/ligero_commit/)
+    void* d_non = nullptr;
+    LF_TRY(lf_scratch3(c, p.block_ext * 32, &d_non));
+    LF_HIP(c, hipMemcpyAsync(d_non, pr->nonces.data(), p.block_ext * 32, hipMemcpyHostToDevice, c->stream));
+    double tv2 = 0;
+    if (verbose) {
+      (void)hipStreamSynchronize(c->stream);
+      tv2 = clock_ms();
+    }
+    LF_TRY(lfgpu_column_commit(c, pol.field, p.nrow, ld, p.dblock, p.block_ext, pr->d_T, d_non, pr->d_layers, root_out));
+    if (verbose)
+      fprintf(stderr, "lfgpu ligero_commit: %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
+              p.nrow, ld, p.block, p.dblock, tv1 - t_call, tv2 - tv1, clock_ms() - tv2);
+    return LFGPU_OK;
+  };
+  const int rc = run();
+  if (rc) (void)hipStreamSynchronize(c->stream);  // a copy out of H may still be pending
+  return rc;
 }
 }  // namespace
 }  // namespace lig

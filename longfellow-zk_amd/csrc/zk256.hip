@@ -21,7 +21,7 @@
 #include <memory>
 #include <string>
 
-#include "ligero_slab.h"  // the Ligero prover record and its prove side, over the policy L32 below
+#include "ligero_slab.h"  // the Ligero prover record, its commit and prove side (and the host layout), over the policy L32 below
 #include "zk_proto.h"  // F256 (the host field), the protocol layer and Wire32
 
 typedef elt32_t E;
@@ -1426,10 +1426,7 @@ namespace {
 // The width policy of ligero_slab.h for Fp256Base: the row kernels above, lfgpu_fp256_rs_encode_rows and lf_column_leaves32.  The
 // prover is bound by a latency chain of short launches, so these steps only enqueue: host vectors go to lf_scratch2
 // by plain asynchronous copies, and whoever reads the result back synchronises.  The one exception is a_rows_sparse.
-struct L32 {
-  using E = elt32_t;
-  static E add(const E& a, const E& b) { return fp256_add(a, b); }
-  static bool is_zero(const E& a) { return e32_is_zero(a); }
+struct L32 : lig::Host32 {
   static int rows_axpy(lfgpu_ctx* c, size_t nrows, size_t n, E* d_y, const E* h_u, const E* d_T, size_t ld) {
     void* du = nullptr;
     LF_TRY(lf_scratch2(c, nrows * 32 + 64, &du));
@@ -1478,121 +1475,28 @@ struct L32 {
     return LFGPU_OK;
   }
   static int rs_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, E* d, size_t ld) { return lfgpu_fp256_rs_encode_rows(c, nrow, n, m, d, ld); }
+  static int rs_rows_mixed(lfgpu_ctx*, size_t, size_t, size_t, size_t, size_t, size_t, E*, size_t) { return LFGPU_ERR_UNSUPPORTED; }  // group by group
   static int column_leaves(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out) {
     return lf_column_leaves32(c, nrow, ld, col0, ncols, d_T, d_nonces, d_out, 0);
   }
 };
 using Lig32 = lig::Slab<E>;  // the prover record: all rows on one GPU, or a slab with a communicator (lfgpu_zk_prover_set_comm above the size threshold)
 
-// the host half of LigeroProver::commit (ligero_prover.h:171-270 + merkle_commitment.h:52-54): every RandomEngine draw in the
-// reference's order (FpGeneric::sample and sample_subfield are the same function, fp_generic.h:360-376)
-int lig256_layout(const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user, E* H, uint8_t* nonces, char* err, bool exact) {
-  const size_t hw = p.dblock;
-  auto elts = [&](E* out, size_t n) {
-    if (exact) {  // one call per attempt, as FpGeneric::sample draws (fp_generic.h:360-371)
-      for (size_t i = 0; i < n; ++i) h256_sample_many(out + i, 1, [&](uint8_t* b, size_t nb) { rng(user, b, nb); });
-    } else {
-      h256_sample_many(out, n, [&](uint8_t* b, size_t nb) { rng(user, b, nb); });
-    }
-  };
-  auto row = [&](size_t i) { return H + i * hw; };
-  std::fill(H, H + p.nrow * hw, e32_zero());
-  elts(row(p.ildt), p.block);  // layout_blinding_rows (:171-205)
-  {
-    E* d = row(p.idot);
-    elts(d, p.dblock);
-    E sum = e32_zero();
-    for (size_t j = 0; j < p.w; ++j) sum = fp256_add(sum, d[p.r + j]);
-    d[p.r] = fp256_sub(d[p.r], sum);
-  }
-  {
-    E* q = row(p.iquad);
-    elts(q, p.dblock);
-    for (size_t j = 0; j < p.w; ++j) q[p.r + j] = e32_zero();
-  }
-  for (size_t i = 0; i < p.nwrow; ++i) {  // layout_witness_rows (:207-231)
-    E* t = row(i + p.iw);
-    elts(t, p.r);
-    const size_t max_col = std::min(p.w, p.nw - i * p.w);
-    for (size_t j = 0; j < max_col; ++j) t[p.r + j] = W[i * p.w + j];
-  }
-  const size_t iqx = p.iq, iqy = iqx + p.nqtriples, iqz = iqy + p.nqtriples;  // layout_quadratic_rows (:233-270)
-  for (size_t i = 0; i < p.nqtriples; ++i) {
-    elts(row(iqx + i), p.r);
-    elts(row(iqy + i), p.r);
-    elts(row(iqz + i), p.r);
-    for (size_t j = 0; j < p.w && j + i * p.w < p.nq; ++j) {
-      const size_t* l = &lqc[3 * (j + i * p.w)];
-      if (l[0] >= p.nw || l[1] >= p.nw || l[2] >= p.nw) {
-        snprintf(err, 256, "ligero_commit: lqc index >= nw");
-        return LFGPU_ERR_ARG;
-      }
-      if (!e32_eq(fp256_mul(W[l[0]], W[l[1]]), W[l[2]])) {
-        snprintf(err, 256, "ligero_commit: invalid quadratic constraints (ligero_prover.h:259-260)");
-        return LFGPU_ERR_ASSERT;
-      }
-      row(iqx + i)[j + p.r] = W[l[0]];
-      row(iqy + i)[j + p.r] = W[l[1]];
-      row(iqz + i)[j + p.r] = W[l[2]];
-    }
-  }
-  if (exact) for (size_t j = 0; j < p.block_ext; ++j) rng(user, nonces + 32 * j, 32);
-  else rng(user, nonces, 32 * p.block_ext);  // MerkleCommitment::commit: one nonce per leaf, after the layout
-  return LFGPU_OK;
-}
-
-// cm != nullptr (more than one rank; the caller has made every rank's `rng` yield the same bytes): every rank lays out the whole
-// host image (it is small next to the encoded tableau), keeps and encodes its row slab, and the columns are committed as in
-// lfgpu_ligero_commit_sharded (lig::column_commit_sharded): one all_to_all of the encoded columns, local leaves, all_gather of
-// the digests, the tree on every rank
+// cm != nullptr (more than one rank; the caller has made every rank's `rng` yield the same bytes): every rank consumes the whole
+// stream and lays out, keeps and encodes its own row slab (lig::layout), and the columns are committed as in
+// lfgpu_ligero_commit_sharded (lig::commit_rows)
 int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user, uint8_t root[32], Lig32** out,
                   const lfgpu_comm_ops* cm = nullptr) {
   if (p.ildt != 0 || p.idot != 1 || p.iquad != 2 || p.iw != 3) return lf_fail(c, LFGPU_ERR_ARG, "ligero256: row order");
+  const double t0 = lig::clock_ms();
   std::unique_ptr<Lig32> L(new Lig32());
-  L->c = c;
-  L->p = p;
-  L->nonces.resize(32 * p.block_ext);
-  L->row_lo = 0;
-  L->row_hi = p.nrow;
-  const int world = cm ? cm->world : 1, rank = cm ? cm->rank : 0;
-  if (cm && world > 1) {
-    L->sharded = true;
-    L->comm = *cm;
-    L->spans.resize(world);
-    for (int q = 0; q < world; ++q) (void)lfgpu_ligero_row_shard(&p, q, world, &L->spans[q].first, &L->spans[q].second);
-    L->row_lo = L->spans[rank].first;
-    L->row_hi = L->spans[rank].second;
-  }
-  std::vector<E> H(p.nrow * p.dblock);
+  L->init(c, p, cm);
+  std::vector<E> H(std::max<size_t>(L->row_hi - L->row_lo, 1) * p.dblock);
   LF_SCRUB_ON_EXIT(H);
   char err[256] = {0};
-  const int rc = lig256_layout(p, W, lqc, rng, user, H.data(), L->nonces.data(), err, c->rng_exact != 0);
+  const int rc = lig::layout(L32(), p, W, 0, lqc, rng, user, c->rng_exact != 0, L->row_lo, L->row_hi, H.data(), L->nonces.data(), err);
   if (rc) return lf_fail(c, rc, "%s", err);
-  const size_t ld = p.block_enc, nr = L->row_hi - L->row_lo, ncols = p.block_ext;
-  const double t_enc = lig::clock_ms();  // (the sharded column commit's LFGPU_VERBOSE line counts upload + encode from here)
-  L->T_bytes = std::max<size_t>(nr, 1) * ld * 32;
-  L->L_bytes = 2 * ncols * 32;
-  if (lf_pool_get(c, L->T_bytes, (void**)&L->d_T) != LFGPU_OK || lf_pool_get(c, L->L_bytes, (void**)&L->d_layers) != LFGPU_OK)
-    return lf_fail(c, LFGPU_ERR_NOMEM, "ligero256: tableau alloc");
-  if (nr) LF_HIP(c, hipMemcpy2DAsync(L->d_T, ld * 32, H.data() + L->row_lo * p.dblock, p.dblock * 32, p.dblock * 32, nr, hipMemcpyHostToDevice, c->stream));
-  // rows IDOT / IQUAD carry dblock values, every other row block (ligero_prover.h:175,184,203,210,237): the slab's share of each group
-  auto encode = [&](size_t g_lo, size_t g_hi, size_t n) -> int {
-    const size_t lo = std::max(g_lo, L->row_lo), hi = std::min(g_hi, L->row_hi);
-    return hi > lo ? lfgpu_fp256_rs_encode_rows(c, hi - lo, n, p.block_enc, L->row(lo), ld) : LFGPU_OK;
-  };
-  LF_TRY(encode(0, 1, p.block));
-  LF_TRY(encode(1, 3, p.dblock));
-  LF_TRY(encode(3, p.nrow, p.block));
-  if (!L->sharded) {
-    void* d_non = nullptr;
-    LF_TRY(lf_scratch3(c, p.block_ext * 32, &d_non));
-    LF_HIP(c, hipMemcpyAsync(d_non, L->nonces.data(), p.block_ext * 32, hipMemcpyHostToDevice, c->stream));
-    LF_TRY(lfgpu_column_commit(c, LFGPU_FIELD_P256, p.nrow, ld, p.dblock, p.block_ext, L->d_T, d_non, L->d_layers, root));
-    LF_HIP(c, hipStreamSynchronize(c->stream));  // H is a local
-    *out = L.release();
-    return LFGPU_OK;
-  }
-  LF_TRY(lig::column_commit_sharded(L.get(), L32(), cm, t_enc, root));  // ends with a synchronise: H may go
+  LF_TRY(lig::commit_rows(L.get(), L32(), H.data(), t0, root));
   *out = L.release();
   return LFGPU_OK;
 }
@@ -1782,12 +1686,9 @@ int zk256_commit(Zk256* z, const void* h_W, lfgpu_rng_fn rng, void* rng_user, co
   static const F256 F;  // (for fill_pad's wc0 * wc1: the constants are built once)
   const size_t pi = zkp::pad_layout<P32>(F, z->C, st.n_witness, st.lqc, draw, &st.pad, Wv.data());
   if (pi != st.param.nw) return lf_fail(c, LFGPU_ERR_ASSERT, "zk256_commit: witness layout");
-  if (draws_only) {
-    std::vector<E> H(st.param.nrow * st.param.dblock);
-    LF_SCRUB_ON_EXIT(H);
-    std::vector<uint8_t> nz(32 * st.param.block_ext);
+  if (draws_only) {  // the empty slab: no image, the nonces dropped
     char err[256] = {0};
-    const int rc = lig256_layout(st.param, Wv.data(), st.lqc.data(), rng, rng_user, H.data(), nz.data(), err, c->rng_exact != 0);
+    const int rc = lig::layout(L32(), st.param, Wv.data(), 0, st.lqc.data(), rng, rng_user, c->rng_exact != 0, 0, 0, (E*)nullptr, nullptr, err);
     return rc ? lf_fail(c, rc, "%s", err) : LFGPU_OK;
   }
   delete z->lp;

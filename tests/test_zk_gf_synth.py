@@ -163,7 +163,7 @@ def test_fixtures_cover_the_shapes():
     assert have("funnel", lambda l: l["nv"] == 1) and have("funnel", lambda l: l["nw"] <= 64)
     assert have("funnel", lambda l: l["nw"] <= 8 and l["nh0"] <= 4)
     assert r["block_enc_arg"] == 0 and P["funnel"]["block"] <= 128 and (r["rate"], r["nreq"]) != FIXED_RATE_NREQ
-    # tall: both row lengths beyond the LDS-resident encoder (4096); ligero_extend_slab encodes the rows after IQUAD in one call
+    # tall: both row lengths beyond the LDS-resident encoder (4096); lig::extend_slab encodes the rows after IQUAD in one call
     # of nrow - 3 rows, and gf_rs_rows_big takes its tower variant from 32 rows on
     r, p = recs["tall"], P["tall"]
     assert r["block_enc_arg"] == p["block_enc"] and p["block"] > 4096 and p["nrow"] >= 32 and p["nrow"] - p["iw"] >= 32
@@ -389,7 +389,7 @@ def test_zk_synth_gf_matches_reference(name):
 @pytest.mark.gpu
 def test_zk_commit_refuses_a_full_field_input_below_the_boundary():
     """odd: the full-field value that stands right after the boundary, moved one input down.  ZkProver.commit and
-    ZkBatch.commit (both reach ligero_layout_host) fail with LFGPU_ERR_ARG naming the index -- of the Ligero witness, which
+    ZkBatch.commit (both reach lig::layout) fail with LFGPU_ERR_ARG naming the index -- of the Ligero witness, which
     starts at the first private input -- after the pads are drawn, as in the reference; the same objects then commit and
     prove the good witness to the reference's bytes."""
     import gpu_util as G
