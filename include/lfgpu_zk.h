@@ -197,6 +197,35 @@ int lfgpu_zk_verify_committed(lfgpu_ctx* ctx, const lfgpu_circuit* c, size_t rat
                               const uint8_t* proof, size_t proof_len, const void* h_pub, const lfgpu_transcript_ops* ts,
                               int* ok, const char** why);
 
+/* ---- LigeroProver::prove / LigeroVerifier::verify on a caller's own statement ----
+ * The Ligero seam without a circuit: the caller brings the linear constraints A w = b as a list of terms and the quadratic
+ * constraints W[z] = W[x] W[y] as lqc, exactly what the reference's classes take.  Fields: GF2_128 (subfield_log_bits 4 or 5)
+ * and Fp128.  Transcript order, as the reference's (lib/ligero/ligero_prover.h:84-146, ligero_verifier.h:42-123):
+ * write hash_of_llterm; draw u_ldt[nwqrow], alphal[nl], alphaq[nq][3], u_quad[nqtriples]; write y_ldt, y_dot, y_quad_0,
+ * y_quad_2; choose(block_ext, nreq).
+ * The matrix of the dot proof is accumulated on the device from the term list AS GIVEN: any order, duplicates allowed
+ * (inner_product_vector, ligero_param.h:382-421); the result does not depend on the order of the terms.
+ * LFGPU_ERR_ARG, found on the host before the first transcript call or launch: a NULL argument (llterm may be NULL when
+ * nllterm = 0, h_lqc when nq = 0, h_b when nl = 0), a term with c >= nl or w >= nw, an lqc index >= nw,
+ * nllterm + 6 nq >= 2^32 (the Fp128 accumulators are 64-bit sums of 32-bit limbs), field P256.
+ * LFGPU_ERR_UNSUPPORTED: a sharded prover, or one from lfgpu_ligero_prover_from_slab. */
+typedef struct { size_t c, w; uint64_t k[2]; } lfgpu_ligero_llterm;   /* LigeroLinearConstraint: A[c][w] += k */
+
+/* LigeroProver::prove on a prover from lfgpu_ligero_commit, whose root the caller has written to ts
+ * (LigeroTranscript::write_commitment).  proof: the write_com_proof bytes (lib/zk/zk_proof.h:137-185); buf = NULL asks for the
+ * size.  The size depends on the proof (subfield runs, Merkle path), so the size query RUNS the proof -- ts advances -- and the
+ * prover keeps the serialised bytes; the next call with a buffer copies those bytes and leaves ts alone (one proof, one
+ * serialisation, as lfgpu_zk_proof_write).  A call with a buffer and no size query in front of it proves and copies in one go.
+ * cap too small: LFGPU_ERR_ARG with *nbytes set, the bytes stay held for the next call with a buffer. */
+int lfgpu_ligero_prove(lfgpu_ligero_prover* pr, const lfgpu_transcript_ops* ts, size_t nl, size_t nllterm,
+                       const lfgpu_ligero_llterm* llterm, const uint8_t hash_of_llterm[32], const size_t* h_lqc,
+                       uint8_t* buf, size_t cap, size_t* nbytes);
+/* LigeroVerifier::verify after receive_commitment (root already in ts).  *ok, *why as lfgpu_zk_verify. */
+int lfgpu_ligero_verify(lfgpu_ctx* ctx, int field, int subfield_log_bits, const lfgpu_ligero_param* p,
+                        const uint8_t root[32], const uint8_t* proof, size_t proof_len, const lfgpu_transcript_ops* ts,
+                        size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm, const uint8_t hash_of_llterm[32],
+                        const void* h_b, const size_t* h_lqc, int* ok, const char** why);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 #ifndef LFGPU_ZK_ADAPTERS_H_
 #define LFGPU_ZK_ADAPTERS_H_
 
+#include <cstddef>
 #include <optional>
 
 #include "lfgpu_adapters.h"
@@ -186,6 +187,211 @@ class GpuZkVerifier {
   const Field& f_;
   size_t rate_, nreq_, block_enc_;
   lfgpu_circuit* circuit_ = nullptr;
+};
+
+// ---- LigeroProver / LigeroVerifier (lib/ligero/ligero_prover.h:34-146, ligero_verifier.h:30-123) on a caller's own statement:
+//
+//     LigeroProver<Field, RSFactory> lp(param);               ->   lfgpu::GpuLigeroProver<Field> lp(ctx, param);
+//     lp.commit(com, ts, W, sfb, lqc, rsf, rng, F);                 lp.commit(com, ts, W, sfb, lqc, rng, F);
+//     lp.prove(proof, ts, nl, nllterm, llterm, h, lqc, rsf, F);     lp.prove(proof, ts, nl, nllterm, llterm, h, lqc, F);
+//     LigeroVerifier<Field, RSFactory>::verify(&why, param, com, proof, ts, nl, nllterm, llterm, h, b, lqc, rsf, F)
+//                                                              ->   lfgpu::GpuLigeroVerifier<Field>(ctx).verify(&why, param, com, proof, ts, nl, ..., b, lqc, F)
+//
+// The argument types are the reference's (LigeroParam, LigeroCommitment, LigeroProof, LigeroLinearConstraint<Field>[],
+// LigeroHash, LigeroQuadraticConstraint[], Transcript, RandomEngine); only the interpolator factory is gone.  The proof crosses
+// the C ABI as the write_com_proof bytes (lib/zk/zk_proof.h:137-185), converted from / to the caller's LigeroProof below with the
+// Field's own to_bytes / of_bytes functions.  GF2_128<k> and Fp128.
+namespace detail {
+constexpr size_t kComMaxRunLen = size_t{1} << 25;
+template <class Field, class LigeroProofT>
+void com_proof_to_wire(const LigeroProofT& pr, const Field& F, std::vector<uint8_t>& o) {
+  uint8_t b[Field::kBytes];
+  auto put = [&](const typename Field::Elt& e) {
+    F.to_bytes_field(b, e);
+    o.insert(o.end(), b, b + Field::kBytes);
+  };
+  auto put_size = [&](size_t n) {
+    for (int i = 0; i < 4; ++i) o.push_back(static_cast<uint8_t>(n >> (8 * i)));
+  };
+  for (const auto& e : pr.y_ldt) put(e);
+  for (const auto& e : pr.y_dot) put(e);
+  for (const auto& e : pr.y_quad_0) put(e);
+  for (const auto& e : pr.y_quad_2) put(e);
+  for (const auto& n : pr.merkle.nonce) o.insert(o.end(), n.bytes, n.bytes + 32);
+  bool sub = false;  // alternating full-field / subfield runs, the first one full-field (possibly empty)
+  for (size_t i = 0, n = pr.req.size(); i < n; sub = !sub) {
+    size_t len = 0;
+    while (i + len < n && len < kComMaxRunLen && F.in_subfield(pr.req[i + len]) == sub) ++len;
+    put_size(len);
+    for (size_t j = i; j < i + len; ++j) {
+      if (sub) {
+        F.to_bytes_subfield(b, pr.req[j]);
+        o.insert(o.end(), b, b + Field::kSubFieldBytes);
+      } else {
+        put(pr.req[j]);
+      }
+    }
+    i += len;
+  }
+  put_size(pr.merkle.path.size());
+  for (const auto& d : pr.merkle.path) o.insert(o.end(), d.data, d.data + 32);
+}
+template <class Field, class LigeroProofT>
+bool com_proof_of_wire(LigeroProofT& pr, const Field& F, const uint8_t* q, size_t left) {
+  auto take = [&](size_t n) {
+    const uint8_t* r = q;
+    q += n;
+    left -= n;
+    return r;
+  };
+  auto get = [&](typename Field::Elt& e) {
+    if (left < Field::kBytes) return false;
+    auto v = F.of_bytes_field(take(Field::kBytes));
+    if (!v.has_value()) return false;
+    e = v.value();
+    return true;
+  };
+  auto get_size = [&](size_t& n) {
+    if (left < 4) return false;
+    const uint8_t* b = take(4);
+    n = size_t{b[0]} | size_t{b[1]} << 8 | size_t{b[2]} << 16 | size_t{b[3]} << 24;
+    return true;
+  };
+  for (auto& e : pr.y_ldt)
+    if (!get(e)) return false;
+  for (auto& e : pr.y_dot)
+    if (!get(e)) return false;
+  for (auto& e : pr.y_quad_0)
+    if (!get(e)) return false;
+  for (auto& e : pr.y_quad_2)
+    if (!get(e)) return false;
+  for (auto& n : pr.merkle.nonce) {
+    if (left < 32) return false;
+    std::memcpy(n.bytes, take(32), 32);
+  }
+  bool sub = false;
+  for (size_t i = 0, n = pr.req.size(); i < n; sub = !sub) {
+    size_t len = 0;
+    if (!get_size(len) || len > n - i) return false;
+    for (size_t j = i; j < i + len; ++j) {
+      if (sub) {
+        if (left < Field::kSubFieldBytes) return false;
+        auto v = F.of_bytes_subfield(take(Field::kSubFieldBytes));
+        if (!v.has_value()) return false;
+        pr.req[j] = v.value();
+      } else if (!get(pr.req[j])) {
+        return false;
+      }
+    }
+    i += len;
+  }
+  size_t npath = 0;
+  if (!get_size(npath) || left != npath * 32) return false;
+  pr.merkle.path.resize(npath);
+  for (auto& d : pr.merkle.path) std::memcpy(d.data, take(32), 32);
+  return true;
+}
+// the reference's constraint records are the C ABI's: { size_t c, w; Elt k } and { size_t x, y, z }
+template <class LlT>
+const lfgpu_ligero_llterm* llterm_image(const LlT* llterm) {
+  static_assert(sizeof(LlT) == sizeof(lfgpu_ligero_llterm) && offsetof(LlT, k) == offsetof(lfgpu_ligero_llterm, k), "LigeroLinearConstraint image");
+  return reinterpret_cast<const lfgpu_ligero_llterm*>(llterm);
+}
+template <class LqcT>
+const size_t* lqc_image(const LqcT* lqc) {
+  static_assert(sizeof(LqcT) == 3 * sizeof(size_t), "LigeroQuadraticConstraint image");
+  return reinterpret_cast<const size_t*>(lqc);
+}
+template <class Field, class ParamT>
+lfgpu_ligero_param ligero_param_of(lfgpu_ctx* ctx, const ParamT& p) {
+  static_assert(field_id<Field>() != LFGPU_FIELD_P256, "GpuLigeroProver / GpuLigeroVerifier: GF2_128 and Fp128");
+  lfgpu_ligero_param q;
+  check(ctx, lfgpu_ligero_param_init(&q, field_id<Field>(), subfield_log_bits<Field>(), p.nw, p.nq, p.rateinv, p.nreq, p.block_enc), "lfgpu_ligero_param_init");
+  if (q.nrow != p.nrow || q.block != p.block || q.dblock != p.dblock || q.block_ext != p.block_ext || q.w != p.w)
+    check(ctx, LFGPU_ERR_ASSERT, "Ligero parameters differ from the caller's LigeroParam");
+  return q;
+}
+}  // namespace detail
+
+template <class Field>
+class GpuLigeroProver {
+  using Elt = typename Field::Elt;
+
+ public:
+  template <class ParamT>
+  GpuLigeroProver(const Context& ctx, const ParamT& p) : c_(ctx), p_(detail::ligero_param_of<Field>(ctx.get(), p)) {}
+  ~GpuLigeroProver() {
+    if (lp_) lfgpu_ligero_free(lp_);
+  }
+  GpuLigeroProver(const GpuLigeroProver&) = delete;
+  GpuLigeroProver& operator=(const GpuLigeroProver&) = delete;
+
+  // LigeroProver::commit (ligero_prover.h:58-79), the root written to ts as LigeroTranscript::write_commitment does
+  template <class CommitmentT, class TranscriptT, class LqcT, class RandomEngineT>
+  void commit(CommitmentT& com, TranscriptT& ts, const Elt W[], size_t subfield_boundary, const LqcT lqc[], RandomEngineT& rng, const Field&) {
+    if (lp_) lfgpu_ligero_free(lp_);
+    lp_ = nullptr;
+    uint8_t root[32];
+    check(c_.get(),
+          lfgpu_ligero_commit(c_.get(), field_id<Field>(), subfield_log_bits<Field>(), &p_, W, subfield_boundary, detail::lqc_image(lqc),
+                              detail::rng_hook<RandomEngineT>, &rng, root, &lp_),
+          "lfgpu_ligero_commit");
+    std::memcpy(com.root.data, root, 32);
+    ts.write(com.root.data, 32);
+  }
+
+  // LigeroProver::prove (ligero_prover.h:84-146)
+  template <class ProofT, class TranscriptT, class LlT, class HashT, class LqcT>
+  void prove(ProofT& proof, TranscriptT& ts, size_t nl, size_t nllterm, const LlT llterm[], const HashT& hash_of_llterm, const LqcT lqc[], const Field& F) {
+    if (!lp_) check(c_.get(), LFGPU_ERR_ARG, "must run commit before prove");
+    detail::TranscriptHook<Field, TranscriptT> hook{&ts, &F, nullptr};
+    const lfgpu_transcript_ops ops = hook.ops();
+    size_t n = 0;  // the size query runs the proof; the second call copies the held bytes
+    check(c_.get(), lfgpu_ligero_prove(lp_, &ops, nl, nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, detail::lqc_image(lqc), nullptr, 0, &n),
+          "lfgpu_ligero_prove");
+    std::vector<uint8_t> wire(n);
+    check(c_.get(), lfgpu_ligero_prove(lp_, &ops, nl, nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, detail::lqc_image(lqc), wire.data(), n, &n),
+          "lfgpu_ligero_prove");
+    if (!detail::com_proof_of_wire(proof, F, wire.data(), n)) check(c_.get(), LFGPU_ERR_ASSERT, "GpuLigeroProver: the library's wire bytes do not parse");
+  }
+
+ private:
+  const Context& c_;
+  lfgpu_ligero_param p_;
+  lfgpu_ligero_prover* lp_ = nullptr;
+};
+
+template <class Field>
+class GpuLigeroVerifier {
+  using Elt = typename Field::Elt;
+
+ public:
+  explicit GpuLigeroVerifier(const Context& ctx) : c_(ctx) {}
+  template <class CommitmentT, class TranscriptT>
+  static void receive_commitment(const CommitmentT& com, TranscriptT& ts) {
+    ts.write(com.root.data, 32);
+  }
+  // LigeroVerifier::verify (ligero_verifier.h:42-123); *why names the failing check with the reference's strings
+  template <class ParamT, class CommitmentT, class ProofT, class TranscriptT, class LlT, class HashT, class LqcT>
+  bool verify(const char** why, const ParamT& p, const CommitmentT& com, const ProofT& proof, TranscriptT& ts, size_t nl, size_t nllterm,
+              const LlT llterm[], const HashT& hash_of_llterm, const Elt b[], const LqcT lqc[], const Field& F) const {
+    const lfgpu_ligero_param q = detail::ligero_param_of<Field>(c_.get(), p);
+    std::vector<uint8_t> wire;
+    detail::com_proof_to_wire(proof, F, wire);
+    detail::TranscriptHook<Field, TranscriptT> hook{&ts, &F, nullptr};
+    const lfgpu_transcript_ops ops = hook.ops();
+    int ok = 0;
+    const char* reason = nullptr;
+    check(c_.get(),
+          lfgpu_ligero_verify(c_.get(), field_id<Field>(), subfield_log_bits<Field>(), &q, com.root.data, wire.data(), wire.size(), &ops, nl,
+                              nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, b, detail::lqc_image(lqc), &ok, &reason),
+          "lfgpu_ligero_verify");
+    if (why) *why = reason;
+    return ok != 0;
+  }
+
+ private:
+  const Context& c_;
 };
 
 }  // namespace lfgpu

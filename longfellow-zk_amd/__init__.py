@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "lfgpu_zk_proof_write", "lfgpu_zk_timings", "lfgpu_zk_prover_free", "lfgpu_zk_verify", "lfgpu_zk_verify_committed",
     "lfgpu_zk_batch_new", "lfgpu_zk_prove_batch", "lfgpu_zk_batch_free",
     "lfgpu_column_commit_batch", "lfgpu_ligero_commit_batch", "lfgpu_zk_commit_batch",
+    "lfgpu_ligero_prove", "lfgpu_ligero_verify",
 ]
 
 
@@ -71,6 +72,26 @@ class TranscriptOps(C.Structure):
     _fields_ = [("user", C.c_void_p), ("write_bytes", C.c_void_p), ("write_elt", C.c_void_p),
                 ("write_elt_array", C.c_void_p), ("gen_bytes", C.c_void_p), ("clone", C.c_void_p), ("free_clone", C.c_void_p),
                 ("write_elt_sized", C.c_void_p), ("write_elt_array_sized", C.c_void_p)]  # 32-byte elements (Fp256Base)
+
+
+class LigeroLlterm(C.Structure):
+    """lfgpu_ligero_llterm == LigeroLinearConstraint (reference lib/ligero/ligero_param.h): A[c][w] += k"""
+    _fields_ = [("c", C.c_size_t), ("w", C.c_size_t), ("k", C.c_uint64 * 2)]
+
+
+LLTERM_DTYPE = [("c", "<u8"), ("w", "<u8"), ("k", "<u8", (2,))]  # the same record as a numpy dtype
+
+
+def llterm_array(llterm):
+    """a list of (c, w, k) -- k a pair of uint64 words, the Elt image -- or an array of LLTERM_DTYPE -> a contiguous array of
+    lfgpu_ligero_llterm records"""
+    import numpy as np
+    if isinstance(llterm, np.ndarray) and llterm.dtype == np.dtype(LLTERM_DTYPE):
+        return np.ascontiguousarray(llterm)
+    a = np.zeros(len(llterm), dtype=LLTERM_DTYPE)
+    for i, (c, w, k) in enumerate(llterm):
+        a[i] = (c, w, (int(k[0]), int(k[1])))
+    return a
 
 
 class CircuitInfo(C.Structure):
@@ -188,6 +209,9 @@ def load_library():
         "lfgpu_ligero_prove_batch": [vp, C.POINTER(vp), sz, vp, C.POINTER(vp), sz, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), vp, vp, vp, vp, vp],
         "lfgpu_ligero_open_batch": [vp, C.POINTER(vp), sz, C.POINTER(sz), vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_zk_commit_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(RNG_FN), C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), vp],
+        "lfgpu_ligero_prove": [vp, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, sz, C.POINTER(sz)],
+        "lfgpu_ligero_verify": [vp, ci, ci, C.POINTER(LigeroParam), vp, vp, sz, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, C.POINTER(ci),
+                                C.POINTER(C.c_char_p)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -622,6 +646,23 @@ class LigeroProver:
                                                   C.c_void_p(path.ctypes.data), cap, C.byref(npath)))
         return req, nonces, [bytes(path[i]) for i in range(npath.value)]
 
+    def prove(self, ts, nl, llterm, hash_of_llterm, lqc):
+        """LigeroProver::prove (:84-146) -> the write_com_proof bytes.  ts: a transcript with .ops() (FsTranscript) that already
+        holds the commitment root; llterm: llterm_array's input, any order, duplicates allowed; lqc as at commit."""
+        import numpy as np
+        gpu = self.gpu
+        ll = llterm_array(llterm)
+        lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
+        ops = ts.ops()
+        h = bytes(hash_of_llterm)
+        n = C.c_size_t()
+        args = (self.h, C.byref(ops) if ops is not None else None, nl, len(ll), C.c_void_p(ll.ctypes.data) if len(ll) else None, h,
+                C.c_void_p(lq.ctypes.data) if lq.size else None)
+        gpu._ck(gpu.L.lfgpu_ligero_prove(*args, None, 0, C.byref(n)))  # proves and reports the size
+        buf = C.create_string_buffer(n.value)
+        gpu._ck(gpu.L.lfgpu_ligero_prove(*args, buf, n.value, C.byref(n)))  # copies the held bytes
+        return buf.raw[:n.value]
+
     def tableau_ptr(self):
         d = C.c_void_p()
         self.gpu._ck(self.gpu.L.lfgpu_ligero_tableau(self.h, C.byref(d)))
@@ -970,6 +1011,23 @@ class ZkBatch:
         if self.h:
             self.gpu.L.lfgpu_zk_batch_free(self.h)
             self.h = None
+
+
+def ligero_verify(gpu, field, p, root, proof, ts, nl, llterm, hash_of_llterm, b, lqc, subfield_log_bits=4):
+    """LigeroVerifier::verify (reference lib/ligero/ligero_verifier.h:42-123) on the write_com_proof bytes -> (accepted, reason);
+    ts: a transcript with .ops() that already holds the commitment root; b: the nl right-hand sides (Elt images)"""
+    import numpy as np
+    ll = llterm_array(llterm)
+    lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
+    b = np.ascontiguousarray(b)
+    ok, why = C.c_int(), C.c_char_p()
+    ops = ts.ops()
+    raw = bytes(proof)
+    gpu._ck(gpu.L.lfgpu_ligero_verify(gpu.h, field, subfield_log_bits, C.byref(p), bytes(root), raw, len(raw), C.byref(ops), nl, len(ll),
+                                       C.c_void_p(ll.ctypes.data) if len(ll) else None, bytes(hash_of_llterm),
+                                       C.c_void_p(b.ctypes.data) if b.size else None, C.c_void_p(lq.ctypes.data) if lq.size else None,
+                                       C.byref(ok), C.byref(why)))
+    return bool(ok.value), (why.value or b"").decode()
 
 
 def zk_verify(gpu, circuit, proof, pub, transcript, rate=7, nreq=132, block_enc=0, committed=False):

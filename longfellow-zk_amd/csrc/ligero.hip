@@ -15,10 +15,15 @@
 
 #include "ctx.h"
 #include "ligero_slab.h"
+#include "runfold.h"
+#include "zkint.h"
 
 // the C ABI's opaque prover: the shared record (ligero_slab.h) over 16-byte elements, plus which of the two fields it serves
 struct lfgpu_ligero_prover : lig::Slab<elt_t> {
   int field = 0, k = 0;
+  // lfgpu_ligero_prove: the write_com_proof bytes between its size query and the copy
+  std::vector<uint8_t> wire;
+  bool wire_held = false;
 };
 
 static size_t ceildiv(size_t a, size_t b) { return (a + b - 1) / b; }
@@ -435,6 +440,109 @@ __global__ void a_rows_sparse_batch_kernel(u32 r, u32 w, size_t ld, const u64* _
   a_rows_sparse_body<F>(r, w, ld, idx + o, val + o, (size_t)(off[b + 1] - o), nflat, rows + (size_t)b * srows);
 }
 
+// ---- inner_product_vector from the caller's term list (LigeroCommon::inner_product_vector, ligero_param.h:382-421): terms in any
+// order, duplicates allowed, one wire read by thousands of terms the normal case.  The sums go into accumulators indexed by the
+// flat position f = i * w + j of A (not into the strided rows): two 64-bit words per entry and atomic XOR for GF(2^128); four
+// 64-bit sums of 32-bit limbs and atomic adds for Fp128 (integer sums of residues, < 2^32 summands per entry, one
+// fp_reduce_limbs pass: the pattern of bindg_emit_fp_kernel, quad.hip).  Both are exact and independent of arrival order.  Runs of
+// equal targets in lane order are folded before the atomics: in the block for GF (runfold.h), in the wave for Fp128.
+struct llterm_t {  // the memory image of lfgpu_ligero_llterm
+  u64 c, w;
+  elt_t k;
+};
+static_assert(sizeof(llterm_t) == 32 && sizeof(lfgpu_ligero_llterm) == 32 && sizeof(size_t) == 8, "lfgpu_ligero_llterm is uploaded as it stands");
+#define AT_THREADS 256
+#define AT_BLOCKS_MAX 1024  // grid stride: AT_THREADS * AT_BLOCKS_MAX terms per sweep
+__global__ __launch_bounds__(AT_THREADS) void a_terms_gf_kernel(size_t n, const llterm_t* __restrict__ t, const elt_t* __restrict__ alphal,
+                                                                u64* __restrict__ acc) {
+  const size_t stride = (size_t)gridDim.x * AT_THREADS;
+  for (size_t base = (size_t)blockIdx.x * AT_THREADS; base < n; base += stride) {  // block-uniform trip count: the fold has barriers
+    const size_t i = base + threadIdx.x;
+    u32 key = 0xffffffffu;
+    elt_t v = elt_zero();
+    if (i < n) {
+      const llterm_t e = t[i];
+      key = (u32)e.w;
+      v = gf_mul(e.k, ld16(&alphal[e.c]));
+    }
+    gf_run_fold_commit<AT_THREADS>(key, v, acc);
+  }
+}
+__global__ __launch_bounds__(AT_THREADS) void a_terms_fp_kernel(size_t n, const llterm_t* __restrict__ t, const elt_t* __restrict__ alphal,
+                                                                u64* __restrict__ acc) {
+  const size_t stride = (size_t)gridDim.x * AT_THREADS;
+  const u32 lane = threadIdx.x & 63;
+  for (size_t base = (size_t)blockIdx.x * AT_THREADS; base < n; base += stride) {  // wave-uniform trip count: the fold shuffles
+    const size_t i = base + threadIdx.x;
+    u32 key = 0xffffffffu;
+    u64 l0 = 0, l1 = 0, l2 = 0, l3 = 0;
+    if (i < n) {
+      const llterm_t e = t[i];
+      key = (u32)e.w;
+      const elt_t v = fp_mul(e.k, ld16(&alphal[e.c]));
+      l0 = (u32)v.lo;
+      l1 = v.lo >> 32;
+      l2 = (u32)v.hi;
+      l3 = v.hi >> 32;
+    }
+    // segmented suffix sums over the wave's runs of equal keys (run id = number of run heads at or before the lane, as runfold.h);
+    // a run's head lane ends with the run's limb sums, < 64 * 2^32 each
+    const u32 pkey = __shfl_up(key, 1, 64);
+    const bool head = lane == 0 || pkey != key;
+    const u64 hmask = __ballot(head);
+    const u32 rid = (u32)__popcll(hmask & ((2ull << lane) - 1));
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const u64 o0 = __shfl_down(l0, off, 64), o1 = __shfl_down(l1, off, 64), o2 = __shfl_down(l2, off, 64), o3 = __shfl_down(l3, off, 64);
+      const u32 orid = __shfl_down(rid, off, 64);
+      if (lane + off < 64 && orid == rid) {
+        l0 += o0;
+        l1 += o1;
+        l2 += o2;
+        l3 += o3;
+      }
+    }
+    if (head && key != 0xffffffffu) {
+      u64* a = acc + 4 * (size_t)key;
+      atomicAdd(&a[0], l0);
+      atomicAdd(&a[1], l1);
+      atomicAdd(&a[2], l2);
+      atomicAdd(&a[3], l3);
+    }
+  }
+}
+template <int F>
+__device__ __forceinline__ void a_terms_acc(u64* __restrict__ acc, u64 f, elt_t v) {
+  if (F == FIELD_GF2_128) {
+    atomicXor(&acc[2 * f], v.lo);
+    atomicXor(&acc[2 * f + 1], v.hi);
+  } else {
+    atomicAdd(&acc[4 * f], (u64)(u32)v.lo);
+    atomicAdd(&acc[4 * f + 1], v.lo >> 32);
+    atomicAdd(&acc[4 * f + 2], (u64)(u32)v.hi);
+    atomicAdd(&acc[4 * f + 3], v.hi >> 32);
+  }
+}
+// the quadratic copy constraints: A[a0 + j * step + iw] += aq, A[lqc[iw][j]] -= aq for aq = alphaq[iw][j], j < 3
+template <int F>
+__global__ void a_terms_quad_kernel(u32 n3 /* 3 nq */, const u64* __restrict__ lqc, const elt_t* __restrict__ alphaq, u64 a0, u64 step, u64* __restrict__ acc) {
+  const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n3) return;
+  const u32 iw = t / 3, j = t % 3;
+  const elt_t aq = ld16(&alphaq[t]);
+  a_terms_acc<F>(acc, a0 + (u64)j * step + iw, aq);
+  a_terms_acc<F>(acc, lqc[t], Fld<F>::sub(elt_zero(), aq));
+}
+// rows[i][r + j] += the sum standing in the accumulators of flat position i * w + j
+template <int F>
+__global__ void a_terms_finish_kernel(u32 r, u32 w, size_t ld, size_t nflat, const u64* __restrict__ acc, elt_t* __restrict__ rows) {
+  const size_t f = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (f >= nflat) return;
+  const elt_t v = F == FIELD_GF2_128 ? elt_t{acc[2 * f], acc[2 * f + 1]} : fp_reduce_limbs(acc[4 * f], acc[4 * f + 1], acc[4 * f + 2], acc[4 * f + 3]);
+  elt_t* dst = &rows[(f / w) * ld + r + f % w];
+  st16(dst, Fld<F>::add(ld16(dst), v));
+}
+
 // ---- the width policy of ligero_slab.h for the two 16-byte fields: it wraps the entry points and kernels that exist and carries
 // the field.  These steps upload their host vectors themselves: lfgpu_rows_axpy and lfgpu_gather_columns end with a synchronise,
 // a short sparse list goes through the pinned staging ring without one.
@@ -479,6 +587,50 @@ struct L16 : lig::Host16 {
     }
     LIG_DISPATCH(field, a_rows_sparse_kernel, dim3((u32)((n + 255) / 256)), dim3(256), (u32)r, (u32)w, ld, (const u64*)d_idx, (const E*)d_val, n, nflat, d_rows);
     LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  // inner_product_vector from an unsorted term list with duplicates (the kernels above), added to what stands in the rows.
+  // The accumulators, the term list (one copy, as the caller holds it) and the challenges (one packed copy) live in scratch2.
+  int a_rows_terms(lfgpu_ctx* c, const lfgpu_ligero_param& p, size_t ld, const LfLigeroTerms& t, E* d_rows) const {
+    const bool gf = field == LFGPU_FIELD_GF2_128;
+    const size_t nflat = p.nwqrow * p.w, n3 = 3 * p.nq, acc_bytes = nflat * (gf ? 16 : 32);
+    const size_t small_bytes = (t.nl + n3) * 16 + n3 * 8;
+    void* d = nullptr;
+    LF_TRY(lf_scratch2(c, acc_bytes + t.nterm * 32 + small_bytes + 64, &d));
+    u64* d_acc = (u64*)d;
+    llterm_t* d_term = (llterm_t*)((uint8_t*)d + acc_bytes);
+    E* d_alphal = (E*)(d_term + t.nterm);
+    E* d_alphaq = d_alphal + t.nl;
+    u64* d_lqc = (u64*)(d_alphaq + n3);
+    LF_HIP(c, hipMemsetAsync(d_acc, 0, acc_bytes, c->stream));
+    if (t.nterm) LF_HIP(c, hipMemcpyAsync(d_term, t.term, t.nterm * 32, hipMemcpyHostToDevice, c->stream));
+    if (small_bytes) {
+      std::vector<uint8_t> pack(small_bytes);
+      if (t.nl) memcpy(pack.data(), t.alphal, t.nl * 16);
+      if (n3) memcpy(pack.data() + t.nl * 16, t.alphaq, n3 * 16);
+      if (n3) memcpy(pack.data() + (t.nl + n3) * 16, t.lqc, n3 * 8);
+      if (small_bytes <= LF_STAGE_SLOT) {
+        LF_TRY(lf_stage_upload(c, d_alphal, pack.data(), small_bytes));
+      } else {
+        LF_HIP(c, hipMemcpyAsync(d_alphal, pack.data(), small_bytes, hipMemcpyHostToDevice, c->stream));
+        LF_HIP(c, hipStreamSynchronize(c->stream));
+      }
+    }
+    if (t.nterm) {
+      const dim3 grid((u32)std::min<size_t>((t.nterm + AT_THREADS - 1) / AT_THREADS, AT_BLOCKS_MAX));
+      if (gf) hipLaunchKernelGGL(a_terms_gf_kernel, grid, dim3(AT_THREADS), 0, c->stream, t.nterm, (const llterm_t*)d_term, (const E*)d_alphal, d_acc);
+      else hipLaunchKernelGGL(a_terms_fp_kernel, grid, dim3(AT_THREADS), 0, c->stream, t.nterm, (const llterm_t*)d_term, (const E*)d_alphal, d_acc);
+      LF_HIP(c, hipGetLastError());
+    }
+    if (n3) {
+      LIG_DISPATCH(field, a_terms_quad_kernel, dim3((u32)((n3 + 255) / 256)), dim3(256), (u32)n3, (const u64*)d_lqc, (const E*)d_alphaq, (u64)(p.nwrow * p.w),
+                   (u64)(p.nqtriples * p.w), d_acc);
+      LF_HIP(c, hipGetLastError());
+    }
+    LIG_DISPATCH(field, a_terms_finish_kernel, dim3((u32)((nflat + 255) / 256)), dim3(256), (u32)p.r, (u32)p.w, ld, nflat, (const u64*)d_acc, d_rows);
+    LF_HIP(c, hipGetLastError());
+    // the term list is the caller's memory: its upload is over before this returns
+    LF_HIP(c, hipStreamSynchronize(c->stream));
     return LFGPU_OK;
   }
   int gather_columns(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, const E* d_T, const size_t* h_idx, size_t nreq, E* d_req) const {
@@ -749,6 +901,24 @@ extern "C" int lfgpu_ligero_dot_proof_sparse(lfgpu_ligero_prover* pr, const void
   LF_HIP(pr->c, hipSetDevice(pr->c->device));
   const elt_t sc = scale ? elt_t{scale[0], scale[1]} : elt_t{0, 0};
   return lig::dot(pr, policy16(pr), (const elt_t*)d_dense, ndense, sc, h_idx, (const elt_t*)h_val, nsparse, (elt_t*)h_y);
+}
+
+// ---- below the C ABI, for lfgpu_ligero_prove / lfgpu_ligero_verify (zk.hip; declared in zkint.h)
+int lf_ligero_a_rows_terms(lfgpu_ctx* c, int field, const lfgpu_ligero_param* p, size_t ld, const LfLigeroTerms* t, void* d_rows) {
+  return L16{{field, 0, nullptr}}.a_rows_terms(c, *p, ld, *t, (elt_t*)d_rows);
+}
+int lf_ligero_dot_terms(lfgpu_ligero_prover* pr, const LfLigeroTerms* t, void* h_y) {
+  LF_HIP(pr->c, hipSetDevice(pr->c->device));
+  return lig::dot_terms(pr, policy16(pr), *t, (elt_t*)h_y);
+}
+void lf_ligero_prover_view(lfgpu_ligero_prover* pr, LfLigeroView* v) {
+  v->c = pr->c;
+  v->field = pr->field;
+  v->k = pr->k;
+  v->p = pr->p;
+  v->whole = !pr->sharded && pr->owns && pr->row_lo == 0 && pr->row_hi == pr->p.nrow;
+  v->wire = &pr->wire;
+  v->wire_held = &pr->wire_held;
 }
 
 extern "C" int lfgpu_ligero_quadratic_proof(lfgpu_ligero_prover* pr, const void* h_u_quad, void* h_y0, void* h_y2) {

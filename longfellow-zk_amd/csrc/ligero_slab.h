@@ -14,6 +14,7 @@
 //   rows_vaxpy     y[j] = T0[j] + sum_i A[i][j] T[i][j]
 //   quad_combo     y[j] = Tq[j] + sum_i u[i] (Z_i[j] - X_i[j] Y_i[j])
 //   a_rows_clear / a_rows_dense / a_rows_sparse   the pieces of a_rows below; the sparse lists are on the host
+//   a_rows_terms   (16-byte policy only) rows += inner_product_vector of a term list in any order, duplicates allowed
 //   gather_columns req[i][j] = T[i][col0 + idx[j]], idx on the host
 //   rs_rows        nrow rows of n values extended to m, in place
 //   rs_rows_mixed  a slab's three row groups in one launch where the width has such a kernel, else LFGPU_ERR_UNSUPPORTED
@@ -220,6 +221,21 @@ int dot(Slab<typename L::E>* pr, const L& pol, const typename L::E* d_dense, siz
   E* dAext = (E*)sc;
   LF_HIP(c, hipMemsetAsync(dAext, 0, p.nwqrow * lda * sizeof(E), c->stream));
   LF_TRY(a_rows(c, pol, p.w, p.r, lda, p.nwqrow, d_dense, ndense, scale, h_idx, h_val, nsparse, dAext));
+  return dot_finish(pr, pol, dAext, dAext + p.nwqrow * lda, y);
+}
+
+// ... with A accumulated on the device from a term list in any order (pol.a_rows_terms: the 16-byte policy's step)
+template <class L, class Terms>
+int dot_terms(Slab<typename L::E>* pr, const L& pol, const Terms& t, typename L::E* y) {
+  using E = typename L::E;
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  const size_t lda = p.dblock, bytes = (p.nwqrow * lda + 2 * p.dblock) * sizeof(E);
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, bytes + 64, &sc));
+  E* dAext = (E*)sc;
+  LF_HIP(c, hipMemsetAsync(dAext, 0, p.nwqrow * lda * sizeof(E), c->stream));
+  LF_TRY(pol.a_rows_terms(c, p, lda, t, dAext));
   return dot_finish(pr, pol, dAext, dAext + p.nwqrow * lda, y);
 }
 

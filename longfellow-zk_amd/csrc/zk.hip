@@ -414,10 +414,10 @@ struct P16 : zkp::Wire16 {
     return lfgpu_ligero_open_batch(c, lp, nb, idx, req, nonces, path, cap, npath);
   }
   // LigeroVerifier: rows [0, nwqrow) = [0^r | A_i] extended block -> block_enc, rows nwqrow.. = y_ldt, y_dot, y_quad;
-  // ext = those rows at the opened columns
-  static int verifier_ext(lfgpu_ctx* c, const HostField& F, const lfgpu_circuit_info& I, const lfgpu_ligero_param& p, const E* d_eq, const E& scale,
-                          const std::vector<uint64_t>& a_idx, const std::vector<E>& a_val, const zkp::ProofBody<E>& pr, const size_t* idx, std::vector<E>& ext) {
-    const int field = F.field;
+  // ext = those rows at the opened columns.  a_rows(d_T, ld): the caller's inner_product_vector step into the cleared rows.
+  template <class ARows>
+  static int verifier_ext_with(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param& p, ARows a_rows, const zkp::ComProof<E>& pr, const size_t* idx,
+                               std::vector<E>& ext) {
     const size_t nrows_dev = p.nwqrow + 3, ld = p.block_enc;
     void* dT = nullptr;
     // scratch4: the RS extension below runs its FFT passes through `scratch` / `scratch2` (fft.hip, lch_bs.hip, rs.hip)
@@ -427,27 +427,35 @@ struct P16 : zkp::Wire16 {
     // only the first dblock columns of a row are inputs: clear them on the device, then strided copies
     LF_HIP(c, hipMemset2DAsync(d_T, ld * 16, 0, p.dblock * 16, nrows_dev, c->stream));
     // inner_product_vector + layout_Aext on the device
-    LF_TRY(lfgpu_ligero_inner_product_rows(c, field, p.w, p.r, ld, p.nwqrow, d_eq + I.npub_in, I.ninputs - I.npub_in, W2(scale).v, a_idx.data(), a_val.data(),
-                                           a_idx.size(), d_T));
+    LF_TRY(a_rows(d_T, ld));
     LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 0) * ld, pr.y_ldt.data(), p.block * 16, hipMemcpyHostToDevice, c->stream));
     LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 1) * ld, pr.y_dot.data(), p.dblock * 16, hipMemcpyHostToDevice, c->stream));
     E* yq = d_T + (p.nwqrow + 2) * ld;  // y_quad = y_quad_0 | 0^w | y_quad_2
     LF_HIP(c, hipMemcpyAsync(yq, pr.y_q0.data(), p.r * 16, hipMemcpyHostToDevice, c->stream));
     LF_HIP(c, hipMemcpyAsync(yq + p.block, pr.y_q2.data(), (p.dblock - p.block) * 16, hipMemcpyHostToDevice, c->stream));
     LF_HIP(c, hipStreamSynchronize(c->stream));
-    LF_TRY(lf_rs_rows(c, field, 4, p.nwqrow + 1, p.block, p.block_enc, d_T, ld));             // A rows and y_ldt
-    LF_TRY(lf_rs_rows(c, field, 4, 2, p.dblock, p.block_enc, d_T + (p.nwqrow + 1) * ld, ld));  // y_dot, y_quad
+    LF_TRY(lf_rs_rows(c, field, k, p.nwqrow + 1, p.block, p.block_enc, d_T, ld));             // A rows and y_ldt
+    LF_TRY(lf_rs_rows(c, field, k, 2, p.dblock, p.block_enc, d_T + (p.nwqrow + 1) * ld, ld));  // y_dot, y_quad
     LF_TRY(lfgpu_gather_columns(c, nrows_dev, ld, p.dblock, d_T, idx, p.nreq, d_req));
     ext.resize(nrows_dev * p.nreq);
     LF_HIP(c, hipMemcpyAsync(ext.data(), d_req, ext.size() * 16, hipMemcpyDeviceToHost, c->stream));
     LF_HIP(c, hipStreamSynchronize(c->stream));
     return LFGPU_OK;
   }
+  // ZkVerifier: A = scale * EQ over the private inputs + the host-folded sparse terms
+  static int verifier_ext(lfgpu_ctx* c, const HostField& F, const lfgpu_circuit_info& I, const lfgpu_ligero_param& p, const E* d_eq, const E& scale,
+                          const std::vector<uint64_t>& a_idx, const std::vector<E>& a_val, const zkp::ComProof<E>& pr, const size_t* idx, std::vector<E>& ext) {
+    auto a_rows = [&](E* d_T, size_t ld) {
+      return lfgpu_ligero_inner_product_rows(c, F.field, p.w, p.r, ld, p.nwqrow, d_eq + I.npub_in, I.ninputs - I.npub_in, W2(scale).v, a_idx.data(), a_val.data(),
+                                             a_idx.size(), d_T);
+    };
+    return verifier_ext_with(c, F.field, 4, p, a_rows, pr, idx, ext);
+  }
 };
-P16 policy16(lfgpu_ctx* c, int field, const zkp::SubfieldSolver* sub) {
+P16 policy16(lfgpu_ctx* c, int field, const zkp::SubfieldSolver* sub, int k = 4) {
   P16 pol;
   pol.field = field;
-  pol.g = lf_gf_ctx(c, 4);
+  pol.g = lf_gf_ctx(c, k);
   pol.sub = sub;
   return pol;
 }
@@ -931,4 +939,105 @@ extern "C" int lfgpu_zk_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rate
 extern "C" int lfgpu_zk_verify_committed(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof,
                                          size_t proof_len, const void* h_pub, const lfgpu_transcript_ops* tso, int* ok, const char** why_out) {
   return zk_verify_impl(c, C, rateinv, nreq, block_enc, proof, proof_len, h_pub, tso, true, ok, why_out);
+}
+
+// ------------------------------------------------------------------ LigeroProver::prove / LigeroVerifier::verify on a caller's statement
+// A second, small driver over zkp::ligero_prove / ligero_verify / com_proof_write / com_proof_read (zk_proto.h): the ZK paths keep
+// their own A step (dense EQ block + host-folded sparse terms), these two accumulate A on the device from the caller's term list.
+namespace {
+// the host scan in front of the first transcript call or launch
+bool ligero_statement_ok(const lfgpu_ligero_param& p, size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm, const size_t* h_lqc) {
+  if ((nllterm && !llterm) || (p.nq && !h_lqc)) return false;
+  if (nllterm >= ((size_t)1 << 32) || nllterm + 6 * p.nq >= ((size_t)1 << 32)) return false;
+  for (size_t t = 0; t < nllterm; ++t)
+    if (llterm[t].c >= nl || llterm[t].w >= p.nw) return false;
+  for (size_t i = 0; i < 3 * p.nq; ++i)
+    if (h_lqc[i] >= p.nw) return false;
+  return true;
+}
+int wire_copy_out(lfgpu_ctx* c, const std::vector<uint8_t>& wire, uint8_t* buf, size_t cap, size_t* nbytes) {
+  *nbytes = wire.size();
+  if (cap < wire.size()) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: buffer too small (%zu < %zu)", cap, wire.size());
+  memcpy(buf, wire.data(), wire.size());
+  return LFGPU_OK;
+}
+}  // namespace
+
+extern "C" int lfgpu_ligero_prove(lfgpu_ligero_prover* lp, const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm,
+                                  const uint8_t hash_of_llterm[32], const size_t* h_lqc, uint8_t* buf, size_t cap, size_t* nbytes) {
+  if (!lp || !tso || !hash_of_llterm || !nbytes) return LFGPU_ERR_ARG;
+  LfLigeroView v;
+  lf_ligero_prover_view(lp, &v);
+  lfgpu_ctx* c = v.c;
+  const lfgpu_ligero_param& p = v.p;
+  if (v.field != LFGPU_FIELD_GF2_128 && v.field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: field");
+  if (!ligero_statement_ok(p, nl, nllterm, llterm, h_lqc))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 terms)");
+  if (!v.whole) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "ligero_prove: the prover must hold the whole tableau on one GPU");
+  if (v.field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, v.k)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: subfield_log_bits must be 4 or 5");
+  if (buf && *v.wire_held) {  // the copy that follows a size query: the same serialisation
+    LF_TRY(wire_copy_out(c, *v.wire, buf, cap, nbytes));
+    *v.wire_held = false;
+    return LFGPU_OK;
+  }
+  *v.wire_held = false;
+  zkp::SubfieldSolver sub;
+  if (v.field == LFGPU_FIELD_GF2_128) sub.build(lf_gf_ctx(c, v.k));
+  const P16 pol = policy16(c, v.field, &sub, v.k);
+  const zkp::Ts<P16> ts{&pol, tso, tso->user};
+  zkp::ComProof<elt_t> pr;
+  double tq[6];
+  auto dot = [&](const std::vector<elt_t>& alphal, const std::vector<elt_t>& alphaq, elt_t* y_dot) {
+    const LfLigeroTerms t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
+    return lf_ligero_dot_terms(lp, &t, y_dot);
+  };
+  LF_TRY(zkp::ligero_prove<P16>(p, lp, ts, hash_of_llterm, nl, dot, pr, tq));
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  if (verbose)
+    fprintf(stderr, "lfgpu ligero_prove: ldt %.2f ms | challenges %.2f | A from %zu terms + dot %.2f | quad %.2f | challenges+open %.2f\n", tq[1] - tq[0],
+            tq[2] - tq[1], nllterm, tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
+  v.wire->clear();
+  zkp::com_proof_write(pol, pr, *v.wire);
+  if (!buf) {
+    *nbytes = v.wire->size();
+    *v.wire_held = true;
+    return LFGPU_OK;
+  }
+  *v.wire_held = true;  // kept if the buffer turns out too small
+  LF_TRY(wire_copy_out(c, *v.wire, buf, cap, nbytes));
+  *v.wire_held = false;
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_ligero_verify(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const uint8_t root[32], const uint8_t* proof, size_t proof_len,
+                                   const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm,
+                                   const uint8_t hash_of_llterm[32], const void* h_b, const size_t* h_lqc, int* ok, const char** why_out) {
+  if (!c || !pp || !root || !proof || !tso || !hash_of_llterm || !ok || (nl && !h_b)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: null argument");
+  *ok = 0;
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: field");
+  if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, k)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: subfield_log_bits must be 4 or 5");
+  const lfgpu_ligero_param& p = *pp;
+  if (!ligero_statement_ok(p, nl, nllterm, llterm, h_lqc))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 terms)");
+  const P16 pol = policy16(c, field, nullptr, k);
+  const HostField F = pol.host_field(c);
+  auto fail = [&](int w) {
+    if (why_out) *why_out = zkp::why_string(w);
+    return (int)LFGPU_OK;
+  };
+  zkp::ComProof<elt_t> pr;
+  zkp::WireReader<P16> rd{pol, proof, proof_len};
+  if (!zkp::com_proof_read(rd, p, pr) || rd.bad || rd.left != 0) return fail(zkp::kWhyParse);
+  LF_HIP(c, hipSetDevice(c->device));
+  const zkp::Ts<P16> ts{&pol, tso, tso->user};
+  auto ext_fn = [&](const std::vector<elt_t>& alphal, const std::vector<elt_t>& alphaq, const size_t* idx, std::vector<elt_t>& ext) {
+    const LfLigeroTerms t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
+    auto a_rows = [&](elt_t* d_T, size_t ld) { return lf_ligero_a_rows_terms(c, field, &p, ld, &t, d_T); };
+    return P16::verifier_ext_with(c, field, k, p, a_rows, pr, idx, ext);
+  };
+  int w = zkp::kWhyOk;
+  double tv[6];
+  LF_TRY(zkp::ligero_verify<P16>(pol, F, p, root, pr, ts, hash_of_llterm, nl, (const elt_t*)h_b, ext_fn, &w, tv));
+  if (w == zkp::kWhyOk) *ok = 1;
+  return fail(w);
 }

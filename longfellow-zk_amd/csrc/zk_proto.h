@@ -10,8 +10,11 @@
 //   ZkProof::write / read              lib/zk/zk_proof.h:90-185,218-345
 //   ZkVerifier::verify                 lib/zk/zk_verifier.h:68-94, LigeroVerifier::verify lib/ligero/ligero_verifier.h:42-270
 //
+// The Ligero halves of prove and verify stand on their own (ligero_prove, ligero_verify, com_proof_write / com_proof_read): the ZK
+// functions call them, and so do lfgpu_ligero_prove / lfgpu_ligero_verify (zk.hip) for a caller's own statement.
+//
 // A policy is a plain struct.  Its host half (Wire16 / Wire32 below) is all that the transcript view, pad_layout,
-// proof_write / proof_read and inner_product_sparse use, so those run with no device context:
+// proof_write / proof_read (com_proof_write / com_proof_read) and inner_product_sparse use, so those run with no device context:
 //   E, Field, kBytes, zero / is_zero / eq, to_bytes / of_bytes / sample, ts_write_elt / ts_write_array (how the transcript
 //   hooks are called), and kSubfieldCodec: whether the wire format's two-byte subfield runs can occur (then also
 //   two_byte_subfield / solve_subfield / of_subfield).
@@ -190,12 +193,17 @@ struct Wire16 {  // GF(2^128) and Fp128; HostField dispatches on the field id
   void ts_write_array(const lfgpu_transcript_ops* o, void* u, const uint8_t* b, size_t n) const { o->write_elt_array(u, b, n); }
   // the elements as the transcript wants them, when that is their storage (GF(2^128)); else nullptr: convert one by one
   const uint8_t* raw_image(const E* e) const { return field == LFGPU_FIELD_GF2_128 ? (const uint8_t*)e : nullptr; }
-  // subfield codec: GF(2^128) sends a subfield element as its 2 coordinate bytes (kSubFieldBytes = 2: the wire format is
-  // GF2_128<4>'s); for Fp128 to/of_bytes_subfield == to/of_bytes_field
+  // subfield codec: GF(2^128) sends a subfield element as its kSubFieldBytes coordinate bytes (2 for GF2_128<4>, the ZK wire
+  // format's; 4 for GF2_128<5>, which only the Ligero entry points serve); for Fp128 to/of_bytes_subfield == to/of_bytes_field
   static constexpr bool kSubfieldCodec = true;
   bool two_byte_subfield() const { return field == LFGPU_FIELD_GF2_128; }
+  size_t subfield_bytes() const { return g->sub_bits / 8; }
   std::pair<E, u32> solve_subfield(const E& e) const { return sub->solve(e); }
-  E of_subfield(const uint8_t b[2]) const { return gf_add(g->sub_tab[0][b[0]], g->sub_tab[1][b[1]]); }  // of_scalar(u) = sum_i bit_i(u) beta_i
+  E of_subfield(const uint8_t* b) const {  // of_scalar(u) = sum_i bit_i(u) beta_i
+    E e = gf_add(g->sub_tab[0][b[0]], g->sub_tab[1][b[1]]);
+    for (size_t i = 2; i < subfield_bytes(); ++i) e = gf_add(e, g->sub_tab[i][b[i]]);
+    return e;
+  }
 };
 
 struct Wire32 {  // Fp256Base: every element is in the subfield, encoded at full width
@@ -269,12 +277,15 @@ struct LayerPad {  // Proof-shaped pad (zk_prover.h:152-188): hp[hand][2 round +
   E wc[2];
 };
 template <class E>
-struct ProofBody {  // ZkProof: what ZkProof::write sends and ZkProof::read parses
-  uint8_t root[32] = {0};
-  std::vector<LayerPad<E>> sc;  // the padded (transmitted) sumcheck values
+struct ComProof {  // LigeroProof: the write_com_proof section of the wire format
   std::vector<E> y_ldt, y_dot, y_q0, y_q2, req;
   std::vector<uint8_t> nonces, path;
   size_t npath = 0;
+};
+template <class E>
+struct ProofBody : ComProof<E> {  // ZkProof: what ZkProof::write sends and ZkProof::read parses
+  uint8_t root[32] = {0};
+  std::vector<LayerPad<E>> sc;  // the padded (transmitted) sumcheck values
 };
 template <class P>
 struct ProverState {  // what a prover keeps between commit, prove and proof_write
@@ -342,10 +353,10 @@ size_t pad_layout(const typename P::Field& F, const lfgpu_circuit* C, size_t n_w
 }
 
 // ------------------------------------------------------------------ ZkProof::write / read
+// write_com_proof (zk_proof.h:137-185), appended to o: the Ligero section, shared by ZkProof::write and lfgpu_ligero_prove
 template <class P>
-void proof_write(const P& pol, const lfgpu_circuit* C, const ProofBody<typename P::E>& pr, std::vector<uint8_t>& o) {
+void com_proof_write(const P& pol, const ComProof<typename P::E>& pr, std::vector<uint8_t>& o) {
   using E = typename P::E;
-  o.clear();
   auto pute = [&](const E& e) {
     uint8_t b[P::kBytes];
     pol.to_bytes(e, b);
@@ -354,32 +365,23 @@ void proof_write(const P& pol, const lfgpu_circuit* C, const ProofBody<typename 
   auto putsz = [&](size_t g) {  // write_size: 4 bytes LE (zk_proof.h:211-216)
     for (int i = 0; i < 4; ++i) o.push_back((uint8_t)(g >> (8 * i)));
   };
-  o.insert(o.end(), pr.root, pr.root + 32);  // write_com
-  for (size_t ly = 0; ly < pr.sc.size(); ++ly) {  // write_sc_proof: p(0) and p(2) of both hands per round, then wc
-    const auto& L = pr.sc[ly];
-    const size_t logw = C->layers[ly].logw;
-    for (size_t wi = 0; wi < logw; ++wi)
-      for (int k = 0; k < 2; ++k) {
-        pute(L.hp[0][2 * wi + k]);
-        pute(L.hp[1][2 * wi + k]);
-      }
-    pute(L.wc[0]);
-    pute(L.wc[1]);
-  }
-  for (const E& e : pr.y_ldt) pute(e);  // write_com_proof
+  for (const E& e : pr.y_ldt) pute(e);
   for (const E& e : pr.y_dot) pute(e);
   for (const E& e : pr.y_q0) pute(e);
   for (const E& e : pr.y_q2) pute(e);
   o.insert(o.end(), pr.nonces.begin(), pr.nonces.end());
   // opened columns: alternating runs of full-field / subfield elements, run-length prefixed (:156-178).  GF(2^128): every
   // opened element is solved against the subfield basis ONCE (residue == 0 iff it lies in the subfield; the coordinates are
-  // its 2-byte image).  A prime field's elements all lie in the subfield: an empty full-field run, then subfield runs.
+  // its kSubFieldBytes image: 2 bytes for GF2_128<4>, 4 for GF2_128<5>).  A prime field's elements all lie in the subfield: an
+  // empty full-field run, then subfield runs.
   const size_t nreq_elts = pr.req.size();
   bool two = false;
+  size_t sub_bytes = 2;
   std::vector<u32> sub_coord;
   std::vector<uint8_t> sub_flag;
   if constexpr (P::kSubfieldCodec) {
     if ((two = pol.two_byte_subfield())) {
+      sub_bytes = pol.subfield_bytes();
       sub_coord.resize(nreq_elts);
       sub_flag.resize(nreq_elts);
       for (size_t i = 0; i < nreq_elts; ++i) {
@@ -402,9 +404,8 @@ void proof_write(const P& pol, const lfgpu_circuit* C, const ProofBody<typename 
     putsz(runlen);
     for (size_t i = ci; i < ci + runlen; ++i) {
       if (subfield_run && two) {
-        const u32 u = sub_coord[i];  // to_bytes_subfield: 2 bytes LE
-        o.push_back((uint8_t)u);
-        o.push_back((uint8_t)(u >> 8));
+        const u32 u = sub_coord[i];  // to_bytes_subfield: kSubFieldBytes LE
+        for (size_t b = 0; b < sub_bytes; ++b) o.push_back((uint8_t)(u >> (8 * b)));
       } else {  // full-field run, or a prime field where to_bytes_subfield == to_bytes_field
         pute(pr.req[i]);
       }
@@ -414,6 +415,29 @@ void proof_write(const P& pol, const lfgpu_circuit* C, const ProofBody<typename 
   }
   putsz(pr.npath);
   o.insert(o.end(), pr.path.begin(), pr.path.begin() + 32 * pr.npath);
+}
+template <class P>
+void proof_write(const P& pol, const lfgpu_circuit* C, const ProofBody<typename P::E>& pr, std::vector<uint8_t>& o) {
+  using E = typename P::E;
+  o.clear();
+  auto pute = [&](const E& e) {
+    uint8_t b[P::kBytes];
+    pol.to_bytes(e, b);
+    o.insert(o.end(), b, b + P::kBytes);
+  };
+  o.insert(o.end(), pr.root, pr.root + 32);  // write_com
+  for (size_t ly = 0; ly < pr.sc.size(); ++ly) {  // write_sc_proof: p(0) and p(2) of both hands per round, then wc
+    const auto& L = pr.sc[ly];
+    const size_t logw = C->layers[ly].logw;
+    for (size_t wi = 0; wi < logw; ++wi)
+      for (int k = 0; k < 2; ++k) {
+        pute(L.hp[0][2 * wi + k]);
+        pute(L.hp[1][2 * wi + k]);
+      }
+    pute(L.wc[0]);
+    pute(L.wc[1]);
+  }
+  com_proof_write(pol, pr, o);
 }
 
 // lfgpu_zk_proof_write: serialised once per proof, the size query and the copy share the bytes
@@ -432,85 +456,103 @@ int proof_write_cached(lfgpu_ctx* c, const P& pol, const lfgpu_circuit* C, const
   return LFGPU_OK;
 }
 
-// ZkProof::read; false on underflow, inconsistent sizes or an element encoding >= p (the reference returns false as well)
+// The cursor of the two readers below: what is left of the input, and whether an of_bytes_field failed (value >= p)
 template <class P>
-bool proof_read(const P& pol, const lfgpu_circuit* C, const lfgpu_ligero_param& p, const uint8_t* buf, size_t len, ProofBody<typename P::E>& pr) {
-  using E = typename P::E;
-  constexpr size_t B = P::kBytes;
-  const uint8_t* q = buf;
-  size_t left = len;
-  bool bad = false;  // an of_bytes_field failed (value >= p)
-  auto have = [&](size_t n) { return left >= n; };
-  auto next = [&](size_t n) {
+struct WireReader {
+  const P& pol;
+  const uint8_t* q;
+  size_t left;
+  bool bad = false;
+  bool have(size_t n) const { return left >= n; }
+  const uint8_t* next(size_t n) {
     const uint8_t* r = q;
     q += n;
     left -= n;
     return r;
-  };
-  auto elt = [&] {
-    E e = P::zero();
-    if (!pol.of_bytes(next(B), e)) bad = true;
+  }
+  typename P::E elt() {
+    typename P::E e = P::zero();
+    if (!pol.of_bytes(next(P::kBytes), e)) bad = true;
     return e;
-  };
-  auto size4 = [&] {
+  }
+  size_t size4() {
     const uint8_t* b = next(4);
     return (size_t)b[0] | (size_t)b[1] << 8 | (size_t)b[2] << 16 | (size_t)b[3] << 24;
+  }
+};
+// read_com_proof (zk_proof.h:262-345): the Ligero section at the cursor; false on underflow or inconsistent sizes (a bad element
+// encoding is left in rd.bad).  Shared by ZkProof::read and lfgpu_ligero_verify.
+template <class P>
+bool com_proof_read(WireReader<P>& rd, const lfgpu_ligero_param& p, ComProof<typename P::E>& pr) {
+  using E = typename P::E;
+  constexpr size_t B = P::kBytes;
+  const P& pol = rd.pol;
+  auto vec = [&](std::vector<E>& v, size_t n) {
+    if (!rd.have(n * B)) return false;
+    v.resize(n);
+    for (auto& e : v) e = rd.elt();
+    return true;
   };
-  if (!have(32)) return false;
-  memcpy(pr.root, next(32), 32);
+  if (!vec(pr.y_ldt, p.block) || !vec(pr.y_dot, p.dblock) || !vec(pr.y_q0, p.r) || !vec(pr.y_q2, p.dblock - p.block)) return false;
+  if (!rd.have(p.nreq * 32)) return false;
+  pr.nonces.assign(rd.q, rd.q + p.nreq * 32);
+  rd.next(p.nreq * 32);
+  const size_t total = p.nreq * p.nrow;
+  bool two = false;
+  size_t sub_bytes = 2;
+  if constexpr (P::kSubfieldCodec) {
+    if ((two = pol.two_byte_subfield())) sub_bytes = pol.subfield_bytes();
+  }
+  pr.req.assign(total, P::zero());
+  size_t ci = 0;
+  bool subfield_run = false;
+  while (ci < total) {  // alternating full-field / subfield runs
+    if (!rd.have(4)) return false;
+    const size_t runlen = rd.size4();
+    if (runlen >= kMaxRunLen || ci + runlen > total) return false;
+    if (subfield_run && two) {
+      if (!rd.have(runlen * sub_bytes)) return false;
+      if constexpr (P::kSubfieldCodec)
+        for (size_t i = ci; i < ci + runlen; ++i) pr.req[i] = pol.of_subfield(rd.next(sub_bytes));  // of_bytes_subfield
+    } else {
+      if (!rd.have(runlen * B)) return false;
+      for (size_t i = ci; i < ci + runlen; ++i) pr.req[i] = rd.elt();
+    }
+    ci += runlen;
+    subfield_run = !subfield_run;
+  }
+  if (!rd.have(4)) return false;
+  const size_t sz = rd.size4();
+  if (sz < p.nreq || sz >= kMaxNumDigests || sz > p.nreq * p.mc_pathlen || !rd.have(sz * 32)) return false;
+  pr.npath = sz;
+  pr.path.assign(rd.q, rd.q + sz * 32);
+  rd.next(sz * 32);
+  return true;
+}
+
+// ZkProof::read; false on underflow, inconsistent sizes or an element encoding >= p (the reference returns false as well)
+template <class P>
+bool proof_read(const P& pol, const lfgpu_circuit* C, const lfgpu_ligero_param& p, const uint8_t* buf, size_t len, ProofBody<typename P::E>& pr) {
+  constexpr size_t B = P::kBytes;
+  WireReader<P> rd{pol, buf, len};
+  if (!rd.have(32)) return false;
+  memcpy(pr.root, rd.next(32), 32);
   pr.sc.assign(C->layers.size(), {});
   for (size_t ly = 0; ly < C->layers.size(); ++ly) {
     const size_t logw = C->layers[ly].logw;
-    if (!have((logw * 4 + 2) * B)) return false;
+    if (!rd.have((logw * 4 + 2) * B)) return false;
     auto& L = pr.sc[ly];
     L.hp[0].resize(2 * logw);
     L.hp[1].resize(2 * logw);
     for (size_t wi = 0; wi < logw; ++wi)
       for (int k = 0; k < 2; ++k) {
-        L.hp[0][2 * wi + k] = elt();
-        L.hp[1][2 * wi + k] = elt();
+        L.hp[0][2 * wi + k] = rd.elt();
+        L.hp[1][2 * wi + k] = rd.elt();
       }
-    L.wc[0] = elt();
-    L.wc[1] = elt();
+    L.wc[0] = rd.elt();
+    L.wc[1] = rd.elt();
   }
-  auto vec = [&](std::vector<E>& v, size_t n) {
-    if (!have(n * B)) return false;
-    v.resize(n);
-    for (auto& e : v) e = elt();
-    return true;
-  };
-  if (!vec(pr.y_ldt, p.block) || !vec(pr.y_dot, p.dblock) || !vec(pr.y_q0, p.r) || !vec(pr.y_q2, p.dblock - p.block)) return false;
-  if (!have(p.nreq * 32)) return false;
-  pr.nonces.assign(q, q + p.nreq * 32);
-  next(p.nreq * 32);
-  const size_t total = p.nreq * p.nrow;
-  bool two = false;
-  if constexpr (P::kSubfieldCodec) two = pol.two_byte_subfield();
-  pr.req.assign(total, P::zero());
-  size_t ci = 0;
-  bool subfield_run = false;
-  while (ci < total) {  // alternating full-field / subfield runs
-    if (!have(4)) return false;
-    const size_t runlen = size4();
-    if (runlen >= kMaxRunLen || ci + runlen > total) return false;
-    if (subfield_run && two) {
-      if (!have(runlen * 2)) return false;
-      if constexpr (P::kSubfieldCodec)
-        for (size_t i = ci; i < ci + runlen; ++i) pr.req[i] = pol.of_subfield(next(2));  // of_bytes_subfield
-    } else {
-      if (!have(runlen * B)) return false;
-      for (size_t i = ci; i < ci + runlen; ++i) pr.req[i] = elt();
-    }
-    ci += runlen;
-    subfield_run = !subfield_run;
-  }
-  if (!have(4)) return false;
-  const size_t sz = size4();
-  if (sz < p.nreq || sz >= kMaxNumDigests || sz > p.nreq * p.mc_pathlen || !have(sz * 32)) return false;
-  pr.npath = sz;
-  pr.path.assign(q, q + sz * 32);
-  next(sz * 32);
-  return !bad;
+  return com_proof_read(rd, p, pr) && !rd.bad;
 }
 
 // ------------------------------------------------------------------ verifier_constraints
@@ -708,6 +750,140 @@ void inner_product_sparse(const typename P::Field& F, const lfgpu_ligero_param& 
   }
 }
 
+// ------------------------------------------------------------------ LigeroProver::prove / LigeroVerifier::verify
+// The Ligero halves of ZkProver::prove and ZkVerifier::verify, also the whole of lfgpu_ligero_prove / lfgpu_ligero_verify.  What
+// differs between the two callers is how the matrix A of inner_product_vector reaches the device (ZK: a dense EQ block on the
+// device + host-folded sparse terms; Ligero entry points: the caller's term list), so that step is the caller's.
+//
+// LigeroProver::prove (ligero_prover.h:84-146) on the committed prover lp: challenges, the three row combinations, the y writes,
+// choose and the opening.  dot(alphal, alphaq, y_dot): the caller's dot proof (it may stamp tq[2] where its host share ends).
+// tq[6]: time stamps for the caller's verbose line.
+template <class P, class Dot>
+int ligero_prove(const lfgpu_ligero_param& p, typename P::Lig* lp, const Ts<P>& ts, const uint8_t hash_of_A[32], size_t nl, Dot dot,
+                 ComProof<typename P::E>& pr, double tq[6]) {
+  using E = typename P::E;
+  ts.write_bytes(hash_of_A, 32);
+  std::vector<E> u_ldt(p.nwqrow);
+  for (auto& e : u_ldt) e = ts.elt();
+  pr.y_ldt.assign(p.block, P::zero());
+  tq[0] = now_ms();
+  LF_TRY(P::low_degree(lp, u_ldt.data(), pr.y_ldt.data()));
+  tq[1] = now_ms();
+  std::vector<E> alphal(nl), alphaq(3 * p.nq);
+  for (auto& e : alphal) e = ts.elt();
+  for (auto& e : alphaq) e = ts.elt();
+  pr.y_dot.assign(p.dblock, P::zero());
+  tq[2] = now_ms();
+  LF_TRY(dot(alphal, alphaq, pr.y_dot.data()));
+  tq[3] = now_ms();
+  std::vector<E> u_quad(p.nqtriples ? p.nqtriples : 1);
+  for (size_t i = 0; i < p.nqtriples; ++i) u_quad[i] = ts.elt();
+  pr.y_q0.assign(p.r, P::zero());
+  pr.y_q2.assign(p.dblock - p.block, P::zero());
+  LF_TRY(P::quadratic(lp, u_quad.data(), pr.y_q0.data(), pr.y_q2.data()));
+  tq[4] = now_ms();
+  ts.write_array(pr.y_ldt.data(), pr.y_ldt.size());
+  ts.write_array(pr.y_dot.data(), pr.y_dot.size());
+  ts.write_array(pr.y_q0.data(), pr.y_q0.size());
+  ts.write_array(pr.y_q2.data(), pr.y_q2.size());
+  std::vector<size_t> idx(p.nreq);
+  ts.choose(p.block_ext, p.nreq, idx.data());
+  pr.req.assign(p.nrow * p.nreq, P::zero());
+  pr.nonces.assign(p.nreq * 32, 0);
+  const size_t cap = p.nreq * p.mc_pathlen + 1;
+  pr.path.assign(cap * 32, 0);
+  LF_TRY(P::open(lp, idx.data(), pr.req.data(), pr.nonces.data(), pr.path.data(), cap, &pr.npath));
+  tq[5] = now_ms();
+  return LFGPU_OK;
+}
+
+// the verdicts of the verifiers: the reference's strings (lib/ligero/ligero_verifier.h:90-130) and ours for a proof that ZkProof::read refuses
+enum { kWhyOk = 0, kWhyParse, kWhyMerkle, kWhyLowDegree, kWhyDot, kWhyDotValue, kWhyQuadratic };
+inline const char* why_string(int w) {
+  static const char* kWhy[] = {"ok", "proof does not parse", "merkle_check failed", "low_degree_check failed", "dot_check failed",
+                               "wrong dot product", "quadratic_check failed"};
+  return kWhy[w];
+}
+// LigeroVerifier::verify (ligero_verifier.h:42-123) over a parsed proof, the root already in the transcript: challenges, the Merkle
+// check, then the three column checks and the value of the inner product against b[nl].  ext_fn(alphal, alphaq, idx, out): the
+// caller's device step -- out[row][j] for the rows [0^r | A_i] (i < nwqrow) and then y_ldt, y_dot, y_quad, Reed-Solomon-extended, at
+// the opened columns idx[j].  *why: the first failing check (kWhy...).  tv[3], tv[4]: time stamps after the Merkle check and the
+// device step.
+template <class P, class Ext>
+int ligero_verify(const P& pol, const typename P::Field& F, const lfgpu_ligero_param& p, const uint8_t root[32], const ComProof<typename P::E>& pr,
+                  const Ts<P>& ts, const uint8_t hash_of_A[32], size_t nl, const typename P::E* b, Ext ext_fn, int* why, double tv[6]) {
+  using E = typename P::E;
+  ts.write_bytes(hash_of_A, 32);
+  std::vector<E> u_ldt(p.nwqrow), alphal(nl), alphaq(3 * p.nq), u_quad(p.nqtriples ? p.nqtriples : 1);
+  for (auto& e : u_ldt) e = ts.elt();
+  for (auto& e : alphal) e = ts.elt();
+  for (auto& e : alphaq) e = ts.elt();
+  for (size_t i = 0; i < p.nqtriples; ++i) u_quad[i] = ts.elt();
+  ts.write_array(pr.y_ldt.data(), pr.y_ldt.size());
+  ts.write_array(pr.y_dot.data(), pr.y_dot.size());
+  ts.write_array(pr.y_q0.data(), pr.y_q0.size());
+  ts.write_array(pr.y_q2.data(), pr.y_q2.size());
+  std::vector<size_t> idx(p.nreq);
+  ts.choose(p.block_ext, p.nreq, idx.data());
+  auto req_at = [&](size_t i, size_t j) -> const E& { return pr.req[i * p.nreq + j]; };
+  auto fail = [&](int w) {
+    *why = w;
+    return LFGPU_OK;
+  };
+
+  {  // merkle_check: leaf r = SHA-256(nonce_r || column r of the opening)
+    std::vector<uint8_t> leaves(p.nreq * 32);
+    for (size_t r = 0; r < p.nreq; ++r) {
+      Sha256 s;
+      s.update(&pr.nonces[32 * r], 32);
+      for (size_t i = 0; i < p.nrow; ++i) {
+        uint8_t eb[P::kBytes];
+        pol.to_bytes(req_at(i, r), eb);
+        s.update(eb, P::kBytes);
+      }
+      s.digest(&leaves[32 * r]);
+    }
+    if (!lf_merkle_verify(p.block_ext, root, pr.path.data(), pr.npath, leaves.data(), idx.data(), p.nreq)) return fail(kWhyMerkle);
+  }
+  tv[3] = now_ms();
+
+  // device: rows [0, nwqrow) = [0^r | A_i] extended block -> block_enc, rows nwqrow.. = y_ldt, y_dot, y_quad; ext = their
+  // opened columns
+  std::vector<E> ext;
+  LF_TRY(ext_fn(alphal, alphaq, idx.data(), ext));
+  auto ext_at = [&](size_t row, size_t j) -> const E& { return ext[row * p.nreq + j]; };
+  tv[4] = now_ms();
+
+  for (size_t j = 0; j < p.nreq; ++j) {  // low_degree_check
+    E yc = req_at(p.ildt, j);
+    for (size_t i = 0; i < p.nwqrow; ++i) yc = F.add(yc, F.mul(u_ldt[i], req_at(i + p.iw, j)));
+    if (!P::eq(yc, ext_at(p.nwqrow, j))) return fail(kWhyLowDegree);
+  }
+  for (size_t j = 0; j < p.nreq; ++j) {  // dot_check
+    E yc = req_at(p.idot, j);
+    for (size_t i = 0; i < p.nwqrow; ++i) yc = F.add(yc, F.mul(ext_at(i, j), req_at(i + p.iw, j)));
+    if (!P::eq(yc, ext_at(p.nwqrow + 1, j))) return fail(kWhyDot);
+  }
+  {  // the putative value of the inner product
+    E want = P::zero(), got = P::zero();
+    for (size_t k = 0; k < nl; ++k) want = F.add(want, F.mul(b[k], alphal[k]));
+    for (size_t j = 0; j < p.w; ++j) got = F.add(got, pr.y_dot[p.r + j]);
+    if (!P::eq(want, got)) return fail(kWhyDotValue);
+  }
+  {  // quadratic_check
+    const size_t iqx = p.iq, iqy = iqx + p.nqtriples, iqz = iqy + p.nqtriples;
+    for (size_t j = 0; j < p.nreq; ++j) {
+      E yc = req_at(p.iquad, j);
+      for (size_t i = 0; i < p.nqtriples; ++i) {
+        const E tmp = F.sub(req_at(iqz + i, j), F.mul(req_at(iqx + i, j), req_at(iqy + i, j)));  // z - x*y
+        yc = F.add(yc, F.mul(u_quad[i], tmp));
+      }
+      if (!P::eq(yc, ext_at(p.nwqrow + 2, j))) return fail(kWhyQuadratic);
+    }
+  }
+  return fail(kWhyOk);
+}
+
 // initialize_sumcheck_fiat_shamir (zk_common.h:163-180)
 template <class P>
 void fs_init(const Ts<P>& ts, const lfgpu_circuit* C, const typename P::E* pub) {
@@ -894,46 +1070,20 @@ int prove_finish(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const typen
   const lfgpu_ligero_param& p = st.param;
   st.ms[4] = now_ms() - t0;
 
-  // LigeroProver::prove (ligero_prover.h:84-146)
+  // LigeroProver::prove (ligero_prover.h:84-146): A = the dense private-input block (the EQ table, on the device) + the sparse terms
   t0 = now_ms();
   {
-    uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};  // zk_prover.h:143
-    ts.write_bytes(hash_of_A, 32);
-    std::vector<E> u_ldt(p.nwqrow);
-    for (auto& e : u_ldt) e = ts.elt();
-    pr.y_ldt.assign(p.block, P::zero());
+    const uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};  // zk_prover.h:143
     static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-    double tq[6] = {now_ms(), 0, 0, 0, 0, 0};
-    LF_TRY(P::low_degree(lp, u_ldt.data(), pr.y_ldt.data()));
-    tq[1] = now_ms();
-    std::vector<E> alphal(cs.n), alphaq(3 * p.nq);
-    for (auto& e : alphal) e = ts.elt();
-    for (auto& e : alphaq) e = ts.elt();
-    std::vector<uint64_t> a_idx;
-    std::vector<E> a_val;
-    inner_product_sparse<P>(F, p, cs.a, alphal, st.lqc, alphaq, a_idx, a_val);
-    pr.y_dot.assign(p.dblock, P::zero());
-    tq[2] = now_ms();
-    LF_TRY(P::dot(lp, d_eq + st.npub, st.n_witness, alphal[cs.n - 1], a_idx.data(), a_val.data(), a_idx.size(), pr.y_dot.data()));
-    tq[3] = now_ms();
-    std::vector<E> u_quad(p.nqtriples ? p.nqtriples : 1);
-    for (size_t i = 0; i < p.nqtriples; ++i) u_quad[i] = ts.elt();
-    pr.y_q0.assign(p.r, P::zero());
-    pr.y_q2.assign(p.dblock - p.block, P::zero());
-    LF_TRY(P::quadratic(lp, u_quad.data(), pr.y_q0.data(), pr.y_q2.data()));
-    tq[4] = now_ms();
-    ts.write_array(pr.y_ldt.data(), pr.y_ldt.size());
-    ts.write_array(pr.y_dot.data(), pr.y_dot.size());
-    ts.write_array(pr.y_q0.data(), pr.y_q0.size());
-    ts.write_array(pr.y_q2.data(), pr.y_q2.size());
-    std::vector<size_t> idx(p.nreq);
-    ts.choose(p.block_ext, p.nreq, idx.data());
-    pr.req.assign(p.nrow * p.nreq, P::zero());
-    pr.nonces.assign(p.nreq * 32, 0);
-    const size_t cap = p.nreq * p.mc_pathlen + 1;
-    pr.path.assign(cap * 32, 0);
-    LF_TRY(P::open(lp, idx.data(), pr.req.data(), pr.nonces.data(), pr.path.data(), cap, &pr.npath));
-    tq[5] = now_ms();
+    double tq[6] = {0, 0, 0, 0, 0, 0};
+    auto dot = [&](const std::vector<E>& alphal, const std::vector<E>& alphaq, E* y_dot) {
+      std::vector<uint64_t> a_idx;
+      std::vector<E> a_val;
+      inner_product_sparse<P>(F, p, cs.a, alphal, st.lqc, alphaq, a_idx, a_val);
+      tq[2] = now_ms();
+      return P::dot(lp, d_eq + st.npub, st.n_witness, alphal[cs.n - 1], a_idx.data(), a_val.data(), a_idx.size(), y_dot);
+    };
+    LF_TRY(ligero_prove<P>(p, lp, ts, hash_of_A, cs.n, dot, pr, tq));
     if (verbose)
       fprintf(stderr, "lfgpu zk ligero_prove: ldt %.2f ms | sparse terms of A %.2f | dot %.2f | quad %.2f | challenges+open %.2f\n", tq[1] - tq[0],
               tq[2] - tq[1], tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
@@ -1193,10 +1343,8 @@ int verify(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const lfgpu_liger
            const lfgpu_transcript_ops* tso, bool committed, EqTable eq_table, int* ok, const char** why_out) {
   using E = typename P::E;
   const typename P::Field F = pol.host_field(c);
-  static const char* kWhy[] = {"ok", "proof does not parse", "merkle_check failed", "low_degree_check failed", "dot_check failed",
-                               "wrong dot product", "quadratic_check failed"};
   auto fail = [&](int w) {
-    if (why_out) *why_out = kWhy[w];
+    if (why_out) *why_out = why_string(w);
     return LFGPU_OK;
   };
   const lfgpu_circuit_info& I = C->info;
@@ -1204,7 +1352,7 @@ int verify(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const lfgpu_liger
   static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
   double tv[6] = {now_ms(), 0, 0, 0, 0, 0};
   ProofBody<E> pr;
-  if (!proof_read(pol, C, p, proof, proof_len, pr)) return fail(1);
+  if (!proof_read(pol, C, p, proof, proof_len, pr)) return fail(kWhyParse);
   tv[1] = now_ms();
   LF_HIP(c, hipSetDevice(c->device));
   const Ts<P> ts{&pol, tso, tso->user};
@@ -1223,80 +1371,22 @@ int verify(lfgpu_ctx* c, const lfgpu_circuit* C, const P& pol, const lfgpu_liger
   std::vector<size_t> lqc;
   pad_layout<P>(F, C, n_witness, lqc, [] { return P::zero(); }, nullptr, nullptr);
   tv[2] = now_ms();
-  // LigeroVerifier::verify: replay the challenges
-  uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};
-  ts.write_bytes(hash_of_A, 32);
-  std::vector<E> u_ldt(p.nwqrow), alphal(cs.n), alphaq(3 * p.nq), u_quad(p.nqtriples ? p.nqtriples : 1);
-  for (auto& e : u_ldt) e = ts.elt();
-  for (auto& e : alphal) e = ts.elt();
-  for (auto& e : alphaq) e = ts.elt();
-  for (size_t i = 0; i < p.nqtriples; ++i) u_quad[i] = ts.elt();
-  ts.write_array(pr.y_ldt.data(), pr.y_ldt.size());
-  ts.write_array(pr.y_dot.data(), pr.y_dot.size());
-  ts.write_array(pr.y_q0.data(), pr.y_q0.size());
-  ts.write_array(pr.y_q2.data(), pr.y_q2.size());
-  std::vector<size_t> idx(p.nreq);
-  ts.choose(p.block_ext, p.nreq, idx.data());
-  auto req_at = [&](size_t i, size_t j) -> const E& { return pr.req[i * p.nreq + j]; };
-
-  {  // merkle_check: leaf r = SHA-256(nonce_r || column r of the opening)
-    std::vector<uint8_t> leaves(p.nreq * 32);
-    for (size_t r = 0; r < p.nreq; ++r) {
-      Sha256 s;
-      s.update(&pr.nonces[32 * r], 32);
-      for (size_t i = 0; i < p.nrow; ++i) {
-        uint8_t eb[P::kBytes];
-        pol.to_bytes(req_at(i, r), eb);
-        s.update(eb, P::kBytes);
-      }
-      s.digest(&leaves[32 * r]);
-    }
-    if (!lf_merkle_verify(p.block_ext, pr.root, pr.path.data(), pr.npath, leaves.data(), idx.data(), p.nreq)) return fail(2);
-  }
-  tv[3] = now_ms();
-
-  // device: rows [0, nwqrow) = [0^r | A_i] extended block -> block_enc, rows nwqrow.. = y_ldt, y_dot, y_quad; ext = their
-  // opened columns
-  std::vector<uint64_t> a_idx;
-  std::vector<E> a_val;
-  inner_product_sparse<P>(F, p, cs.a, alphal, lqc, alphaq, a_idx, a_val);
-  std::vector<E> ext;
-  LF_TRY(P::verifier_ext(c, F, I, p, d_eq, alphal[cs.n - 1], a_idx, a_val, pr, idx.data(), ext));
-  auto ext_at = [&](size_t row, size_t j) -> const E& { return ext[row * p.nreq + j]; };
-  tv[4] = now_ms();
-
-  for (size_t j = 0; j < p.nreq; ++j) {  // low_degree_check
-    E yc = req_at(p.ildt, j);
-    for (size_t i = 0; i < p.nwqrow; ++i) yc = F.add(yc, F.mul(u_ldt[i], req_at(i + p.iw, j)));
-    if (!P::eq(yc, ext_at(p.nwqrow, j))) return fail(3);
-  }
-  for (size_t j = 0; j < p.nreq; ++j) {  // dot_check
-    E yc = req_at(p.idot, j);
-    for (size_t i = 0; i < p.nwqrow; ++i) yc = F.add(yc, F.mul(ext_at(i, j), req_at(i + p.iw, j)));
-    if (!P::eq(yc, ext_at(p.nwqrow + 1, j))) return fail(4);
-  }
-  {  // the putative value of the inner product
-    E want = P::zero(), got = P::zero();
-    for (size_t k = 0; k < cs.n; ++k) want = F.add(want, F.mul(cs.b[k], alphal[k]));
-    for (size_t j = 0; j < p.w; ++j) got = F.add(got, pr.y_dot[p.r + j]);
-    if (!P::eq(want, got)) return fail(5);
-  }
-  {  // quadratic_check
-    const size_t iqx = p.iq, iqy = iqx + p.nqtriples, iqz = iqy + p.nqtriples;
-    for (size_t j = 0; j < p.nreq; ++j) {
-      E yc = req_at(p.iquad, j);
-      for (size_t i = 0; i < p.nqtriples; ++i) {
-        const E tmp = F.sub(req_at(iqz + i, j), F.mul(req_at(iqx + i, j), req_at(iqy + i, j)));  // z - x*y
-        yc = F.add(yc, F.mul(u_quad[i], tmp));
-      }
-      if (!P::eq(yc, ext_at(p.nwqrow + 2, j))) return fail(6);
-    }
-  }
+  // LigeroVerifier::verify; A = the dense private-input block (the EQ table, on the device) + the sparse terms
+  const uint8_t hash_of_A[32] = {0xde, 0xad, 0xbe, 0xef};
+  auto ext_fn = [&](const std::vector<E>& alphal, const std::vector<E>& alphaq, const size_t* idx, std::vector<E>& ext) {
+    std::vector<uint64_t> a_idx;
+    std::vector<E> a_val;
+    inner_product_sparse<P>(F, p, cs.a, alphal, lqc, alphaq, a_idx, a_val);
+    return P::verifier_ext(c, F, I, p, d_eq, alphal[cs.n - 1], a_idx, a_val, pr, idx, ext);
+  };
+  int w = kWhyOk;
+  LF_TRY(ligero_verify<P>(pol, F, p, pr.root, pr, ts, hash_of_A, cs.n, cs.b.data(), ext_fn, &w, tv));
+  if (w != kWhyOk) return fail(w);
   if (verbose)
     fprintf(stderr, "lfgpu zk_verify: parse %.2f ms | FS init + constraints (bind_gh_all) %.2f | challenges + merkle %.2f | A + RS extension %.2f | checks %.2f\n",
             tv[1] - tv[0], tv[2] - tv[1], tv[3] - tv[2], tv[4] - tv[3], now_ms() - tv[4]);
   *ok = 1;
-  return fail(0);
+  return fail(kWhyOk);
 }
 }  // namespace
 }  // namespace zkp

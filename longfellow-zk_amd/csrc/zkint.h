@@ -38,5 +38,29 @@ int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nr
                  const lfgpu_transcript_ops* ts, bool committed, int* ok, const char** why);
 // MerkleTreeVerifier::verify_compressed_proof (lib/merkle/merkle_tree.h:160-209), host (zk.hip)
 bool lf_merkle_verify(size_t n, const uint8_t root[32], const uint8_t* path, size_t npath, const uint8_t* leaves, const size_t* pos, size_t np);
+// ---- ligero.hip: what lfgpu_ligero_prove / lfgpu_ligero_verify (zk.hip) need below the C ABI.
+// inner_product_vector's inputs (lib/ligero/ligero_param.h:382-421), all on the host and already validated: term[t].c < nl,
+// term[t].w < nw, lqc[.] < nw, nterm + 6 nq < 2^32.  The term list may come in any order and hold duplicates.
+struct LfLigeroTerms {
+  const lfgpu_ligero_llterm* term;
+  size_t nterm;
+  const elt_t* alphal;  // [nl]
+  size_t nl;
+  const size_t* lqc;    // [nq][3]
+  const elt_t* alphaq;  // [nq][3]
+};
+// rows[i][r + j] += A[i * w + j] for the nwqrow rows [0^r | A_i] at stride ld of parameter set p (the dense part, if any, is there)
+int lf_ligero_a_rows_terms(lfgpu_ctx* c, int field, const lfgpu_ligero_param* p, size_t ld, const LfLigeroTerms* t, void* d_rows);
+// dot_proof with A = inner_product_vector(terms), on a prover that holds the whole tableau
+int lf_ligero_dot_terms(lfgpu_ligero_prover* pr, const LfLigeroTerms* t, void* h_y);
+struct LfLigeroView {
+  lfgpu_ctx* c;
+  int field, k;
+  lfgpu_ligero_param p;
+  bool whole;                  // one GPU, all rows: not sharded, not from a slab
+  std::vector<uint8_t>* wire;  // the write_com_proof bytes a size query of lfgpu_ligero_prove left behind
+  bool* wire_held;
+};
+void lf_ligero_prover_view(lfgpu_ligero_prover* pr, LfLigeroView* v);
 // K11 over 32-byte elements (quad.hip forwards field 1 here)
 int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail);
