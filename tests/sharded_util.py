@@ -13,8 +13,8 @@ from oracle_lib import FP, GF, P, elt, arr
 class OracleSlabProver:
     """the prove entry points of a row slab, restated with the oracle's Blas (partial sums, like lfgpu_ligero_prover_from_slab)"""
 
-    def __init__(self, field, p, row_lo, row_hi, slab, layers, nonces):
-        self.f, self.p, self.lo, self.hi = field, p, row_lo, row_hi
+    def __init__(self, field, p, row_lo, row_hi, slab, layers, nonces, subfield_log_bits=4):
+        self.f, self.p, self.lo, self.hi, self.k = field, p, row_lo, row_hi, subfield_log_bits
         self.T = slab.numpy().view(np.uint64).reshape(row_hi - row_lo, p.block_enc, 2)
         self.layers, self.nonces = layers, nonces
 
@@ -42,7 +42,7 @@ class OracleSlabProver:
         for i in self._wq():
             ext = np.zeros((p.dblock, 2), dtype=np.uint64)
             ext[p.r:p.r + p.w] = A[i * p.w:(i + 1) * p.w]
-            _rs(self.f, p.block, p.dblock, ext)
+            _rs(self.f, p.block, p.dblock, ext, self.k)
             o.lfo_vaxpy(self.f, p.dblock, P(y), P(ext), P(self._row(p.iw + i, p.dblock)))
         return y
 
@@ -86,10 +86,10 @@ def merkle_open_host(n, layers, pos):
     return out
 
 
-def _rs(field, n, m, row):
+def _rs(field, n, m, row, subfield_log_bits=4):
     o = ol.oracle()
     if field == GF:
-        o.lfo_lch14_rs_interpolate(C.byref(ol.gf_ctx(4)), n, m, P(row))
+        o.lfo_lch14_rs_interpolate(C.byref(ol.gf_ctx(subfield_log_bits)), n, m, P(row))
     else:
         o.lfo_fp_rs_interpolate(n, m, P(row))
 

@@ -23,7 +23,8 @@ tampered copies.
 
 test_fixtures_cover_the_shapes holds what the cases are FOR: a fixture regenerated with less coverage fails it.
 
-Not reached: the rejection branch of elt_sample (a draw >= p, about 2^-20 per draw) needs a crafted transcript."""
+The rejection branch of elt_sample (a draw >= p, about 2^-20 per draw) is reached by test_verifier_checks.py, which splices such
+draws into a scripted transcript; the same file makes each check of the verifier the one that refuses, with its exact reason."""
 import hashlib
 import json
 import lzma
