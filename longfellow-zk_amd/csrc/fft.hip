@@ -209,10 +209,12 @@ __global__ __launch_bounds__(FFT_THREADS) void fp_fft_tile(TilePlan p, const elt
 // of fp_fft_two_pass: O::one() and outputs of the host product O::hmul): a stage twiddle out of LDS or W
 // (t4_stages) or an entry of the inter-pass table (pass A's store side, pass B's load side).  fpt_mul rests on that: it leaves
 // out three carry captures that b3 <= 0xfffff000 makes impossible.  x may be lazy.  Never swap the two.
+// mul_tw_sw(x, w): the same product for a wave-uniform w held in SGPRs (fpt_mul_sw); fp_fft_tile_1024x4_tw2 only.
 template <class O>
 struct T4Ops : O {
   static __device__ __forceinline__ elt_t add_lazy(elt_t a, elt_t b) { return O::add(a, b); }
   static __device__ __forceinline__ elt_t canon(elt_t a) { return a; }
+  static __device__ __forceinline__ elt_t mul_tw_sw(elt_t a, elt_t w) { return O::mul_tw(a, w); }
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 template <>
@@ -222,6 +224,7 @@ struct T4Ops<Fp128Ops> : Fp128Ops {
   static __device__ __forceinline__ elt_t canon(elt_t a) { return fpt_canon(a); }
   static __device__ __forceinline__ elt_t sub(elt_t a, elt_t b) { return fpt_sub(a, b); }
   static __device__ __forceinline__ elt_t mul_tw(elt_t a, elt_t w) { return fpt_mul(a, w); }
+  static __device__ __forceinline__ elt_t mul_tw_sw(elt_t a, elt_t w) { return fpt_mul_sw(a, w); }  // w wave-uniform, in SGPRs
 };
 #endif
 
@@ -545,6 +548,188 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws_canon(TilePlan 
   fp_fft_tile_1024x4_tws_body<O, KFAST_SRC, false>(p, W, wshift, tw, row_fast);
 }
 
+// ------------------------------------------------------------------ K1: the 1024 x 4 pair with a wave-uniform round 1
+// fp_fft_tile_1024x4_tw2 is fp_fft_tile_1024x4_tws (LAZY) with another lane map in round 1 and, to carry it, another LDS layout;
+// loads, stores, the inter-pass product, the lazy rules of rounds 0, 2 and 3 and the bytes that come out are the same.  Round 0's
+// three uniform twiddles (w^128, w^256, w^384) are scalar operands of its products like round 1's, not moved into VGPRs.  It has
+// round helpers and a slot function of its own (t4w_*): t4_slot and the t4_round* above belong to the kernels above.
+//
+// Round 1.  A wave takes one j: j = tid >> 6 (made scalar), lanes = (c, h) = (lane & 3, lane >> 2), positions 64h + j + 8a.  The
+// round has 56 twiddles per workgroup, 7 per j: w_1024^(64 j) for stage 3, ^(32 (j + 8k)), k < 2, for stage 4, ^(16 (j + 8k)),
+// k < 4, for stage 5 (t4_stages' jj << sh).  The wave fetches its seven by scalar loads from W, in flight beside the tile's loads,
+// and they are the scalar operand of the products (T4Ops::mul_tw_sw): no LDS read and no slot arithmetic for them.  The j = 0
+// wave takes a uniform branch to a round without its seven products by w^0 (all four of stage 3, k = 0 of stages 4 and 5), five
+// products instead of twelve.  Lazy rule of that wave: a butterfly's v has to be canonical (fpt_add_lazy, fpt_sub), and a v that
+// is not multiplied is not.  Round 0's rule (full adds on canonical inputs make those v) does not carry over, because this round's
+// inputs come lazy out of round 0: every one of the seven v is either such an input (x[1], x[3], x[5], x[7] at stage 3) or a sum
+// whose u is one (x[2], x[6] at stage 4; x[4] at stage 5), and a full add wants u canonical as well.  So each skipped product
+// becomes T4Ops::canon(v), 8 instructions for 50; the sums stay lazy.
+//
+// LDS layout: position p, column c at slot (4p + c) ^ L(p), L(p) = (p >> 7) ^ ((p >> 4) & 12): a GF(2)-linear map of p6..p9 into
+// the low four slot bits (p6 -> 4, p7 -> 9, p8 -> 2, p9 -> 4), inside an aligned 16-slot row like (4p + c) ^ (p >> 7), under
+// which the (c, h) lanes above would meet 4-way bank conflicts.  With ds_read_b128 served 16 lanes at a time on 64 banks (slots
+// mod 16 distinct) and ds_write_b128 8 lanes at a time on 32 banks (slots mod 8 distinct), a lane group is free of conflicts when
+//   round-0 write, pass A (lanes c, then p9, ..): L(p9) has bit 2;      pass B (lanes p9, p8, p7, ..): L(p7), L(p8), L(p9) are
+//   independent in bits 0-2;      round-1 read (lanes c, p6, p7): L(p6), L(p7) independent in bits 2-3;      round-1 write (c, p6):
+//   L(p6) has bit 2;      rounds 2 and 3 (lanes c, p0, p1): always.
+// tests/test_fp128_tile_r1wave_layout.py is the model.  Offsets: L moves with the register index a only where a reaches p6..p9.
+// Round 0 (positions 8b + a): a & 3 lands in slot bits 2-3, which L also writes, so four bases s0 ^ 4 (a & 3), + 16 for a >= 4.
+// Round 1: one base, + 32 a.  Round 2 (a = p6, p7): (s0 ^ L(64 a)) + 256 a.  Round 3 (a = p8, p9): (s0 ^ 2a) + 1024 a.
+__device__ __forceinline__ u32 t4w_swz(u32 p) { return (p >> 7) ^ ((p >> 4) & 12u); }  // L(p), p < 1024
+__device__ __forceinline__ u32 t4w_slot(u32 p, u32 c) { return ((p << 2) | c) ^ t4w_swz(p); }
+
+// Index into the stage-twiddle table w_1024^i of a radix-8 round's twiddle m < 7 at j, the round starting at stage ST:
+// m = 2^t - 1 + k is stage ST + t's (a mod 2^t) = k, as t4_stages' jj << sh
+template <u32 ST>
+__device__ __forceinline__ u32 t4w_tw_index(u32 j, u32 m) {
+  const u32 t = m < 1 ? 0 : m < 3 ? 1 : 2, k = m + 1 - (1u << t);
+  return (j + (k << ST)) << (9 - ST - t);
+}
+// Three stages on the register group x[a] with the wave's seven twiddles w[m] (t4w_tw_index) in SGPRs, all sums lazy but for
+// T4W_R0.  T4W_R1: every product.  T4W_R0 and T4W_R1_J0 (j = 0) leave out the products by w^0 (k = 0; w[0], w[1], w[3] are not
+// read): T4W_R0 with t4_stages' ROUND0 rule, full adds where a sum becomes the v of such a butterfly; T4W_R1_J0 makes each such v
+// canonical (see above).
+enum : u32 { T4W_R0 = 0, T4W_R1 = 1, T4W_R1_J0 = 2 };
+template <class O, u32 MODE>
+__device__ __forceinline__ void t4w_stages(elt_t* x, const elt_t* w) {
+#pragma unroll
+  for (u32 t = 0; t < 3; ++t) {
+    const u32 half = 1u << t;
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) {
+      if (a & half) continue;
+      const u32 k = a & (half - 1);
+      const bool skip = MODE != T4W_R1 && k == 0, full = MODE == T4W_R0 && ((t == 0 && a != 0) || (t == 1 && a == 4));
+      const elt_t u = x[a], v = !skip ? T4Ops<O>::mul_tw_sw(x[a + half], w[half - 1 + k]) : MODE == T4W_R1_J0 ? T4Ops<O>::canon(x[a + half]) : x[a + half];
+      x[a] = full ? T4Ops<O>::add(u, v) : T4Ops<O>::add_lazy(u, v);
+      x[a + half] = T4Ops<O>::sub(u, v);
+    }
+  }
+}
+// Round 0, as t4_round0, with its twiddles w (t4w_tw_index<0>(0, m)) in SGPRs
+template <class O>
+__device__ __forceinline__ void t4w_round0(elt_t* s, const elt_t* y, u32 kb, u32 c, const elt_t* w) {
+  elt_t x[8];
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];
+  t4w_stages<O, T4W_R0>(x, w);
+  const u32 s0 = t4w_slot((__brev(kb) >> 25) << 3, c);
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) st16(&s[(s0 ^ (4 * (a & 3))) + 16 * (a >> 2)], x[a]);
+}
+// Round 1 of the wave with twiddle index j (uniform): group (c, h < 16) = positions 64h + j + 8a
+template <class O, u32 MODE>
+__device__ __forceinline__ void t4w_round1_wave(elt_t* s, u32 s0, const elt_t* w) {
+  elt_t x[8];
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
+  t4w_stages<O, MODE>(x, w);
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
+}
+// Each path loads and stores for itself: with the eight values joined in registers behind the branch the kernel takes 16 VGPRs
+// more.  The two asm comments differ, so the compiler cannot merge the paths' loads and stores again.
+template <class O>
+__device__ __forceinline__ void t4w_round1(elt_t* s, u32 tid, u32 j, const elt_t* w) {
+  const u32 c = tid & 3, h = (tid >> 2) & 15;
+  const u32 s0 = t4w_slot(64 * h + j, c);
+  if (j == 0) {
+    asm volatile("; round 1, j = 0");
+    t4w_round1_wave<O, T4W_R1_J0>(s, s0, w);
+    asm volatile("; round 1, j = 0: stored");
+  } else {
+    asm volatile("; round 1, j > 0");
+    t4w_round1_wave<O, T4W_R1>(s, s0, w);
+    asm volatile("; round 1, j > 0: stored");
+  }
+}
+// Round 2, one group e = tid + 512 g, as t4_round2: positions 256h + j + 64a
+template <class O>
+__device__ __forceinline__ void t4w_round2(elt_t* s, u32 e, const elt_t* wl, const elt_t* __restrict__ W, u32 wshift) {
+  const u32 c = e & 3, h = e >> 8, j = (e >> 2) & 63;
+  const u32 s0 = t4w_slot(256 * h + j, c);
+  elt_t x[4];
+#pragma unroll
+  for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ t4w_swz(64 * a)) + 256 * a]);
+  t4_stages<O, 6, 2, false, T4_LAZY>(x, j, wl, W, wshift);
+#pragma unroll
+  for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ t4w_swz(64 * a)) + 256 * a], x[a]);
+}
+// Round 3's LDS loads of one group e = tid + 512 g, as t4_round3_load: positions j + 256a
+__device__ __forceinline__ void t4w_round3_load(elt_t* x, const elt_t* s, u32 e) {
+  const u32 s0 = t4w_slot(e >> 2, e & 3);
+#pragma unroll
+  for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ (2 * a)) + 1024 * a]);
+}
+
+template <class O, bool KFAST_SRC>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tw2(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                                 const elt_t* __restrict__ tw, u32 row_fast) {
+  extern __shared__ elt_t s[];
+  elt_t* const wl = s + 4096;
+  const u32 tid = threadIdx.x, j1 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  u32 bx, by;  // (tile, batch row)
+  if (KFAST_SRC) {
+    bx = row_fast ? blockIdx.y : blockIdx.x;
+    by = row_fast ? blockIdx.x : blockIdx.y;
+  } else {
+    t4_xcd_order(p.nbatch >> 2, blockIdx.x, bx, by);
+  }
+  elt_t w0[7] = {}, w1[7];  // the stage twiddles of rounds 0 and 1
+  {  // round 0
+    const u32 c = KFAST_SRC ? tid >> 7 : tid & 3, kb = KFAST_SRC ? tid & 127 : tid >> 2;
+    const elt_t* src = p.src + (long long)by * p.src_row + (long long)bx * p.src_tile;
+    const u32 sk = (u32)p.sk, off = kb * sk + c * (u32)p.sc;
+    elt_t y[8], t[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) y[a] = ld16(src + (off + 128 * a * sk));
+    if (KFAST_SRC) {
+      const elt_t* twt = tw + ((size_t)bx << 12);
+      const u32 toff = (c << 10) + kb;
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) t[a] = ld16(twt + (toff + 128 * a));
+    }
+    const elt_t wv = ld16(&W[(size_t)tid << wshift]);
+#pragma unroll
+    for (u32 m = 0; m < 7; ++m) {  // scalar loads; round 0 multiplies by w^128, w^256 (twice: m = 2 and 5) and w^384
+      w1[m] = ld16(&W[(size_t)t4w_tw_index<3>(j1, m) << wshift]);
+      if (m >= 4) w0[m] = ld16(&W[(size_t)t4w_tw_index<0>(0, m) << wshift]);
+    }
+#pragma unroll
+    for (u32 m = 0; m < 7; ++m) {  // the empty asm keeps them here, all ten behind one wait: the compiler would sink them to their rounds
+      asm volatile("" : "+s"(w1[m].lo), "+s"(w1[m].hi));
+      if (m >= 4) asm volatile("" : "+s"(w0[m].lo), "+s"(w0[m].hi));
+    }
+    w0[2] = w0[5];
+    __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first wait, as in fp_fft_tile_1024x4
+    if (KFAST_SRC) {
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) y[a] = T4Ops<O>::mul_tw(y[a], t[a]);
+    }
+    t4w_round0<O>(s, y, kb, c, w0);
+    st16(&wl[t4_wslot(tid)], wv);
+  }
+  __syncthreads();
+  t4w_round1<O>(s, tid, j1, w1);
+  __syncthreads();
+#pragma unroll
+  for (u32 g = 0; g < 2; ++g) t4w_round2<O>(s, tid + 512 * g, wl, W, wshift);
+  __syncthreads();
+  {  // round 3
+    elt_t* dst = p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile;
+    const u32 dk = (u32)p.dk, dc = (u32)p.dc;
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {
+      const u32 e = tid + 512 * g, c = e & 3, j = e >> 2;
+      elt_t x[4];
+      t4w_round3_load(x, s, e);
+      t4_stages<O, 8, 2, false, KFAST_SRC ? T4_LAZY_OUT : T4_LAZY>(x, j, wl, W, wshift);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), x[a]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ K2: LCH14
 // Stage ii of the tile (global stage i = i_lo + ii) uses
 //   tw = tbl[off[ii] + u_local]  (^ base[ii*nb + cbase + c] when base != null)
@@ -629,7 +814,9 @@ static int set_lds_limit(lfgpu_ctx* c) {
                               (const void*)fp_fft_tile_1024x4_tws<Fp128Ops, false>,
                               (const void*)fp_fft_tile_1024x4_tws<Fp128Ops, true>,
                               (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, false>,
-                              (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, true>};
+                              (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, true>,
+                              (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, false>,
+                              (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, true>};
     for (const void* k : t4) LF_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
@@ -663,6 +850,7 @@ struct FpSwitches {
   int twside;       // LFGPU_FP_TWSIDE (default 1): see fp_twside_mode
   bool other_plan;  // LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 is set at all, to whatever value
   bool lazy;        // LFGPU_FP_LAZY (default 1): 0 launches fp_fft_tile_1024x4_tws_canon
+  bool r1wave;      // LFGPU_FP_R1WAVE (default 1): 0 launches fp_fft_tile_1024x4_tws where fp_fft_tile_1024x4_tw2 is the default
   bool two_level;   // LFGPU_FP_TW=2: the two-level inter-pass table
   bool row_fast;    // LFGPU_FP_ROWFAST (default 1): 0 keeps pass A's tiles fastest in the grid
 };
@@ -675,6 +863,7 @@ static const FpSwitches& fp_switches() {
     w.twside = num("LFGPU_FP_TWSIDE", 1);
     w.other_plan = getenv("LFGPU_FP_PERSIST") || getenv("LFGPU_FP_TILE1024");
     w.lazy = num("LFGPU_FP_LAZY", 1) != 0;
+    w.r1wave = num("LFGPU_FP_R1WAVE", 1) != 0;
     w.two_level = num("LFGPU_FP_TW", 0) == 2;
     w.row_fast = num("LFGPU_FP_ROWFAST", 1) != 0;
     return w;
@@ -732,8 +921,9 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
 // The pair fp_fft_tile_1024x4_tws (inter-pass product on pass B's load side): the default for Fp128 when both passes are 1024 x 4
 // tiles (n = 2^20) and the full table is in use.  LFGPU_FP_TWSIDE=0, or any setting of LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 (which
 // choose among the kernels of the other plan), keeps the product in pass A; =2 runs pass B with the rows fastest in the grid.
-// LFGPU_FP_LAZY=0 launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; it has
-// no effect where this plan is not taken.
+// LFGPU_FP_LAZY=0 launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; otherwise the pair
+// is fp_fft_tile_1024x4_tw2 (round 1 wave-uniform), and LFGPU_FP_R1WAVE=0 puts fp_fft_tile_1024x4_tws back.  Neither switch has
+// an effect where this plan is not taken.
 template <class O>
 static int fp_twside_mode(const lfgpu_ctx* c, u32 logn1, size_t rows, bool two_level) {
   const int mode = fp_switches().other_plan ? 0 : fp_switches().twside;
@@ -750,8 +940,9 @@ static bool launch_tile_1024x4_tws(lfgpu_ctx* c, u32 rows, size_t lds, const Til
     if (KFAST_SRC && (p.sk != 1 || p.sc != 1024 || p.src_tile != 4096)) return false;  // the table's layout [j1][k2]
     if (KFAST_SRC && (row_fast ? ncb : rows) > 65535) row_fast = !row_fast;
     const dim3 grid = !KFAST_SRC ? dim3(ncb * rows) : row_fast ? dim3(rows, ncb) : dim3(ncb, rows);
-    if (fp_switches().lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
-    else hipLaunchKernelGGL((fp_fft_tile_1024x4_tws_canon<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    if (!fp_switches().lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws_canon<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    else if (fp_switches().r1wave) hipLaunchKernelGGL((fp_fft_tile_1024x4_tw2<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    else hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     return true;
   }
   return false;

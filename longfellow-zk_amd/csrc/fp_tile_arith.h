@@ -142,12 +142,45 @@ __device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
   return FP_PACK(d0, d1, d2, d3);
 }
 
-// acc(64) += x*y; the carry-out is WRITTEN to ov (the first carry of a column: ov would be 0) or added to it
-#define FPT_MADW(acc, ov, x, y) \
-  asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\ts_nop 1\n\tv_addc_co_u32 %1, vcc, 0, 0, vcc" : "+v"(acc), "=v"(ov) : "v"(x), "v"(y) : "vcc")
+// acc(64) += x*y, y a limb of the twiddle under the constraint C: "v", or "s" for a wave-uniform twiddle held in SGPRs (the one
+// scalar source a VOP3 instruction may read; everything else of the product stays in VGPRs).  FPT_MADW WRITES the carry-out to
+// ov (the first carry of a column: ov would be 0), FPT_MADC adds it, FPT_MAD has none to catch.
+#define FPT_MAD(C, acc, x, y) asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(acc) : "v"(x), C(y) : "vcc")
+#define FPT_MADC(C, acc, ov, x, y) \
+  asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\ts_nop 1\n\tv_addc_co_u32 %1, vcc, 0, %1, vcc" : "+v"(acc), "+v"(ov) : "v"(x), C(y) : "vcc")
+#define FPT_MADW(C, acc, ov, x, y) \
+  asm("v_mad_u64_u32 %0, vcc, %2, %3, %0\n\ts_nop 1\n\tv_addc_co_u32 %1, vcc, 0, 0, vcc" : "+v"(acc), "=v"(ov) : "v"(x), C(y) : "vcc")
 #define FPT_COL(tk, acc, ov) \
   tk = (u32)(acc);           \
   acc = ((acc) >> 32) | ((u64)(ov) << 32)
+// T = a w in product scanning, t0..t7, for the twiddle's limbs under C.  Column 1's first mad is out of place, its addend
+// {acc0.hi, 0} (< 2^64: (2^32 - 1)^2 + 2^32 - 1).  The bare FPT_MADs cannot carry: a0 b2 for every a and w, a0 b3, a1 b3 and
+// a2 b3 for b3 <= 0xfffff000 (see fpt_mul).
+#define FPT_COLUMNS(C)                                                                                 \
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(acc0) : "v"(a0), C(b0) : "vcc");                       \
+  t0 = (u32)acc0;                                                                                      \
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(acc) : "v"(a0), C(b1), "v"(acc0 >> 32) : "vcc");      \
+  FPT_MADW(C, acc, ov, a1, b0);                                                                        \
+  FPT_COL(t1, acc, ov);                                                                                \
+  FPT_MAD(C, acc, a0, b2);                                                                             \
+  FPT_MADW(C, acc, ov, a1, b1);                                                                        \
+  FPT_MADC(C, acc, ov, a2, b0);                                                                        \
+  FPT_COL(t2, acc, ov);                                                                                \
+  FPT_MAD(C, acc, a0, b3);                                                                             \
+  FPT_MADW(C, acc, ov, a1, b2);                                                                        \
+  FPT_MADC(C, acc, ov, a2, b1);                                                                        \
+  FPT_MADC(C, acc, ov, a3, b0);                                                                        \
+  FPT_COL(t3, acc, ov);                                                                                \
+  FPT_MAD(C, acc, a1, b3);                                                                             \
+  FPT_MADW(C, acc, ov, a2, b2);                                                                        \
+  FPT_MADC(C, acc, ov, a3, b1);                                                                        \
+  FPT_COL(t4, acc, ov);                                                                                \
+  FPT_MAD(C, acc, a2, b3);                                                                             \
+  FPT_MADW(C, acc, ov, a3, b2);                                                                        \
+  FPT_COL(t5, acc, ov);                                                                                \
+  FPT_MAD(C, acc, a3, b3);                                                                             \
+  t6 = (u32)acc;                                                                                       \
+  t7 = (u32)(acc >> 32)
 
 // a * w / 2^128 mod p (Montgomery), as fp_mul for a, w < p.  a may be any 128-bit value (lazy) as long as w < p: T = a w < 2^128 p,
 // so T_hi < p, (T + m p) / 2^128 < 2p and W in [-p, p) as below, and the result is canonical.  Product scanning with 16 v_mad_u64_u32; the carries of column k
@@ -168,36 +201,21 @@ __device__ __forceinline__ elt_t fpt_sub(elt_t a, elt_t b) {
 // captures.  Column 0 has no carry, so column 1's accumulator is {acc0.hi, 0}; its first mad takes that pair as the addend
 // of an out-of-place v_mad_u64_u32 (the pair's high half is a register the compiler keeps at zero, its low half one v_mov_b32)
 // instead of shifting acc0 in place, which cost a v_mov_b32 and a v_mov_b64.  52 -> 50 (tests/test_fp_tile_mul50.py).
-__device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
+//
+// SW: the twiddle is wave-uniform and its limbs are SGPR operands of the mads (fpt_mul_sw; the stage twiddles of a round whose
+// twiddle index is the same in every lane of a wave, fetched by scalar loads).  A value that is not uniform must not come here:
+// the compiler would take its first active lane's.  Same schedule, same values.
+template <bool SW>
+__device__ __forceinline__ elt_t fpt_mul_t(elt_t a, elt_t b) {
   FP_W(a, a0, a1, a2, a3);
   FP_W(b, b0, b1, b2, b3);
   u32 t0, t1, t2, t3, t4, t5, t6, t7, ov;
   u64 acc0, acc;
-  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(acc0) : "v"(a0), "v"(b0) : "vcc");
-  t0 = (u32)acc0;
-  // out of place, the addend {acc0.hi, 0}; < 2^64: (2^32 - 1)^2 + 2^32 - 1
-  asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=v"(acc) : "v"(a0), "v"(b1), "v"(acc0 >> 32) : "vcc");
-  FPT_MADW(acc, ov, a1, b0);
-  FPT_COL(t1, acc, ov);
-  FP_MAD(acc, a0, b2);  // < 2^64 for every a and w (see above)
-  FPT_MADW(acc, ov, a1, b1);
-  FP_MADC(acc, ov, a2, b0);
-  FPT_COL(t2, acc, ov);
-  FP_MAD(acc, a0, b3);  // < 2^64 for b3 <= 0xfffff000: no capture (see above), and so in columns 4 and 5
-  FPT_MADW(acc, ov, a1, b2);
-  FP_MADC(acc, ov, a2, b1);
-  FP_MADC(acc, ov, a3, b0);
-  FPT_COL(t3, acc, ov);
-  FP_MAD(acc, a1, b3);
-  FPT_MADW(acc, ov, a2, b2);
-  FP_MADC(acc, ov, a3, b1);
-  FPT_COL(t4, acc, ov);
-  FP_MAD(acc, a2, b3);
-  FPT_MADW(acc, ov, a3, b2);
-  FPT_COL(t5, acc, ov);
-  FP_MAD(acc, a3, b3);
-  t6 = (u32)acc;
-  t7 = (u32)(acc >> 32);
+  if constexpr (SW) {
+    FPT_COLUMNS("s");
+  } else {
+    FPT_COLUMNS("v");
+  }
   // REDC in one 128-bit step, with U = (t0, t1, t2, u3), u3 = t3 + k, k = t0 << 12 (mod 2^32), cy = carry of t3 + k.
   // fp_mul computes m = -U and (T + m p) / 2^128 = T_hi + m - (m >> 20) + delta, delta = carry-out of T_lo + m, which is
   // cy | ([k = 0] & [U != 0]).  For U != 0, m >> 20 = 2^108 - ceil(U / 2^20) with ceil(U / 2^20) = (U >> 20) + [k != 0]
@@ -251,6 +269,8 @@ __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) {
   }
   return FP_PACK(d0, d1, d2, d3);
 }
+__device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) { return fpt_mul_t<false>(a, b); }
+__device__ __forceinline__ elt_t fpt_mul_sw(elt_t a, elt_t b) { return fpt_mul_t<true>(a, b); }
 #else
 // the host pass of a kernel that calls them, and host code: the portable forms (same values)
 LF_HD elt_t fpt_add(elt_t a, elt_t b) { return fp_add_c(a, b); }
@@ -262,4 +282,5 @@ LF_HD elt_t fpt_add_lazy(elt_t a, elt_t b) {  // the fold of the carry: 2^128 = 
   return elt_t{lo - FP_P_LO, hi - FP_P_HI - (lo < FP_P_LO)};
 }
 LF_HD elt_t fpt_mul(elt_t a, elt_t b) { return fp_mul_c(fp_canon128(a), b); }
+LF_HD elt_t fpt_mul_sw(elt_t a, elt_t b) { return fpt_mul(a, b); }
 #endif
