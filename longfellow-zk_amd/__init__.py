@@ -304,6 +304,27 @@ class LfGpu:
     def sync(self):
         self._ck(self.L.lfgpu_sync(self.h))
 
+    # --- device memory without torch: for callers whose threads each drive a context and stream of their own
+    def malloc(self, nbytes):
+        d = C.c_void_p()
+        self._ck(self.L.lfgpu_malloc(self.h, nbytes, C.byref(d)))
+        return d.value
+
+    def free(self, d_ptr):
+        self._ck(self.L.lfgpu_free(self.h, C.c_void_p(d_ptr)))
+
+    def memcpy_h2d(self, d_ptr, a):
+        """a: a contiguous numpy array; copied on the context's stream, complete on return"""
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("memcpy_h2d: contiguous array needed")
+        self._ck(self.L.lfgpu_memcpy_h2d(self.h, C.c_void_p(d_ptr), C.c_void_p(a.ctypes.data), a.nbytes))
+
+    def memcpy_d2h(self, a, d_ptr):
+        """fills the contiguous numpy array a; ordered behind the context's earlier calls, complete on return"""
+        if not a.flags["C_CONTIGUOUS"]:
+            raise ValueError("memcpy_d2h: contiguous array needed")
+        self._ck(self.L.lfgpu_memcpy_d2h(self.h, C.c_void_p(a.ctypes.data), C.c_void_p(d_ptr), a.nbytes))
+
     # --- K1 FFT<Fp128>::fftb / fftf (reference lib/algebra/fft.h:185-201)
     def fp128_fft(self, d_ptr, rows, n, ld=None, forward=False, omega=None, omega_order=1 << 32):
         omega = _u64x2(fp128_to_montgomery(FP128_OMEGA32) if omega is None else omega)

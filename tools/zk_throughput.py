@@ -8,11 +8,15 @@ are what fills it.  A job is one statement: `flatsha32` = commit + prove of the 
 run_mdoc_prover does (lib/circuits/mdoc/mdoc_zk.cc:494-522): both commits (hash circuit over GF2_128, signature circuit over
 Fp256Base), then both proofs.  Every worker first proves each of its circuits once with the fixtures' RandomEngine and
 transcript seed and REQUIRES the reference's wire bytes (untimed); the timed jobs then draw from a C-speed engine, the way the
-benchmark uses SecureRandomEngine.
+benchmark uses SecureRandomEngine.  That first comparison is made while all the other workers are idle; with --check-every N
+every Nth timed job of a worker (its jobs 0, N, 2N, ...) is that same parity proof, made while the other workers are proving,
+and must again give the reference's wire bytes.
 
-  python tools/zk_throughput.py [--jobs flatsha32,mdoc] [--k 1,2,4,8,16] [--seconds 2.0] [--json]
+  python tools/zk_throughput.py [--jobs flatsha32,mdoc] [--k 1,2,4,8,16] [--seconds 2.0] [--check-every N] [--json]
 
-Prints one JSON object: {job: {"k": {K: {"proofs_per_s", "ms_per_proof_latency", "proofs"}}, ...}}."""
+Prints one JSON object: {job: {"k": {K: {"proofs_per_s", "ms_per_proof_latency", "proofs"}}, ...}}; with --check-every also
+"checked" (parity proofs among the timed ones) and "checked_min_per_worker".  Every single proof of a fixed job list compared
+byte for byte: tests/test_zk_concurrent_parity.py."""
 import ctypes as C
 import hashlib
 import json
@@ -66,6 +70,8 @@ class Worker:
         self.done = 0
         self.lat = []
         self.err = None
+        self.check_every = 0  # --check-every: 0 = every timed job is one_job()
+        self.checked = 0
         self.phases = None  # {stem.phase: summed ms} when the caller wants the provers' own phase timers
 
     def check_parity(self):
@@ -105,7 +111,11 @@ class Worker:
             start_evt.wait()
             while time.perf_counter() < stop_at[0]:
                 t0 = time.perf_counter()
-                self.one_job()
+                if self.check_every and self.done % self.check_every == 0:
+                    self.check_parity()  # counts as a proof; its latency is listed with the others
+                    self.checked += 1
+                else:
+                    self.one_job()
                 self.lat.append(time.perf_counter() - t0)
                 self.done += 1
         except Exception as e:  # surfaces in the main thread
@@ -151,7 +161,7 @@ class SmiSampler:
         return round(sum(self.vals) / len(self.vals), 1) if self.vals else None
 
 
-def measure(pkg, base_gpu, job, ks, seconds, warm_jobs=2, log=None, device=0, smi=False, phases=False):
+def measure(pkg, base_gpu, job, ks, seconds, warm_jobs=2, log=None, device=0, smi=False, phases=False, check_every=0):
     stems = [load_stem(s) for s in JOBS[job]]
     base = {st["stem"]: pkg.Circuit(base_gpu, st["raw"]) for st in stems}
     out = {}
@@ -167,6 +177,7 @@ def measure(pkg, base_gpu, job, ks, seconds, warm_jobs=2, log=None, device=0, sm
             act = workers[:K]
             for w in act:
                 w.done, w.lat, w.phases = 0, [], ({} if phases else None)
+                w.check_every, w.checked = check_every, 0
             start, stop_at = threading.Event(), [0.0]
             th = [threading.Thread(target=w.run, args=(start, stop_at)) for w in act]
             for t in th:
@@ -189,6 +200,9 @@ def measure(pkg, base_gpu, job, ks, seconds, warm_jobs=2, log=None, device=0, sm
             lat = sorted(x for w in act for x in w.lat)
             out[str(K)] = {"proofs_per_s": round(n / wall, 2), "proofs": n, "wall_s": round(wall, 3),
                            "ms_per_proof_latency_median": round(1e3 * lat[len(lat) // 2], 3) if lat else None}
+            if check_every:
+                out[str(K)]["checked"] = sum(w.checked for w in act)
+                out[str(K)]["checked_min_per_worker"] = min(w.checked for w in act)
             if sampler:
                 out[str(K)]["gpu_busy_pct_mean_rocm_smi"] = sampler.mean()
             if phases and n:
@@ -213,6 +227,7 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--smi", action="store_true", help="sample rocm-smi --showuse during every run")
+    ap.add_argument("--check-every", type=int, default=0, help="every Nth timed job of a worker is the parity proof (fixtures' engine and seed, the reference's wire SHA-256 required); 0 = off")
     ap.add_argument("--phases", action="store_true", help="mean of the provers' own phase timers (lfgpu_zk_timings) per proof")
     a = ap.parse_args()
     import __graft_entry__ as ge
@@ -223,7 +238,7 @@ def main():
     res = {"hw_queues_env": os.environ.get("GPU_MAX_HW_QUEUES")}
     log = (lambda s: print(s, file=sys.stderr, flush=True))
     for job in a.jobs.split(","):
-        res[job] = {"circuits": JOBS[job], "k": measure(pkg, base_gpu, job, [int(k) for k in a.k.split(",")], a.seconds, log=log, device=a.device, smi=a.smi, phases=a.phases)}
+        res[job] = {"circuits": JOBS[job], "k": measure(pkg, base_gpu, job, [int(k) for k in a.k.split(",")], a.seconds, log=log, device=a.device, smi=a.smi, phases=a.phases, check_every=a.check_every)}
     base_gpu.close()
     print(json.dumps(res))
 
