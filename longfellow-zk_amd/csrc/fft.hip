@@ -215,6 +215,15 @@ struct T4Ops : O {
   static __device__ __forceinline__ elt_t add_lazy(elt_t a, elt_t b) { return O::add(a, b); }
   static __device__ __forceinline__ elt_t canon(elt_t a) { return a; }
   static __device__ __forceinline__ elt_t mul_tw_sw(elt_t a, elt_t w) { return O::mul_tw(a, w); }
+  // the paired forms of fp_fft_tile_1024x4_ilp, in place: two products, two values made canonical, (x, y) <- (x + y lazy, x - y)
+  static __device__ __forceinline__ void mul2_tw(elt_t& a, elt_t w, elt_t& b, elt_t v) { a = O::mul_tw(a, w), b = O::mul_tw(b, v); }
+  static __device__ __forceinline__ void mul2_tw_sw(elt_t& a, elt_t w, elt_t& b, elt_t v) { mul2_tw(a, w, b, v); }
+  static __device__ __forceinline__ void canon2(elt_t&, elt_t&) {}
+  static __device__ __forceinline__ void bfly_lazy(elt_t& x, elt_t& y) {
+    const elt_t u = x, t = y;
+    x = O::add(u, t), y = O::sub(u, t);
+  }
+  static __device__ __forceinline__ void bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) { bfly_lazy(xp, yp), bfly_lazy(xq, yq); }
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 template <>
@@ -225,8 +234,24 @@ struct T4Ops<Fp128Ops> : Fp128Ops {
   static __device__ __forceinline__ elt_t sub(elt_t a, elt_t b) { return fpt_sub(a, b); }
   static __device__ __forceinline__ elt_t mul_tw(elt_t a, elt_t w) { return fpt_mul(a, w); }
   static __device__ __forceinline__ elt_t mul_tw_sw(elt_t a, elt_t w) { return fpt_mul_sw(a, w); }  // w wave-uniform, in SGPRs
+  static __device__ __forceinline__ void mul2_tw(elt_t& a, elt_t w, elt_t& b, elt_t v) { fpt_mul2(a, w, b, v); }
+  static __device__ __forceinline__ void mul2_tw_sw(elt_t& a, elt_t w, elt_t& b, elt_t v) { fpt_mul2_sw(a, w, b, v); }  // w, v wave-uniform
+  static __device__ __forceinline__ void canon2(elt_t& a, elt_t& b) { fpt_canon2(a, b); }
+  static __device__ __forceinline__ void bfly_lazy(elt_t& x, elt_t& y) { fpt_bfly_lazy(x, y); }
+  static __device__ __forceinline__ void bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) { fpt_bfly2_lazy(xp, yp, xq, yq); }
 };
 #endif
+// T4Ilp<O>: the field O, its tile arithmetic issued in pairs.  fp_fft_tile_1024x4_tw2<T4Ilp<O>, ..> is the kernel
+// fp_fft_tile_1024x4_tw2<O, ..> with the stage helpers t4i_* in place of t4w_stages and t4_stages: one kernel source for both, and
+// the instantiation for O itself is untouched by the other's existence.
+template <class O>
+struct T4Ilp : O {};
+template <class O>
+struct T4IsIlp : std::false_type {};
+template <class O>
+struct T4IsIlp<T4Ilp<O>> : std::true_type {};
+template <class O>
+struct T4Ops<T4Ilp<O>> : T4Ops<O> {};
 
 // LDS layout of the tile, defined here and nowhere else: position p (bit-reversed order), column c at slot (4p + c) ^ (p >> 7),
 // the XOR staying inside an aligned 16-slot row.  It is conflict-free for every access of the four rounds (ds_write_b128: 8 x 8
@@ -553,6 +578,9 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws_canon(TilePlan 
 // loads, stores, the inter-pass product, the lazy rules of rounds 0, 2 and 3 and the bytes that come out are the same.  Round 0's
 // three uniform twiddles (w^128, w^256, w^384) are scalar operands of its products like round 1's, not moved into VGPRs.  It has
 // round helpers and a slot function of its own (t4w_*): t4_slot and the t4_round* above belong to the kernels above.
+// The default is its instantiation for T4Ilp<Fp128Ops> (LFGPU_FP_ILP=0: for Fp128Ops): the same kernel with the stage helpers
+// t4i_*, which issue a stage's products, canons and butterflies two at a time (fp_tile_arith.h), carry links filled with the
+// other operation's instructions instead of s_nop.  Same values and VALU counts; DESIGN 4.1, profiles/k1_ilp/.
 //
 // Round 1.  A wave takes one j: j = tid >> 6 (made scalar), lanes = (c, h) = (lane & 3, lane >> 2), positions 64h + j + 8a.  The
 // round has 56 twiddles per workgroup, 7 per j: w_1024^(64 j) for stage 3, ^(32 (j + 8k)), k < 2, for stage 4, ^(16 (j + 8k)),
@@ -606,13 +634,87 @@ __device__ __forceinline__ void t4w_stages(elt_t* x, const elt_t* w) {
     }
   }
 }
+// The same three stages for fp_fft_tile_1024x4_ilp: what a stage has of products, of canons and of lazy butterflies is done two
+// at a time by the paired routines of fp_tile_arith.h (T4Ops::mul2_tw_sw, canon2, bfly2_lazy), products first, and an odd one
+// left over by the single form; round 0's four butterflies with full adds stay on add / sub.  Same values: only the order in
+// which independent operations are issued differs.  t4i_plan sorts stage t's four butterflies (named by the index a of u) into
+// those lists with t4w_stages' own conditions.
+struct T4iStage {
+  u32 np, prod[4], nc, can[4], nl, lazy[4], nf, full[4];
+};
+template <u32 MODE>
+constexpr T4iStage t4i_plan(u32 t) {
+  T4iStage s{};
+  const u32 half = 1u << t;
+  for (u32 a = 0; a < 8; ++a) {
+    if (a & half) continue;
+    const bool skip = MODE != T4W_R1 && (a & (half - 1)) == 0, full = MODE == T4W_R0 && ((t == 0 && a != 0) || (t == 1 && a == 4));
+    if (!skip) s.prod[s.np++] = a;
+    else if (MODE == T4W_R1_J0) s.can[s.nc++] = a;
+    if (full) s.full[s.nf++] = a;
+    else s.lazy[s.nl++] = a;
+  }
+  return s;
+}
+template <class O, u32 MODE, u32 T>
+__device__ __forceinline__ void t4i_stage(elt_t* x, const elt_t* w) {
+  constexpr T4iStage S = t4i_plan<MODE>(T);
+  constexpr u32 half = 1u << T, first = half - 1;  // stage T's twiddles are w[first + k], k = a mod half
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.np; i += 2) {
+    const u32 a = S.prod[i], b = S.prod[i + 1];
+    T4Ops<O>::mul2_tw_sw(x[a + half], w[first + (a & first)], x[b + half], w[first + (b & first)]);
+  }
+  if constexpr (S.np & 1) x[S.prod[S.np - 1] + half] = T4Ops<O>::mul_tw_sw(x[S.prod[S.np - 1] + half], w[first + (S.prod[S.np - 1] & first)]);
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.nc; i += 2) T4Ops<O>::canon2(x[S.can[i] + half], x[S.can[i + 1] + half]);
+  if constexpr (S.nc & 1) x[S.can[S.nc - 1] + half] = T4Ops<O>::canon(x[S.can[S.nc - 1] + half]);
+#pragma unroll
+  for (u32 i = 0; i < S.nf; ++i) {
+    const u32 a = S.full[i];
+    const elt_t u = x[a], v = x[a + half];
+    x[a] = T4Ops<O>::add(u, v);
+    x[a + half] = T4Ops<O>::sub(u, v);
+  }
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.nl; i += 2) T4Ops<O>::bfly2_lazy(x[S.lazy[i]], x[S.lazy[i] + half], x[S.lazy[i + 1]], x[S.lazy[i + 1] + half]);
+  if constexpr (S.nl & 1) T4Ops<O>::bfly_lazy(x[S.lazy[S.nl - 1]], x[S.lazy[S.nl - 1] + half]);
+}
+template <class O, u32 MODE>
+__device__ __forceinline__ void t4i_stages(elt_t* x, const elt_t* w) {
+  t4i_stage<O, MODE, 0>(x, w);
+  t4i_stage<O, MODE, 1>(x, w);
+  t4i_stage<O, MODE, 2>(x, w);
+}
+// Rounds 2 and 3 (ST = 6, 8), as t4_stages<O, ST, 2, false, LZ> with LZ = T4_LAZY or T4_LAZY_OUT: a radix-4 stage is one pair
+template <class O, u32 ST, u32 LZ>
+__device__ __forceinline__ void t4i_stages4(elt_t* x, u32 j, const elt_t* wl) {
+#pragma unroll
+  for (u32 t = 0; t < 2; ++t) {
+    const u32 half = 1u << t, a = 0, b = 2 >> t, sh = 9 - ST - t;
+    T4Ops<O>::mul2_tw(x[a + half], ld16(&wl[t4_wslot(j << sh)]), x[b + half], ld16(&wl[t4_wslot((j + (b & (half - 1)) * (1u << ST)) << sh)]));
+    if (LZ == T4_LAZY_OUT && t == 1) {
+      T4Ops<O>::canon2(x[a], x[b]);
+#pragma unroll
+      for (u32 i = 0; i < 2; ++i) {
+        const elt_t u = x[i], v = x[i + half];
+        x[i] = T4Ops<O>::add(u, v);
+        x[i + half] = T4Ops<O>::sub(u, v);
+      }
+    } else {
+      T4Ops<O>::bfly2_lazy(x[a], x[a + half], x[b], x[b + half]);
+    }
+  }
+}
+// The round helpers below serve both pairs: T4IsIlp<O> chooses the stage helper and nothing else.
 // Round 0, as t4_round0, with its twiddles w (t4w_tw_index<0>(0, m)) in SGPRs
 template <class O>
 __device__ __forceinline__ void t4w_round0(elt_t* s, const elt_t* y, u32 kb, u32 c, const elt_t* w) {
   elt_t x[8];
 #pragma unroll
   for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];
-  t4w_stages<O, T4W_R0>(x, w);
+  if constexpr (T4IsIlp<O>::value) t4i_stages<O, T4W_R0>(x, w);
+  else t4w_stages<O, T4W_R0>(x, w);
   const u32 s0 = t4w_slot((__brev(kb) >> 25) << 3, c);
 #pragma unroll
   for (u32 a = 0; a < 8; ++a) st16(&s[(s0 ^ (4 * (a & 3))) + 16 * (a >> 2)], x[a]);
@@ -623,7 +725,8 @@ __device__ __forceinline__ void t4w_round1_wave(elt_t* s, u32 s0, const elt_t* w
   elt_t x[8];
 #pragma unroll
   for (u32 a = 0; a < 8; ++a) x[a] = ld16(&s[s0 + 32 * a]);
-  t4w_stages<O, MODE>(x, w);
+  if constexpr (T4IsIlp<O>::value) t4i_stages<O, MODE>(x, w);
+  else t4w_stages<O, MODE>(x, w);
 #pragma unroll
   for (u32 a = 0; a < 8; ++a) st16(&s[s0 + 32 * a], x[a]);
 }
@@ -651,7 +754,8 @@ __device__ __forceinline__ void t4w_round2(elt_t* s, u32 e, const elt_t* wl, con
   elt_t x[4];
 #pragma unroll
   for (u32 a = 0; a < 4; ++a) x[a] = ld16(&s[(s0 ^ t4w_swz(64 * a)) + 256 * a]);
-  t4_stages<O, 6, 2, false, T4_LAZY>(x, j, wl, W, wshift);
+  if constexpr (T4IsIlp<O>::value) t4i_stages4<O, 6, T4_LAZY>(x, j, wl);
+  else t4_stages<O, 6, 2, false, T4_LAZY>(x, j, wl, W, wshift);
 #pragma unroll
   for (u32 a = 0; a < 4; ++a) st16(&s[(s0 ^ t4w_swz(64 * a)) + 256 * a], x[a]);
 }
@@ -703,8 +807,13 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tw2(TilePlan p, con
     w0[2] = w0[5];
     __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first wait, as in fp_fft_tile_1024x4
     if (KFAST_SRC) {
+      if constexpr (T4IsIlp<O>::value) {
 #pragma unroll
-      for (u32 a = 0; a < 8; ++a) y[a] = T4Ops<O>::mul_tw(y[a], t[a]);
+        for (u32 a = 0; a < 8; a += 2) T4Ops<O>::mul2_tw(y[a], t[a], y[a + 1], t[a + 1]);
+      } else {
+#pragma unroll
+        for (u32 a = 0; a < 8; ++a) y[a] = T4Ops<O>::mul_tw(y[a], t[a]);
+      }
     }
     t4w_round0<O>(s, y, kb, c, w0);
     st16(&wl[t4_wslot(tid)], wv);
@@ -723,7 +832,8 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tw2(TilePlan p, con
       const u32 e = tid + 512 * g, c = e & 3, j = e >> 2;
       elt_t x[4];
       t4w_round3_load(x, s, e);
-      t4_stages<O, 8, 2, false, KFAST_SRC ? T4_LAZY_OUT : T4_LAZY>(x, j, wl, W, wshift);
+      if constexpr (T4IsIlp<O>::value) t4i_stages4<O, 8, KFAST_SRC ? T4_LAZY_OUT : T4_LAZY>(x, j, wl);
+      else t4_stages<O, 8, 2, false, KFAST_SRC ? T4_LAZY_OUT : T4_LAZY>(x, j, wl, W, wshift);
 #pragma unroll
       for (u32 a = 0; a < 4; ++a) st16(dst + ((j + 256 * a) * dk + c * dc), x[a]);
     }
@@ -816,7 +926,9 @@ static int set_lds_limit(lfgpu_ctx* c) {
                               (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, false>,
                               (const void*)fp_fft_tile_1024x4_tws_canon<Fp128Ops, true>,
                               (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, false>,
-                              (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, true>};
+                              (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, true>,
+                              (const void*)fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, false>,
+                              (const void*)fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, true>};
     for (const void* k : t4) LF_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
@@ -850,7 +962,8 @@ struct FpSwitches {
   int twside;       // LFGPU_FP_TWSIDE (default 1): see fp_twside_mode
   bool other_plan;  // LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 is set at all, to whatever value
   bool lazy;        // LFGPU_FP_LAZY (default 1): 0 launches fp_fft_tile_1024x4_tws_canon
-  bool r1wave;      // LFGPU_FP_R1WAVE (default 1): 0 launches fp_fft_tile_1024x4_tws where fp_fft_tile_1024x4_tw2 is the default
+  bool r1wave;      // LFGPU_FP_R1WAVE (default 1): 0 launches fp_fft_tile_1024x4_tws where the wave-uniform round 1 is the default
+  bool ilp;         // LFGPU_FP_ILP (default 1): 0 launches fp_fft_tile_1024x4_tw2 where fp_fft_tile_1024x4_ilp is the default
   bool two_level;   // LFGPU_FP_TW=2: the two-level inter-pass table
   bool row_fast;    // LFGPU_FP_ROWFAST (default 1): 0 keeps pass A's tiles fastest in the grid
 };
@@ -864,6 +977,7 @@ static const FpSwitches& fp_switches() {
     w.other_plan = getenv("LFGPU_FP_PERSIST") || getenv("LFGPU_FP_TILE1024");
     w.lazy = num("LFGPU_FP_LAZY", 1) != 0;
     w.r1wave = num("LFGPU_FP_R1WAVE", 1) != 0;
+    w.ilp = num("LFGPU_FP_ILP", 1) != 0;
     w.two_level = num("LFGPU_FP_TW", 0) == 2;
     w.row_fast = num("LFGPU_FP_ROWFAST", 1) != 0;
     return w;
@@ -922,8 +1036,8 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
 // tiles (n = 2^20) and the full table is in use.  LFGPU_FP_TWSIDE=0, or any setting of LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 (which
 // choose among the kernels of the other plan), keeps the product in pass A; =2 runs pass B with the rows fastest in the grid.
 // LFGPU_FP_LAZY=0 launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; otherwise the pair
-// is fp_fft_tile_1024x4_tw2 (round 1 wave-uniform), and LFGPU_FP_R1WAVE=0 puts fp_fft_tile_1024x4_tws back.  Neither switch has
-// an effect where this plan is not taken.
+// is fp_fft_tile_1024x4_ilp (round 1 wave-uniform, arithmetic in pairs); LFGPU_FP_ILP=0 puts fp_fft_tile_1024x4_tw2 back (the same
+// without the pairs) and LFGPU_FP_R1WAVE=0 fp_fft_tile_1024x4_tws.  None of the switches has an effect where this plan is not taken.
 template <class O>
 static int fp_twside_mode(const lfgpu_ctx* c, u32 logn1, size_t rows, bool two_level) {
   const int mode = fp_switches().other_plan ? 0 : fp_switches().twside;
@@ -941,6 +1055,7 @@ static bool launch_tile_1024x4_tws(lfgpu_ctx* c, u32 rows, size_t lds, const Til
     if (KFAST_SRC && (row_fast ? ncb : rows) > 65535) row_fast = !row_fast;
     const dim3 grid = !KFAST_SRC ? dim3(ncb * rows) : row_fast ? dim3(rows, ncb) : dim3(ncb, rows);
     if (!fp_switches().lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws_canon<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    else if (fp_switches().r1wave && fp_switches().ilp) hipLaunchKernelGGL((fp_fft_tile_1024x4_tw2<T4Ilp<O>, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     else if (fp_switches().r1wave) hipLaunchKernelGGL((fp_fft_tile_1024x4_tw2<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     else hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     return true;

@@ -23,6 +23,10 @@
 // in front of the SALU instructions that read a mask a VALU wrote.  Each asm statement keeps VCC and its SGPR masks live
 // only inside itself, and the ones with SALU instructions clobber SCC: the compiler may hold a live SCC across them (the carry
 // of a 64-bit address add, a loop's branch condition).
+//
+// The default pair at n = 2^20 (fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, ..>) issues the same arithmetic two operations at a time:
+// fpt_mul2_t, fpt_bfly2_lazy, fpt_bfly_lazy and fpt_canon2 at the end of this file fill those wait states with the other
+// operation's instructions.  Same values, same VALU instructions; the single routines above serve every other kernel.
 #pragma once
 #include "fields.h"
 
@@ -271,6 +275,325 @@ __device__ __forceinline__ elt_t fpt_mul_t(elt_t a, elt_t b) {
 }
 __device__ __forceinline__ elt_t fpt_mul(elt_t a, elt_t b) { return fpt_mul_t<false>(a, b); }
 __device__ __forceinline__ elt_t fpt_mul_sw(elt_t a, elt_t b) { return fpt_mul_t<true>(a, b); }
+
+// ------------------------------------------------------------------ the paired routines (fp_fft_tile_1024x4_ilp)
+// The same values as the routines above, two independent operations per call, issued so that a carry's consumer stands behind
+// its producer by independent VALU instructions of the other operation instead of an `s_nop 1`: each chain keeps its carry in a
+// register of its own, VCC or an SGPR pair (the VOP3 forms take any pair as carry-in and carry-out).  The rule is the one above,
+// 2 wait states between a VALU write of VCC or an SGPR pair and a VALU read of it; every instruction in between counts one, and
+// where only one lies in between an `s_nop 0` supplies the other.  tests/test_fp128_tile_ilp.py checks the rule on the built code.
+
+// Two butterflies: (x, y) = (u + t lazy, u - t) for (u, t) = (xp, yp) and (xq, yq), t < p.  Four chains of fpt_add_lazy / fpt_sub,
+// limb by limb: u + t of p in VCC, u - t of p in c1, q's in c2 and c3, three instructions between every link.  y's limbs take t's
+// registers (u_i + t_i is read first).  36 VALU instructions, no s_nop.
+__device__ __forceinline__ void fpt_bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) {
+  FP_W(xp, up0, up1, up2, up3);
+  FP_W(yp, tp0, tp1, tp2, tp3);
+  FP_W(xq, uq0, uq1, uq2, uq3);
+  FP_W(yq, tq0, tq1, tq2, tq3);
+  u32 dp0, dp1, dp2, dp3, dq0, dq1, dq2, dq3, eap, esp, eaq, esq;
+  u64 c1, c2, c3;
+  asm("v_add_co_u32 %[dp0], vcc, %[up0], %[tp0]\n\t"
+      "v_sub_co_u32 %[tp0], %[c1], %[up0], %[tp0]\n\t"
+      "v_add_co_u32 %[dq0], %[c2], %[uq0], %[tq0]\n\t"
+      "v_sub_co_u32 %[tq0], %[c3], %[uq0], %[tq0]\n\t"
+      "v_addc_co_u32 %[dp1], vcc, %[up1], %[tp1], vcc\n\t"
+      "v_subb_co_u32 %[tp1], %[c1], %[up1], %[tp1], %[c1]\n\t"
+      "v_addc_co_u32 %[dq1], %[c2], %[uq1], %[tq1], %[c2]\n\t"
+      "v_subb_co_u32 %[tq1], %[c3], %[uq1], %[tq1], %[c3]\n\t"
+      "v_addc_co_u32 %[dp2], vcc, %[up2], %[tp2], vcc\n\t"
+      "v_subb_co_u32 %[tp2], %[c1], %[up2], %[tp2], %[c1]\n\t"
+      "v_addc_co_u32 %[dq2], %[c2], %[uq2], %[tq2], %[c2]\n\t"
+      "v_subb_co_u32 %[tq2], %[c3], %[uq2], %[tq2], %[c3]\n\t"
+      "v_addc_co_u32 %[dp3], vcc, %[up3], %[tp3], vcc\n\t"  // the carries and borrows out: lane masks
+      "v_subb_co_u32 %[tp3], %[c1], %[up3], %[tp3], %[c1]\n\t"
+      "v_addc_co_u32 %[dq3], %[c2], %[uq3], %[tq3], %[c2]\n\t"
+      "v_subb_co_u32 %[tq3], %[c3], %[uq3], %[tq3], %[c3]\n\t"
+      // carry => - p, borrow => + p: -+ the mask at limb 0 (it is the borrow- or carry-in), -+ 0xfffff000 at limb 3
+      "v_cndmask_b32 %[eap], 0, %[k], vcc\n\t"
+      "v_cndmask_b32 %[esp], 0, %[k], %[c1]\n\t"
+      "v_cndmask_b32 %[eaq], 0, %[k], %[c2]\n\t"
+      "v_cndmask_b32 %[esq], 0, %[k], %[c3]\n\t"
+      "v_subbrev_co_u32 %[dp0], vcc, 0, %[dp0], vcc\n\t"
+      "v_addc_co_u32 %[tp0], %[c1], 0, %[tp0], %[c1]\n\t"
+      "v_subbrev_co_u32 %[dq0], %[c2], 0, %[dq0], %[c2]\n\t"
+      "v_addc_co_u32 %[tq0], %[c3], 0, %[tq0], %[c3]\n\t"
+      "v_subbrev_co_u32 %[dp1], vcc, 0, %[dp1], vcc\n\t"
+      "v_addc_co_u32 %[tp1], %[c1], 0, %[tp1], %[c1]\n\t"
+      "v_subbrev_co_u32 %[dq1], %[c2], 0, %[dq1], %[c2]\n\t"
+      "v_addc_co_u32 %[tq1], %[c3], 0, %[tq1], %[c3]\n\t"
+      "v_subbrev_co_u32 %[dp2], vcc, 0, %[dp2], vcc\n\t"
+      "v_addc_co_u32 %[tp2], %[c1], 0, %[tp2], %[c1]\n\t"
+      "v_subbrev_co_u32 %[dq2], %[c2], 0, %[dq2], %[c2]\n\t"
+      "v_addc_co_u32 %[tq2], %[c3], 0, %[tq2], %[c3]\n\t"
+      "v_subb_co_u32 %[dp3], vcc, %[dp3], %[eap], vcc\n\t"
+      "v_addc_co_u32 %[tp3], %[c1], %[esp], %[tp3], %[c1]\n\t"
+      "v_subb_co_u32 %[dq3], %[c2], %[dq3], %[eaq], %[c2]\n\t"
+      "v_addc_co_u32 %[tq3], %[c3], %[esq], %[tq3], %[c3]"
+      : [dp0] "=&v"(dp0), [dp1] "=&v"(dp1), [dp2] "=&v"(dp2), [dp3] "=&v"(dp3), [dq0] "=&v"(dq0), [dq1] "=&v"(dq1), [dq2] "=&v"(dq2),
+        [dq3] "=&v"(dq3), [tp0] "+v"(tp0), [tp1] "+v"(tp1), [tp2] "+v"(tp2), [tp3] "+v"(tp3), [tq0] "+v"(tq0), [tq1] "+v"(tq1),
+        [tq2] "+v"(tq2), [tq3] "+v"(tq3), [eap] "=&v"(eap), [esp] "=&v"(esp), [eaq] "=&v"(eaq), [esq] "=&v"(esq), [c1] "=&s"(c1),
+        [c2] "=&s"(c2), [c3] "=&s"(c3)
+      : [up0] "v"(up0), [up1] "v"(up1), [up2] "v"(up2), [up3] "v"(up3), [uq0] "v"(uq0), [uq1] "v"(uq1), [uq2] "v"(uq2), [uq3] "v"(uq3),
+        [k] "v"(0xfffff000u)
+      : "vcc");
+  xp = FP_PACK(dp0, dp1, dp2, dp3);
+  yp = FP_PACK(tp0, tp1, tp2, tp3);
+  xq = FP_PACK(dq0, dq1, dq2, dq3);
+  yq = FP_PACK(tq0, tq1, tq2, tq3);
+}
+
+// One butterfly, (x, y) = (u + t lazy, u - t) for (u, t) = (x, y): the two chains of fpt_bfly2_lazy (VCC and c1), one
+// instruction between every link and an `s_nop 0` beside it; the two v_cndmask stand between the masks and their folds.  18 VALU.
+// y has registers of its own here: tied to t's, round 0 of pass A copied two limbs of a loaded tuple out of the way.
+__device__ __forceinline__ void fpt_bfly_lazy(elt_t& x, elt_t& y) {
+  FP_W(x, u0, u1, u2, u3);
+  FP_W(y, t0, t1, t2, t3);
+  u32 d0, d1, d2, d3, y0, y1, y2, y3, ea, es;
+  u64 c1;
+  asm("v_add_co_u32 %[d0], vcc, %[u0], %[t0]\n\t"
+      "v_sub_co_u32 %[y0], %[c1], %[u0], %[t0]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[d1], vcc, %[u1], %[t1], vcc\n\t"
+      "v_subb_co_u32 %[y1], %[c1], %[u1], %[t1], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[d2], vcc, %[u2], %[t2], vcc\n\t"
+      "v_subb_co_u32 %[y2], %[c1], %[u2], %[t2], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[d3], vcc, %[u3], %[t3], vcc\n\t"
+      "v_subb_co_u32 %[y3], %[c1], %[u3], %[t3], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_cndmask_b32 %[ea], 0, %[k], vcc\n\t"
+      "v_cndmask_b32 %[es], 0, %[k], %[c1]\n\t"
+      "v_subbrev_co_u32 %[d0], vcc, 0, %[d0], vcc\n\t"
+      "v_addc_co_u32 %[y0], %[c1], 0, %[y0], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_subbrev_co_u32 %[d1], vcc, 0, %[d1], vcc\n\t"
+      "v_addc_co_u32 %[y1], %[c1], 0, %[y1], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_subbrev_co_u32 %[d2], vcc, 0, %[d2], vcc\n\t"
+      "v_addc_co_u32 %[y2], %[c1], 0, %[y2], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_subb_co_u32 %[d3], vcc, %[d3], %[ea], vcc\n\t"
+      "v_addc_co_u32 %[y3], %[c1], %[es], %[y3], %[c1]"
+      : [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [y0] "=&v"(y0), [y1] "=&v"(y1), [y2] "=&v"(y2), [y3] "=&v"(y3),
+        [ea] "=&v"(ea), [es] "=&v"(es), [c1] "=&s"(c1)
+      : [u0] "v"(u0), [u1] "v"(u1), [u2] "v"(u2), [u3] "v"(u3), [t0] "v"(t0), [t1] "v"(t1), [t2] "v"(t2), [t3] "v"(t3), [k] "v"(0xfffff000u)
+      : "vcc");
+  x = FP_PACK(d0, d1, d2, d3);
+  y = FP_PACK(y0, y1, y2, y3);
+}
+
+// Two values lazy -> canonical, as fpt_canon: p's chain in VCC, q's in c1
+__device__ __forceinline__ void fpt_canon2(elt_t& p, elt_t& q) {
+  FP_W(p, a0, a1, a2, a3);
+  FP_W(q, b0, b1, b2, b3);
+  u32 d0, d1, d2, d3, e0, e1, e2, e3;
+  u64 c1;
+  asm("v_subrev_co_u32 %[d0], vcc, 1, %[a0]\n\t"
+      "v_subrev_co_u32 %[e0], %[c1], 1, %[b0]\n\t"
+      "s_nop 0\n\t"
+      "v_subbrev_co_u32 %[d1], vcc, 0, %[a1], vcc\n\t"
+      "v_subbrev_co_u32 %[e1], %[c1], 0, %[b1], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_subbrev_co_u32 %[d2], vcc, 0, %[a2], vcc\n\t"
+      "v_subbrev_co_u32 %[e2], %[c1], 0, %[b2], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_subb_co_u32 %[d3], vcc, %[a3], %[k], vcc\n\t"  // borrow <=> the value < p: keep it
+      "v_subb_co_u32 %[e3], %[c1], %[b3], %[k], %[c1]\n\t"
+      "s_nop 0\n\t"
+      "v_cndmask_b32 %[d0], %[d0], %[a0], vcc\n\t"
+      "v_cndmask_b32 %[d1], %[d1], %[a1], vcc\n\t"
+      "v_cndmask_b32 %[d2], %[d2], %[a2], vcc\n\t"
+      "v_cndmask_b32 %[d3], %[d3], %[a3], vcc\n\t"
+      "v_cndmask_b32 %[e0], %[e0], %[b0], %[c1]\n\t"
+      "v_cndmask_b32 %[e1], %[e1], %[b1], %[c1]\n\t"
+      "v_cndmask_b32 %[e2], %[e2], %[b2], %[c1]\n\t"
+      "v_cndmask_b32 %[e3], %[e3], %[b3], %[c1]"
+      : [d0] "=&v"(d0), [d1] "=&v"(d1), [d2] "=&v"(d2), [d3] "=&v"(d3), [e0] "=&v"(e0), [e1] "=&v"(e1), [e2] "=&v"(e2), [e3] "=&v"(e3),
+        [c1] "=&s"(c1)
+      : [a0] "v"(a0), [a1] "v"(a1), [a2] "v"(a2), [a3] "v"(a3), [b0] "v"(b0), [b1] "v"(b1), [b2] "v"(b2), [b3] "v"(b3), [k] "v"(0xfffff000u)
+      : "vcc");
+  p = FP_PACK(d0, d1, d2, d3);
+  q = FP_PACK(e0, e1, e2, e3);
+}
+
+// The columns of two products P = pa pb and Q = qa qb (FPT_COLUMNS twice), one asm statement per column with both products'
+// mads and captures.  Each capturing mad writes its carry to an SGPR pair of its own and the captures follow the column's
+// last mad, so every capture stands at least two VALU instructions behind its mad; columns 1 and 5, with one capturing mad per
+// product, take an `s_nop 0`.  The bare mads (carry to VCC, never read) and the MADW / MADC distinction are those of FPT_COLUMNS.
+// Column 1's addends {acc0.hi, 0} are live together and the compiler keeps one register at zero: p's pair is made in C, as
+// FPT_COLUMNS' (one v_mov_b32 into the low half beside that zero), q's by a 64-bit shift in the statement, which needs no zero.
+#define FPT_M2 "v_mad_u64_u32 "
+#define FPT_C2 "v_addc_co_u32 "
+#define FPT_COLUMNS2(C)                                                                                                          \
+  asm(FPT_M2 "%[pacc], vcc, %[pa0], %[pb0], 0\n\t"                                                                                \
+      FPT_M2 "%[qacc], vcc, %[qa0], %[qb0], 0"                                                                                    \
+      : [pacc] "=&v"(pacc0), [qacc] "=&v"(qacc0)                                                                                  \
+      : [pa0] "v"(pa0), [pb0] C(pb0), [qa0] "v"(qa0), [qb0] C(qb0)                                                                \
+      : "vcc");                                                                                                                   \
+  pt0 = (u32)pacc0;                                                                                                               \
+  qt0 = (u32)qacc0;                                                                                                               \
+  asm("v_lshrrev_b64 %[qin], 32, %[qacc0]\n\t"                                                                                    \
+      FPT_M2 "%[pacc], vcc, %[pa0], %[pb1], %[pin]\n\t"                                                                           \
+      FPT_M2 "%[qacc], vcc, %[qa0], %[qb1], %[qin]\n\t"                                                                           \
+      FPT_M2 "%[pacc], %[s1], %[pa1], %[pb0], %[pacc]\n\t"                                                                        \
+      FPT_M2 "%[qacc], %[s2], %[qa1], %[qb0], %[qacc]\n\t"                                                                        \
+      "s_nop 0\n\t"                                                                                                               \
+      FPT_C2 "%[pov], vcc, 0, 0, %[s1]\n\t"                                                                                       \
+      FPT_C2 "%[qov], vcc, 0, 0, %[s2]"                                                                                           \
+      : [pacc] "=&v"(pacc), [qacc] "=&v"(qacc), [pov] "=&v"(pov), [qov] "=&v"(qov), [s1] "=&s"(s1), [s2] "=&s"(s2),               \
+        [qin] "=&v"(qin)                                                                                                          \
+      : [pa0] "v"(pa0), [pa1] "v"(pa1), [pb0] C(pb0), [pb1] C(pb1), [qa0] "v"(qa0), [qa1] "v"(qa1), [qb0] C(qb0), [qb1] C(qb1),   \
+        [pin] "v"(pacc0 >> 32), [qacc0] "v"(qacc0)                                                                                \
+      : "vcc");                                                                                                                   \
+  FPT_COL(pt1, pacc, pov);                                                                                                        \
+  FPT_COL(qt1, qacc, qov);                                                                                                        \
+  FPT_COLUMN2_3(C, 0, 2, 1, 1, 2, 0);                                                                                             \
+  FPT_COL(pt2, pacc, pov);                                                                                                        \
+  FPT_COL(qt2, qacc, qov);                                                                                                        \
+  asm(FPT_M2 "%[pacc], vcc, %[pa0], %[pb3], %[pacc]\n\t"                                                                          \
+      FPT_M2 "%[qacc], vcc, %[qa0], %[qb3], %[qacc]\n\t"                                                                          \
+      FPT_M2 "%[pacc], %[s1], %[pa1], %[pb2], %[pacc]\n\t"                                                                        \
+      FPT_M2 "%[qacc], %[s2], %[qa1], %[qb2], %[qacc]\n\t"                                                                        \
+      FPT_M2 "%[pacc], %[s3], %[pa2], %[pb1], %[pacc]\n\t"                                                                        \
+      FPT_M2 "%[qacc], %[s4], %[qa2], %[qb1], %[qacc]\n\t"                                                                        \
+      FPT_M2 "%[pacc], %[s5], %[pa3], %[pb0], %[pacc]\n\t"                                                                        \
+      FPT_M2 "%[qacc], %[s6], %[qa3], %[qb0], %[qacc]\n\t"                                                                        \
+      FPT_C2 "%[pov], vcc, 0, 0, %[s1]\n\t"                                                                                       \
+      FPT_C2 "%[qov], vcc, 0, 0, %[s2]\n\t"                                                                                       \
+      FPT_C2 "%[pov], vcc, 0, %[pov], %[s3]\n\t"                                                                                  \
+      FPT_C2 "%[qov], vcc, 0, %[qov], %[s4]\n\t"                                                                                  \
+      FPT_C2 "%[pov], vcc, 0, %[pov], %[s5]\n\t"                                                                                  \
+      FPT_C2 "%[qov], vcc, 0, %[qov], %[s6]"                                                                                      \
+      : [pacc] "+v"(pacc), [qacc] "+v"(qacc), [pov] "=&v"(pov), [qov] "=&v"(qov), [s1] "=&s"(s1), [s2] "=&s"(s2), [s3] "=&s"(s3), \
+        [s4] "=&s"(s4), [s5] "=&s"(s5), [s6] "=&s"(s6)                                                                            \
+      : [pa0] "v"(pa0), [pa1] "v"(pa1), [pa2] "v"(pa2), [pa3] "v"(pa3), [pb0] C(pb0), [pb1] C(pb1), [pb2] C(pb2), [pb3] C(pb3),   \
+        [qa0] "v"(qa0), [qa1] "v"(qa1), [qa2] "v"(qa2), [qa3] "v"(qa3), [qb0] C(qb0), [qb1] C(qb1), [qb2] C(qb2), [qb3] C(qb3)    \
+      : "vcc");                                                                                                                   \
+  FPT_COL(pt3, pacc, pov);                                                                                                        \
+  FPT_COL(qt3, qacc, qov);                                                                                                        \
+  FPT_COLUMN2_3(C, 1, 3, 2, 2, 3, 1);                                                                                             \
+  FPT_COL(pt4, pacc, pov);                                                                                                        \
+  FPT_COL(qt4, qacc, qov);                                                                                                        \
+  asm(FPT_M2 "%[pacc], vcc, %[pa2], %[pb3], %[pacc]\n\t"                                                                          \
+      FPT_M2 "%[qacc], vcc, %[qa2], %[qb3], %[qacc]\n\t"                                                                          \
+      FPT_M2 "%[pacc], %[s1], %[pa3], %[pb2], %[pacc]\n\t"                                                                        \
+      FPT_M2 "%[qacc], %[s2], %[qa3], %[qb2], %[qacc]\n\t"                                                                        \
+      "s_nop 0\n\t"                                                                                                               \
+      FPT_C2 "%[pov], vcc, 0, 0, %[s1]\n\t"                                                                                       \
+      FPT_C2 "%[qov], vcc, 0, 0, %[s2]"                                                                                           \
+      : [pacc] "+v"(pacc), [qacc] "+v"(qacc), [pov] "=&v"(pov), [qov] "=&v"(qov), [s1] "=&s"(s1), [s2] "=&s"(s2)                  \
+      : [pa2] "v"(pa2), [pa3] "v"(pa3), [pb2] C(pb2), [pb3] C(pb3), [qa2] "v"(qa2), [qa3] "v"(qa3), [qb2] C(qb2), [qb3] C(qb3)    \
+      : "vcc");                                                                                                                   \
+  FPT_COL(pt5, pacc, pov);                                                                                                        \
+  FPT_COL(qt5, qacc, qov);                                                                                                        \
+  asm(FPT_M2 "%[pacc], vcc, %[pa3], %[pb3], %[pacc]\n\t"                                                                          \
+      FPT_M2 "%[qacc], vcc, %[qa3], %[qb3], %[qacc]"                                                                              \
+      : [pacc] "+v"(pacc), [qacc] "+v"(qacc)                                                                                      \
+      : [pa3] "v"(pa3), [pb3] C(pb3), [qa3] "v"(qa3), [qb3] C(qb3)                                                                \
+      : "vcc");                                                                                                                   \
+  pt6 = (u32)pacc;                                                                                                                \
+  pt7 = (u32)(pacc >> 32);                                                                                                        \
+  qt6 = (u32)qacc;                                                                                                                \
+  qt7 = (u32)(qacc >> 32)
+// a column of three mads per product, a_i b_j + a_k b_l + a_m b_n (columns 2 and 4): bare, MADW, MADC
+#define FPT_COLUMN2_3(C, i, j, k, l, m, n)                                                                                        \
+  asm(FPT_M2 "%[pacc], vcc, %[pi], %[pj], %[pacc]\n\t"                                                                            \
+      FPT_M2 "%[qacc], vcc, %[qi], %[qj], %[qacc]\n\t"                                                                            \
+      FPT_M2 "%[pacc], %[s1], %[pk], %[pl], %[pacc]\n\t"                                                                          \
+      FPT_M2 "%[qacc], %[s2], %[qk], %[ql], %[qacc]\n\t"                                                                          \
+      FPT_M2 "%[pacc], %[s3], %[pm], %[pn], %[pacc]\n\t"                                                                          \
+      FPT_M2 "%[qacc], %[s4], %[qm], %[qn], %[qacc]\n\t"                                                                          \
+      FPT_C2 "%[pov], vcc, 0, 0, %[s1]\n\t"                                                                                       \
+      FPT_C2 "%[qov], vcc, 0, 0, %[s2]\n\t"                                                                                       \
+      FPT_C2 "%[pov], vcc, 0, %[pov], %[s3]\n\t"                                                                                  \
+      FPT_C2 "%[qov], vcc, 0, %[qov], %[s4]"                                                                                      \
+      : [pacc] "+v"(pacc), [qacc] "+v"(qacc), [pov] "=&v"(pov), [qov] "=&v"(qov), [s1] "=&s"(s1), [s2] "=&s"(s2), [s3] "=&s"(s3), \
+        [s4] "=&s"(s4)                                                                                                            \
+      : [pi] "v"(pa##i), [pk] "v"(pa##k), [pm] "v"(pa##m), [pj] C(pb##j), [pl] C(pb##l), [pn] C(pb##n), [qi] "v"(qa##i),          \
+        [qk] "v"(qa##k), [qm] "v"(qa##m), [qj] C(qb##j), [ql] C(qb##l), [qn] C(qb##n)                                             \
+      : "vcc")
+
+// Two products, a w / 2^128 mod p each as fpt_mul_t (same schedule per product, same preconditions: pw, qw < p, and
+// wave-uniform under SW), instruction for instruction.  The reduction is one statement: p's chains run in VCC, q's in the pair
+// qs; the shifts U >> 20 stand between the links of the two T_hi - U chains (each overwrites a limb of U behind its last reader)
+// and the two v_cndmask between the first links of the + p chains; the links of + (U >> 20) + cy have one instruction between them
+// and an `s_nop 0`.  One s_andn2_b64 per product, as before, two instructions behind the mask's VALU write.
+template <bool SW>
+__device__ __forceinline__ void fpt_mul2_t(elt_t& pa, elt_t pw, elt_t& qa, elt_t qw) {
+  FP_W(pa, pa0, pa1, pa2, pa3);
+  FP_W(pw, pb0, pb1, pb2, pb3);
+  FP_W(qa, qa0, qa1, qa2, qa3);
+  FP_W(qw, qb0, qb1, qb2, qb3);
+  u32 pt0, pt1, pt2, pt3, pt4, pt5, pt6, pt7, pov, qt0, qt1, qt2, qt3, qt4, qt5, qt6, qt7, qov;
+  u64 pacc0, pacc, qacc0, qacc, qin, s1, s2, s3, s4, s5, s6;
+  if constexpr (SW) {
+    FPT_COLUMNS2("s");
+  } else {
+    FPT_COLUMNS2("v");
+  }
+  const u32 pk = pt0 << 12, qk = qt0 << 12;
+  u32 pd0, pd1, pd2, pd3, qd0, qd1, qd2, qd3, pe, qe;
+  u64 pcy, pb, qcy, qb, qs;
+  asm("v_add_co_u32 %[pt3], %[pcy], %[pt3], %[pk]\n\t"  // u3 (in t3's register), cy
+      "v_add_co_u32 %[qt3], %[qcy], %[qt3], %[qk]\n\t"
+      "v_sub_co_u32 %[pd0], vcc, %[pt4], %[pt0]\n\t"  // T_hi - U
+      "v_sub_co_u32 %[qd0], %[qs], %[qt4], %[qt0]\n\t"
+      "v_alignbit_b32 %[pt0], %[pt1], %[pt0], 20\n\t"  // U >> 20, in U's registers
+      "v_alignbit_b32 %[qt0], %[qt1], %[qt0], 20\n\t"
+      "v_subb_co_u32 %[pd1], vcc, %[pt5], %[pt1], vcc\n\t"
+      "v_subb_co_u32 %[qd1], %[qs], %[qt5], %[qt1], %[qs]\n\t"
+      "v_alignbit_b32 %[pt1], %[pt2], %[pt1], 20\n\t"
+      "v_alignbit_b32 %[qt1], %[qt2], %[qt1], 20\n\t"
+      "v_subb_co_u32 %[pd2], vcc, %[pt6], %[pt2], vcc\n\t"
+      "v_subb_co_u32 %[qd2], %[qs], %[qt6], %[qt2], %[qs]\n\t"
+      "v_alignbit_b32 %[pt2], %[pt3], %[pt2], 20\n\t"
+      "v_alignbit_b32 %[qt2], %[qt3], %[qt2], 20\n\t"
+      "v_subb_co_u32 %[pd3], %[pb], %[pt7], %[pt3], vcc\n\t"  // borrow-out: lane masks pb, qb
+      "v_subb_co_u32 %[qd3], %[qb], %[qt7], %[qt3], %[qs]\n\t"
+      "v_lshrrev_b32 %[pt3], 20, %[pt3]\n\t"
+      "v_lshrrev_b32 %[qt3], 20, %[qt3]\n\t"
+      "v_addc_co_u32 %[pd0], vcc, %[pd0], %[pt0], %[pcy]\n\t"  // + (U >> 20) + cy, cy the carry-in
+      "v_addc_co_u32 %[qd0], %[qs], %[qd0], %[qt0], %[qcy]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[pd1], vcc, %[pd1], %[pt1], vcc\n\t"
+      "v_addc_co_u32 %[qd1], %[qs], %[qd1], %[qt1], %[qs]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[pd2], vcc, %[pd2], %[pt2], vcc\n\t"
+      "v_addc_co_u32 %[qd2], %[qs], %[qd2], %[qt2], %[qs]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[pd3], %[pcy], %[pd3], %[pt3], vcc\n\t"  // carry-out: lane masks c (in cy's SGPR pairs)
+      "v_addc_co_u32 %[qd3], %[qcy], %[qd3], %[qt3], %[qs]\n\t"
+      "s_nop 0\n\t"
+      "s_andn2_b64 %[pcy], %[pb], %[pcy]\n\t"  // W < 0 <=> b and no c
+      "s_andn2_b64 %[qcy], %[qb], %[qcy]\n\t"
+      // W < 0 => + p: + 1 at limb 0 (the mask is the carry-in), + 0xfffff000 at limb 3
+      "v_addc_co_u32 %[pd0], vcc, 0, %[pd0], %[pcy]\n\t"
+      "v_addc_co_u32 %[qd0], %[qs], 0, %[qd0], %[qcy]\n\t"
+      "v_cndmask_b32 %[pe], 0, %[k], %[pcy]\n\t"
+      "v_cndmask_b32 %[qe], 0, %[k], %[qcy]\n\t"
+      "v_addc_co_u32 %[pd1], vcc, 0, %[pd1], vcc\n\t"
+      "v_addc_co_u32 %[qd1], %[qs], 0, %[qd1], %[qs]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[pd2], vcc, 0, %[pd2], vcc\n\t"
+      "v_addc_co_u32 %[qd2], %[qs], 0, %[qd2], %[qs]\n\t"
+      "s_nop 0\n\t"
+      "v_addc_co_u32 %[pd3], vcc, %[pe], %[pd3], vcc\n\t"
+      "v_addc_co_u32 %[qd3], %[qs], %[qe], %[qd3], %[qs]"
+      : [pd0] "=&v"(pd0), [pd1] "=&v"(pd1), [pd2] "=&v"(pd2), [pd3] "=&v"(pd3), [qd0] "=&v"(qd0), [qd1] "=&v"(qd1), [qd2] "=&v"(qd2),
+        [qd3] "=&v"(qd3), [pt0] "+v"(pt0), [pt1] "+v"(pt1), [pt2] "+v"(pt2), [pt3] "+v"(pt3), [qt0] "+v"(qt0), [qt1] "+v"(qt1),
+        [qt2] "+v"(qt2), [qt3] "+v"(qt3), [pe] "=&v"(pe), [qe] "=&v"(qe), [pcy] "=&s"(pcy), [pb] "=&s"(pb), [qcy] "=&s"(qcy),
+        [qb] "=&s"(qb), [qs] "=&s"(qs)
+      : [pk] "v"(pk), [qk] "v"(qk), [k] "v"(0xfffff000u), [pt4] "v"(pt4), [pt5] "v"(pt5), [pt6] "v"(pt6), [pt7] "v"(pt7), [qt4] "v"(qt4),
+        [qt5] "v"(qt5), [qt6] "v"(qt6), [qt7] "v"(qt7)
+      : "vcc", "scc");
+  // pt0..pt3 and qt0..qt3 hold U >> 20 from here on
+  pa = FP_PACK(pd0, pd1, pd2, pd3);
+  qa = FP_PACK(qd0, qd1, qd2, qd3);
+}
+__device__ __forceinline__ void fpt_mul2(elt_t& pa, elt_t pw, elt_t& qa, elt_t qw) { fpt_mul2_t<false>(pa, pw, qa, qw); }
+__device__ __forceinline__ void fpt_mul2_sw(elt_t& pa, elt_t pw, elt_t& qa, elt_t qw) { fpt_mul2_t<true>(pa, pw, qa, qw); }
 #else
 // the host pass of a kernel that calls them, and host code: the portable forms (same values)
 LF_HD elt_t fpt_add(elt_t a, elt_t b) { return fp_add_c(a, b); }
@@ -283,4 +606,23 @@ LF_HD elt_t fpt_add_lazy(elt_t a, elt_t b) {  // the fold of the carry: 2^128 = 
 }
 LF_HD elt_t fpt_mul(elt_t a, elt_t b) { return fp_mul_c(fp_canon128(a), b); }
 LF_HD elt_t fpt_mul_sw(elt_t a, elt_t b) { return fpt_mul(a, b); }
+// the paired routines: the single ones twice
+LF_HD void fpt_bfly_lazy(elt_t& x, elt_t& y) {
+  const elt_t u = x, t = y;
+  x = fpt_add_lazy(u, t);
+  y = fpt_sub(u, t);
+}
+LF_HD void fpt_bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) {
+  fpt_bfly_lazy(xp, yp);
+  fpt_bfly_lazy(xq, yq);
+}
+LF_HD void fpt_canon2(elt_t& p, elt_t& q) {
+  p = fpt_canon(p);
+  q = fpt_canon(q);
+}
+LF_HD void fpt_mul2(elt_t& pa, elt_t pw, elt_t& qa, elt_t qw) {
+  pa = fpt_mul(pa, pw);
+  qa = fpt_mul(qa, qw);
+}
+LF_HD void fpt_mul2_sw(elt_t& pa, elt_t pw, elt_t& qa, elt_t qw) { fpt_mul2(pa, pw, qa, qw); }
 #endif

@@ -4,7 +4,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include "../longfellow-zk_amd/csrc/fields.h"
+#include "../longfellow-zk_amd/csrc/fp_tile_arith.h"
 
 #define ITERS 4096
 #define CHK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("HIP error %s at %d\n", hipGetErrorString(e), __LINE__); exit(1);} } while (0)
@@ -185,7 +185,63 @@ void runf(const char* name) {
   CHK(hipFree(d));
 }
 
+// --ilp: K1's tile arithmetic as a dependent sequence, two independent streams per lane, in the single and in the paired form of
+// csrc/fp_tile_arith.h: y <- y w (fpt_mul), then (x, y) <- (x + y lazy, x - y) (fpt_add_lazy, fpt_sub), against fpt_mul2 and
+// fpt_bfly2_lazy on the two streams at once.  Same instructions per lane either way; the single form spends its carry links on
+// `s_nop 1`, the paired one on the other stream's instructions.
+template <bool PAIRED>
+__global__ __launch_bounds__(256) void kp(elt_t* out, u64 seed) {
+  elt_t xp{threadIdx.x * 0x9E3779B97F4A7C15ull + seed, seed ^ 0x1234567ull}, yp{seed * 3 + 1, 0x0FFFFFFFFFFFFFFFull & (seed * 7)};
+  elt_t xq{xp.hi, xp.lo}, yq{yp.lo ^ 0x55ull, yp.hi >> 1};
+  const elt_t w{seed * 5 + 2, 0x0FFFFFFFFFFFFFFFull & (seed * 11)};  // < p
+  for (int i = 0; i < ITERS / 4; ++i) {
+    if (PAIRED) {
+      fpt_mul2(yp, w, yq, w);
+      fpt_bfly2_lazy(xp, yp, xq, yq);
+    } else {
+      yp = fpt_mul(yp, w);
+      yq = fpt_mul(yq, w);
+      const elt_t up = xp, uq = xq;
+      xp = fpt_add_lazy(up, yp);
+      yp = fpt_sub(up, yp);
+      xq = fpt_add_lazy(uq, yq);
+      yq = fpt_sub(uq, yq);
+    }
+  }
+  out[blockIdx.x * 256 + threadIdx.x] = elt_t{xp.lo ^ yp.lo ^ xq.lo ^ yq.lo, xp.hi ^ yp.hi ^ xq.hi ^ yq.hi};
+}
+template <bool PAIRED>
+double run_ilp(size_t lds) {
+  elt_t* d;
+  const int blocks = 256 * 16;
+  CHK(hipMalloc(&d, blocks * 256 * sizeof(elt_t)));
+  CHK(hipFuncSetAttribute((const void*)kp<PAIRED>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  hipEvent_t e0, e1;
+  CHK(hipEventCreate(&e0));
+  CHK(hipEventCreate(&e1));
+  hipLaunchKernelGGL(kp<PAIRED>, dim3(blocks), dim3(256), lds, 0, d, 99ull);
+  CHK(hipDeviceSynchronize());
+  CHK(hipEventRecord(e0));
+  for (int r = 0; r < 5; ++r) hipLaunchKernelGGL(kp<PAIRED>, dim3(blocks), dim3(256), lds, 0, d, 99ull + r);
+  CHK(hipEventRecord(e1));
+  CHK(hipEventSynchronize(e1));
+  float ms;
+  CHK(hipEventElapsedTime(&ms, e0, e1));
+  const double g = 5.0 * blocks * 256.0 * (ITERS / 4) * 2 / (ms * 1e-3) / 1e9;
+  printf("%-8s %4zu KiB LDS/WG (%zu waves/SIMD) %8.2f G (product + butterfly)/s  (%.3f ms)\n", PAIRED ? "paired" : "single", lds >> 10,
+         (160 * 1024) / lds, g, ms / 5);
+  CHK(hipFree(d));
+  return g;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && !strcmp(argv[1], "--ilp")) {  // 160 / 80 / 40 KiB of LDS per 256-thread workgroup: 1 / 2 / 4 waves per SIMD
+    for (size_t lds : {(size_t)160 * 1024, (size_t)80 * 1024, (size_t)40 * 1024}) {
+      const double s1 = run_ilp<false>(lds), s2 = run_ilp<true>(lds);
+      printf("         paired / single = %.3f\n", s2 / s1);
+    }
+    return 0;
+  }
   if (argc > 1 && !strcmp(argv[1], "--rates4")) {  // 40 KiB of LDS per 256-thread workgroup: 4 waves per SIMD
     const size_t lds = 40 * 1024;
     run_occ<4>("v_xor_b32 (fast ref)", 4, lds);
