@@ -48,8 +48,15 @@ extern "C" {
 #define LFGPU_FIELD_FP128 6
 #define LFGPU_FIELD_P256 1 /* Fp256Base, the P-256 base field: 32-byte elements (lib/algebra/fp_p256.h); accepted by
                               lfgpu_fp256_rs_encode_rows[_host], lfgpu_column_commit[_host] / lfgpu_column_leaves,
-                              lfgpu_field_binop, lfgpu_quad_upload (kvec: 32-byte elements) and the whole prover-level ABI of
-                              lfgpu_zk.h (circuits with field id 1); ld / n then count 32-byte elements.  The per-step
+                              lfgpu_field_binop, lfgpu_quad_upload (kvec: 32-byte elements), the Ligero prover of one GPU
+                              (lfgpu_ligero_layout_rows, _commit, _low_degree_proof, _dot_proof, _quadratic_proof, _open,
+                              _tableau, _free; lfgpu_ligero_prove256 / _verify256 in lfgpu_zk.h; subfield_log_bits and
+                              subfield_boundary are ignored) and the whole prover-level ABI of lfgpu_zk.h (circuits with
+                              field id 1); ld / n then count 32-byte elements, and host elements are 32-byte Montgomery
+                              images.  The other Ligero entry points refuse the field, or a prover made over it, on the host
+                              before any launch: commit_batch, commit_sharded, layout_rows_sharded, encode_rows,
+                              prover_from_slab, dot_proof_sparse (LFGPU_ERR_ARG); inner_product_rows, prove_batch, open_batch
+                              (LFGPU_ERR_UNSUPPORTED).  The per-step
                               sumcheck entry points below (partials, scatter, binds, bind_g, sumcheck_layer) take the
                               16-byte fields only: for Fp256Base those steps run inside lfgpu_zk_prove / lfgpu_zk_verify */
 
@@ -342,7 +349,9 @@ typedef struct lfgpu_ligero_prover lfgpu_ligero_prover;
  * columns [dblock, block_enc).  h_W: nw host elements; h_lqc: nq x {x,y,z}.  GF2_128: every h_W[i], i < subfield_boundary,
  * must lie in the subfield (the reference's check, :63-66; such rows are blinded with subfield randomness): LFGPU_ERR_ARG with
  * the index in the message otherwise, before anything is drawn from rng.  The same holds for every entry point below that
- * lays out witness rows (commit_batch, layout_rows, layout_rows_sharded, commit_sharded). */
+ * lays out witness rows (commit_batch, layout_rows, layout_rows_sharded, commit_sharded).
+ * Fields: GF2_128, Fp128 and P256 (h_W: 32-byte Montgomery elements; the returned prover serves low_degree_proof, dot_proof,
+ * quadratic_proof, open, tableau, free and lfgpu_ligero_prove256, and is refused by every other entry point that takes one). */
 int lfgpu_ligero_commit(lfgpu_ctx* ctx, int field, int subfield_log_bits, const lfgpu_ligero_param* p,
                         const void* h_W, size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng,
                         void* rng_user, uint8_t root_out[32], lfgpu_ligero_prover** out);
@@ -375,7 +384,9 @@ int lfgpu_ligero_commit_batch(lfgpu_ctx* ctx, int field, int subfield_log_bits, 
  *    consistent slabs of one tableau.  h_nonces: block_ext * 32 bytes, or NULL.
  *  lfgpu_ligero_encode_rows: uploads h_rows and RS-extends each row to block_enc into d_slab [(row_hi-row_lo)][block_enc]
  *    (rows IDOT / IQUAD carry dblock values, the others block).
- * lfgpu_ligero_commit is exactly layout_rows + encode_rows on [0, nrow) followed by lfgpu_column_commit. */
+ * lfgpu_ligero_commit is exactly layout_rows + encode_rows on [0, nrow) followed by lfgpu_column_commit.
+ * layout_rows takes all three fields (P256: h_W and h_rows hold 32-byte elements); encode_rows the two 16-byte fields (for P256
+ * the rows go through lfgpu_fp256_rs_encode_rows: block values for every row but IDOT / IQUAD, which carry dblock). */
 int lfgpu_ligero_layout_rows(int field, int subfield_log_bits, const lfgpu_ligero_param* p, const void* h_W,
                              size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng, void* rng_user,
                              size_t row_lo, size_t row_hi, void* h_rows, uint8_t* h_nonces);
@@ -430,7 +441,8 @@ int lfgpu_ligero_commit_sharded(lfgpu_ctx* ctx, int field, int subfield_log_bits
 int lfgpu_comm_selftest(const lfgpu_comm_ops* comm);
 /* low_degree_proof (:281-291): y[block] = T[ildt] + sum_i u_ldt[i] T[iw+i] */
 int lfgpu_ligero_low_degree_proof(lfgpu_ligero_prover* pr, const void* h_u_ldt, void* h_y);
-/* dot_proof (:293-309): y[dblock] = T[idot] + sum_i RS(block->dblock)([0^r | A_i]) (.) T[iw+i] */
+/* dot_proof (:293-309): y[dblock] = T[idot] + sum_i RS(block->dblock)([0^r | A_i]) (.) T[iw+i]; h_A: nwqrow x w host elements.
+ * This one, low_degree_proof, quadratic_proof and open take a prover of any of the three fields. */
 int lfgpu_ligero_dot_proof(lfgpu_ligero_prover* pr, const void* h_A, void* h_y);
 /* The same with the matrix A built on the device (inner_product_vector + layout_Aext, ligero_param.h:382-430):
  *   A[t] = scale * d_dense[t] for t < ndense  (the private-input block of the last constraint: d_dense is the
@@ -442,6 +454,7 @@ int lfgpu_ligero_dot_proof(lfgpu_ligero_prover* pr, const void* h_A, void* h_y);
 int lfgpu_ligero_inner_product_rows(lfgpu_ctx* ctx, int field, size_t w, size_t r, size_t ld, size_t nrows, const void* d_dense,
                                     size_t ndense, const uint64_t scale[2], const uint64_t* h_idx, const void* h_val,
                                     size_t nsparse, void* d_rows);
+/* (16-byte fields; a P-256 prover: LFGPU_ERR_ARG) */
 int lfgpu_ligero_dot_proof_sparse(lfgpu_ligero_prover* pr, const void* d_dense, size_t ndense, const uint64_t scale[2],
                                   const uint64_t* h_idx, const void* h_val, size_t nsparse, void* h_y);
 /* quadratic_proof (:311-344); LFGPU_ERR_ASSERT if the W part of y is non-zero */
@@ -477,7 +490,7 @@ int lfgpu_ligero_prove_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, siz
                              const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2);
 int lfgpu_ligero_open_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx /*[nb][nreq]*/,
                             void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath /*[nb]*/);
-/* device pointer of the resident tableau (nrow x block_enc elements) */
+/* device pointer of the resident tableau (nrow x block_enc elements of the prover's field: 16 bytes, P256 32) */
 int lfgpu_ligero_tableau(lfgpu_ligero_prover* pr, void** d_T);
 int lfgpu_ligero_free(lfgpu_ligero_prover* pr);
 

@@ -207,7 +207,8 @@ int lfgpu_zk_verify_committed(lfgpu_ctx* ctx, const lfgpu_circuit* c, size_t rat
  * (inner_product_vector, ligero_param.h:382-421); the result does not depend on the order of the terms.
  * LFGPU_ERR_ARG, found on the host before the first transcript call or launch: a NULL argument (llterm may be NULL when
  * nllterm = 0, h_lqc when nq = 0, h_b when nl = 0), a term with c >= nl or w >= nw, an lqc index >= nw,
- * nllterm + 6 nq >= 2^32 (the Fp128 accumulators are 64-bit sums of 32-bit limbs), field P256.
+ * nllterm + 6 nq >= 2^32 (the Fp128 accumulators are 64-bit sums of 32-bit limbs), field P256 or a P-256 prover (those take
+ * lfgpu_ligero_prove256 / lfgpu_ligero_verify256 below).
  * LFGPU_ERR_UNSUPPORTED: a sharded prover, or one from lfgpu_ligero_prover_from_slab. */
 typedef struct { size_t c, w; uint64_t k[2]; } lfgpu_ligero_llterm;   /* LigeroLinearConstraint: A[c][w] += k */
 
@@ -225,6 +226,30 @@ int lfgpu_ligero_verify(lfgpu_ctx* ctx, int field, int subfield_log_bits, const 
                         const uint8_t root[32], const uint8_t* proof, size_t proof_len, const lfgpu_transcript_ops* ts,
                         size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm, const uint8_t hash_of_llterm[32],
                         const void* h_b, const size_t* h_lqc, int* ok, const char** why);
+
+
+/* ---- the same two over Fp256Base (LFGPU_FIELD_P256) ----
+ * A P-256 coefficient does not fit the 16-byte term record, so the field has names of its own; everything else is as above:
+ * the transcript order, the size-query protocol (a size query RUNS the proof, ts advances, the bytes are held for the copy),
+ * the reference's *why strings and "proof does not parse".  pr comes from lfgpu_ligero_commit(field = LFGPU_FIELD_P256); k, h_b
+ * and every element on the wire are 32-byte Montgomery images; the elements go to the transcript through write_elt_array_sized
+ * with nbytes = 32.  The matrix of the dot proof is accumulated on the device from the 48-byte records AS GIVEN (one upload),
+ * exact and independent of their order: every product k * alphal[c] is added as eight 32-bit limbs into 64-bit integer
+ * accumulators of its entry A[w] and reduced once.  SUMMAND BOUND: an entry may take every term and both copy terms of every
+ * quadratic triple; the reduction (fp256_reduce_limbs) needs each 64-bit limb sum to hold (N <= 2^32 summands) and the part of
+ * the sum above 2^256 to stay below 2^40 (N <= 2^40), so a statement with nllterm + 6 nq >= 2^32 is refused.
+ * LFGPU_ERR_ARG, found on the host before the first transcript call or launch: a NULL argument (llterm may be NULL when
+ * nllterm = 0, h_lqc when nq = 0, h_b when nl = 0), a term with c >= nl or w >= nw, an lqc index >= nw, the summand bound, a
+ * transcript without write_elt_sized / write_elt_array_sized, lfgpu_ligero_prove256 on a prover of a 16-byte field (and
+ * lfgpu_ligero_prove on a P-256 prover). */
+typedef struct { size_t c, w; uint64_t k[4]; } lfgpu_ligero_llterm256; /* A[c][w] += k, k a 32-byte Montgomery image */
+int lfgpu_ligero_prove256(lfgpu_ligero_prover* pr, const lfgpu_transcript_ops* ts, size_t nl, size_t nllterm,
+                          const lfgpu_ligero_llterm256* llterm, const uint8_t hash_of_llterm[32], const size_t* h_lqc,
+                          uint8_t* buf, size_t cap, size_t* nbytes);
+int lfgpu_ligero_verify256(lfgpu_ctx* ctx, const lfgpu_ligero_param* p, const uint8_t root[32], const uint8_t* proof,
+                           size_t proof_len, const lfgpu_transcript_ops* ts, size_t nl, size_t nllterm,
+                           const lfgpu_ligero_llterm256* llterm, const uint8_t hash_of_llterm[32], const void* h_b,
+                           const size_t* h_lqc, int* ok, const char** why);
 
 #ifdef __cplusplus
 }

@@ -200,7 +200,8 @@ class GpuZkVerifier {
 // The argument types are the reference's (LigeroParam, LigeroCommitment, LigeroProof, LigeroLinearConstraint<Field>[],
 // LigeroHash, LigeroQuadraticConstraint[], Transcript, RandomEngine); only the interpolator factory is gone.  The proof crosses
 // the C ABI as the write_com_proof bytes (lib/zk/zk_proof.h:137-185), converted from / to the caller's LigeroProof below with the
-// Field's own to_bytes / of_bytes functions.  GF2_128<k> and Fp128.
+// Field's own to_bytes / of_bytes functions.  GF2_128<k>, Fp128 and Fp256Base (the last through lfgpu_ligero_prove256 /
+// lfgpu_ligero_verify256: its term record holds a 32-byte coefficient).
 namespace detail {
 constexpr size_t kComMaxRunLen = size_t{1} << 25;
 template <class Field, class LigeroProofT>
@@ -297,6 +298,21 @@ const lfgpu_ligero_llterm* llterm_image(const LlT* llterm) {
   static_assert(sizeof(LlT) == sizeof(lfgpu_ligero_llterm) && offsetof(LlT, k) == offsetof(lfgpu_ligero_llterm, k), "LigeroLinearConstraint image");
   return reinterpret_cast<const lfgpu_ligero_llterm*>(llterm);
 }
+template <class LlT>
+const lfgpu_ligero_llterm256* llterm256_image(const LlT* llterm) {  // Fp256Base: k is the 32-byte Montgomery image
+  static_assert(sizeof(LlT) == sizeof(lfgpu_ligero_llterm256) && offsetof(LlT, k) == offsetof(lfgpu_ligero_llterm256, k), "LigeroLinearConstraint image");
+  return reinterpret_cast<const lfgpu_ligero_llterm256*>(llterm);
+}
+// lfgpu_ligero_prove, or lfgpu_ligero_prove256 for Fp256Base
+template <class Field, class LlT>
+int ligero_prove_call(lfgpu_ligero_prover* lp, const lfgpu_transcript_ops* ops, size_t nl, size_t nllterm, const LlT* llterm, const uint8_t* hash,
+                      const size_t* lqc, uint8_t* buf, size_t cap, size_t* n) {
+  if constexpr (field_id<Field>() == LFGPU_FIELD_P256) {
+    return lfgpu_ligero_prove256(lp, ops, nl, nllterm, llterm256_image(llterm), hash, lqc, buf, cap, n);
+  } else {
+    return lfgpu_ligero_prove(lp, ops, nl, nllterm, llterm_image(llterm), hash, lqc, buf, cap, n);
+  }
+}
 template <class LqcT>
 const size_t* lqc_image(const LqcT* lqc) {
   static_assert(sizeof(LqcT) == 3 * sizeof(size_t), "LigeroQuadraticConstraint image");
@@ -304,7 +320,6 @@ const size_t* lqc_image(const LqcT* lqc) {
 }
 template <class Field, class ParamT>
 lfgpu_ligero_param ligero_param_of(lfgpu_ctx* ctx, const ParamT& p) {
-  static_assert(field_id<Field>() != LFGPU_FIELD_P256, "GpuLigeroProver / GpuLigeroVerifier: GF2_128 and Fp128");
   lfgpu_ligero_param q;
   check(ctx, lfgpu_ligero_param_init(&q, field_id<Field>(), subfield_log_bits<Field>(), p.nw, p.nq, p.rateinv, p.nreq, p.block_enc), "lfgpu_ligero_param_init");
   if (q.nrow != p.nrow || q.block != p.block || q.dblock != p.dblock || q.block_ext != p.block_ext || q.w != p.w)
@@ -347,10 +362,10 @@ class GpuLigeroProver {
     detail::TranscriptHook<Field, TranscriptT> hook{&ts, &F, nullptr};
     const lfgpu_transcript_ops ops = hook.ops();
     size_t n = 0;  // the size query runs the proof; the second call copies the held bytes
-    check(c_.get(), lfgpu_ligero_prove(lp_, &ops, nl, nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, detail::lqc_image(lqc), nullptr, 0, &n),
+    check(c_.get(), detail::ligero_prove_call<Field>(lp_, &ops, nl, nllterm, llterm, hash_of_llterm.bytes, detail::lqc_image(lqc), nullptr, 0, &n),
           "lfgpu_ligero_prove");
     std::vector<uint8_t> wire(n);
-    check(c_.get(), lfgpu_ligero_prove(lp_, &ops, nl, nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, detail::lqc_image(lqc), wire.data(), n, &n),
+    check(c_.get(), detail::ligero_prove_call<Field>(lp_, &ops, nl, nllterm, llterm, hash_of_llterm.bytes, detail::lqc_image(lqc), wire.data(), n, &n),
           "lfgpu_ligero_prove");
     if (!detail::com_proof_of_wire(proof, F, wire.data(), n)) check(c_.get(), LFGPU_ERR_ASSERT, "GpuLigeroProver: the library's wire bytes do not parse");
   }
@@ -382,10 +397,17 @@ class GpuLigeroVerifier {
     const lfgpu_transcript_ops ops = hook.ops();
     int ok = 0;
     const char* reason = nullptr;
-    check(c_.get(),
-          lfgpu_ligero_verify(c_.get(), field_id<Field>(), subfield_log_bits<Field>(), &q, com.root.data, wire.data(), wire.size(), &ops, nl,
-                              nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, b, detail::lqc_image(lqc), &ok, &reason),
-          "lfgpu_ligero_verify");
+    if constexpr (field_id<Field>() == LFGPU_FIELD_P256) {
+      check(c_.get(),
+            lfgpu_ligero_verify256(c_.get(), &q, com.root.data, wire.data(), wire.size(), &ops, nl, nllterm, detail::llterm256_image(llterm),
+                                   hash_of_llterm.bytes, b, detail::lqc_image(lqc), &ok, &reason),
+            "lfgpu_ligero_verify256");
+    } else {
+      check(c_.get(),
+            lfgpu_ligero_verify(c_.get(), field_id<Field>(), subfield_log_bits<Field>(), &q, com.root.data, wire.data(), wire.size(), &ops, nl,
+                                nllterm, detail::llterm_image(llterm), hash_of_llterm.bytes, b, detail::lqc_image(lqc), &ok, &reason),
+            "lfgpu_ligero_verify");
+    }
     if (why) *why = reason;
     return ok != 0;
   }

@@ -94,6 +94,30 @@ def llterm_array(llterm):
     return a
 
 
+class LigeroLlterm256(C.Structure):
+    """lfgpu_ligero_llterm256: the same term over Fp256Base, k a 32-byte Montgomery image"""
+    _fields_ = [("c", C.c_size_t), ("w", C.c_size_t), ("k", C.c_uint64 * 4)]
+
+
+LLTERM256_DTYPE = [("c", "<u8"), ("w", "<u8"), ("k", "<u8", (4,))]
+
+
+def llterm256_array(llterm):
+    """llterm_array for Fp256Base: (c, w, k) with k four uint64 words, or an array of LLTERM256_DTYPE"""
+    import numpy as np
+    if isinstance(llterm, np.ndarray) and llterm.dtype == np.dtype(LLTERM256_DTYPE):
+        return np.ascontiguousarray(llterm)
+    a = np.zeros(len(llterm), dtype=LLTERM256_DTYPE)
+    for i, (c, w, k) in enumerate(llterm):
+        a[i] = (c, w, tuple(int(x) for x in k))
+    return a
+
+
+def elt_words(field):
+    """uint64 words of one host element: 4 for Fp256Base, 2 for the 16-byte fields"""
+    return 4 if field == FIELD_P256 else 2
+
+
 class CircuitInfo(C.Structure):
     """lfgpu_circuit_info"""
     _fields_ = [("field", C.c_int)] + [(n, C.c_size_t) for n in (
@@ -212,6 +236,9 @@ def load_library():
         "lfgpu_ligero_prove": [vp, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_ligero_verify": [vp, ci, ci, C.POINTER(LigeroParam), vp, vp, sz, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, C.POINTER(ci),
                                 C.POINTER(C.c_char_p)],
+        "lfgpu_ligero_prove256": [vp, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, sz, C.POINTER(sz)],
+        "lfgpu_ligero_verify256": [vp, C.POINTER(LigeroParam), vp, vp, sz, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, C.POINTER(ci),
+                                   C.POINTER(C.c_char_p)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -506,13 +533,40 @@ def ligero_param(field, nw, nq, rateinv, nreq, block_enc, subfield_log_bits=4):
     return p
 
 
+def ligero_layout_rows(field, param, W, subfield_boundary, lqc, rng_bytes, row_lo=0, row_hi=None, subfield_log_bits=4):
+    """lfgpu_ligero_layout_rows (host only, no device): every RandomEngine draw of LigeroProver::commit in the reference's order
+    -> (the un-encoded rows [row_lo, row_hi) as [rows][dblock] elements, the block_ext Merkle nonces).  All three fields;
+    FIELD_P256: W and the rows are (n, 4) uint64 arrays of 32-byte Montgomery images."""
+    import numpy as np
+    L = load_library()
+    row_hi = param.nrow if row_hi is None else row_hi
+
+    def cb(_user, buf, n):
+        C.memmove(buf, rng_bytes(n), n)
+
+    fn = RNG_FN(cb)
+    lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
+    W = np.ascontiguousarray(W, dtype=np.uint64)
+    rows = np.zeros((max(row_hi - row_lo, 0), param.dblock, elt_words(field)), dtype=np.uint64)
+    nonces = np.zeros((param.block_ext, 32), dtype=np.uint8)
+    rc = L.lfgpu_ligero_layout_rows(field, subfield_log_bits, C.byref(param), C.c_void_p(W.ctypes.data) if W.size else None, subfield_boundary,
+                                    C.c_void_p(lq.ctypes.data) if lq.size else None, fn, None, row_lo, row_hi,
+                                    C.c_void_p(rows.ctypes.data) if rows.size else None, C.c_void_p(nonces.ctypes.data))
+    if rc != 0:
+        raise LfGpuError("lfgpu error %d: lfgpu_ligero_layout_rows" % rc)
+    return rows, nonces
+
+
 class LigeroProver:
     """Mirror of LigeroProver<Field, InterpolatorFactory> (reference lib/ligero/ligero_prover.h:34-359)
     over the C ABI: the tableau lives in HBM; the caller owns the transcript and the RandomEngine.
-    `rng_bytes(n) -> bytes` plays RandomEngine::bytes."""
+    `rng_bytes(n) -> bytes` plays RandomEngine::bytes.  Elements are (n, 2) uint64 arrays for GF(2^128) and Fp128 and (n, 4) --
+    32-byte Montgomery images -- for FIELD_P256, which commit, low_degree_proof, dot_proof, quadratic_proof, open and prove serve
+    (the batch, sharded, slab and sparse forms are for the 16-byte fields)."""
 
     def __init__(self, gpu, field, param, subfield_log_bits=4):
         self.gpu, self.field, self.p, self.k = gpu, field, param, subfield_log_bits
+        self.ew = elt_words(field)
         self.h = None
 
     def commit(self, W, subfield_boundary, lqc, rng_bytes):
@@ -619,14 +673,14 @@ class LigeroProver:
 
     def low_degree_proof(self, u_ldt):
         import numpy as np
-        y = np.zeros((self.p.block, 2), dtype=np.uint64)
+        y = np.zeros((self.p.block, self.ew), dtype=np.uint64)
         u = np.ascontiguousarray(u_ldt)
         self.gpu._ck(self.gpu.L.lfgpu_ligero_low_degree_proof(self.h, C.c_void_p(u.ctypes.data), C.c_void_p(y.ctypes.data)))
         return y
 
     def dot_proof(self, A):
         import numpy as np
-        y = np.zeros((self.p.dblock, 2), dtype=np.uint64)
+        y = np.zeros((self.p.dblock, self.ew), dtype=np.uint64)
         A = np.ascontiguousarray(A)
         self.gpu._ck(self.gpu.L.lfgpu_ligero_dot_proof(self.h, C.c_void_p(A.ctypes.data), C.c_void_p(y.ctypes.data)))
         return y
@@ -645,8 +699,8 @@ class LigeroProver:
 
     def quadratic_proof(self, u_quad):
         import numpy as np
-        y0 = np.zeros((self.p.r, 2), dtype=np.uint64)
-        y2 = np.zeros((self.p.dblock - self.p.block, 2), dtype=np.uint64)
+        y0 = np.zeros((self.p.r, self.ew), dtype=np.uint64)
+        y2 = np.zeros((self.p.dblock - self.p.block, self.ew), dtype=np.uint64)
         u = np.ascontiguousarray(u_quad)
         self.gpu._ck(self.gpu.L.lfgpu_ligero_quadratic_proof(self.h, C.c_void_p(u.ctypes.data) if u.size else None,
                                                              C.c_void_p(y0.ctypes.data), C.c_void_p(y2.ctypes.data)))
@@ -658,7 +712,7 @@ class LigeroProver:
         import numpy as np
         p = self.p
         idx_a = (C.c_size_t * p.nreq)(*idx)
-        req = np.zeros((p.nrow if rows is None else rows, p.nreq, 2), dtype=np.uint64)
+        req = np.zeros((p.nrow if rows is None else rows, p.nreq, self.ew), dtype=np.uint64)
         nonces = np.zeros((p.nreq, 32), dtype=np.uint8)
         cap = p.nreq * p.mc_pathlen + 1
         path = np.zeros((cap, 32), dtype=np.uint8)
@@ -669,19 +723,22 @@ class LigeroProver:
 
     def prove(self, ts, nl, llterm, hash_of_llterm, lqc):
         """LigeroProver::prove (:84-146) -> the write_com_proof bytes.  ts: a transcript with .ops() (FsTranscript) that already
-        holds the commitment root; llterm: llterm_array's input, any order, duplicates allowed; lqc as at commit."""
+        holds the commitment root; llterm: llterm_array's input (FIELD_P256: llterm256_array's, through lfgpu_ligero_prove256),
+        any order, duplicates allowed; lqc as at commit."""
         import numpy as np
         gpu = self.gpu
-        ll = llterm_array(llterm)
+        p256 = self.field == FIELD_P256
+        fn = gpu.L.lfgpu_ligero_prove256 if p256 else gpu.L.lfgpu_ligero_prove
+        ll = llterm256_array(llterm) if p256 else llterm_array(llterm)
         lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
         ops = ts.ops()
         h = bytes(hash_of_llterm)
         n = C.c_size_t()
         args = (self.h, C.byref(ops) if ops is not None else None, nl, len(ll), C.c_void_p(ll.ctypes.data) if len(ll) else None, h,
                 C.c_void_p(lq.ctypes.data) if lq.size else None)
-        gpu._ck(gpu.L.lfgpu_ligero_prove(*args, None, 0, C.byref(n)))  # proves and reports the size
+        gpu._ck(fn(*args, None, 0, C.byref(n)))  # proves and reports the size
         buf = C.create_string_buffer(n.value)
-        gpu._ck(gpu.L.lfgpu_ligero_prove(*args, buf, n.value, C.byref(n)))  # copies the held bytes
+        gpu._ck(fn(*args, buf, n.value, C.byref(n)))  # copies the held bytes
         return buf.raw[:n.value]
 
     def tableau_ptr(self):
@@ -1048,6 +1105,23 @@ def ligero_verify(gpu, field, p, root, proof, ts, nl, llterm, hash_of_llterm, b,
                                        C.c_void_p(ll.ctypes.data) if len(ll) else None, bytes(hash_of_llterm),
                                        C.c_void_p(b.ctypes.data) if b.size else None, C.c_void_p(lq.ctypes.data) if lq.size else None,
                                        C.byref(ok), C.byref(why)))
+    return bool(ok.value), (why.value or b"").decode()
+
+
+def ligero_verify256(gpu, p, root, proof, ts, nl, llterm, hash_of_llterm, b, lqc):
+    """ligero_verify over Fp256Base (lfgpu_ligero_verify256): llterm as llterm256_array takes it, b the nl right-hand sides as
+    32-byte Montgomery images; ts needs the sized element writes (FsTranscript has them)"""
+    import numpy as np
+    ll = llterm256_array(llterm)
+    lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
+    b = np.ascontiguousarray(b)
+    ok, why = C.c_int(), C.c_char_p()
+    ops = ts.ops()
+    raw = bytes(proof)
+    gpu._ck(gpu.L.lfgpu_ligero_verify256(gpu.h, C.byref(p), bytes(root), raw, len(raw), C.byref(ops), nl, len(ll),
+                                          C.c_void_p(ll.ctypes.data) if len(ll) else None, bytes(hash_of_llterm),
+                                          C.c_void_p(b.ctypes.data) if b.size else None, C.c_void_p(lq.ctypes.data) if lq.size else None,
+                                          C.byref(ok), C.byref(why)))
     return bool(ok.value), (why.value or b"").decode()
 
 

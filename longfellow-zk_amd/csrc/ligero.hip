@@ -18,9 +18,15 @@
 #include "runfold.h"
 #include "zkint.h"
 
-// the C ABI's opaque prover: the shared record (ligero_slab.h) over 16-byte elements, plus which of the two fields it serves
+// the C ABI's opaque prover: the shared record (ligero_slab.h) over 16-byte elements, plus which field it serves.  For field
+// P256 the record over 32-byte elements lives in zk256.hip behind `p256`, and of the 16-byte base only c and p are set: every
+// entry point below looks at the field on the host before it touches the slab.
 struct lfgpu_ligero_prover : lig::Slab<elt_t> {
   int field = 0, k = 0;
+  Lig256* p256 = nullptr;
+  ~lfgpu_ligero_prover() {
+    if (p256) lf_lig256_free(p256);
+  }
   // lfgpu_ligero_prove: the write_com_proof bytes between its size query and the copy
   std::vector<uint8_t> wire;
   bool wire_held = false;
@@ -117,8 +123,10 @@ int lf_rs_rows(lfgpu_ctx* c, int field, int k, size_t nrow, size_t n, size_t m, 
   return lfgpu_fp128_rs_encode_rows(c, nrow, n, m, om, (uint64_t)1 << 32, d, ld);
 }
 
-static bool ligero_args_ok(int field, int k, const lfgpu_ligero_param* pp, const void* h_W, const size_t* h_lqc, lfgpu_rng_fn rng) {
+// p256_ok: the entry point also serves Fp256Base (lfgpu_ligero_commit, lfgpu_ligero_layout_rows)
+static bool ligero_args_ok(int field, int k, const lfgpu_ligero_param* pp, const void* h_W, const size_t* h_lqc, lfgpu_rng_fn rng, bool p256_ok = false) {
   if (!pp || !rng || (pp->nw && !h_W) || (pp->nq && !h_lqc)) return false;
+  if (field == LFGPU_FIELD_P256) return p256_ok;
   if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return false;
   if (field == LFGPU_FIELD_GF2_128 && k != 4 && k != 5) return false;
   return true;
@@ -128,10 +136,12 @@ static bool ligero_args_ok(int field, int k, const lfgpu_ligero_param* pp, const
 extern "C" int lfgpu_ligero_layout_rows(int field, int k, const lfgpu_ligero_param* pp, const void* h_W, size_t subfield_boundary,
                                         const size_t* h_lqc, lfgpu_rng_fn rng, void* user, size_t row_lo, size_t row_hi, void* h_rows,
                                         uint8_t* h_nonces) {
-  if (!ligero_args_ok(field, k, pp, h_W, h_lqc, rng) || row_lo > row_hi || row_hi > pp->nrow || (row_hi > row_lo && !h_rows)) return LFGPU_ERR_ARG;
+  if (!ligero_args_ok(field, k, pp, h_W, h_lqc, rng, true) || row_lo > row_hi || row_hi > pp->nrow || (row_hi > row_lo && !h_rows)) return LFGPU_ERR_ARG;
+  char err[256];
+  if (field == LFGPU_FIELD_P256)
+    return lig::layout(lig::Host32{}, *pp, (const elt32_t*)h_W, 0, h_lqc, rng, user, false, row_lo, row_hi, (elt32_t*)h_rows, h_nonces, err);
   GfHostCtx g;
   if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx_build(&g, k)) return LFGPU_ERR_ARG;
-  char err[256];
   return lig::layout(lig::Host16{field, k, &g}, *pp, (const elt_t*)h_W, subfield_boundary, h_lqc, rng, user, false, row_lo, row_hi, (elt_t*)h_rows, h_nonces, err);
 }
 
@@ -286,7 +296,7 @@ extern "C" int lfgpu_ligero_free(lfgpu_ligero_prover* pr) {
 }
 extern "C" int lfgpu_ligero_tableau(lfgpu_ligero_prover* pr, void** d_T) {
   if (!pr || !d_T) return LFGPU_ERR_ARG;
-  *d_T = pr->d_T;
+  *d_T = pr->p256 ? lf_lig256_tableau(pr->p256) : pr->d_T;
   return LFGPU_OK;
 }
 
@@ -674,10 +684,19 @@ extern "C" int lfgpu_ligero_encode_rows(lfgpu_ctx* c, int field, int k, const lf
 extern "C" int lfgpu_ligero_commit(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const void* h_W,
                                    size_t subfield_boundary, const size_t* h_lqc, lfgpu_rng_fn rng, void* user,
                                    uint8_t root_out[32], lfgpu_ligero_prover** out) {
-  if (!c || !root_out || !out || !ligero_args_ok(field, k, pp, h_W, h_lqc, rng))
+  if (!c || !root_out || !out || !ligero_args_ok(field, k, pp, h_W, h_lqc, rng, true))
     return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit: bad argument (null pointer, field or subfield_log_bits)");
   const lfgpu_ligero_param& p = *pp;
   LF_HIP(c, hipSetDevice(c->device));
+  if (field == LFGPU_FIELD_P256) {  // the 32-byte record and its policy are zk256.hip's
+    std::unique_ptr<lfgpu_ligero_prover> pr(new lfgpu_ligero_prover());
+    pr->c = c;
+    pr->p = p;
+    pr->field = field;
+    LF_TRY(lf_lig256_commit(c, pp, h_W, h_lqc, rng, user, root_out, &pr->p256));
+    *out = pr.release();
+    return LFGPU_OK;
+  }
   const L16 pol = policy16(c, field, k);
   const double t0 = lig::clock_ms();
   std::unique_ptr<lfgpu_ligero_prover> pr(new_prover16(c, field, k, p, nullptr));
@@ -873,6 +892,7 @@ extern "C" int lfgpu_ligero_inner_product_rows(lfgpu_ctx* c, int field, size_t w
 extern "C" int lfgpu_ligero_low_degree_proof(lfgpu_ligero_prover* pr, const void* h_u, void* h_y) {
   if (!pr || !h_u || !h_y) return LFGPU_ERR_ARG;
   LF_HIP(pr->c, hipSetDevice(pr->c->device));
+  if (pr->p256) return lf_lig256_low_degree(pr->p256, h_u, h_y);
   return lig::low_degree(pr, policy16(pr), (const elt_t*)h_u, (elt_t*)h_y);
 }
 
@@ -881,6 +901,7 @@ extern "C" int lfgpu_ligero_dot_proof(lfgpu_ligero_prover* pr, const void* h_A, 
   lfgpu_ctx* c = pr->c;
   const lfgpu_ligero_param& p = pr->p;
   LF_HIP(c, hipSetDevice(c->device));
+  if (pr->p256) return lf_lig256_dot_dense(pr->p256, h_A, h_y);
   const size_t lda = p.dblock;
   void* sc = nullptr;
   LF_TRY(lf_scratch3(c, (p.nwqrow * p.w + p.nwqrow * lda + 2 * p.dblock) * 16 + 64, &sc));
@@ -897,6 +918,7 @@ extern "C" int lfgpu_ligero_dot_proof(lfgpu_ligero_prover* pr, const void* h_A, 
 extern "C" int lfgpu_ligero_dot_proof_sparse(lfgpu_ligero_prover* pr, const void* d_dense, size_t ndense, const uint64_t scale[2],
                                              const uint64_t* h_idx, const void* h_val, size_t nsparse, void* h_y) {
   if (!pr || !h_y) return LFGPU_ERR_ARG;
+  if (pr->p256) return lf_fail(pr->c, LFGPU_ERR_ARG, "ligero_dot_proof_sparse: 16-byte fields only (an Fp256Base prover takes lfgpu_ligero_dot_proof or lfgpu_ligero_prove256)");
   if (ndense && !scale) return lf_fail(pr->c, LFGPU_ERR_ARG, "ligero_dot_proof_sparse: a dense block needs its scale");
   LF_HIP(pr->c, hipSetDevice(pr->c->device));
   const elt_t sc = scale ? elt_t{scale[0], scale[1]} : elt_t{0, 0};
@@ -919,11 +941,13 @@ void lf_ligero_prover_view(lfgpu_ligero_prover* pr, LfLigeroView* v) {
   v->whole = !pr->sharded && pr->owns && pr->row_lo == 0 && pr->row_hi == pr->p.nrow;
   v->wire = &pr->wire;
   v->wire_held = &pr->wire_held;
+  v->lig256 = pr->p256;
 }
 
 extern "C" int lfgpu_ligero_quadratic_proof(lfgpu_ligero_prover* pr, const void* h_u_quad, void* h_y0, void* h_y2) {
   if (!pr || !h_y0 || !h_y2 || (pr->p.nqtriples && !h_u_quad)) return LFGPU_ERR_ARG;
   LF_HIP(pr->c, hipSetDevice(pr->c->device));
+  if (pr->p256) return lf_lig256_quadratic(pr->p256, h_u_quad, h_y0, h_y2);
   return lig::quadratic(pr, policy16(pr), (const elt_t*)h_u_quad, (elt_t*)h_y0, (elt_t*)h_y2);
 }
 
@@ -943,6 +967,10 @@ extern "C" int lfgpu_ligero_prover_from_slab(lfgpu_ctx* c, int field, int k, con
 extern "C" int lfgpu_ligero_open(lfgpu_ligero_prover* pr, const size_t* idx, void* h_req, uint8_t* h_nonces,
                                  uint8_t* h_path, size_t path_cap, size_t* npath) {
   if (!pr || !idx || !h_req || !h_nonces || !npath) return LFGPU_ERR_ARG;
+  if (pr->p256) {
+    LF_HIP(pr->c, hipSetDevice(pr->c->device));
+    return lf_lig256_open(pr->p256, idx, h_req, h_nonces, h_path, path_cap, npath);
+  }
   return lig::open(pr, policy16(pr), idx, (elt_t*)h_req, h_nonces, h_path, path_cap, npath);
 }
 

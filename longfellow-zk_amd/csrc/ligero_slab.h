@@ -14,7 +14,7 @@
 //   rows_vaxpy     y[j] = T0[j] + sum_i A[i][j] T[i][j]
 //   quad_combo     y[j] = Tq[j] + sum_i u[i] (Z_i[j] - X_i[j] Y_i[j])
 //   a_rows_clear / a_rows_dense / a_rows_sparse   the pieces of a_rows below; the sparse lists are on the host
-//   a_rows_terms   (16-byte policy only) rows += inner_product_vector of a term list in any order, duplicates allowed
+//   a_rows_terms   rows += inner_product_vector of a term list in any order, duplicates allowed
 //   gather_columns req[i][j] = T[i][col0 + idx[j]], idx on the host
 //   rs_rows        nrow rows of n values extended to m, in place
 //   rs_rows_mixed  a slab's three row groups in one launch where the width has such a kernel, else LFGPU_ERR_UNSUPPORTED
@@ -224,7 +224,7 @@ int dot(Slab<typename L::E>* pr, const L& pol, const typename L::E* d_dense, siz
   return dot_finish(pr, pol, dAext, dAext + p.nwqrow * lda, y);
 }
 
-// ... with A accumulated on the device from a term list in any order (pol.a_rows_terms: the 16-byte policy's step)
+// ... with A accumulated on the device from a term list in any order (pol.a_rows_terms)
 template <class L, class Terms>
 int dot_terms(Slab<typename L::E>* pr, const L& pol, const Terms& t, typename L::E* y) {
   using E = typename L::E;

@@ -95,6 +95,60 @@ __global__ __launch_bounds__(Z_THREADS) void eval_quad256_kernel(size_t n, const
   run_fold_commit256(key, t, acc);
 }
 
+// ---- inner_product_vector from a caller's term list (LigeroCommon::inner_product_vector, ligero_param.h:382-421), the step of
+// lfgpu_ligero_prove256 / lfgpu_ligero_verify256: terms in any order, duplicates allowed, one wire read by thousands of terms the
+// normal case.  The contract of a_terms_fp_kernel (ligero.hip) over 32-byte elements: the product k * alphal[c] of every term goes
+// into the accumulators of flat position w of A -- eight 64-bit sums of 32-bit limbs, the 64 contiguous bytes acc[8 w .. 8 w + 8)
+// -- with integer atomic adds, after the runs of equal w in lane order have been folded in the wave (run_fold_commit256: one run
+// head per entry issues the eight adds); then one fp256_reduce_limbs per entry.  Exact and independent of term and arrival order.
+// Summands per entry: every atomic adds the limbs of ONE canonical residue (a product, a folded run, or +-alphaq), so an entry
+// that has taken N adds holds limb sums <= N (2^32 - 1) and a total S < N 2^256.  fp256_reduce_limbs wants every limb sum to fit
+// 64 bits (N <= 2^32) and the part of S above 2^256 below 2^40 (N <= 2^40): N < 2^32 serves both.  The worst entry takes every
+// term and both copy terms of every quadratic triple, so the host refuses nllterm + 6 nq >= 2^32 (lfgpu_zk.h).
+struct llterm256_t {  // the memory image of lfgpu_ligero_llterm256
+  u64 c, w;
+  E k;
+};
+static_assert(sizeof(llterm256_t) == 48 && sizeof(lfgpu_ligero_llterm256) == 48 && sizeof(size_t) == 8, "lfgpu_ligero_llterm256 is uploaded as it stands");
+#define AT256_THREADS 256
+#define AT256_BLOCKS_MAX 1024  // grid stride: AT256_THREADS * AT256_BLOCKS_MAX terms per sweep
+__global__ __launch_bounds__(AT256_THREADS) void a_terms256_kernel(size_t n, const llterm256_t* __restrict__ t, const E* __restrict__ alphal,
+                                                                   u64* __restrict__ acc) {
+  const size_t stride = (size_t)gridDim.x * AT256_THREADS;
+  for (size_t base = (size_t)blockIdx.x * AT256_THREADS; base < n; base += stride) {  // wave-uniform trip count: the fold shuffles
+    const size_t i = base + threadIdx.x;
+    u32 key = 0xffffffffu;
+    E v = e32_zero();
+    if (i < n) {
+      const uint4 cw = *reinterpret_cast<const uint4*>(&t[i]);  // c | w (the record is 48 bytes: 16-byte aligned)
+      key = cw.z;                                                // w < nw < 2^28 (LigeroParam), checked on the host
+      v = fp256_mul(ld32(&t[i].k), ld32(&alphal[(u64)cw.x | ((u64)cw.y << 32)]));
+    }
+    run_fold_commit256(key, v, acc);
+  }
+}
+// the quadratic copy constraints: A[a0 + j * step + iw] += aq, A[lqc[iw][j]] -= aq for aq = alphaq[iw][j], j < 3
+__global__ __launch_bounds__(Z_THREADS) void a_terms_quad256_kernel(u32 n3 /* 3 nq */, const u64* __restrict__ lqc, const E* __restrict__ alphaq, u64 a0, u64 step,
+                                                                    u64* __restrict__ acc) {
+  const u32 t = blockIdx.x * Z_THREADS + threadIdx.x;
+  if (t >= n3) return;
+  const u32 iw = t / 3, j = t % 3;
+  const E aq = ld32(&alphaq[t]);
+  limbs_atomic_add(acc + 8 * (size_t)(a0 + (u64)j * step + iw), aq);
+  limbs_atomic_add(acc + 8 * (size_t)lqc[t], fp256_sub(e32_zero(), aq));
+}
+// rows[i][r + j] += the sum standing in the accumulators of flat position i * w + j
+__global__ __launch_bounds__(Z_THREADS) void a_terms_finish256_kernel(u32 r, u32 w, size_t ld, size_t nflat, const u64* __restrict__ acc, E rsq,
+                                                                      E* __restrict__ rows) {
+  const size_t f = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+  if (f >= nflat) return;
+  u64 a[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) a[k] = acc[8 * f + k];
+  E* dst = &rows[(f / w) * ld + r + f % w];
+  st32(dst, fp256_add(ld32(dst), fp256_reduce_limbs(a, rsq)));
+}
+
 // eq[i] = EQ(G0, i) + alpha EQ(G1, i), EQ(G, i) = prod_l (bit_l(i) ? G[l] : 1 - G[l]); G = G0 | G1 | 1-G0 | 1-G1
 __global__ __launch_bounds__(Z_THREADS) void raw_eq2_256_kernel(u32 logn, u32 n, const E* __restrict__ G, E alpha, E one, E* __restrict__ eq) {
   const u32 i = blockIdx.x * Z_THREADS + threadIdx.x;
@@ -1426,6 +1480,15 @@ namespace {
 // The width policy of ligero_slab.h for Fp256Base: the row kernels above, lfgpu_fp256_rs_encode_rows and lf_column_leaves32.  The
 // prover is bound by a latency chain of short launches, so these steps only enqueue: host vectors go to lf_scratch2
 // by plain asynchronous copies, and whoever reads the result back synchronises.  The one exception is a_rows_sparse.
+// inner_product_vector's inputs for a_rows_terms (LfLigeroTerms of zkint.h over 32-byte elements), all on the host
+struct Terms256 {
+  const lfgpu_ligero_llterm256* term;
+  size_t nterm;
+  const E* alphal;  // [nl]
+  size_t nl;
+  const size_t* lqc;  // [nq][3]
+  const E* alphaq;    // [nq][3]
+};
 struct L32 : lig::Host32 {
   static int rows_axpy(lfgpu_ctx* c, size_t nrows, size_t n, E* d_y, const E* h_u, const E* d_T, size_t ld) {
     void* du = nullptr;
@@ -1464,6 +1527,49 @@ struct L32 : lig::Host32 {
     LF_HIP(c, hipStreamSynchronize(c->stream));  // the staging area is the Reed-Solomon encoder's work space next
     return LFGPU_OK;
   }
+  // inner_product_vector from an unsorted term list with duplicates (a_terms256_kernel and its two companions), added to what
+  // stands in the rows.  The accumulators, the term list (one copy, as the caller holds it) and the challenges (one packed copy)
+  // live in scratch2, which is the Reed-Solomon encoder's work space next, and the term list is the caller's memory: this step
+  // ends with a synchronise.  The caller has validated the statement (terms256_ok).
+  static int a_rows_terms(lfgpu_ctx* c, const lfgpu_ligero_param& p, size_t ld, const Terms256& t, E* d_rows) {
+    const size_t nflat = p.nwqrow * p.w, n3 = 3 * p.nq, acc_bytes = nflat * 64;
+    const size_t small_bytes = (t.nl + n3) * 32 + n3 * 8;
+    void* d = nullptr;
+    LF_TRY(lf_scratch2(c, acc_bytes + t.nterm * 48 + small_bytes + 64, &d));
+    u64* d_acc = (u64*)d;
+    llterm256_t* d_term = (llterm256_t*)((uint8_t*)d + acc_bytes);
+    E* d_alphal = (E*)(d_term + t.nterm);
+    E* d_alphaq = d_alphal + t.nl;
+    u64* d_lqc = (u64*)(d_alphaq + n3);
+    LF_HIP(c, hipMemsetAsync(d_acc, 0, acc_bytes, c->stream));
+    if (t.nterm) LF_HIP(c, hipMemcpyAsync(d_term, t.term, t.nterm * 48, hipMemcpyHostToDevice, c->stream));
+    std::vector<uint8_t> pack(small_bytes);
+    if (small_bytes) {
+      if (t.nl) memcpy(pack.data(), t.alphal, t.nl * 32);
+      if (n3) memcpy(pack.data() + t.nl * 32, t.alphaq, n3 * 32);
+      if (n3) memcpy(pack.data() + (t.nl + n3) * 32, t.lqc, n3 * 8);
+      LF_HIP(c, hipMemcpyAsync(d_alphal, pack.data(), small_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    auto run = [&]() -> int {
+      if (t.nterm) {
+        const dim3 grid((u32)std::min<size_t>((t.nterm + AT256_THREADS - 1) / AT256_THREADS, AT256_BLOCKS_MAX));
+        hipLaunchKernelGGL(a_terms256_kernel, grid, dim3(AT256_THREADS), 0, c->stream, t.nterm, (const llterm256_t*)d_term, (const E*)d_alphal, d_acc);
+      }
+      if (n3)
+        hipLaunchKernelGGL(a_terms_quad256_kernel, dim3(nblk(n3)), dim3(Z_THREADS), 0, c->stream, (u32)n3, (const u64*)d_lqc, (const E*)d_alphaq, (u64)(p.nwrow * p.w),
+                           (u64)(p.nqtriples * p.w), d_acc);
+      if (nflat)
+        hipLaunchKernelGGL(a_terms_finish256_kernel, dim3(nblk(nflat)), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, ld, nflat, (const u64*)d_acc, h256_rsq(),
+                           d_rows);
+      LF_HIP(c, hipGetLastError());
+      return LFGPU_OK;
+    };
+    const int rc = run();
+    const hipError_t e = hipStreamSynchronize(c->stream);  // also after a failed launch: the copies out of `pack` and the caller's list may be pending
+    if (rc) return rc;
+    LF_HIP(c, e);
+    return LFGPU_OK;
+  }
   // h_idx is the caller's array and outlives the read-back that follows
   static int gather_columns(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, const E* d_T, const size_t* h_idx, size_t nreq, E* d_req) {
     static_assert(sizeof(size_t) == sizeof(u64), "the kernel reads the indices as u64");
@@ -1500,7 +1606,49 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
   *out = L.release();
   return LFGPU_OK;
 }
+Lig32* lig32_of(Lig256* L) { return reinterpret_cast<Lig32*>(L); }
 }  // namespace
+
+// ---- behind lfgpu_ligero_commit / low_degree_proof / dot_proof / quadratic_proof / open / tableau / free for field P256
+// (ligero.hip; declared in zkint.h): one GPU, all rows
+int lf_lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param* p, const void* h_W, const size_t* h_lqc, lfgpu_rng_fn rng, void* user, uint8_t root[32], Lig256** out) {
+  Lig32* L = nullptr;
+  LF_TRY(lig256_commit(c, *p, (const E*)h_W, h_lqc, rng, user, root, &L));
+  *out = reinterpret_cast<Lig256*>(L);
+  return LFGPU_OK;
+}
+void lf_lig256_free(Lig256* L) { delete lig32_of(L); }  // ~Slab scrubs the buffers and returns them to the context's pool
+void* lf_lig256_tableau(Lig256* L) { return lig32_of(L)->d_T; }
+int lf_lig256_low_degree(Lig256* L, const void* h_u, void* h_y) { return lig::low_degree(lig32_of(L), L32(), (const E*)h_u, (E*)h_y); }
+// dot_proof (:293-309) with the caller's dense A (nwqrow x w, host): layout_Aext (ligero_param.h:423-430) is one strided copy
+int lf_lig256_dot_dense(Lig256* L, const void* h_A, void* h_y) {
+  Lig32* pr = lig32_of(L);
+  lfgpu_ctx* c = pr->c;
+  const lfgpu_ligero_param& p = pr->p;
+  const size_t lda = p.dblock;
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, (p.nwqrow * p.w + p.nwqrow * lda + 2 * p.dblock) * 32 + 64, &sc));
+  E* dA = (E*)sc;
+  E* dAext = dA + p.nwqrow * p.w;
+  E* dy = dAext + p.nwqrow * lda;
+  LF_HIP(c, hipMemcpyAsync(dA, h_A, p.nwqrow * p.w * 32, hipMemcpyHostToDevice, c->stream));
+  LF_HIP(c, hipMemsetAsync(dAext, 0, p.nwqrow * lda * 32, c->stream));
+  if (p.nwqrow) LF_HIP(c, hipMemcpy2DAsync(dAext + p.r, lda * 32, dA, p.w * 32, p.w * 32, p.nwqrow, hipMemcpyDeviceToDevice, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));  // h_A is the caller's: its upload is over before the first error return below
+  return lig::dot_finish(pr, L32(), dAext, dy, (E*)h_y);
+}
+int lf_lig256_quadratic(Lig256* L, const void* h_u, void* h_y0, void* h_y2) { return lig::quadratic(lig32_of(L), L32(), (const E*)h_u, (E*)h_y0, (E*)h_y2); }
+int lf_lig256_open(Lig256* L, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath) {
+  return lig::open(lig32_of(L), L32(), idx, (E*)h_req, h_nonces, h_path, path_cap, npath);
+}
+int lf_lig256_a_rows_terms(lfgpu_ctx* c, const lfgpu_ligero_param* p, size_t ld, const lfgpu_ligero_llterm256* term, size_t nterm, const void* h_alphal, size_t nl,
+                           const size_t* h_lqc, const void* h_alphaq, void* d_rows) {
+  const Terms256 t{term, nterm, (const E*)h_alphal, nl, h_lqc, (const E*)h_alphaq};
+  return L32::a_rows_terms(c, *p, ld, t, (E*)d_rows);
+}
+int lf_lig256_a_rows_sparse(lfgpu_ctx* c, const lfgpu_ligero_param* p, size_t ld, const uint64_t* h_idx, const void* h_val, size_t n, void* d_rows) {
+  return lig::a_rows(c, L32(), p->w, p->r, ld, p->nwqrow, (const E*)nullptr, 0, e32_zero(), h_idx, (const E*)h_val, n, (E*)d_rows);
+}
 
 // ------------------------------------------------------------------ the Fp256Base policy
 namespace {
@@ -1566,11 +1714,20 @@ struct P32 : zkp::Wire32 {
   // EQ table of the input constraint | the rows | the gathered columns.
   static int verifier_ext(lfgpu_ctx* c, const F256&, const lfgpu_circuit_info& I, const lfgpu_ligero_param& p, const E* d_eq, const E& scale,
                           const std::vector<uint64_t>& a_idx, const std::vector<E>& a_val, const zkp::ProofBody<E>& pr, const size_t* idx, std::vector<E>& ext) {
-    const size_t nrows_dev = p.nwqrow + 3, ld = p.block_enc, n_witness = I.ninputs - I.npub_in;
-    E* d_T = (E*)d_eq + I.ninputs;
+    const size_t n_witness = I.ninputs - I.npub_in;
+    auto a_rows = [&](E* d_T, size_t ld) {
+      return lig::a_rows(c, L32(), p.w, p.r, ld, p.nwqrow, d_eq + I.npub_in, n_witness, scale, a_idx.data(), a_val.data(), a_idx.size(), d_T);
+    };
+    return verifier_ext_with(c, p, (E*)d_eq + I.ninputs, a_rows, pr, idx, ext);
+  }
+  // ... with the A rows from the caller's step a_rows(d_T, ld) (ZkVerifier above; lfgpu_ligero_verify256: the term list), in
+  // d_T: room for (nwqrow + 3) * (block_enc + nreq) elements
+  template <class ARows>
+  static int verifier_ext_with(lfgpu_ctx* c, const lfgpu_ligero_param& p, E* d_T, ARows a_rows, const zkp::ComProof<E>& pr, const size_t* idx, std::vector<E>& ext) {
+    const size_t nrows_dev = p.nwqrow + 3, ld = p.block_enc;
     E* d_req = d_T + nrows_dev * ld;
     LF_HIP(c, hipMemset2DAsync(d_T, ld * 32, 0, p.dblock * 32, nrows_dev, c->stream));
-    LF_TRY(lig::a_rows(c, L32(), p.w, p.r, ld, p.nwqrow, d_eq + I.npub_in, n_witness, scale, a_idx.data(), a_val.data(), a_idx.size(), d_T));
+    LF_TRY(a_rows(d_T, ld));
     LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 0) * ld, pr.y_ldt.data(), p.block * 32, hipMemcpyHostToDevice, c->stream));
     LF_HIP(c, hipMemcpyAsync(d_T + (p.nwqrow + 1) * ld, pr.y_dot.data(), p.dblock * 32, hipMemcpyHostToDevice, c->stream));
     E* yq = d_T + (p.nwqrow + 2) * ld;  // y_quad = y_quad_0 | 0^w | y_quad_2
@@ -1729,4 +1886,100 @@ int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nr
     return (int)LFGPU_OK;
   };
   return zkp::verify<P32>(c, C, P32(), p, proof, proof_len, h_pub, tso, committed, eq_table, ok, why_out);
+}
+
+// ------------------------------------------------------------------ LigeroProver::prove / LigeroVerifier::verify on a caller's statement
+// lfgpu_ligero_prove / lfgpu_ligero_verify (zk.hip) over Fp256Base: thin drivers over zkp::ligero_prove / ligero_verify /
+// com_proof_write / com_proof_read with the policy P32; the A step is L32::a_rows_terms on the caller's term list.
+namespace {
+// the host scan in front of the first transcript call or launch (the summand bound: see a_terms256_kernel)
+bool terms256_ok(const lfgpu_ligero_param& p, size_t nl, size_t nllterm, const lfgpu_ligero_llterm256* llterm, const size_t* h_lqc) {
+  if ((nllterm && !llterm) || (p.nq && !h_lqc)) return false;
+  if (nllterm >= ((size_t)1 << 32) || nllterm + 6 * p.nq >= ((size_t)1 << 32)) return false;
+  if (p.nw > p.nwrow * p.w || p.nq > p.nqtriples * p.w || p.nwqrow * p.w >= 0xffffffffull) return false;  // a hand-made lfgpu_ligero_param: the flat positions
+  for (size_t t = 0; t < nllterm; ++t)
+    if (llterm[t].c >= nl || llterm[t].w >= p.nw) return false;
+  for (size_t i = 0; i < 3 * p.nq; ++i)
+    if (h_lqc[i] >= p.nw) return false;
+  return true;
+}
+}  // namespace
+
+extern "C" int lfgpu_ligero_prove256(lfgpu_ligero_prover* lp, const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm256* llterm,
+                                     const uint8_t hash_of_llterm[32], const size_t* h_lqc, uint8_t* buf, size_t cap, size_t* nbytes) {
+  if (!lp || !tso || !hash_of_llterm || !nbytes) return LFGPU_ERR_ARG;
+  LfLigeroView v;
+  lf_ligero_prover_view(lp, &v);
+  lfgpu_ctx* c = v.c;
+  const lfgpu_ligero_param& p = v.p;
+  if (!v.lig256) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove256: the prover is not over Fp256Base (lfgpu_ligero_prove serves the 16-byte fields)");
+  LF_TRY(ts256_ok(c, tso));
+  if (!terms256_ok(p, nl, nllterm, llterm, h_lqc))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove256: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 summands)");
+  auto copy_out = [&]() {
+    *nbytes = v.wire->size();
+    if (cap < v.wire->size()) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove256: buffer too small (%zu < %zu)", cap, v.wire->size());
+    memcpy(buf, v.wire->data(), v.wire->size());
+    *v.wire_held = false;
+    return (int)LFGPU_OK;
+  };
+  if (buf && *v.wire_held) return copy_out();  // the copy that follows a size query: the same serialisation
+  *v.wire_held = false;
+  LF_HIP(c, hipSetDevice(c->device));
+  Lig32* L = lig32_of(v.lig256);
+  const P32 pol;
+  const zkp::Ts<P32> ts{&pol, tso, tso->user};
+  zkp::ComProof<E> pr;
+  double tq[6];
+  auto dot = [&](const std::vector<E>& alphal, const std::vector<E>& alphaq, E* y_dot) {
+    const Terms256 t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
+    return lig::dot_terms(L, L32(), t, y_dot);
+  };
+  LF_TRY(zkp::ligero_prove<P32>(p, L, ts, hash_of_llterm, nl, dot, pr, tq));
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  if (verbose)
+    fprintf(stderr, "lfgpu ligero_prove256: ldt %.2f ms | challenges %.2f | A from %zu terms + dot %.2f | quad %.2f | challenges+open %.2f\n", tq[1] - tq[0],
+            tq[2] - tq[1], nllterm, tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
+  v.wire->clear();
+  zkp::com_proof_write(pol, pr, *v.wire);
+  *v.wire_held = true;  // kept after a size query, and if the buffer turns out too small
+  if (!buf) {
+    *nbytes = v.wire->size();
+    return LFGPU_OK;
+  }
+  return copy_out();
+}
+
+extern "C" int lfgpu_ligero_verify256(lfgpu_ctx* c, const lfgpu_ligero_param* pp, const uint8_t root[32], const uint8_t* proof, size_t proof_len,
+                                      const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm256* llterm,
+                                      const uint8_t hash_of_llterm[32], const void* h_b, const size_t* h_lqc, int* ok, const char** why_out) {
+  if (!c || !pp || !root || !proof || !tso || !hash_of_llterm || !ok || (nl && !h_b)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify256: null argument");
+  *ok = 0;
+  LF_TRY(ts256_ok(c, tso));
+  const lfgpu_ligero_param& p = *pp;
+  if (!terms256_ok(p, nl, nllterm, llterm, h_lqc))
+    return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify256: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 summands)");
+  const P32 pol;
+  static const F256 F;
+  auto fail = [&](int w) {
+    if (why_out) *why_out = zkp::why_string(w);
+    return (int)LFGPU_OK;
+  };
+  zkp::ComProof<E> pr;
+  zkp::WireReader<P32> rd{pol, proof, proof_len};
+  if (!zkp::com_proof_read(rd, p, pr) || rd.bad || rd.left != 0) return fail(zkp::kWhyParse);
+  LF_HIP(c, hipSetDevice(c->device));
+  const zkp::Ts<P32> ts{&pol, tso, tso->user};
+  auto ext_fn = [&](const std::vector<E>& alphal, const std::vector<E>& alphaq, const size_t* idx, std::vector<E>& ext) {
+    const Terms256 t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
+    auto a_rows = [&](E* d_T, size_t ld) { return L32::a_rows_terms(c, p, ld, t, d_T); };
+    void* dv = nullptr;
+    LF_TRY(lf_scratch4(c, (p.nwqrow + 3) * (p.block_enc + p.nreq) * 32 + 256, &dv));
+    return P32::verifier_ext_with(c, p, (E*)dv, a_rows, pr, idx, ext);
+  };
+  int w = zkp::kWhyOk;
+  double tv[6];
+  LF_TRY(zkp::ligero_verify<P32>(pol, F, p, root, pr, ts, hash_of_llterm, nl, (const E*)h_b, ext_fn, &w, tv));
+  if (w == zkp::kWhyOk) *ok = 1;
+  return fail(w);
 }

@@ -53,13 +53,33 @@ struct LfLigeroTerms {
 int lf_ligero_a_rows_terms(lfgpu_ctx* c, int field, const lfgpu_ligero_param* p, size_t ld, const LfLigeroTerms* t, void* d_rows);
 // dot_proof with A = inner_product_vector(terms), on a prover that holds the whole tableau
 int lf_ligero_dot_terms(lfgpu_ligero_prover* pr, const LfLigeroTerms* t, void* h_y);
+// ---- zk256.hip: the Ligero prover over Fp256Base behind the kernel-level ABI.  lfgpu_ligero_prover (ligero.hip) carries one of
+// these for field P256 and forwards its entry points here; the record itself (lig::Slab over 32-byte elements) and its policy
+// never leave zk256.hip, so the handle is opaque.  Arguments are already checked for NULL; all host vectors are 32-byte
+// Montgomery elements.
+struct Lig256;
+int lf_lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param* p, const void* h_W, const size_t* h_lqc, lfgpu_rng_fn rng, void* user, uint8_t root[32],
+                     Lig256** out);
+void lf_lig256_free(Lig256* L);
+void* lf_lig256_tableau(Lig256* L);
+int lf_lig256_low_degree(Lig256* L, const void* h_u, void* h_y);
+int lf_lig256_dot_dense(Lig256* L, const void* h_A, void* h_y);  // A: nwqrow x w
+int lf_lig256_quadratic(Lig256* L, const void* h_u, void* h_y0, void* h_y2);
+int lf_lig256_open(Lig256* L, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath);
+// the A step of the dot proof alone (tools/bench_ligero_a_step256.hip): rows[i][r + j] += A[i * w + j] at stride ld, with A
+// accumulated on the device from a validated term list (L32::a_rows_terms), or scattered from a host-folded list of strictly
+// increasing flat indices (lig::a_rows, the route of the ZK paths)
+int lf_lig256_a_rows_terms(lfgpu_ctx* c, const lfgpu_ligero_param* p, size_t ld, const lfgpu_ligero_llterm256* term, size_t nterm, const void* h_alphal, size_t nl,
+                           const size_t* h_lqc, const void* h_alphaq, void* d_rows);
+int lf_lig256_a_rows_sparse(lfgpu_ctx* c, const lfgpu_ligero_param* p, size_t ld, const uint64_t* h_idx, const void* h_val, size_t n, void* d_rows);
 struct LfLigeroView {
   lfgpu_ctx* c;
   int field, k;
   lfgpu_ligero_param p;
   bool whole;                  // one GPU, all rows: not sharded, not from a slab
-  std::vector<uint8_t>* wire;  // the write_com_proof bytes a size query of lfgpu_ligero_prove left behind
+  std::vector<uint8_t>* wire;  // the write_com_proof bytes a size query of lfgpu_ligero_prove / lfgpu_ligero_prove256 left behind
   bool* wire_held;
+  Lig256* lig256;              // field P256: the prover's 32-byte slab; null for the 16-byte fields
 };
 void lf_ligero_prover_view(lfgpu_ligero_prover* pr, LfLigeroView* v);
 // K11 over 32-byte elements (quad.hip forwards field 1 here)
