@@ -224,6 +224,8 @@ struct T4Ops : O {
     x = O::add(u, t), y = O::sub(u, t);
   }
   static __device__ __forceinline__ void bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) { bfly_lazy(xp, yp), bfly_lazy(xq, yq); }
+  // fp_fft_tile_1024x4_lean: two butterflies with full sums on canonical inputs
+  static __device__ __forceinline__ void bfly2_full(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) { bfly_lazy(xp, yp), bfly_lazy(xq, yq); }
 };
 #if defined(__HIP_DEVICE_COMPILE__)
 template <>
@@ -239,6 +241,7 @@ struct T4Ops<Fp128Ops> : Fp128Ops {
   static __device__ __forceinline__ void canon2(elt_t& a, elt_t& b) { fpt_canon2(a, b); }
   static __device__ __forceinline__ void bfly_lazy(elt_t& x, elt_t& y) { fpt_bfly_lazy(x, y); }
   static __device__ __forceinline__ void bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) { fpt_bfly2_lazy(xp, yp, xq, yq); }
+  static __device__ __forceinline__ void bfly2_full(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) { fpt_bfly2_full(xp, yp, xq, yq); }
 };
 #endif
 // T4Ilp<O>: the field O, its tile arithmetic issued in pairs.  fp_fft_tile_1024x4_tw2<T4Ilp<O>, ..> is the kernel
@@ -578,7 +581,8 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tws_canon(TilePlan 
 // loads, stores, the inter-pass product, the lazy rules of rounds 0, 2 and 3 and the bytes that come out are the same.  Round 0's
 // three uniform twiddles (w^128, w^256, w^384) are scalar operands of its products like round 1's, not moved into VGPRs.  It has
 // round helpers and a slot function of its own (t4w_*): t4_slot and the t4_round* above belong to the kernels above.
-// The default is its instantiation for T4Ilp<Fp128Ops> (LFGPU_FP_ILP=0: for Fp128Ops): the same kernel with the stage helpers
+// Its instantiation for T4Ilp<Fp128Ops> (LFGPU_FP_LEAN=0 launches it, and LFGPU_FP_ILP=0 the one for Fp128Ops; the default is
+// fp_fft_tile_1024x4_lean further down, which computes the same) is the same kernel with the stage helpers
 // t4i_*, which issue a stage's products, canons and butterflies two at a time (fp_tile_arith.h), carry links filled with the
 // other operation's instructions instead of s_nop.  Same values and VALU counts; DESIGN 4.1, profiles/k1_ilp/.
 //
@@ -840,6 +844,247 @@ __global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_tw2(TilePlan p, con
   }
 }
 
+// ------------------------------------------------------------------ K1: the 1024 x 4 pair without the address arithmetic
+// fp_fft_tile_1024x4_lean is fp_fft_tile_1024x4_tw2<T4Ilp<O>, ..> with fewer VALU instructions that are not arithmetic: the same
+// tile loads, values, LDS tile (layout (4p + c) ^ L(p)) and stores, the same products, canons and lazy butterflies in the same
+// order.  The default for Fp128 where that pair was (LFGPU_FP_LEAN=0 launches it again).  It has round helpers of its own
+// (t4l_*); DESIGN 4.1, profiles/k1_lean/.
+//
+// Global memory.  A tile's source, destination and (pass B) table slice are 64-bit bases in SGPRs and a thread's offsets are
+// 32-bit byte offsets in VGPRs, the scalar-address form of global_load / global_store: no 64-bit vector arithmetic.  The step
+// between a thread's eight points is uniform (128 sk elements on the load side, 128 dk between the two groups and 256 dk inside
+// a group on the store side) and is added to the base on the scalar unit: eight bases, one offset.  Built the other way as well,
+// one base and eight offsets (7 v_add_u32 per eight accesses): 21.20 against 21.17 ms per bench.py step, both below the 21.49 ms
+// of fp_fft_tile_1024x4_tw2<T4Ilp<..>> (profiles/k1_lean/), so plain scalar adds cost no time that shows and the fewer VALU
+// instructions stay.
+// The 32 bits suffice because the host launches this pair only when a tile spans less than 2^32 bytes on both sides,
+// 16 (1024 sk + 4 sc) and 16 (1024 dk + 4 dc) <= 2^32 - 1 (launch_tile_1024x4_tws), and every other plan goes to
+// fp_fft_tile_1024x4_tw2.  The plans that reach the pair: pass A reads and writes rows of 2^20 points in columns of 4 (sk = dk =
+// 1024, sc = dc = 1: 16 MiB); pass B reads 4 contiguous rows of 1024 points (64 KiB) and writes with dk = 1024 d, dc = d, where
+// d = 1 for n = 2^20 and d = n / 2^20 <= 8 for the inner transforms of n = 2^21 .. 2^23 (16 MiB d <= 128 MiB; d >= 256, n >= 2^28,
+// is refused).  A row stride ld > n enters only the 64-bit bases (by * src_row, by * dst_row).
+//
+// Tile order.  Pass A's column-block count is a power of two 2^lcb >= 8 (the host sends any other to fp_fft_tile_1024x4_tw2), so
+// t4_xcd_order's quotient and remainder are shifts and masks of the workgroup index on the scalar unit.
+//
+// LDS.  Every address is a byte address computed once per thread and round, t4l_byte(p, c) = 16 ((4p + c) ^ L(p)), and the other
+// slots of the round are that one XOR a constant plus an immediate offset; the kernel has no static LDS, so the tile starts at
+// LDS address 0 and the addresses are plain integers.  With p = p0 + 2^k a and bit k of p0 clear, bit k moves (4p + c) by
+// 64 2^k bytes, an immediate, and L(p) by 16 L(2^k), an XOR: L(64) = 4, L(128) = 9, L(256) = 2, L(512) = 4 (t4w_swz).
+//   round 0: 8b + a, a < 8: a & 3 reaches slot bits 2-3 (XOR 64 (a & 3)), a >> 2 is + 256.
+//   round 1: 64h + j + 8a with j uniform: j < 8 lies below every bit L reads, so the base is t4l_byte(64h, c) ^ 64 j, + 512 a.
+//   round 2: 256h + j + 64a, h = h0 + 2g for group g: a moves p6, p7: XOR 16 L(64a) = {0, 64, 144, 208}, + 4096 a.  g moves p9:
+//            + 32768 and XOR 64, and since {0, 64, 144, 208} ^ 64 is the same set, group 1 reuses group 0's four addresses.
+//   round 3: j0 + 128g + 256a: a moves p8, p9: XOR 32 a, + 16384 a; g moves p7: XOR 144, + 8192.
+// Stage twiddles of rounds 2 and 3, the one thing this pair keeps elsewhere in LDS: w_1024^i, i < 512, at byte T4L_W + 16 i with
+// no swizzle, and behind them w_1024^(8j), j < 64, at T4L_W8 + 16 j (1 KiB more: 73 KiB per workgroup, two per CU).  Lanes walk c,
+// then j, so the 16 lanes of a ds_read_b128 group read four consecutive j, four lanes each the same address.  Round 2 reads
+// i = 8j from the second table (slots j .. j + 3) and i = 4j, 4j + 256 from the first (slots 4j .. 4j + 12, + 4096 bytes), the same
+// for both groups; round 3 reads i = 2j, j, j + 256 with j = j0 + 128 g (slots 2j .. 2j + 6 and j .. j + 3; g is + 4096 and
+// + 2048 bytes): distinct mod 16 in every group, which t4_wslot was there to achieve for the readers of the other kernels.  Two
+// addresses per round, each a shift and a mask of tid, and immediates.  The first table is written as before, one entry per
+// thread; wave 0 loads the 64 entries of the second beside the tile's loads and stores them on its own path of round 1.
+__device__ __forceinline__ u32 t4l_byte(u32 p, u32 c) { return ((p << 6) | (c << 4)) ^ ((p >> 3) & 0x70u) ^ (p & 0xc0u); }  // 16 t4w_slot(p, c)
+enum : u32 { T4L_W = 65536, T4L_W8 = T4L_W + 8192, T4L_LDS = T4L_W8 + 1024 };  // behind the tile; the workgroup's LDS bytes
+typedef u32 t4l_v4 __attribute__((ext_vector_type(4)));  // a plain vector: uint4 is a class on the host pass
+typedef __attribute__((address_space(3))) t4l_v4 t4l_lds_t;
+__device__ __forceinline__ elt_t t4l_ld(u32 byte) {
+  const t4l_v4 v = *(const t4l_lds_t*)(uintptr_t)byte;
+  return elt_t{((u64)v.y << 32) | v.x, ((u64)v.w << 32) | v.z};
+}
+__device__ __forceinline__ void t4l_st(u32 byte, elt_t e) {
+  const t4l_v4 v = {(u32)e.lo, (u32)(e.lo >> 32), (u32)e.hi, (u32)(e.hi >> 32)};
+  *(t4l_lds_t*)(uintptr_t)byte = v;
+}
+// base + step + off in global memory for a uniform base and step
+typedef __attribute__((address_space(1))) t4l_v4 t4l_glb_t;
+__device__ __forceinline__ t4l_glb_t* t4l_at(const char* base, u32 step, u32 off) {
+  u64 b = (u64)base + step;
+  asm("" : "+s"(b));  // the sum stays on the scalar unit: left alone, the compiler adds step to base + off in VGPRs
+  return (t4l_glb_t*)(b + off);
+}
+__device__ __forceinline__ elt_t t4l_gld(const t4l_glb_t* q) {
+  const t4l_v4 v = *q;
+  return elt_t{((u64)v.y << 32) | v.x, ((u64)v.w << 32) | v.z};
+}
+__device__ __forceinline__ void t4l_gst(t4l_glb_t* q, elt_t e) {
+  const t4l_v4 v = {(u32)e.lo, (u32)(e.lo >> 32), (u32)e.hi, (u32)(e.hi >> 32)};
+  *q = v;
+}
+// The three stages of rounds 0 and 1, as t4i_stage, with the butterflies that add in full (round 0) in pairs as well
+template <class O, u32 MODE, u32 T>
+__device__ __forceinline__ void t4l_stage(elt_t* x, const elt_t* w) {
+  constexpr T4iStage S = t4i_plan<MODE>(T);
+  constexpr u32 half = 1u << T, first = half - 1;
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.np; i += 2) {
+    const u32 a = S.prod[i], b = S.prod[i + 1];
+    T4Ops<O>::mul2_tw_sw(x[a + half], w[first + (a & first)], x[b + half], w[first + (b & first)]);
+  }
+  if constexpr (S.np & 1) x[S.prod[S.np - 1] + half] = T4Ops<O>::mul_tw_sw(x[S.prod[S.np - 1] + half], w[first + (S.prod[S.np - 1] & first)]);
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.nc; i += 2) T4Ops<O>::canon2(x[S.can[i] + half], x[S.can[i + 1] + half]);
+  if constexpr (S.nc & 1) x[S.can[S.nc - 1] + half] = T4Ops<O>::canon(x[S.can[S.nc - 1] + half]);
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.nf; i += 2) T4Ops<O>::bfly2_full(x[S.full[i]], x[S.full[i] + half], x[S.full[i + 1]], x[S.full[i + 1] + half]);
+  if constexpr (S.nf & 1) {  // stage 0's third and stage 1's only one: the latter reads the former's result, they make no pair
+    const u32 a = S.full[S.nf - 1];
+    const elt_t u = x[a], v = x[a + half];
+    x[a] = T4Ops<O>::add(u, v);
+    x[a + half] = T4Ops<O>::sub(u, v);
+  }
+#pragma unroll
+  for (u32 i = 0; i + 1 < S.nl; i += 2) T4Ops<O>::bfly2_lazy(x[S.lazy[i]], x[S.lazy[i] + half], x[S.lazy[i + 1]], x[S.lazy[i + 1] + half]);
+  if constexpr (S.nl & 1) T4Ops<O>::bfly_lazy(x[S.lazy[S.nl - 1]], x[S.lazy[S.nl - 1] + half]);
+}
+template <class O, u32 MODE>
+__device__ __forceinline__ void t4l_stages(elt_t* x, const elt_t* w) {
+  t4l_stage<O, MODE, 0>(x, w);
+  t4l_stage<O, MODE, 1>(x, w);
+  t4l_stage<O, MODE, 2>(x, w);
+}
+// Rounds 2 and 3, as t4i_stages4, with the stage's three twiddles w^(2i), w^i, w^(i + 256) read by the caller; the two butterflies
+// of T4_LAZY_OUT's last stage are one pair
+template <class O, u32 LZ>
+__device__ __forceinline__ void t4l_stages4(elt_t* x, elt_t w2, elt_t w1, elt_t w1h) {
+  T4Ops<O>::mul2_tw(x[1], w2, x[3], w2);
+  T4Ops<O>::bfly2_lazy(x[0], x[1], x[2], x[3]);
+  T4Ops<O>::mul2_tw(x[2], w1, x[3], w1h);
+  if (LZ == T4_LAZY_OUT) {
+    T4Ops<O>::canon2(x[0], x[1]);
+    T4Ops<O>::bfly2_full(x[0], x[2], x[1], x[3]);
+  } else {
+    T4Ops<O>::bfly2_lazy(x[0], x[2], x[1], x[3]);
+  }
+}
+template <class O>
+__device__ __forceinline__ void t4l_round0(const elt_t* y, u32 kb, u32 c, const elt_t* w) {
+  elt_t x[8];
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) x[a] = y[((a & 1) << 2) | (a & 2) | (a >> 2)];
+  t4l_stages<O, T4W_R0>(x, w);
+  const u32 s0 = t4l_byte((__brev(kb) >> 25) << 3, c);
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) t4l_st((s0 ^ (64 * (a & 3))) + 256 * (a >> 2), x[a]);
+}
+template <class O, u32 MODE>
+__device__ __forceinline__ void t4l_round1_wave(u32 s0, const elt_t* w) {
+  elt_t x[8];
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) x[a] = t4l_ld(s0 + 512 * a);
+  t4l_stages<O, MODE>(x, w);
+#pragma unroll
+  for (u32 a = 0; a < 8; ++a) t4l_st(s0 + 512 * a, x[a]);
+}
+// as t4w_round1: each path loads and stores for itself, the asm comments keep the compiler from merging them
+template <class O>
+__device__ __forceinline__ void t4l_round1(u32 tid, u32 j, const elt_t* w, elt_t w8) {
+  const u32 s0 = t4l_byte(((tid >> 2) & 15) << 6, tid & 3) ^ (j << 6);
+  if (j == 0) {
+    t4l_st(T4L_W8 + (tid << 4), w8);  // wave 0: tid < 64
+    asm volatile("; round 1, j = 0");
+    t4l_round1_wave<O, T4W_R1_J0>(s0, w);
+    asm volatile("; round 1, j = 0: stored");
+  } else {
+    asm volatile("; round 1, j > 0");
+    t4l_round1_wave<O, T4W_R1>(s0, w);
+    asm volatile("; round 1, j > 0: stored");
+  }
+}
+// Round 2, both groups: the thread's four addresses serve group 0 in the order a and group 1, + 32768, in the order a ^ 1
+template <class O>
+__device__ __forceinline__ void t4l_round2(u32 tid) {
+  const u32 j = (tid >> 2) & 63, s0 = t4l_byte(((tid >> 8) << 8) | j, tid & 3);
+  const u32 sa[4] = {s0, s0 ^ 64, s0 ^ 144, s0 ^ 208};  // 16 L(64a) = 0, 64, 144, 208
+  const u32 j16 = (tid << 2) & 0x3f0u;  // 16 j
+  u32 wa = T4L_W8 + j16, wb = T4L_W + 4 * j16;
+  asm("" : "+v"(wa), "+v"(wb));  // opaque, here and in round 3: + 4096 stays an immediate instead of a second address
+  const elt_t w2 = t4l_ld(wa), w1 = t4l_ld(wb), w1h = t4l_ld(wb + 4096);
+#pragma unroll
+  for (u32 g = 0; g < 2; ++g) {
+    elt_t x[4];
+#pragma unroll
+    for (u32 a = 0; a < 4; ++a) x[a] = t4l_ld(sa[a ^ g] + 4096 * a + 32768 * g);
+    t4l_stages4<O, T4_LAZY>(x, w2, w1, w1h);
+#pragma unroll
+    for (u32 a = 0; a < 4; ++a) t4l_st(sa[a ^ g] + 4096 * a + 32768 * g, x[a]);
+  }
+}
+
+template <class O, bool KFAST_SRC>
+__global__ __launch_bounds__(512, 4) void fp_fft_tile_1024x4_lean(TilePlan p, const elt_t* __restrict__ W, u32 wshift,
+                                                                  const elt_t* __restrict__ tw, u32 row_fast, u32 lcb) {
+  const u32 tid = threadIdx.x, j1 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  u32 bx, by;  // (tile, batch row)
+  if (KFAST_SRC) {
+    bx = row_fast ? blockIdx.y : blockIdx.x;
+    by = row_fast ? blockIdx.x : blockIdx.y;
+  } else {  // t4_xcd_order for 2^lcb column blocks, lcb >= 3
+    const u32 i = blockIdx.x >> 3, sh = lcb - 3;
+    bx = ((blockIdx.x & 7) << sh) + (i & ((1u << sh) - 1));
+    by = i >> sh;
+  }
+  elt_t w0[7] = {}, w1[7], wv8;  // the stage twiddles of rounds 0 and 1, and w^(8 lane)
+  {  // round 0
+    const u32 c = KFAST_SRC ? tid >> 7 : tid & 3, kb = KFAST_SRC ? tid & 127 : tid >> 2;
+    const char* src = (const char*)(p.src + (long long)by * p.src_row + (long long)bx * p.src_tile);
+    const u32 sk = (u32)p.sk << 4, off = kb * sk + c * ((u32)p.sc << 4);
+    elt_t y[8], t[8];
+#pragma unroll
+    for (u32 a = 0; a < 8; ++a) y[a] = t4l_gld(t4l_at(src, 128 * a * sk, off));
+    if (KFAST_SRC) {
+      const char* twt = (const char*)(tw + ((size_t)bx << 12));
+      const u32 toff = ((c << 10) + kb) << 4;
+#pragma unroll
+      for (u32 a = 0; a < 8; ++a) t[a] = t4l_gld(t4l_at(twt, 2048 * a, toff));
+    }
+    const elt_t wv = t4l_gld(t4l_at((const char*)W, 0, tid << (wshift + 4)));
+    wv8 = t4l_gld(t4l_at((const char*)W, 0, (tid & 63) << (wshift + 7)));  // w^(8 lane): wave 0 keeps it
+#pragma unroll
+    for (u32 m = 0; m < 7; ++m) {  // scalar loads, as fp_fft_tile_1024x4_tw2
+      w1[m] = ld16(&W[(size_t)t4w_tw_index<3>(j1, m) << wshift]);
+      if (m >= 4) w0[m] = ld16(&W[(size_t)t4w_tw_index<0>(0, m) << wshift]);
+    }
+#pragma unroll
+    for (u32 m = 0; m < 7; ++m) {
+      asm volatile("" : "+s"(w1[m].lo), "+s"(w1[m].hi));
+      if (m >= 4) asm volatile("" : "+s"(w0[m].lo), "+s"(w0[m].hi));
+    }
+    w0[2] = w0[5];
+    __builtin_amdgcn_sched_barrier(0);  // every load in flight before the first wait
+    if (KFAST_SRC) {
+#pragma unroll
+      for (u32 a = 0; a < 8; a += 2) T4Ops<O>::mul2_tw(y[a], t[a], y[a + 1], t[a + 1]);
+    }
+    t4l_round0<O>(y, kb, c, w0);
+    asm volatile("" ::"v"(wv8.lo), "v"(wv8.hi));  // loaded here, beside wv: the compiler would move the load to wave 0's path of round 1
+    t4l_st(T4L_W + (tid << 4), wv);
+  }
+  __syncthreads();
+  t4l_round1<O>(tid, j1, w1, wv8);
+  __syncthreads();
+  t4l_round2<O>(tid);
+  __syncthreads();
+  {  // round 3: group g holds j = j0 + 128 g, its outputs the points j + 256 a
+    char* dst = (char*)(p.dst + (long long)by * p.dst_row + (long long)bx * p.dst_tile);
+    const u32 j0 = tid >> 2, c = tid & 3, dk = (u32)p.dk << 4, off = j0 * dk + c * ((u32)p.dc << 4);
+    const u32 s0 = t4l_byte(j0, c);
+    u32 wa = T4L_W + ((tid << 3) & ~31u), wb = T4L_W + ((tid << 2) & ~15u);  // w^(2 j0), w^j0
+    asm("" : "+v"(wa), "+v"(wb));
+#pragma unroll
+    for (u32 g = 0; g < 2; ++g) {
+      const u32 sg = g ? s0 ^ 144 : s0;
+      elt_t x[4];
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) x[a] = t4l_ld((sg ^ (32 * a)) + 16384 * a + 8192 * g);
+      const elt_t w2 = t4l_ld(wa + 4096 * g), w1s = t4l_ld(wb + 2048 * g), w1h = t4l_ld(wb + 2048 * g + 4096);
+      t4l_stages4<O, KFAST_SRC ? T4_LAZY_OUT : T4_LAZY>(x, w2, w1s, w1h);
+#pragma unroll
+      for (u32 a = 0; a < 4; ++a) t4l_gst(t4l_at(dst, (128 * g + 256 * a) * dk, off), x[a]);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ K2: LCH14
 // Stage ii of the tile (global stage i = i_lo + ii) uses
 //   tw = tbl[off[ii] + u_local]  (^ base[ii*nb + cbase + c] when base != null)
@@ -928,7 +1173,9 @@ static int set_lds_limit(lfgpu_ctx* c) {
                               (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, false>,
                               (const void*)fp_fft_tile_1024x4_tw2<Fp128Ops, true>,
                               (const void*)fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, false>,
-                              (const void*)fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, true>};
+                              (const void*)fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, true>,
+                              (const void*)fp_fft_tile_1024x4_lean<T4Ilp<Fp128Ops>, false>,
+                              (const void*)fp_fft_tile_1024x4_lean<T4Ilp<Fp128Ops>, true>};
     for (const void* k : t4) LF_HIP(c, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
     LF_TRY(set_lds_limit_fp<F64x2Ops<true>>(c));
     LF_TRY(set_lds_limit_fp<F64x2Ops<false>>(c));
@@ -964,6 +1211,7 @@ struct FpSwitches {
   bool lazy;        // LFGPU_FP_LAZY (default 1): 0 launches fp_fft_tile_1024x4_tws_canon
   bool r1wave;      // LFGPU_FP_R1WAVE (default 1): 0 launches fp_fft_tile_1024x4_tws where the wave-uniform round 1 is the default
   bool ilp;         // LFGPU_FP_ILP (default 1): 0 launches fp_fft_tile_1024x4_tw2 where fp_fft_tile_1024x4_ilp is the default
+  bool lean;        // LFGPU_FP_LEAN (default 1): 0 launches fp_fft_tile_1024x4_ilp where fp_fft_tile_1024x4_lean is the default
   bool two_level;   // LFGPU_FP_TW=2: the two-level inter-pass table
   bool row_fast;    // LFGPU_FP_ROWFAST (default 1): 0 keeps pass A's tiles fastest in the grid
 };
@@ -978,6 +1226,7 @@ static const FpSwitches& fp_switches() {
     w.lazy = num("LFGPU_FP_LAZY", 1) != 0;
     w.r1wave = num("LFGPU_FP_R1WAVE", 1) != 0;
     w.ilp = num("LFGPU_FP_ILP", 1) != 0;
+    w.lean = num("LFGPU_FP_LEAN", 1) != 0;
     w.two_level = num("LFGPU_FP_TW", 0) == 2;
     w.row_fast = num("LFGPU_FP_ROWFAST", 1) != 0;
     return w;
@@ -990,6 +1239,16 @@ static bool tile_1024x4_fits(const TilePlan& p, bool kfast_src, bool offsets32) 
   if (p.logT != 10 || p.logC != 2 || !p.wlds || p.kfast_src != (kfast_src ? 1u : 0u) || p.kfast_dst != 0 || (p.nbatch & 3) != 0) return false;
   return !offsets32 || (p.sk >= 0 && p.sc >= 0 && p.dk >= 0 && p.dc >= 0 && (u64)p.sk * 1024 + (u64)p.sc * 4 <= 0xffffffffu &&
                         (u64)p.dk * 1024 + (u64)p.dc * 4 <= 0xffffffffu);
+}
+// May a plan that fits fp_fft_tile_1024x4_tw2 go to fp_fft_tile_1024x4_lean?  Its offsets inside a tile are 32-bit byte offsets, so
+// a tile spans less than 2^32 bytes on the load and the store side (and the stage-twiddle table, 512 entries 2^wshift apart); its
+// tile order wants the column-block count a power of two, in pass A with 8 or more blocks.  *lcb: log2 of that count.
+static bool tile_1024x4_lean_fits(const TilePlan& p, bool kfast_src, u32 wshift, u32* lcb) {
+  const u32 ncb = p.nbatch >> 2;
+  if (ncb == 0 || (ncb & (ncb - 1)) != 0 || (!kfast_src && ncb < 8) || wshift > 16) return false;
+  if (((u64)p.sk * 1024 + (u64)p.sc * 4) * 16 > 0xffffffffu || ((u64)p.dk * 1024 + (u64)p.dc * 4) * 16 > 0xffffffffu) return false;
+  *lcb = lf_log2(ncb);
+  return true;
 }
 // Pass A through fp_fft_tile_1024x4_persist.  LFGPU_FP_PERSIST: 0 = fp_fft_tile_1024x4 in the grid order of the caller, 1 (default)
 // = one tile per workgroup in the XCD-aware tile order, 2 = the tile loop on as many workgroups as the CUs hold at once (measured
@@ -1036,8 +1295,10 @@ static bool launch_tile_1024x4(lfgpu_ctx* c, dim3 grid, size_t lds, const TilePl
 // tiles (n = 2^20) and the full table is in use.  LFGPU_FP_TWSIDE=0, or any setting of LFGPU_FP_PERSIST or LFGPU_FP_TILE1024 (which
 // choose among the kernels of the other plan), keeps the product in pass A; =2 runs pass B with the rows fastest in the grid.
 // LFGPU_FP_LAZY=0 launches the pair with canonical butterflies, fp_fft_tile_1024x4_tws_canon, for both passes; otherwise the pair
-// is fp_fft_tile_1024x4_ilp (round 1 wave-uniform, arithmetic in pairs); LFGPU_FP_ILP=0 puts fp_fft_tile_1024x4_tw2 back (the same
-// without the pairs) and LFGPU_FP_R1WAVE=0 fp_fft_tile_1024x4_tws.  None of the switches has an effect where this plan is not taken.
+// is fp_fft_tile_1024x4_lean (round 1 wave-uniform, arithmetic in pairs, scalar bases and byte addresses) for every plan it takes
+// (tile_1024x4_lean_fits); LFGPU_FP_LEAN=0, and any other plan, launches fp_fft_tile_1024x4_ilp (the same values with the address
+// arithmetic of fp_fft_tile_1024x4_tw2), LFGPU_FP_ILP=0 puts fp_fft_tile_1024x4_tw2 back (the same without the pairs) and
+// LFGPU_FP_R1WAVE=0 fp_fft_tile_1024x4_tws.  None of the switches has an effect where this plan is not taken.
 template <class O>
 static int fp_twside_mode(const lfgpu_ctx* c, u32 logn1, size_t rows, bool two_level) {
   const int mode = fp_switches().other_plan ? 0 : fp_switches().twside;
@@ -1054,7 +1315,10 @@ static bool launch_tile_1024x4_tws(lfgpu_ctx* c, u32 rows, size_t lds, const Til
     if (KFAST_SRC && (p.sk != 1 || p.sc != 1024 || p.src_tile != 4096)) return false;  // the table's layout [j1][k2]
     if (KFAST_SRC && (row_fast ? ncb : rows) > 65535) row_fast = !row_fast;
     const dim3 grid = !KFAST_SRC ? dim3(ncb * rows) : row_fast ? dim3(rows, ncb) : dim3(ncb, rows);
+    u32 lcb = 0;
     if (!fp_switches().lazy) hipLaunchKernelGGL((fp_fft_tile_1024x4_tws_canon<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
+    else if (fp_switches().r1wave && fp_switches().ilp && fp_switches().lean && tile_1024x4_lean_fits(p, KFAST_SRC, wshift, &lcb))
+      hipLaunchKernelGGL((fp_fft_tile_1024x4_lean<T4Ilp<O>, KFAST_SRC>), grid, dim3(512), T4L_LDS, c->stream, p, W, wshift, tw, row_fast, lcb);
     else if (fp_switches().r1wave && fp_switches().ilp) hipLaunchKernelGGL((fp_fft_tile_1024x4_tw2<T4Ilp<O>, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     else if (fp_switches().r1wave) hipLaunchKernelGGL((fp_fft_tile_1024x4_tw2<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);
     else hipLaunchKernelGGL((fp_fft_tile_1024x4_tws<O, KFAST_SRC>), grid, dim3(512), lds, c->stream, p, W, wshift, tw, row_fast);

@@ -24,9 +24,10 @@
 // only inside itself, and the ones with SALU instructions clobber SCC: the compiler may hold a live SCC across them (the carry
 // of a 64-bit address add, a loop's branch condition).
 //
-// The default pair at n = 2^20 (fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, ..>) issues the same arithmetic two operations at a time:
-// fpt_mul2_t, fpt_bfly2_lazy, fpt_bfly_lazy and fpt_canon2 at the end of this file fill those wait states with the other
-// operation's instructions.  Same values, same VALU instructions; the single routines above serve every other kernel.
+// The default pair at n = 2^20 (fp_fft_tile_1024x4_lean, and fp_fft_tile_1024x4_tw2<T4Ilp<Fp128Ops>, ..> before it) issues the
+// same arithmetic two operations at a time: fpt_mul2_t, fpt_bfly2_lazy, fpt_bfly_lazy and fpt_canon2 at the end of this file
+// fill those wait states with the other operation's instructions, and fpt_bfly2_full does the same for two butterflies with
+// full sums (fp_fft_tile_1024x4_lean only).  Same values, same VALU instructions; the single routines above serve every other kernel.
 #pragma once
 #include "fields.h"
 
@@ -343,6 +344,79 @@ __device__ __forceinline__ void fpt_bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, 
   yq = FP_PACK(tq0, tq1, tq2, tq3);
 }
 
+// Two butterflies with full sums: (x, y) = (u + t, u - t) canonical for (u, t) = (xp, yp) and (xq, yq), all four < p: fpt_add and
+// fpt_sub twice, interleaved like fpt_bfly2_lazy.  Six chains: the sums s = u + t (carry-out kept in ap / aq until the end), the
+// differences u - t (borrow in sp / sq, which then carries the + p chain, as in fpt_sub), and s - p (borrow in VCC / bq).  Every
+// link has at least two VALU instructions of other chains between its write and its read, the two s_andn2_b64 (keep s <=> borrow
+// and no carry, as fpt_add) stand two VALU instructions behind the last write of their masks, and the v_cndmask that follow read
+// a mask an SALU instruction wrote.  y's limbs take t's registers.  42 VALU instructions, the same as two fpt_add and two
+// fpt_sub, no s_nop.
+__device__ __forceinline__ void fpt_bfly2_full(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) {
+  FP_W(xp, up0, up1, up2, up3);
+  FP_W(yp, tp0, tp1, tp2, tp3);
+  FP_W(xq, uq0, uq1, uq2, uq3);
+  FP_W(yq, tq0, tq1, tq2, tq3);
+  u32 sp0, sp1, sp2, sp3, sq0, sq1, sq2, sq3, dp0, dp1, dp2, dp3, dq0, dq1, dq2, dq3, ep, eq;
+  u64 ap, aq, sp, sq, bq;
+  asm("v_add_co_u32 %[sp0], %[ap], %[up0], %[tp0]\n\t"
+      "v_sub_co_u32 %[tp0], %[sp], %[up0], %[tp0]\n\t"
+      "v_add_co_u32 %[sq0], %[aq], %[uq0], %[tq0]\n\t"
+      "v_sub_co_u32 %[tq0], %[sq], %[uq0], %[tq0]\n\t"
+      "v_addc_co_u32 %[sp1], %[ap], %[up1], %[tp1], %[ap]\n\t"
+      "v_subb_co_u32 %[tp1], %[sp], %[up1], %[tp1], %[sp]\n\t"
+      "v_addc_co_u32 %[sq1], %[aq], %[uq1], %[tq1], %[aq]\n\t"
+      "v_subb_co_u32 %[tq1], %[sq], %[uq1], %[tq1], %[sq]\n\t"
+      "v_addc_co_u32 %[sp2], %[ap], %[up2], %[tp2], %[ap]\n\t"
+      "v_subb_co_u32 %[tp2], %[sp], %[up2], %[tp2], %[sp]\n\t"
+      "v_addc_co_u32 %[sq2], %[aq], %[uq2], %[tq2], %[aq]\n\t"
+      "v_subb_co_u32 %[tq2], %[sq], %[uq2], %[tq2], %[sq]\n\t"
+      "v_addc_co_u32 %[sp3], %[ap], %[up3], %[tp3], %[ap]\n\t"  // the carries and borrows out: lane masks
+      "v_subb_co_u32 %[tp3], %[sp], %[up3], %[tp3], %[sp]\n\t"
+      "v_addc_co_u32 %[sq3], %[aq], %[uq3], %[tq3], %[aq]\n\t"
+      "v_subb_co_u32 %[tq3], %[sq], %[uq3], %[tq3], %[sq]\n\t"
+      // s - p, p = {1, 0, 0, 0xfffff000}, beside u - t + p under the borrow mask (+ the mask at limb 0, + 0xfffff000 at limb 3)
+      "v_subrev_co_u32 %[dp0], vcc, 1, %[sp0]\n\t"
+      "v_subrev_co_u32 %[dq0], %[bq], 1, %[sq0]\n\t"
+      "v_cndmask_b32 %[ep], 0, %[k], %[sp]\n\t"
+      "v_cndmask_b32 %[eq], 0, %[k], %[sq]\n\t"
+      "v_subbrev_co_u32 %[dp1], vcc, 0, %[sp1], vcc\n\t"
+      "v_subbrev_co_u32 %[dq1], %[bq], 0, %[sq1], %[bq]\n\t"
+      "v_addc_co_u32 %[tp0], %[sp], 0, %[tp0], %[sp]\n\t"
+      "v_addc_co_u32 %[tq0], %[sq], 0, %[tq0], %[sq]\n\t"
+      "v_subbrev_co_u32 %[dp2], vcc, 0, %[sp2], vcc\n\t"
+      "v_subbrev_co_u32 %[dq2], %[bq], 0, %[sq2], %[bq]\n\t"
+      "v_addc_co_u32 %[tp1], %[sp], 0, %[tp1], %[sp]\n\t"
+      "v_addc_co_u32 %[tq1], %[sq], 0, %[tq1], %[sq]\n\t"
+      "v_subb_co_u32 %[dp3], vcc, %[sp3], %[k], vcc\n\t"  // final borrow set <=> s < p
+      "v_subb_co_u32 %[dq3], %[bq], %[sq3], %[k], %[bq]\n\t"
+      "v_addc_co_u32 %[tp2], %[sp], 0, %[tp2], %[sp]\n\t"
+      "v_addc_co_u32 %[tq2], %[sq], 0, %[tq2], %[sq]\n\t"
+      "s_andn2_b64 vcc, vcc, %[ap]\n\t"  // keep s <=> (c:s) < p <=> borrow and no carry
+      "s_andn2_b64 %[bq], %[bq], %[aq]\n\t"
+      "v_cndmask_b32 %[dp0], %[dp0], %[sp0], vcc\n\t"
+      "v_cndmask_b32 %[dq0], %[dq0], %[sq0], %[bq]\n\t"
+      "v_addc_co_u32 %[tp3], %[sp], %[ep], %[tp3], %[sp]\n\t"
+      "v_addc_co_u32 %[tq3], %[sq], %[eq], %[tq3], %[sq]\n\t"
+      "v_cndmask_b32 %[dp1], %[dp1], %[sp1], vcc\n\t"
+      "v_cndmask_b32 %[dq1], %[dq1], %[sq1], %[bq]\n\t"
+      "v_cndmask_b32 %[dp2], %[dp2], %[sp2], vcc\n\t"
+      "v_cndmask_b32 %[dq2], %[dq2], %[sq2], %[bq]\n\t"
+      "v_cndmask_b32 %[dp3], %[dp3], %[sp3], vcc\n\t"
+      "v_cndmask_b32 %[dq3], %[dq3], %[sq3], %[bq]"
+      : [sp0] "=&v"(sp0), [sp1] "=&v"(sp1), [sp2] "=&v"(sp2), [sp3] "=&v"(sp3), [sq0] "=&v"(sq0), [sq1] "=&v"(sq1), [sq2] "=&v"(sq2),
+        [sq3] "=&v"(sq3), [dp0] "=&v"(dp0), [dp1] "=&v"(dp1), [dp2] "=&v"(dp2), [dp3] "=&v"(dp3), [dq0] "=&v"(dq0), [dq1] "=&v"(dq1),
+        [dq2] "=&v"(dq2), [dq3] "=&v"(dq3), [tp0] "+v"(tp0), [tp1] "+v"(tp1), [tp2] "+v"(tp2), [tp3] "+v"(tp3), [tq0] "+v"(tq0),
+        [tq1] "+v"(tq1), [tq2] "+v"(tq2), [tq3] "+v"(tq3), [ep] "=&v"(ep), [eq] "=&v"(eq), [ap] "=&s"(ap), [aq] "=&s"(aq), [sp] "=&s"(sp),
+        [sq] "=&s"(sq), [bq] "=&s"(bq)
+      : [up0] "v"(up0), [up1] "v"(up1), [up2] "v"(up2), [up3] "v"(up3), [uq0] "v"(uq0), [uq1] "v"(uq1), [uq2] "v"(uq2), [uq3] "v"(uq3),
+        [k] "v"(0xfffff000u)
+      : "vcc", "scc");
+  xp = FP_PACK(dp0, dp1, dp2, dp3);
+  yp = FP_PACK(tp0, tp1, tp2, tp3);
+  xq = FP_PACK(dq0, dq1, dq2, dq3);
+  yq = FP_PACK(tq0, tq1, tq2, tq3);
+}
+
 // One butterfly, (x, y) = (u + t lazy, u - t) for (u, t) = (x, y): the two chains of fpt_bfly2_lazy (VCC and c1), one
 // instruction between every link and an `s_nop 0` beside it; the two v_cndmask stand between the masks and their folds.  18 VALU.
 // y has registers of its own here: tied to t's, round 0 of pass A copied two limbs of a loaded tuple out of the way.
@@ -619,6 +693,11 @@ LF_HD void fpt_bfly2_lazy(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) {
 LF_HD void fpt_canon2(elt_t& p, elt_t& q) {
   p = fpt_canon(p);
   q = fpt_canon(q);
+}
+LF_HD void fpt_bfly2_full(elt_t& xp, elt_t& yp, elt_t& xq, elt_t& yq) {
+  const elt_t up = xp, tp = yp, uq = xq, tq = yq;
+  xp = fpt_add(up, tp), yp = fpt_sub(up, tp);
+  xq = fpt_add(uq, tq), yq = fpt_sub(uq, tq);
 }
 LF_HD void fpt_mul2(elt_t& pa, elt_t pw, elt_t& qa, elt_t qw) {
   pa = fpt_mul(pa, pw);
