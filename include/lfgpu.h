@@ -58,7 +58,9 @@ extern "C" {
                               prover_from_slab, dot_proof_sparse (LFGPU_ERR_ARG); inner_product_rows, prove_batch, open_batch
                               (LFGPU_ERR_UNSUPPORTED).  The per-step
                               sumcheck entry points below (partials, scatter, binds, bind_g, sumcheck_layer) take the
-                              16-byte fields only: for Fp256Base those steps run inside lfgpu_zk_prove / lfgpu_zk_verify */
+                              16-byte fields only: for Fp256Base those steps run inside lfgpu_zk_prove / lfgpu_zk_verify, and
+                              the whole layer has entry points of its own: lfgpu_sumcheck_layer256,
+                              lfgpu_sumcheck_layer_batch256 and lfgpu_eval_quad_batch256 */
 
 typedef struct lfgpu_ctx lfgpu_ctx;
 
@@ -269,6 +271,45 @@ int lfgpu_sumcheck_layer_batch(lfgpu_quad* q, size_t nb, size_t logv, const void
  * Fields: GF2_128 and Fp128; LFGPU_ERR_UNSUPPORTED for P256. */
 int lfgpu_eval_quad_batch(lfgpu_quad* q, size_t nb, size_t nw, const void* d_W, size_t ldw, void* d_V, size_t ldv,
                           int* ok_out /*[nb]*/);
+
+/* ---- the sumcheck layer over Fp256Base (field 1), single and in lock-step -------------------------------
+ * Elements are 4 x u64 LE Montgomery images (R = 2^256), canonical (< p); ld / strides count 32-byte elements.  These take
+ * quads of LFGPU_FIELD_P256 only (LFGPU_ERR_ARG for a quad of a 16-byte field), as the entry points above take the 16-byte
+ * fields only.  All argument errors are found on the host before the first launch: LFGPU_ERR_ARG for a NULL argument, nb
+ * outside 1..LFGPU_SC_BATCH_MAX, ldw < nw, nw <= the largest hand index, 2^logv < nv, ldv < nv; LFGPU_ERR_NOMEM when the
+ * per-statement scratch does not fit (the limb accumulators alone are 64 bytes per entry and statement).  A NULL quad returns
+ * LFGPU_ERR_ARG without a context.
+ *
+ * lfgpu_sumcheck_layer256: lfgpu_sumcheck_layer for Fp256Base -- the layer lfgpu_zk_prove runs, with all its modes (the
+ * resident grid, the per-launch kernels, the LFGPU_P256_* switches).  h_G0 / h_G1: logv host elements.  Unlike the 16-byte
+ * call, d_W is LEFT INTACT: both hands bind into buffers of the context. */
+typedef void (*lfgpu_sc_round256_fn)(void* user, size_t hand, size_t round, const uint64_t evals[3][4],
+                                     uint64_t challenge_out[4]);
+int lfgpu_sumcheck_layer256(lfgpu_quad* q, size_t logv, const void* h_G0, const void* h_G1, const uint64_t alpha[4],
+                            const uint64_t beta[4], size_t logw, size_t nw, const void* d_W, const uint64_t wc_in[2][4],
+                            lfgpu_sc_round256_fn round, void* user, uint64_t wc_out[2][4],
+                            uint64_t* g_out /*[2][logw][4]*/, uint64_t bound_quad[4]);
+/* lfgpu_sumcheck_layer_batch (K14) for Fp256Base: nb statements of ONE quad through the same launches, ONE call of `round` per
+ * round-hand for all statements, in the order (round 0, hand 0), (round 0, hand 1), (round 1, hand 0), ...  Statement b's
+ * evaluations, wc_out, g_out and bound_quad are byte-identical to what lfgpu_sumcheck_layer256 gives for statement b alone
+ * under the same challenges.  h_G0 / h_G1: [nb][logv]; alpha, beta: [nb][4]; d_W: statement b's nw wires at d_W + b * ldw
+ * elements, ldw >= nw (device; NOT modified, its padding included); wc_in, wc_out: [nb][2][4]; g_out: [nb][2][logw][4];
+ * bound_quad: [nb][4] or NULL.  1 <= nb <= LFGPU_SC_BATCH_MAX (the challenges of a round-hand are then 2 KiB of kernel
+ * arguments).  The challenges the callback returns must be canonical (a precondition, not checked).
+ * No resident grid: while the HQUAD or a hand array has more than LFGPU_P256_BATCH_SMALL_MAX entries a round-hand is three
+ * launches whatever nb; from then on it is one launch of nb workgroups that keeps a statement's accumulators in LDS.
+ * LFGPU_P256_BATCH_SMALL=0 (environment, read once per process) keeps the three launches throughout: the same bytes. */
+#define LFGPU_P256_BATCH_SMALL_MAX 2048
+typedef void (*lfgpu_sc_round_batch256_fn)(void* user, size_t hand, size_t round, size_t nb, const uint64_t (*evals)[3][4],
+                                           uint64_t (*challenge_out)[4]);
+int lfgpu_sumcheck_layer_batch256(lfgpu_quad* q, size_t nb, size_t logv, const void* h_G0, const void* h_G1,
+                                  const uint64_t* alpha, const uint64_t* beta, size_t logw, size_t nw, const void* d_W,
+                                  size_t ldw, const uint64_t* wc_in, lfgpu_sc_round_batch256_fn round, void* user,
+                                  uint64_t* wc_out, uint64_t* g_out, uint64_t* bound_quad /* may be NULL */);
+/* lfgpu_eval_quad_batch for Fp256Base: statement b reads its nw wires at d_W + b * ldw (ldw >= nw), writes its nv outputs at
+ * d_V + b * ldv (ldv >= nv); ok_out[b] = 0 only for the statements whose assert-zero terms fail, the others are unaffected. */
+int lfgpu_eval_quad_batch256(lfgpu_quad* q, size_t nb, size_t nw, const void* d_W, size_t ldw, void* d_V, size_t ldv,
+                             int* ok_out /*[nb]*/);
 
 /* ---- circuits with nc > 1 copies: the copy rounds of the sumcheck (K13) ------------------------------
  * The reference's data-parallel axis: every wire array is Dense(n0 = nc, n1 = nw), stored W[wire * nc + c] (copy index

@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "lfgpu_quad_upload", "lfgpu_quad_free", "lfgpu_eval_quad", "lfgpu_quad_bind_g", "lfgpu_sumcheck_layer", "lfgpu_raw_eq2", "lfgpu_quad_bind_gh_all",
     "lfgpu_eval_quad_copies", "lfgpu_sumcheck_evaluations_c", "lfgpu_dense_bind_rows", "lfgpu_eqs", "lfgpu_sumcheck_layer_copies",
     "lfgpu_sumcheck_layer_batch", "lfgpu_eval_quad_batch",
+    "lfgpu_sumcheck_layer256", "lfgpu_sumcheck_layer_batch256", "lfgpu_eval_quad_batch256",
     # include/lfgpu_zk.h
     "lfgpu_transcript_new", "lfgpu_transcript_free", "lfgpu_transcript_get_ops", "lfgpu_transcript_write_bytes",
     "lfgpu_transcript_write_elt", "lfgpu_transcript_write_elt_array", "lfgpu_transcript_bytes", "lfgpu_transcript_write_elt_sized", "lfgpu_transcript_write_elt_array_sized", "lfgpu_sha256",
@@ -65,6 +66,10 @@ SC_ROUND_C_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
 # round callback of lfgpu_sumcheck_layer_batch: (user, hand, round, nb, evals[nb][3][2], challenge_out[nb][2])
 SC_ROUND_BATCH_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
 SC_BATCH_MAX = 64  # LFGPU_SC_BATCH_MAX
+# the same two callbacks over Fp256Base (4-word elements): evals[3][4] -> challenge_out[4]; evals[nb][3][4] -> challenge_out[nb][4]
+SC_ROUND256_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+SC_ROUND_BATCH256_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64))
+P256_BATCH_SMALL_MAX = 2048  # LFGPU_P256_BATCH_SMALL_MAX: the hand-off bound of lfgpu_sumcheck_layer_batch256's one-launch step
 
 
 class TranscriptOps(C.Structure):
@@ -209,6 +214,9 @@ def load_library():
         "lfgpu_eqs": [vp, ci, sz, sz, vp, vp],
         "lfgpu_sumcheck_layer_copies": [vp, sz, sz, vp, sz, vp, vp, pu64, pu64, sz, sz, vp, pu64, SC_ROUND_C_FN, SC_ROUND_FN, vp, pu64, pu64, pu64, pu64],
         "lfgpu_sumcheck_layer_batch": [vp, sz, sz, vp, vp, pu64, pu64, sz, sz, vp, sz, pu64, SC_ROUND_BATCH_FN, vp, pu64, pu64, pu64],
+        "lfgpu_sumcheck_layer256": [vp, sz, vp, vp, pu64, pu64, sz, sz, vp, pu64, SC_ROUND256_FN, vp, pu64, pu64, pu64],
+        "lfgpu_sumcheck_layer_batch256": [vp, sz, sz, vp, vp, pu64, pu64, sz, sz, vp, sz, pu64, SC_ROUND_BATCH256_FN, vp, pu64, pu64, pu64],
+        "lfgpu_eval_quad_batch256": [vp, sz, sz, vp, sz, vp, sz, C.POINTER(ci)],
         "lfgpu_circuit_from_lfc1": [vp, vp, sz, C.POINTER(vp)],
         "lfgpu_circuit_share": [vp, vp, C.POINTER(vp)],
         "lfgpu_circuit_get_info": [vp, C.POINTER(CircuitInfo)],
@@ -262,6 +270,13 @@ def _u64x2(v):
     if isinstance(v, int):
         v = (v & (2**64 - 1), v >> 64)
     return (C.c_uint64 * 2)(int(v[0]), int(v[1]))
+
+
+def _u64x4(v):
+    """int (canonical 256-bit image) or sequence of four u64 -> (c_uint64 * 4)"""
+    if isinstance(v, int):
+        v = tuple((v >> (64 * k)) & (2**64 - 1) for k in range(4))
+    return (C.c_uint64 * 4)(*[int(x) for x in v])
 
 
 def fp128_to_montgomery(x):
@@ -884,6 +899,64 @@ class Quad:
               for b in range(B)]
         return ([[(wco[4 * b], wco[4 * b + 1]), (wco[4 * b + 2], wco[4 * b + 3])] for b in range(B)], ch,
                 [(bq[2 * b], bq[2 * b + 1]) for b in range(B)])
+
+    # ---- Fp256Base (field 1): elements are 4-word tuples (Montgomery images, little-endian words)
+    def eval_quad_batch256(self, nb, nw, d_W, ldw, d_V, ldv):
+        """eval_batch over Fp256Base (32-byte elements) -> [bool] * nb"""
+        ok = (C.c_int * max(1, nb))()
+        self.gpu._ck(self.gpu.L.lfgpu_eval_quad_batch256(self.h, nb, nw, C.c_void_p(d_W), ldw, C.c_void_p(d_V), ldv, ok))
+        return [bool(ok[b]) for b in range(nb)]
+
+    def sumcheck_layer256(self, logv, G0, G1, alpha, beta, logw, nw, d_W, wc_in, round_cb):
+        """sumcheck_layer over Fp256Base: G0, G1: [logv][4] words; alpha, beta, the claims, evaluations and challenges are
+        4-word tuples.  d_W is left intact.  Returns (wc_out[2], challenges[2][logw], bound_quad)."""
+        import numpy as np
+        G0, G1 = np.ascontiguousarray(G0, dtype=np.uint64), np.ascontiguousarray(G1, dtype=np.uint64)
+
+        def cb(_user, hand, rnd, evals, out):
+            r = round_cb(hand, rnd, [tuple(evals[4 * k + j] for j in range(4)) for k in range(3)])
+            for j in range(4):
+                out[j] = int(r[j])
+
+        cfn = SC_ROUND256_FN(cb)
+        wci = (C.c_uint64 * 8)(*[int(x) for e in wc_in for x in e])
+        wco = (C.c_uint64 * 8)()
+        gout = (C.c_uint64 * (8 * max(1, logw)))()
+        bq = (C.c_uint64 * 4)()
+        self.gpu._ck(self.gpu.L.lfgpu_sumcheck_layer256(self.h, logv, C.c_void_p(G0.ctypes.data), C.c_void_p(G1.ctypes.data),
+                                                        _u64x4(alpha), _u64x4(beta), logw, nw, C.c_void_p(d_W), wci, cfn, None, wco, gout, bq))
+        ch = [[tuple(gout[(h * logw + r) * 4 + j] for j in range(4)) for r in range(logw)] for h in range(2)]
+        return [tuple(wco[0:4]), tuple(wco[4:8])], ch, tuple(bq)
+
+    def sumcheck_layer_batch256(self, logv, G0, G1, alphas, betas, logw, nw, d_W, ldw, wc_ins, round_cb):
+        """sumcheck_layer_batch over Fp256Base for B = len(alphas) statements: G0, G1: [B][logv][4] words; alphas, betas: B
+        4-word tuples; d_W: statement b's nw wires at d_W + b * ldw 32-byte elements (device, left intact); wc_ins: B pairs
+        of 4-word tuples.  round_cb(hand, round, evals) gets evals[b] = 3 4-word tuples and returns B 4-word challenges.
+        Returns (wc_out[B], challenges[B][2][logw], bound_quad[B])."""
+        import numpy as np
+        B = len(alphas)
+        G0, G1 = np.ascontiguousarray(G0, dtype=np.uint64), np.ascontiguousarray(G1, dtype=np.uint64)
+
+        def cb(_user, hand, rnd, nb, evals, out):
+            ev = [tuple(tuple(evals[12 * b + 4 * k + j] for j in range(4)) for k in range(3)) for b in range(nb)]
+            rs = round_cb(hand, rnd, ev)
+            for b in range(nb):
+                for j in range(4):
+                    out[4 * b + j] = int(rs[b][j])
+
+        cfn = SC_ROUND_BATCH256_FN(cb)
+        n = max(1, B)
+        al = (C.c_uint64 * (4 * n))(*[int(x) for a in alphas for x in a])
+        be = (C.c_uint64 * (4 * n))(*[int(x) for a in betas for x in a])
+        wci = (C.c_uint64 * (8 * n))(*[int(x) for w in wc_ins for e in w for x in e])
+        wco = (C.c_uint64 * (8 * n))()
+        gout = (C.c_uint64 * (8 * n * max(1, logw)))()
+        bq = (C.c_uint64 * (4 * n))()
+        self.gpu._ck(self.gpu.L.lfgpu_sumcheck_layer_batch256(self.h, B, logv, C.c_void_p(G0.ctypes.data), C.c_void_p(G1.ctypes.data), al, be,
+                                                              logw, nw, C.c_void_p(d_W), ldw, wci, cfn, None, wco, gout, bq))
+        ch = [[[tuple(gout[((b * 2 + h) * logw + r) * 4 + j] for j in range(4)) for r in range(logw)] for h in range(2)] for b in range(B)]
+        return ([[tuple(wco[8 * b:8 * b + 4]), tuple(wco[8 * b + 4:8 * b + 8])] for b in range(B)], ch,
+                [tuple(bq[4 * b:4 * b + 4]) for b in range(B)])
 
     def close(self):
         if self.h:

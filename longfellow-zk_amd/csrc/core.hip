@@ -286,6 +286,7 @@ int lfgpu_shutdown(lfgpu_ctx* c) {
   if (c->mailbox_h) hipHostFree(c->mailbox_h);
   if (c->poll_h) hipHostFree((void*)c->poll_h);
   if (c->sc_batch_h) hipHostFree((void*)c->sc_batch_h);
+  if (c->sc_batch256_h) hipHostFree((void*)c->sc_batch256_h);
   if (c->sc_batch_pts_ev) hipEventDestroy(c->sc_batch_pts_ev);
   if (c->sc_batch_pts_h) hipHostFree(c->sc_batch_pts_h);
   if (c->cb_stage_h) {

@@ -69,6 +69,9 @@ struct lfgpu_ctx {
   // lfgpu_sumcheck_layer_batch: one slot of LF_SC_BATCH_SLOT_WORDS coherent pinned words per statement, each laid out like
   // poll_h; allocated at the first batched call, sequence numbers from poll_seq
   volatile u64* sc_batch_h = nullptr;
+  // lfgpu_sumcheck_layer_batch256: the same for 32-byte elements (zk256.hip), 32 words per statement: the 16 limb words of a
+  // round-hand's two sums, then the sequence number
+  volatile u64* sc_batch256_h = nullptr;
   // ... and the pinned image of the B binding-point sets of its bind_g (quad.hip: lf_quad_bind_g_batch), rewritten per layer once
   // sc_batch_pts_ev (recorded after its copy) has completed
   void* sc_batch_pts_h = nullptr;

@@ -73,11 +73,17 @@ __global__ __launch_bounds__(Z_THREADS) void limb_normalize256_kernel(size_t n, 
   if (i >= n) return;
   st32(&out[i], take_acc256(acc, i, rsq));
 }
+// ... of statement blockIdx.y: its accumulators at acc + y * s_acc words, its elements at out + y * s_out
+__global__ __launch_bounds__(Z_THREADS) void limb_normalize256_batch_kernel(size_t n, u64* __restrict__ acc, size_t s_acc, E rsq, E* __restrict__ out, size_t s_out) {
+  const size_t i = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+  if (i >= n) return;
+  st32(&out[(size_t)blockIdx.y * s_out + i], take_acc256(acc + (size_t)blockIdx.y * s_acc, i, rsq));
+}
 
 // K11: V[g] = sum_{terms of g} kvec[vi] * W[h1] * W[h0]; assert-zero terms must vanish.  One term per lane over the
 // by-gate order (a gate's terms are contiguous: one gate of the signature circuit has 769), summed as above.
-__global__ __launch_bounds__(Z_THREADS) void eval_quad256_kernel(size_t n, const corner4* __restrict__ terms, const E* __restrict__ kvec,
-                                                                 const E* __restrict__ W, u64* __restrict__ acc, int* __restrict__ fail) {
+__device__ __forceinline__ void eval_quad256_body(size_t n, const corner4* __restrict__ terms, const E* __restrict__ kvec, const E* __restrict__ W,
+                                                  u64* __restrict__ acc, int* __restrict__ fail) {
   const size_t i = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
   u32 key = 0xffffffffu;
   E t = e32_zero();
@@ -93,6 +99,16 @@ __global__ __launch_bounds__(Z_THREADS) void eval_quad256_kernel(size_t n, const
     }
   }
   run_fold_commit256(key, t, acc);
+}
+__global__ __launch_bounds__(Z_THREADS) void eval_quad256_kernel(size_t n, const corner4* __restrict__ terms, const E* __restrict__ kvec,
+                                                                 const E* __restrict__ W, u64* __restrict__ acc, int* __restrict__ fail) {
+  eval_quad256_body(n, terms, kvec, W, acc, fail);
+}
+// statement blockIdx.y of a batch: its wires at W + y * ldw, its accumulators at acc + y * s_acc words, its flag fail[y]
+__global__ __launch_bounds__(Z_THREADS) void eval_quad256_batch_kernel(size_t n, const corner4* __restrict__ terms, const E* __restrict__ kvec,
+                                                                       const E* __restrict__ W, size_t ldw, u64* __restrict__ acc, size_t s_acc,
+                                                                       int* __restrict__ fail) {
+  eval_quad256_body(n, terms, kvec, W + (size_t)blockIdx.y * ldw, acc + (size_t)blockIdx.y * s_acc, fail + blockIdx.y);
 }
 
 // ---- inner_product_vector from a caller's term list (LigeroCommon::inner_product_vector, ligero_param.h:382-421), the step of
@@ -150,7 +166,7 @@ __global__ __launch_bounds__(Z_THREADS) void a_terms_finish256_kernel(u32 r, u32
 }
 
 // eq[i] = EQ(G0, i) + alpha EQ(G1, i), EQ(G, i) = prod_l (bit_l(i) ? G[l] : 1 - G[l]); G = G0 | G1 | 1-G0 | 1-G1
-__global__ __launch_bounds__(Z_THREADS) void raw_eq2_256_kernel(u32 logn, u32 n, const E* __restrict__ G, E alpha, E one, E* __restrict__ eq) {
+__device__ __forceinline__ void raw_eq2_256_body(u32 logn, u32 n, const E* __restrict__ G, const E& alpha, const E& one, E* __restrict__ eq) {
   const u32 i = blockIdx.x * Z_THREADS + threadIdx.x;
   if (i >= n) return;
   E e0 = one, e1 = alpha;
@@ -161,11 +177,20 @@ __global__ __launch_bounds__(Z_THREADS) void raw_eq2_256_kernel(u32 logn, u32 n,
   }
   st32(&eq[i], fp256_add(e0, e1));
 }
+__global__ __launch_bounds__(Z_THREADS) void raw_eq2_256_kernel(u32 logn, u32 n, const E* __restrict__ G, E alpha, E one, E* __restrict__ eq) {
+  raw_eq2_256_body(logn, n, G, alpha, one, eq);
+}
+// The batch twins of the EQ kernels: statement blockIdx.y has its point table at G + y * gs (the table of raw_eq2_256 followed by
+// the statement's alpha at 4 logn and its beta at 4 logn + 1), its factor tables at tab + y * ts, its vector at eq + y * n
+__global__ __launch_bounds__(Z_THREADS) void raw_eq2_256_batch_kernel(u32 logn, u32 n, const E* __restrict__ G, size_t gs, E one, E* __restrict__ eq) {
+  const E* Gb = G + (size_t)blockIdx.y * gs;
+  raw_eq2_256_body(logn, n, Gb, ld32(&Gb[4 * logn]), one, eq + (size_t)blockIdx.y * n);
+}
 
 // The same vector with 2 products per entry instead of 2 logn: EQ(G, i) = LO[i mod 2^lb] * HI[i >> lb].  eq_tables256_kernel
 // builds the four factor tables LO0 | HI0 | LO1 | HI1 (alpha folded into HI1), one thread per entry (<= 2^ceil(logn / 2)
 // entries each), raw_eq2_split256_kernel combines them.  Exact field arithmetic: the association does not matter.
-__global__ __launch_bounds__(Z_THREADS) void eq_tables256_kernel(u32 logn, u32 lb, const E* __restrict__ G, E alpha, E one, E* __restrict__ tab) {
+__device__ __forceinline__ void eq_tables256_body(u32 logn, u32 lb, const E* __restrict__ G, const E& alpha, const E& one, E* __restrict__ tab) {
   const u32 hb = logn - lb, nlo = 1u << lb, nhi = 1u << hb;
   const u32 t = blockIdx.x * Z_THREADS + threadIdx.x;
   if (t >= 2 * (nlo + nhi)) return;
@@ -179,7 +204,14 @@ __global__ __launch_bounds__(Z_THREADS) void eq_tables256_kernel(u32 logn, u32 l
   }
   st32(&tab[t], e);
 }
-__global__ __launch_bounds__(Z_THREADS) void raw_eq2_split256_kernel(u32 logn, u32 lb, u32 n, const E* __restrict__ tab, E* __restrict__ eq) {
+__global__ __launch_bounds__(Z_THREADS) void eq_tables256_kernel(u32 logn, u32 lb, const E* __restrict__ G, E alpha, E one, E* __restrict__ tab) {
+  eq_tables256_body(logn, lb, G, alpha, one, tab);
+}
+__global__ __launch_bounds__(Z_THREADS) void eq_tables256_batch_kernel(u32 logn, u32 lb, const E* __restrict__ G, size_t gs, E one, E* __restrict__ tab, size_t ts) {
+  const E* Gb = G + (size_t)blockIdx.y * gs;
+  eq_tables256_body(logn, lb, Gb, ld32(&Gb[4 * logn]), one, tab + (size_t)blockIdx.y * ts);
+}
+__device__ __forceinline__ void raw_eq2_split256_body(u32 logn, u32 lb, u32 n, const E* __restrict__ tab, E* __restrict__ eq) {
   const u32 i = blockIdx.x * Z_THREADS + threadIdx.x;
   if (i >= n) return;
   const u32 nlo = 1u << lb, nhi = 1u << (logn - lb);
@@ -188,14 +220,21 @@ __global__ __launch_bounds__(Z_THREADS) void raw_eq2_split256_kernel(u32 logn, u
   const E e1 = fp256_mul(ld32(&tab[nlo + nhi + lo]), ld32(&tab[2 * nlo + nhi + hi]));
   st32(&eq[i], fp256_add(e0, e1));
 }
+__global__ __launch_bounds__(Z_THREADS) void raw_eq2_split256_kernel(u32 logn, u32 lb, u32 n, const E* __restrict__ tab, E* __restrict__ eq) {
+  raw_eq2_split256_body(logn, lb, n, tab, eq);
+}
+__global__ __launch_bounds__(Z_THREADS) void raw_eq2_split256_batch_kernel(u32 logn, u32 lb, u32 n, const E* __restrict__ tab, size_t ts, E* __restrict__ eq) {
+  raw_eq2_split256_body(logn, lb, n, tab + (size_t)blockIdx.y * ts, eq + (size_t)blockIdx.y * n);
+}
 
 // Quad::bind_g: every term computes prep_v(v, beta) * eq[g]; the terms of a run (equal hand pair, contiguous in canonical
 // order) add into the run's limb accumulators
 __device__ __forceinline__ bool is_head256(const corner4* t, size_t i) { return i == 0 || t[i].h0 != t[i - 1].h0 || t[i].h1 != t[i - 1].h1; }
-__global__ __launch_bounds__(BG_THREADS) void bindg_emit256_kernel(size_t n, const corner4* __restrict__ t, const E* __restrict__ kvec,
-                                                                   const E* __restrict__ eq, E beta, const u32* __restrict__ block_off,
-                                                                   uint2* __restrict__ hc_out, u64* __restrict__ acc) {
-  __shared__ u32 wave_off[BG_THREADS / 64];
+// WRITE_HC = false (statements b > 0 of a batch): the corners are circuit constants, the same for every statement -- only
+// statement 0 writes them (as K14's kernels do, sumcheck.hip)
+template <bool WRITE_HC>
+__device__ __forceinline__ void bindg_emit256_body(u32* wave_off, size_t n, const corner4* __restrict__ t, const E* __restrict__ kvec, const E* __restrict__ eq,
+                                                   const E& beta, const u32* __restrict__ block_off, uint2* __restrict__ hc_out, u64* __restrict__ acc) {
   const size_t i = (size_t)blockIdx.x * BG_THREADS + threadIdx.x;
   const bool valid = i < n;
   const bool head = valid && is_head256(t, i);
@@ -212,15 +251,33 @@ __global__ __launch_bounds__(BG_THREADS) void bindg_emit256_kernel(size_t n, con
     E v = ld32(&kvec[c0.vi]);
     if (e32_is_zero(v)) v = beta;
     pv = fp256_mul(v, ld32(&eq[c0.g]));
-    if (head) hc_out[ri] = make_uint2(c0.h0, c0.h1);
+    if (WRITE_HC && head) hc_out[ri] = make_uint2(c0.h0, c0.h1);
   }
   run_fold_commit256(valid ? ri : 0xffffffffu, pv, acc);
 }
+__global__ __launch_bounds__(BG_THREADS) void bindg_emit256_kernel(size_t n, const corner4* __restrict__ t, const E* __restrict__ kvec,
+                                                                   const E* __restrict__ eq, E beta, const u32* __restrict__ block_off,
+                                                                   uint2* __restrict__ hc_out, u64* __restrict__ acc) {
+  __shared__ u32 wave_off[BG_THREADS / 64];
+  bindg_emit256_body<true>(wave_off, n, t, kvec, eq, beta, block_off, hc_out, acc);
+}
+// statement blockIdx.y: its EQ vector at eq + y * nv, its beta in its point table (G + y * gs)[ibeta], its run accumulators at
+// acc + y * s_acc words -- no two statements share an accumulator
+__global__ __launch_bounds__(BG_THREADS) void bindg_emit256_batch_kernel(size_t n, const corner4* __restrict__ t, const E* __restrict__ kvec,
+                                                                         const E* __restrict__ eq, size_t nv, const E* __restrict__ G, size_t gs, u32 ibeta,
+                                                                         const u32* __restrict__ block_off, uint2* __restrict__ hc_out, u64* __restrict__ acc,
+                                                                         size_t s_acc) {
+  __shared__ u32 wave_off[BG_THREADS / 64];
+  const size_t b = blockIdx.y;
+  const E beta = ld32(&G[b * gs + ibeta]);
+  if (b == 0) bindg_emit256_body<true>(wave_off, n, t, kvec, eq, beta, block_off, hc_out, acc);
+  else bindg_emit256_body<false>(wave_off, n, t, kvec, eq + b * nv, beta, block_off, hc_out, acc + b * s_acc);
+}
 
 // QW[h[hand]] += v * Wother[h[1-hand]]
-__global__ __launch_bounds__(Z_THREADS) void qw_scatter256_kernel(size_t n, const uint2* __restrict__ hc, const E* __restrict__ vc, int hand,
-                                                                  const E* __restrict__ Wo, u64* __restrict__ acc) {
-  const size_t i = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+__device__ __forceinline__ void qw_scatter256_body(size_t blk, size_t n, const uint2* __restrict__ hc, const E* __restrict__ vc, int hand,
+                                                   const E* __restrict__ Wo, u64* __restrict__ acc) {
+  const size_t i = blk * Z_THREADS + threadIdx.x;
   u32 key = 0xffffffffu;
   E t = e32_zero();
   if (i < n) {
@@ -229,6 +286,16 @@ __global__ __launch_bounds__(Z_THREADS) void qw_scatter256_kernel(size_t n, cons
     t = fp256_mul(ld32(&vc[i]), ld32(&Wo[hand ? h.x : h.y]));
   }
   run_fold_commit256(key, t, acc);
+}
+__global__ __launch_bounds__(Z_THREADS) void qw_scatter256_kernel(size_t n, const uint2* __restrict__ hc, const E* __restrict__ vc, int hand,
+                                                                  const E* __restrict__ Wo, u64* __restrict__ acc) {
+  qw_scatter256_body(blockIdx.x, n, hc, vc, hand, Wo, acc);
+}
+// statement blockIdx.y: shared corners, its values at vc + y * s_vc, the other hand at Wo + y * s_wo, its targets at acc + y * s_acc words
+__global__ __launch_bounds__(Z_THREADS) void qw_scatter256_batch_kernel(size_t n, const uint2* __restrict__ hc, const E* __restrict__ vc, size_t s_vc, int hand,
+                                                                        const E* __restrict__ Wo, size_t s_wo, u64* __restrict__ acc, size_t s_acc) {
+  const size_t b = blockIdx.y;
+  qw_scatter256_body(blockIdx.x, n, hc, vc + b * s_vc, hand, Wo + b * s_wo, acc + b * s_acc);
 }
 
 __device__ __forceinline__ E block_sum256(E v, E* sh) {
@@ -248,35 +315,37 @@ __device__ __forceinline__ E block_sum256(E v, E* sh) {
 // (out[0..8) = a0, out[8..16) = a2) that the host reduces.
 // post != nullptr: the block that finishes last copies the 16 words to coherent pinned host memory (post[0..16)), clears
 // them and publishes `seq` at post[16] -- the host spins on that word instead of a copy + stream synchronisation.
-__global__ __launch_bounds__(Z_THREADS) void partials256_kernel(size_t n, u64* __restrict__ acc, E rsq, const E* __restrict__ W, u64* __restrict__ out,
-                                                                u32* __restrict__ done, volatile u64* __restrict__ post, u64 seq) {
-  __shared__ E sh[Z_THREADS];
-  __shared__ u32 s_last;
+// the two sums of this thread over the pairs of blocks blk, blk + nblk, ...  (acc: the scatter's accumulators, left zeroed)
+__device__ __forceinline__ void partials256_thread(size_t blk, size_t nblk, size_t n, u64* __restrict__ acc, const E& rsq, const E* __restrict__ W, E& a0, E& a2) {
   const size_t nodd = n / 2;
-  E a0 = e32_zero(), a2 = e32_zero();
-  for (size_t i = (size_t)blockIdx.x * Z_THREADS + threadIdx.x; i < nodd; i += (size_t)gridDim.x * Z_THREADS) {
+  for (size_t i = blk * Z_THREADS + threadIdx.x; i < nodd; i += nblk * Z_THREADS) {
     const E q0 = take_acc256(acc, 2 * i, rsq), q1 = take_acc256(acc, 2 * i + 1, rsq), w0 = ld32(&W[2 * i]), w1 = ld32(&W[2 * i + 1]);
     a0 = fp256_add(a0, fp256_mul(q0, w0));
     a2 = fp256_add(a2, fp256_mul(fp256_sub(q1, q0), fp256_sub(w1, w0)));
   }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && 2 * nodd < n) {  // odd tail (:381-388)
+  if (blk == 0 && threadIdx.x == 0 && 2 * nodd < n) {  // odd tail (:381-388)
     const E t = fp256_mul(take_acc256(acc, 2 * nodd, rsq), ld32(&W[2 * nodd]));
     a0 = fp256_add(a0, t);
     a2 = fp256_add(a2, t);
   }
+}
+__device__ __forceinline__ void partials256_body(E* sh, u32* s_last, size_t n, u64* __restrict__ acc, const E& rsq, const E* __restrict__ W, u64* __restrict__ out,
+                                                 u32* __restrict__ done, volatile u64* __restrict__ post, u64 seq) {
+  E a0 = e32_zero(), a2 = e32_zero();
+  partials256_thread(blockIdx.x, gridDim.x, n, acc, rsq, W, a0, a2);
   a0 = block_sum256(a0, sh);
   a2 = block_sum256(a2, sh);
   if (threadIdx.x == 0) {
     limbs_atomic_add(out, a0);
     limbs_atomic_add(out + 8, a2);
-    s_last = 0;
+    *s_last = 0;
     if (post) {
       __threadfence();
-      s_last = atomicAdd(done, 1u) == gridDim.x - 1 ? 1u : 0u;
+      *s_last = atomicAdd(done, 1u) == gridDim.x - 1 ? 1u : 0u;
     }
   }
   __syncthreads();
-  if (s_last && threadIdx.x < 64) {  // every block's adds are visible (each fenced before its increment); 16 lanes of one wave read,
+  if (*s_last && threadIdx.x < 64) {  // every block's adds are visible (each fenced before its increment); 16 lanes of one wave read,
     if (threadIdx.x < 16) {          // clear and copy one word each (the round trips overlap), lane 0 then publishes
       post[threadIdx.x] = __hip_atomic_exchange(&out[threadIdx.x], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __threadfence_system();
@@ -286,6 +355,23 @@ __global__ __launch_bounds__(Z_THREADS) void partials256_kernel(size_t n, u64* _
       __hip_atomic_store((u64*)&post[16], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
+}
+__global__ __launch_bounds__(Z_THREADS) void partials256_kernel(size_t n, u64* __restrict__ acc, E rsq, const E* __restrict__ W, u64* __restrict__ out,
+                                                                u32* __restrict__ done, volatile u64* __restrict__ post, u64 seq) {
+  __shared__ E sh[Z_THREADS];
+  __shared__ u32 s_last;
+  partials256_body(sh, &s_last, n, acc, rsq, W, out, done, post, seq);
+}
+// statement blockIdx.y (gridDim.x blocks each): its accumulators at acc + y * s_acc words, its hand at W + y * s_w, its 16 sum
+// words at out + 16 y and its block counter done[y]; the block of the statement that finishes last posts to slot y of the pinned
+// batch mailbox (SCB256_SLOT_WORDS words per slot, laid out like the single call's post)
+#define SCB256_SLOT_WORDS 32
+__global__ __launch_bounds__(Z_THREADS) void partials256_batch_kernel(size_t n, u64* __restrict__ acc, size_t s_acc, E rsq, const E* __restrict__ W, size_t s_w,
+                                                                      u64* __restrict__ out, u32* __restrict__ done, volatile u64* __restrict__ post, u64 seq) {
+  __shared__ E sh[Z_THREADS];
+  __shared__ u32 s_last;
+  const size_t b = blockIdx.y;
+  partials256_body(sh, &s_last, n, acc + b * s_acc, rsq, W + b * s_w, out + 16 * b, done + b, post + b * SCB256_SLOT_WORDS, seq);
 }
 
 // out[i] = in[2i] + r (in[2i+1] - in[2i]); tail: in (1 - r)   (dense.h:70-87, affine.h:26-52)
@@ -341,17 +427,10 @@ __global__ __launch_bounds__(1024) void scan256_kernel(u32 nblocks, u32* __restr
   }
   if (threadIdx.x == 0) *total = carry;
 }
-// Dense::bind of the hand that just received its challenge (blocks [0, nbd)) and HQuad::bind_h (the blocks after them) in
-// one launch
-__global__ __launch_bounds__(Z_THREADS) void bind256_kernel(u32 nbd, size_t n0, const E* __restrict__ win, E* __restrict__ wout, size_t n,
-                                                            const uint2* __restrict__ hc, const E* __restrict__ vc, E r, int hand,
-                                                            const u32* __restrict__ block_off, uint2* __restrict__ hc_out, E* __restrict__ vc_out) {
-  __shared__ u32 wave_off[Z_THREADS / 64];
-  if (blockIdx.x < nbd) {
-    dense_bind256((size_t)blockIdx.x * Z_THREADS + threadIdx.x, n0, r, win, wout);
-    return;
-  }
-  const u32 blk = blockIdx.x - nbd;
+// block blk of HQuad::bind_h; WRITE_HC as in bindg_emit256_body.  Every thread of the block must call this.
+template <bool WRITE_HC>
+__device__ __forceinline__ void hquad_bind256_body(u32* wave_off, u32 blk, size_t n, const uint2* __restrict__ hc, const E* __restrict__ vc, const E& r, int hand,
+                                                   const u32* __restrict__ block_off, uint2* __restrict__ hc_out, E* __restrict__ vc_out) {
   const size_t i = (size_t)blk * Z_THREADS + threadIdx.x;
   const bool head = i < n && !is_second256(hc, i, hand);
   const u64 mask = __ballot(head);
@@ -371,8 +450,130 @@ __global__ __launch_bounds__(Z_THREADS) void bind256_kernel(u32 nbd, size_t n0, 
   else v = fp256_mul(v0, r);                                                                                            // ..._z_nz
   if (hand) h.y = hh >> 1;
   else h.x = hh >> 1;
-  hc_out[off] = h;
+  if (WRITE_HC) hc_out[off] = h;
   st32(&vc_out[off], v);
+}
+// Dense::bind of the hand that just received its challenge (blocks [0, nbd)) and HQuad::bind_h (the blocks after them) in
+// one launch
+__global__ __launch_bounds__(Z_THREADS) void bind256_kernel(u32 nbd, size_t n0, const E* __restrict__ win, E* __restrict__ wout, size_t n,
+                                                            const uint2* __restrict__ hc, const E* __restrict__ vc, E r, int hand,
+                                                            const u32* __restrict__ block_off, uint2* __restrict__ hc_out, E* __restrict__ vc_out) {
+  __shared__ u32 wave_off[Z_THREADS / 64];
+  if (blockIdx.x < nbd) {
+    dense_bind256((size_t)blockIdx.x * Z_THREADS + threadIdx.x, n0, r, win, wout);
+    return;
+  }
+  hquad_bind256_body<true>(wave_off, blockIdx.x - nbd, n, hc, vc, r, hand, block_off, hc_out, vc_out);
+}
+// statement blockIdx.y with its challenge ch.r[y] (kernel arguments: 2 KiB at LFGPU_SC_BATCH_MAX statements): its hand at
+// win + y * s_in -> wout + y * s_out, its HQUAD values at vc + y * s_vc -> vc_out + y * s_vc; the corners and the recorded
+// offsets are shared, statement 0 writes the bound corners
+struct Chal256 {
+  E r[LFGPU_SC_BATCH_MAX];
+};
+__global__ __launch_bounds__(Z_THREADS) void bind256_batch_kernel(u32 nbd, size_t n0, const E* __restrict__ win, size_t s_in, E* __restrict__ wout, size_t s_out,
+                                                                  size_t n, const uint2* __restrict__ hc, const E* __restrict__ vc, size_t s_vc, Chal256 ch, int hand,
+                                                                  const u32* __restrict__ block_off, uint2* __restrict__ hc_out, E* __restrict__ vc_out) {
+  __shared__ u32 wave_off[Z_THREADS / 64];
+  const size_t b = blockIdx.y;
+  const E r = ch.r[b];
+  if (blockIdx.x < nbd) {
+    dense_bind256((size_t)blockIdx.x * Z_THREADS + threadIdx.x, n0, r, win + b * s_in, wout + b * s_out);
+    return;
+  }
+  if (b == 0) hquad_bind256_body<true>(wave_off, blockIdx.x - nbd, n, hc, vc, r, hand, block_off, hc_out, vc_out);
+  else hquad_bind256_body<false>(wave_off, blockIdx.x - nbd, n, hc, vc + b * s_vc, r, hand, block_off, hc_out, vc_out + b * s_vc);
+}
+
+// ---- one round-hand of a batch in ONE launch once the HQUAD and both hand arrays have <= SCB256_SMALL_MAX entries: workgroup
+// y = statement y does the pending Dense::bind + HQuad::bind_h with the previous challenge, the QW scatter, the two sums and its
+// post, with block barriers between the phases.  The scatter's limb accumulators and the bound corners stay in LDS from one
+// phase to the next; the bound values and hand array go to the statement's device arrays, which the next step starts from.
+// The bound: LDS holds 64 bytes of accumulators and 8 bytes of corners per entry next to the 8 KiB of the block sum, and a
+// workgroup may take 160 KiB: 72 N + 8 KiB <= 160 KiB gives N <= 2161, and 2048 is the largest power of two below that.
+// The arithmetic is the bodies above, block by block, so every statement gets the bytes of the three-launch path.
+#define SCB256_SMALL_MAX LFGPU_P256_BATCH_SMALL_MAX  // 2048 (lfgpu.h)
+static_assert(SCB256_SMALL_MAX * 72 + Z_THREADS * 32 + 64 <= 160 * 1024, "the fused step's LDS: accumulators, corners, block sum");
+#define SCB256_SMALL_LDS ((size_t)SCB256_SMALL_MAX * 72)
+struct Small256 {
+  int do_bind, bind_hand, do_eval, eval_hand;
+  const uint2* hc_in;  // shared corners before the bind
+  uint2* hc_out;       // ... after it (statement 0 writes them)
+  const E* vc_in;      // HQUAD values, statement y at + y * s_vc
+  E* vc_out;
+  size_t s_vc;
+  u32 nh, nh_out;  // HQUAD size before / after the bind (host-known: a circuit constant)
+  const E* W[2];   // hand arrays before the bind, statement y at + y * s_W[h]
+  size_t s_W[2];
+  u32 nW[2];
+  E* Wdst;  // destination of the dense bind, statement y at + y * s_Wdst
+  size_t s_Wdst;
+  const u32* block_off;  // the recorded offsets of the bind's round-hand
+  E rsq;
+};
+__global__ __launch_bounds__(Z_THREADS) void sc_small_step_batch256_kernel(Small256 a, Chal256 ch, volatile u64* __restrict__ post, u64 seq) {
+  extern __shared__ __attribute__((aligned(16))) u64 s_dyn[];
+  __shared__ E sh[Z_THREADS];
+  __shared__ u32 wave_off[Z_THREADS / 64];
+  u64* qw = s_dyn;                                       // 8 words per target
+  uint2* s_hc = (uint2*)(s_dyn + 8 * SCB256_SMALL_MAX);  // the corners after the bind
+  const size_t b = blockIdx.x;
+  const uint2* hc = a.hc_in;
+  const E* vc = a.vc_in + b * a.s_vc;
+  u32 nh = a.nh;
+  const E* W[2] = {a.W[0] + b * a.s_W[0], a.W[1] + b * a.s_W[1]};
+  u32 nW[2] = {a.nW[0], a.nW[1]};
+  if (a.do_bind) {
+    const E r = ch.r[b];
+    const int h = a.bind_hand;
+    E* dst = a.Wdst + b * a.s_Wdst;
+    E* vco = a.vc_out + b * a.s_vc;
+    for (u32 blk = 0; (size_t)blk * Z_THREADS < (nW[h] + 1) / 2; ++blk) dense_bind256((size_t)blk * Z_THREADS + threadIdx.x, nW[h], r, W[h], dst);
+    for (u32 blk = 0; (size_t)blk * Z_THREADS < nh; ++blk) {  // block-uniform trip count: the body holds a barrier
+      hquad_bind256_body<true>(wave_off, blk, nh, hc, vc, r, h, a.block_off, s_hc, vco);
+      __syncthreads();  // wave_off is free again; after the last block: everything bound is visible to the workgroup
+    }
+    __threadfence_block();
+    __syncthreads();
+    nh = nh ? a.nh_out : 0;
+    if (b == 0)
+      for (u32 i = threadIdx.x; i < nh; i += Z_THREADS) a.hc_out[i] = s_hc[i];
+    hc = s_hc;
+    vc = vco;
+    W[h] = dst;
+    nW[h] = (nW[h] + 1) / 2;
+  }
+  if (!a.do_eval) return;
+  const int h = a.eval_hand;
+  for (u32 i = threadIdx.x; i < 8 * nW[h]; i += Z_THREADS) qw[i] = 0;
+  __syncthreads();
+  for (u32 blk = 0; (size_t)blk * Z_THREADS < nh; ++blk) qw_scatter256_body(blk, nh, hc, vc, h, W[1 - h], qw);
+  __syncthreads();
+  E a0 = e32_zero(), a2 = e32_zero();
+  partials256_thread(0, 1, nW[h], qw, a.rsq, W[h], a0, a2);
+  a0 = block_sum256(a0, sh);
+  a2 = block_sum256(a2, sh);
+  if (threadIdx.x < 64) {  // the sums as the 16 limb words the three-launch path posts; lane 0 then publishes
+    volatile u64* slot = post + b * SCB256_SLOT_WORDS;
+    if (threadIdx.x < 16) {
+      u64 l = 0;
+#pragma unroll
+      for (u32 k = 0; k < 4; ++k)
+        if (((threadIdx.x & 7) >> 1) == k) l = threadIdx.x < 8 ? a0.l[k] : a2.l[k];
+      slot[threadIdx.x] = (threadIdx.x & 1) ? l >> 32 : (u64)(u32)l;
+      __threadfence_system();
+    }
+    if (threadIdx.x == 0) __hip_atomic_store((u64*)&slot[16], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
+}
+// out[3 y + 0 / 1 / 2] = statement y's W[0][0], W[1][0] and HQUAD scalar at the end of a layer
+__global__ __launch_bounds__(Z_THREADS) void readout256_batch_kernel(u32 nb, const E* __restrict__ W0, size_t s0, const E* __restrict__ W1, size_t s1,
+                                                                     const E* __restrict__ vc, size_t s_vc, E* __restrict__ out) {
+  const u32 t = threadIdx.x;
+  if (t >= 3 * nb) return;
+  const size_t b = t / 3;
+  const u32 k = t % 3;
+  st32(&out[t], ld32(k == 0 ? &W0[b * s0] : k == 1 ? &W1[b * s1] : &vc[b * s_vc]));
 }
 
 // ---- the rest of a layer in ONE launch of co-resident workgroups (what sc_grid_layer_kernel is for the 16-byte fields,
@@ -1192,6 +1393,28 @@ int raw_eq2_256(lfgpu_ctx* c, const F256& F, size_t logn, size_t n, const E* G0,
 
 typedef void (*round256_fn)(void* user, size_t hand, size_t rnd, const E ev[3], E* chal);
 
+// The merge structure of HQuad::bind_h at round-hand rh (per-block output offsets + the size after the bind) is a circuit
+// constant: counted from the corners `hc` (nh entries) by the first call that reaches the round-hand on a per-launch path, kept
+// with the quad from then on.  The single and the batched layer both record through here, so either may run first on a quad.
+int bind_shape256(lfgpu_quad* q, size_t rh, size_t nh, const uint2* hc, int hand) {
+  lfgpu_ctx* c = q->c;
+  if (q->bind_shape.size() <= rh) q->bind_shape.resize(rh + 1, lfgpu_quad::BindShape{nullptr, 0, 0});
+  lfgpu_quad::BindShape& bs = q->bind_shape[rh];
+  if (!nh || (bs.d_off && bs.n_in == nh)) return LFGPU_OK;
+  const u32 nbh = nblk(nh);
+  if (bs.d_off) (void)hipFree(bs.d_off);
+  bs = lfgpu_quad::BindShape{nullptr, nh, 0};
+  if (hipMalloc((void**)&bs.d_off, (size_t)nbh * 4) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "sumcheck_layer256: bind offsets");
+  u32* total = (u32*)((uint8_t*)c->mailbox_d + 64);
+  hipLaunchKernelGGL(hquad_count256_kernel, dim3(nbh), dim3(Z_THREADS), 0, c->stream, nh, hc, hand, bs.d_off);
+  hipLaunchKernelGGL(scan256_kernel, dim3(1), dim3(1024), 0, c->stream, nbh, bs.d_off, total);
+  u32 tot = 0;
+  LF_HIP(c, hipMemcpyAsync(&tot, total, 4, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  bs.n_out = tot;
+  return LFGPU_OK;
+}
+
 // One layer of the sumcheck (ProverLayers::layer): bind_g, then per round and hand the QW scatter, the two partial sums
 // (one read-back), the caller's transcript step, Dense::bind and HQuad::bind_h.  d_W (the layer's inputs) is left intact:
 // both hands bind into ping-pong buffers.
@@ -1424,20 +1647,9 @@ int sumcheck_layer256(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, co
       sum = F.eval_lagrange(ev, r);
       // Dense::bind of this hand + HQuad::bind_h: one launch.  The merge structure of a round-hand is a circuit constant:
       // counted at the first proof, kept with the layer from then on
-      lfgpu_quad::BindShape& bs = q->bind_shape[2 * rnd + hand];
       const u32 nbh = nh ? nblk(nh) : 0, nbd = nblk((nW[hand] + 1) / 2);
-      if (nh && !(bs.d_off && bs.n_in == nh)) {
-        if (bs.d_off) (void)hipFree(bs.d_off);
-        bs = lfgpu_quad::BindShape{nullptr, nh, 0};
-        if (hipMalloc((void**)&bs.d_off, (size_t)nbh * 4) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "sumcheck_layer256: bind offsets");
-        u32* total = (u32*)((uint8_t*)c->mailbox_d + 64);
-        hipLaunchKernelGGL(hquad_count256_kernel, dim3(nbh), dim3(Z_THREADS), 0, c->stream, nh, (const uint2*)hc[cur], hand, bs.d_off);
-        hipLaunchKernelGGL(scan256_kernel, dim3(1), dim3(1024), 0, c->stream, nbh, bs.d_off, total);
-        u32 tot = 0;
-        LF_HIP(c, hipMemcpyAsync(&tot, total, 4, hipMemcpyDeviceToHost, c->stream));
-        LF_HIP(c, hipStreamSynchronize(c->stream));
-        bs.n_out = tot;
-      }
+      LF_TRY(bind_shape256(q, 2 * rnd + hand, nh, hc[cur], hand));
+      lfgpu_quad::BindShape& bs = q->bind_shape[2 * rnd + hand];
       E* dst = wb[hand][wsel[hand]];
       hipLaunchKernelGGL(bind256_kernel, dim3(nbd + nbh), dim3(Z_THREADS), 0, c->stream, nbd, nW[hand], WH[hand], dst, nh, (const uint2*)hc[cur],
                          (const E*)vc[cur], r, hand, (const u32*)bs.d_off, hc[1 - cur], vc[1 - cur]);
@@ -1461,7 +1673,338 @@ int sumcheck_layer256(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, co
   if (bound_quad) *bound_quad = h_out[2];
   return LFGPU_OK;
 }
+
+// ------------------------------------------------------------------ the batch axis (K14 over Fp256Base)
+typedef void (*round_batch256_fn)(void* user, size_t hand, size_t rnd, size_t nb, const uint64_t (*ev)[3][4], uint64_t (*chal)[4]);
+
+int scb256_mailbox(lfgpu_ctx* c) {
+  if (c->sc_batch256_h) return LFGPU_OK;
+  void* p = nullptr;
+  const size_t bytes = (size_t)LFGPU_SC_BATCH_MAX * SCB256_SLOT_WORDS * 8;
+  if (hipHostMalloc(&p, bytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
+    (void)hipGetLastError();
+    return lf_fail(c, LFGPU_ERR_NOMEM, "sumcheck_layer_batch256: the pinned mailbox");
+  }
+  memset(p, 0, bytes);
+  c->sc_batch256_h = (volatile u64*)p;
+  return LFGPU_OK;
+}
+// one spin for all B slots (lf_scb_wait, sumcheck.hip: the stream is looked at after 50 ms without a post)
+int scb256_wait(lfgpu_ctx* c, size_t B, u64 seq) {
+  volatile u64* const mb = c->sc_batch256_h;
+  u64 spins = 0;
+  double t_first = 0;
+  for (size_t b = 0; b < B;) {
+    const u64* w = (const u64*)&mb[b * SCB256_SLOT_WORDS + 16];
+    if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == seq) {
+      ++b;
+      continue;
+    }
+    if (spins > 0x8000 && (spins & 0xff) == 0) sched_yield();
+    if ((++spins & 0xfff) == 0) {
+      const double t = now_ms();
+      if (t_first == 0) t_first = t;
+      if (t - t_first < 50.0) continue;
+      const hipError_t qe = hipStreamQuery(c->stream);
+      if (qe == hipSuccess) {  // the kernel is over: every post must be visible now
+        if (__atomic_load_n(w, __ATOMIC_ACQUIRE) == seq) continue;
+        return lf_fail(c, LFGPU_ERR_ASSERT, "sumcheck_layer_batch256: kernel finished without posting statement %zu", b);
+      }
+      if (qe != hipErrorNotReady) return lf_fail(c, LFGPU_ERR_HIP, "sumcheck_layer_batch256: %s", hipGetErrorString(qe));
+    }
+  }
+  return LFGPU_OK;
+}
+
+// Eqs::raw_eq2 of B point sets in one upload and one launch chain.  The uploaded table holds, per statement, the 4 logn
+// elements of raw_eq2_256 followed by alpha and beta (gs = 4 logn + 2 elements); it stays in scratch2 for the batched bind_g,
+// which reads beta from it.  *d_pts_out: the device table.
+int raw_eq2_256_batch(lfgpu_ctx* c, const F256& F, size_t B, size_t logn, size_t n, const E* G0, const E* G1, const E* alpha, const E* beta, E* d_eq,
+                      const E** d_pts_out) {
+  const size_t gs = 4 * logn + 2;
+  std::vector<E> Gt(B * gs);
+  for (size_t b = 0; b < B; ++b) {
+    E* g = &Gt[b * gs];
+    for (size_t l = 0; l < logn; ++l) {
+      g[l] = G0[b * logn + l];
+      g[logn + l] = G1[b * logn + l];
+      g[2 * logn + l] = F.sub(F.one, G0[b * logn + l]);
+      g[3 * logn + l] = F.sub(F.one, G1[b * logn + l]);
+    }
+    g[4 * logn] = alpha[b];
+    g[4 * logn + 1] = beta[b];
+  }
+  const u32 lb = (u32)(logn / 2), hb = (u32)logn - lb;
+  const size_t ntab = 2 * (((size_t)1 << lb) + ((size_t)1 << hb));
+  void* d_G = nullptr;
+  LF_TRY(lf_scratch2(c, B * (gs + ntab) * 32 + 64, &d_G));
+  E* d_tab = (E*)d_G + B * gs;
+  LF_HIP(c, hipMemcpyAsync(d_G, Gt.data(), Gt.size() * 32, hipMemcpyHostToDevice, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));  // Gt is a local
+  *d_pts_out = (const E*)d_G;
+  if (n == 0) return LFGPU_OK;
+  if (logn < 6) {
+    hipLaunchKernelGGL(raw_eq2_256_batch_kernel, dim3(nblk(n), (u32)B), dim3(Z_THREADS), 0, c->stream, (u32)logn, (u32)n, (const E*)d_G, gs, F.one, d_eq);
+  } else {
+    hipLaunchKernelGGL(eq_tables256_batch_kernel, dim3(nblk(ntab), (u32)B), dim3(Z_THREADS), 0, c->stream, (u32)logn, lb, (const E*)d_G, gs, F.one, d_tab, ntab);
+    hipLaunchKernelGGL(raw_eq2_split256_batch_kernel, dim3(nblk(n), (u32)B), dim3(Z_THREADS), 0, c->stream, (u32)logn, lb, (u32)n, (const E*)d_tab, ntab, d_eq);
+  }
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+// sumcheck_layer256 for B statements of one quad in lock-step.  Only the values (vc), the hand arrays, the accumulators and the
+// sums carry a statement stride; the corners, the merge structure and the recorded bind shapes are the circuit's.  No resident
+// grid: above SCB256_SMALL_MAX a round-hand is three launches of B times the single call's blocks, at or below it one launch
+// of B workgroups (LFGPU_P256_BATCH_SMALL = 0: three launches throughout).  d_W is left intact.
+int sumcheck_layer_batch256(lfgpu_quad* q, const F256& F, size_t B, size_t logv, const E* G0, const E* G1, const E* alpha, const E* beta, size_t logw, size_t nw,
+                            const E* d_W, size_t ldw, const E* wc_in /*[B][2]*/, round_batch256_fn round, void* user, E* wc_out /*[B][2]*/,
+                            E* g_out /*[B][2][logw]*/, E* bound_quad /*[B] or nullptr*/) {
+  lfgpu_ctx* c = q->c;
+  const size_t nt = q->n, nh0 = q->nh0, half = (nw + 1) / 2, nv = q->nv;
+  const size_t acc_n = std::max(nh0, nw);
+  // scratch per statement: eq | limb accumulators (64 bytes per entry) | 2 HQUAD value arrays | 4 half hand buffers | sums;
+  // shared: the two corner arrays
+  const size_t per = nv * 32 + acc_n * 64 + 2 * nh0 * 32 + 4 * half * 32 + 16 * 8 + 64 + 3 * 32;
+  if ((acc_n >> 32) || per > ((size_t)1 << 40) / B) return lf_fail(c, LFGPU_ERR_NOMEM, "sumcheck_layer_batch256: %zu bytes of scratch per statement, %zu statements", per, B);
+  void* sc = nullptr;
+  LF_TRY(lf_scratch(c, B * per + 2 * nh0 * 8 + 1024, &sc));
+  LF_TRY(scb256_mailbox(c));
+  volatile u64* const mb = c->sc_batch256_h;
+  uint8_t* p = (uint8_t*)sc;
+  E* d_eq = (E*)p;                      p += B * nv * 32;
+  u64* acc = (u64*)p;                   p += B * acc_n * 64;
+  E* vc[2] = {(E*)p, (E*)p + B * nh0};  p += 2 * B * nh0 * 32;
+  E* wb[2][2];
+  for (int k = 0; k < 4; ++k) {
+    wb[k >> 1][k & 1] = (E*)p;
+    p += B * half * 32;
+  }
+  E* d_out = (E*)p;                     p += B * 3 * 32;
+  u64* d_sums = (u64*)p;                p += B * 16 * 8;
+  u32* d_done = (u32*)p;                p += B * 64;
+  uint2* hc[2] = {(uint2*)p, (uint2*)p + nh0};
+  const size_t s_acc = acc_n * 8;  // words between two statements' accumulators
+  // Quad::bind_g of all statements: the EQ vectors, the runs, their normalisation
+  const E* d_pts = nullptr;
+  LF_TRY(raw_eq2_256_batch(c, F, B, logv, nv, G0, G1, alpha, beta, d_eq, &d_pts));
+  LF_HIP(c, hipMemsetAsync(acc, 0, B * acc_n * 64, c->stream));
+  LF_HIP(c, hipMemsetAsync(d_sums, 0, B * (16 * 8 + 64), c->stream));  // the sum words + the block counters
+  hipLaunchKernelGGL(bindg_emit256_batch_kernel, dim3(nblk(nt, BG_THREADS), (u32)B), dim3(BG_THREADS), 0, c->stream, nt, (const corner4*)q->d_morton,
+                     (const E*)q->d_kvec, (const E*)d_eq, nv, d_pts, 4 * logv + 2, (u32)(4 * logv + 1), (const u32*)q->d_runoff, hc[0], acc, s_acc);
+  hipLaunchKernelGGL(limb_normalize256_batch_kernel, dim3(nblk(nh0), (u32)B), dim3(Z_THREADS), 0, c->stream, nh0, acc, s_acc, F.rsq, vc[0], nh0);
+  LF_HIP(c, hipGetLastError());
+  size_t nh = nh0;
+  int cur = 0;
+  std::vector<E> sum(B);
+  for (size_t b = 0; b < B; ++b) sum[b] = F.add(wc_in[2 * b], F.mul(alpha[b], wc_in[2 * b + 1]));
+  const E* WH[2] = {d_W, d_W};
+  size_t sW[2] = {ldw, ldw};
+  size_t nW[2] = {nw, nw};
+  int wsel[2] = {0, 0};
+  // LFGPU_P256_BATCH_SMALL [1]: 0 = three launches per round-hand throughout (A/B: the same bytes)
+  static const int small_env = getenv("LFGPU_P256_BATCH_SMALL") ? atoi(getenv("LFGPU_P256_BATCH_SMALL")) : 1;
+  if (small_env && !(c->attr_done & 32u)) {
+    LF_HIP(c, hipFuncSetAttribute((const void*)sc_small_step_batch256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)SCB256_SMALL_LDS));
+    c->attr_done |= 32u;
+  }
+  Chal256 ch{};
+  bool pending = false;  // the binds of round-hand prh with the challenges in ch ride at the head of the next fused step
+  size_t prh = 0;
+  // the fused step: [pending binds] + [scatter, sums and post of eval_hand]
+  auto small_step = [&](int do_eval, int eval_hand, u64 seq) -> int {
+    Small256 a{};
+    a.do_bind = pending ? 1 : 0;
+    a.do_eval = do_eval;
+    a.eval_hand = eval_hand;
+    a.hc_in = hc[cur];
+    a.vc_in = vc[cur];
+    a.s_vc = nh0;
+    a.nh = (u32)nh;
+    for (int k = 0; k < 2; ++k) {
+      a.W[k] = WH[k];
+      a.s_W[k] = sW[k];
+      a.nW[k] = (u32)nW[k];
+    }
+    a.rsq = F.rsq;
+    int ph = 0;
+    if (pending) {
+      ph = (int)(prh & 1);
+      LF_TRY(bind_shape256(q, prh, nh, hc[cur], ph));
+      const lfgpu_quad::BindShape& bs = q->bind_shape[prh];
+      a.bind_hand = ph;
+      a.hc_out = hc[1 - cur];
+      a.vc_out = vc[1 - cur];
+      a.nh_out = (u32)bs.n_out;
+      a.block_off = bs.d_off;
+      a.Wdst = wb[ph][wsel[ph]];
+      a.s_Wdst = half;
+    }
+    hipLaunchKernelGGL(sc_small_step_batch256_kernel, dim3((u32)B), dim3(Z_THREADS), SCB256_SMALL_LDS, c->stream, a, ch, mb, seq);
+    LF_HIP(c, hipGetLastError());
+    if (pending) {
+      WH[ph] = a.Wdst;
+      sW[ph] = half;
+      wsel[ph] ^= 1;
+      nW[ph] = (nW[ph] + 1) / 2;
+      if (nh) {
+        nh = a.nh_out;
+        cur = 1 - cur;
+      }
+      pending = false;
+    }
+    return LFGPU_OK;
+  };
+  std::vector<uint64_t> evw(B * 12), rr(B * 4);
+  std::vector<E> ev(3 * B);
+  for (size_t rnd = 0; rnd < logw; ++rnd)
+    for (int hand = 0; hand < 2; ++hand) {
+      const bool fused = small_env && std::max(nh, std::max(nW[0], nW[1])) <= SCB256_SMALL_MAX;
+      const u64 seq = ++c->poll_seq;
+      if (fused) {
+        LF_TRY(small_step(1, hand, seq));
+      } else {
+        if (nh) hipLaunchKernelGGL(qw_scatter256_batch_kernel, dim3(nblk(nh), (u32)B), dim3(Z_THREADS), 0, c->stream, nh, (const uint2*)hc[cur], (const E*)vc[cur], nh0,
+                                   hand, WH[1 - hand], sW[1 - hand], acc, s_acc);
+        hipLaunchKernelGGL(partials256_batch_kernel, dim3(std::min<u32>(nblk(nW[hand] / 2), 256), (u32)B), dim3(Z_THREADS), 0, c->stream, nW[hand], acc, s_acc, F.rsq,
+                           WH[hand], sW[hand], d_sums, d_done, mb, seq);
+        LF_HIP(c, hipGetLastError());
+      }
+      LF_TRY(scb256_wait(c, B, seq));
+      // per statement as in sumcheck_layer256: coef[0] = a0, coef[2] = a2, coef[1] from the running sum
+      for (size_t b = 0; b < B; ++b) {
+        u64 w[16];
+        for (int k = 0; k < 16; ++k) w[k] = mb[b * SCB256_SLOT_WORDS + k];
+        E coef[3];
+        coef[0] = fp256_reduce_limbs(w, F.rsq);
+        coef[2] = fp256_reduce_limbs(w + 8, F.rsq);
+        coef[1] = F.sub(F.sub(F.sub(sum[b], coef[0]), coef[0]), coef[2]);
+        for (int k = 0; k < 3; ++k) {
+          ev[3 * b + k] = F.eval_monomial(coef, F.pts[k]);
+          memcpy(&evw[12 * b + 4 * k], ev[3 * b + k].l, 32);
+        }
+      }
+      round(user, (size_t)hand, rnd, B, (const uint64_t(*)[3][4])evw.data(), (uint64_t(*)[4])rr.data());
+      for (size_t b = 0; b < B; ++b) {
+        E r;
+        memcpy(r.l, &rr[4 * b], 32);
+        g_out[(b * 2 + hand) * logw + rnd] = r;
+        sum[b] = F.eval_lagrange(&ev[3 * b], r);
+        ch.r[b] = r;
+      }
+      if (fused) {
+        pending = true;
+        prh = 2 * rnd + hand;
+        continue;
+      }
+      // Dense::bind of this hand + HQuad::bind_h of all statements: one launch
+      const u32 nbh = nh ? nblk(nh) : 0, nbd = nblk((nW[hand] + 1) / 2);
+      LF_TRY(bind_shape256(q, 2 * rnd + hand, nh, hc[cur], hand));
+      const lfgpu_quad::BindShape& bs = q->bind_shape[2 * rnd + hand];
+      E* dst = wb[hand][wsel[hand]];
+      hipLaunchKernelGGL(bind256_batch_kernel, dim3(nbd + nbh, (u32)B), dim3(Z_THREADS), 0, c->stream, nbd, nW[hand], WH[hand], sW[hand], dst, half, nh,
+                         (const uint2*)hc[cur], (const E*)vc[cur], nh0, ch, hand, (const u32*)bs.d_off, hc[1 - cur], vc[1 - cur]);
+      LF_HIP(c, hipGetLastError());
+      WH[hand] = dst;
+      sW[hand] = half;
+      wsel[hand] ^= 1;
+      nW[hand] = (nW[hand] + 1) / 2;
+      if (nh) {
+        nh = bs.n_out;
+        cur = 1 - cur;
+      }
+    }
+  if (pending) LF_TRY(small_step(0, 0, 0));  // the last binds
+  if (nh != 1) return lf_fail(c, LFGPU_ERR_ASSERT, "sumcheck_layer_batch256: HQUAD did not fold to one entry (%zu)", nh);
+  hipLaunchKernelGGL(readout256_batch_kernel, dim3(1), dim3(Z_THREADS), 0, c->stream, (u32)B, WH[0], sW[0], WH[1], sW[1], (const E*)vc[cur], nh0, d_out);
+  LF_HIP(c, hipGetLastError());
+  std::vector<E> h_out(3 * B);
+  LF_HIP(c, hipMemcpyAsync(h_out.data(), d_out, 3 * B * 32, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b < B; ++b) {
+    wc_out[2 * b] = h_out[3 * b];
+    wc_out[2 * b + 1] = h_out[3 * b + 1];
+    if (bound_quad) bound_quad[b] = h_out[3 * b + 2];
+  }
+  return LFGPU_OK;
+}
 }  // namespace
+
+// ------------------------------------------------------------------ the sumcheck layer of Fp256Base behind the kernel ABI
+static_assert(LFGPU_SC_BATCH_MAX * 3 <= Z_THREADS, "readout256_batch_kernel: one block reads all statements out");
+static inline E e_of(const uint64_t* w) {
+  E e;
+  memcpy(e.l, w, 32);
+  return e;
+}
+static inline std::vector<E> es_of(const void* w, size_t n) {
+  std::vector<E> v(n + 1);
+  if (n) memcpy((void*)v.data(), w, n * 32);
+  return v;
+}
+namespace {
+struct Tramp256 {
+  lfgpu_sc_round256_fn fn;
+  void* user;
+};
+void tramp256_cb(void* u, size_t hand, size_t rnd, const E ev[3], E* chal) {
+  const Tramp256* t = (const Tramp256*)u;
+  uint64_t e[3][4], r[4];
+  for (int k = 0; k < 3; ++k) memcpy(e[k], ev[k].l, 32);
+  t->fn(t->user, hand, rnd, e, r);
+  memcpy(chal->l, r, 32);
+}
+}  // namespace
+
+extern "C" int lfgpu_sumcheck_layer256(lfgpu_quad* q, size_t logv, const void* h_G0, const void* h_G1, const uint64_t alpha[4], const uint64_t beta[4],
+                                       size_t logw, size_t nw, const void* d_W, const uint64_t wc_in[2][4], lfgpu_sc_round256_fn round, void* user,
+                                       uint64_t wc_out[2][4], uint64_t* g_out, uint64_t bound_quad[4]) {
+  if (!q) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = q->c;
+  if (!alpha || !beta || !d_W || !wc_in || !round || !wc_out || (logw && !g_out) || (logv && (!h_G0 || !h_G1)))
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer256: null argument");
+  if (q->field != LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer256: the quad is over a 16-byte field (lfgpu_sumcheck_layer)");
+  LF_HIP(c, hipSetDevice(c->device));
+  const F256 F;
+  const E wi[2] = {e_of(wc_in[0]), e_of(wc_in[1])};
+  E wo[2], bq;
+  Tramp256 t{round, user};
+  // the caller's arrays are words (8-byte aligned), the elements want 16: everything crosses the boundary by copy
+  const std::vector<E> G0 = es_of(h_G0, logv), G1 = es_of(h_G1, logv);
+  std::vector<E> g(2 * logw + 1);
+  LF_TRY(sumcheck_layer256(q, F, logv, G0.data(), G1.data(), e_of(alpha), e_of(beta), logw, nw, (const E*)d_W, wi, tramp256_cb, &t, wo, g.data(), &bq));
+  if (logw) memcpy(g_out, g.data(), 2 * logw * 32);
+  memcpy(wc_out[0], wo[0].l, 32);
+  memcpy(wc_out[1], wo[1].l, 32);
+  if (bound_quad) memcpy(bound_quad, bq.l, 32);
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_sumcheck_layer_batch256(lfgpu_quad* q, size_t nb, size_t logv, const void* h_G0, const void* h_G1, const uint64_t* alpha,
+                                             const uint64_t* beta, size_t logw, size_t nw, const void* d_W, size_t ldw, const uint64_t* wc_in,
+                                             lfgpu_sc_round_batch256_fn round, void* user, uint64_t* wc_out, uint64_t* g_out, uint64_t* bound_quad) {
+  if (!q) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = q->c;
+  if (!alpha || !beta || !d_W || !wc_in || !round || !wc_out || (logw && !g_out) || (logv && (!h_G0 || !h_G1)))
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch256: null argument");
+  if (q->field != LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch256: the quad is over a 16-byte field (lfgpu_sumcheck_layer_batch)");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch256: nb must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (nw == 0 || logw > 40 || nw > ((size_t)1 << logw) || nw <= q->hmax)
+    return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch256: nw = %zu must exceed the largest hand index %zu and fit 2^logw", nw, q->hmax);
+  if (ldw < nw || ((ldw * nb) >> 40)) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch256: ldw = %zu < nw = %zu", ldw, nw);
+  if (logv > 40 || ((size_t)1 << logv) < q->nv) return lf_fail(c, LFGPU_ERR_ARG, "sumcheck_layer_batch256: 2^logv < nv");
+  LF_HIP(c, hipSetDevice(c->device));
+  const F256 F;
+  static_assert(sizeof(E) == 32, "the ABI's [4] words are an element");
+  const std::vector<E> G0 = es_of(h_G0, nb * logv), G1 = es_of(h_G1, nb * logv), al = es_of(alpha, nb), be = es_of(beta, nb), wi = es_of(wc_in, 2 * nb);
+  std::vector<E> wo(2 * nb), g(2 * nb * logw + 1), bq(nb);
+  LF_TRY(sumcheck_layer_batch256(q, F, nb, logv, G0.data(), G1.data(), al.data(), be.data(), logw, nw, (const E*)d_W, ldw, wi.data(), round, user, wo.data(),
+                                 g.data(), bq.data()));
+  memcpy(wc_out, wo.data(), 2 * nb * 32);
+  if (logw) memcpy(g_out, g.data(), 2 * nb * logw * 32);
+  if (bound_quad) memcpy(bound_quad, bq.data(), nb * 32);
+  return LFGPU_OK;
+}
 
 int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail) {
   lfgpu_ctx* c = q->c;
@@ -1472,6 +2015,33 @@ int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail
                      (u64*)acc, d_fail);
   hipLaunchKernelGGL(limb_normalize256_kernel, dim3(nblk(q->nv)), dim3(Z_THREADS), 0, c->stream, q->nv, (u64*)acc, h256_rsq(), (E*)d_V);
   LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+// ProverLayers::eval_quad for nb statements of one quad: two launches whatever nb; 64 bytes of limb accumulators per output and
+// statement, so no two statements share one
+extern "C" int lfgpu_eval_quad_batch256(lfgpu_quad* q, size_t nb, size_t nw, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* ok_out) {
+  if (!q) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = q->c;
+  if (!d_W || !d_V || !ok_out) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch256: null argument");
+  if (q->field != LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch256: the quad is over a 16-byte field (lfgpu_eval_quad_batch)");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch256: nb must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (nw <= q->hmax || ldw < nw || ldv < q->nv || ((ldw * nb) >> 40) || ((ldv * nb) >> 40))
+    return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch256: nw = %zu (a corner reads wire %zu), ldw = %zu, ldv = %zu (nv = %zu)", nw, q->hmax, ldw, ldv, q->nv);
+  if ((q->nv * 64) > ((size_t)1 << 40) / nb) return lf_fail(c, LFGPU_ERR_NOMEM, "eval_quad_batch256: %zu bytes of accumulators per statement", q->nv * 64);
+  LF_HIP(c, hipSetDevice(c->device));
+  void* acc = nullptr;
+  LF_TRY(lf_scratch2(c, nb * q->nv * 64 + 64, &acc));
+  int* d_fail = (int*)((uint8_t*)c->mailbox_d + LF_EVALB_FAIL_OFF);
+  LF_HIP(c, hipMemsetAsync(d_fail, 0, nb * 4, c->stream));
+  LF_HIP(c, hipMemsetAsync(acc, 0, nb * q->nv * 64, c->stream));
+  hipLaunchKernelGGL(eval_quad256_batch_kernel, dim3(nblk(q->n), (u32)nb), dim3(Z_THREADS), 0, c->stream, q->n, (const corner4*)q->d_bygate, (const E*)q->d_kvec,
+                     (const E*)d_W, ldw, (u64*)acc, q->nv * 8, d_fail);
+  hipLaunchKernelGGL(limb_normalize256_batch_kernel, dim3(nblk(q->nv), (u32)nb), dim3(Z_THREADS), 0, c->stream, q->nv, (u64*)acc, q->nv * 8, h256_rsq(), (E*)d_V, ldv);
+  LF_HIP(c, hipGetLastError());
+  LF_HIP(c, hipMemcpyAsync(c->mailbox_h, d_fail, nb * 4, hipMemcpyDeviceToHost, c->stream));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  for (size_t b = 0; b < nb; ++b) ok_out[b] = ((const int*)c->mailbox_h)[b] ? 0 : 1;
   return LFGPU_OK;
 }
 
