@@ -56,7 +56,9 @@ extern "C" {
                               images.  The other Ligero entry points refuse the field, or a prover made over it, on the host
                               before any launch: commit_batch, commit_sharded, layout_rows_sharded, encode_rows,
                               prover_from_slab, dot_proof_sparse (LFGPU_ERR_ARG); inner_product_rows, prove_batch, open_batch
-                              (LFGPU_ERR_UNSUPPORTED).  The per-step
+                              (LFGPU_ERR_UNSUPPORTED; an Fp256Base prover takes lfgpu_ligero_prove_batch256 /
+                              lfgpu_ligero_open_batch256, and lfgpu_zk_batch256_new / lfgpu_zk_prove_batch256 in lfgpu_zk.h
+                              are the batched prover of such a circuit).  The per-step
                               sumcheck entry points below (partials, scatter, binds, bind_g, sumcheck_layer) take the
                               16-byte fields only: for Fp256Base those steps run inside lfgpu_zk_prove / lfgpu_zk_verify, and
                               the whole layer has entry points of its own: lfgpu_sumcheck_layer256,
@@ -531,6 +533,29 @@ int lfgpu_ligero_prove_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, siz
                              const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2);
 int lfgpu_ligero_open_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx /*[nb][nreq]*/,
                             void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath /*[nb]*/);
+/* ---- the same two over Fp256Base: nb provers from lfgpu_ligero_commit(field = LFGPU_FIELD_P256) of ONE context and ONE
+ * lfgpu_ligero_param ----
+ * Semantics, argument layout and error rules are those of lfgpu_ligero_prove_batch / lfgpu_ligero_open_batch with 32-byte
+ * Montgomery images throughout (scale: [nb][4]; every element count above is in 32-byte elements).  Per chain of statements:
+ * one upload, one memset, one dense and one sparse launch for the A rows of all statements (the sparse lists ragged, 0 terms
+ * allowed), ONE lfgpu_fp256_rs_encode_rows over the chain's nwqrow rows per statement (they stand contiguously), the dot-proof,
+ * low-degree and quadratic combinations (one launch each) and one read-back of all three y vectors; the opening is one column
+ * gather, one digest gather and one read-back.  Results are byte-identical per statement to lfgpu_ligero_low_degree_proof,
+ * lfgpu_ligero_dot_proof (A = scale * dense + the sparse terms, as the ZK path builds it), lfgpu_ligero_quadratic_proof and
+ * lfgpu_ligero_open on that prover alone.  The reference's sanity check is made per statement: LFGPU_ERR_ASSERT naming the
+ * statement whose y_quad has a non-zero W part.  Statements are chunked so that a chain's working set and the encoder's
+ * scratch stay under 256 MiB; LFGPU_LP_CHUNK overrides (read once).
+ * LFGPU_ERR_ARG, found before anything is enqueued: a NULL entry, nb out of 1..LFGPU_SC_BATCH_MAX, a prover of a 16-byte field
+ * or of another context, provers whose lfgpu_ligero_param differ, the same prover twice, a prover without a commitment, a
+ * sparse index out of range or not strictly increasing, an opened index out of range or given twice, a path buffer too small,
+ * a dense block inside the call's scratch.  LFGPU_ERR_UNSUPPORTED: a sharded prover or one that holds a slab.
+ * Not batched for this field: the commit (lfgpu_column_commit_batch / lfgpu_ligero_commit_batch keep refusing it). */
+int lfgpu_ligero_prove_batch256(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const void* h_u_ldt,
+                                const void* const* d_dense, size_t ndense, const uint64_t* scale /*[nb][4]*/,
+                                const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse /*[nb]*/,
+                                const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2);
+int lfgpu_ligero_open_batch256(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx /*[nb][nreq]*/,
+                               void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap, size_t* npath /*[nb]*/);
 /* device pointer of the resident tableau (nrow x block_enc elements of the prover's field: 16 bytes, P256 32) */
 int lfgpu_ligero_tableau(lfgpu_ligero_prover* pr, void** d_T);
 int lfgpu_ligero_free(lfgpu_ligero_prover* pr);

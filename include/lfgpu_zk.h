@@ -154,13 +154,39 @@ int lfgpu_zk_prover_free(lfgpu_zk_prover* zk);
  * zero bytes), the constraints, proof_write -- is serial inside one batch.  A caller that wants more throughput runs several
  * batches in several contexts (lfgpu_own_stream, lfgpu_circuit_share), as examples/zk_throughput.cc does with provers.
  * 1 <= nb <= nb_max <= LFGPU_SC_BATCH_MAX.  LFGPU_ERR_ARG: a NULL argument, nb out of range, a prover of another context or
- * circuit, one that has not committed, the same prover twice.  LFGPU_ERR_UNSUPPORTED: an Fp256Base circuit (at _new), a
- * prover with a communicator set.  LFGPU_ERR_NOMEM from _new when the slabs do not fit. */
+ * circuit, one that has not committed, the same prover twice.  LFGPU_ERR_UNSUPPORTED: an Fp256Base circuit (at _new: those
+ * take lfgpu_zk_batch256_new / lfgpu_zk_prove_batch256 below), a prover with a communicator set.  LFGPU_ERR_NOMEM from _new when
+ * the slabs do not fit. */
 typedef struct lfgpu_zk_batch lfgpu_zk_batch;
 int lfgpu_zk_batch_new(lfgpu_ctx* ctx, const lfgpu_circuit* c, size_t nb_max, lfgpu_zk_batch** out);
 int lfgpu_zk_prove_batch(lfgpu_zk_batch* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
                          const lfgpu_transcript_ops* const* ts, int* ok /*[nb]*/);
 int lfgpu_zk_batch_free(lfgpu_zk_batch* batch);
+/* ---- the same over Fp256Base (circuits with field id LFGPU_FIELD_P256) ----
+ * The contract of lfgpu_zk_prove_batch with 32-byte Montgomery images, under names of its own (the three calls above keep
+ * refusing the field): nb provers of ONE context and ONE Fp256Base circuit, each committed by lfgpu_zk_commit, through one
+ * chain -- lfgpu_eval_quad_batch256's two launches per layer, one lfgpu_sumcheck_layer_batch256 per layer, then for the
+ * statements with a good witness the constraints per statement on the host, ONE launch chain for the EQ tables of their input
+ * constraints (the public parts of all tables back in one copy), ONE lfgpu_ligero_prove_batch256 and ONE
+ * lfgpu_ligero_open_batch256 (lfgpu.h).  Statement b's proof is byte-identical to lfgpu_zk_prove(zk[b], h_W[b], ts[b]) and
+ * ts[b] is left in the same state; ok[b] = 0 for a bad witness: that prover holds no proof, the others are unaffected.
+ * LFGPU_LIGERO_PROVE_BATCH256=0 (read once per process; the 16-byte fields keep LFGPU_LIGERO_PROVE_BATCH) runs constraints,
+ * Ligero prove and opening per statement with the code of lfgpu_zk_prove: the same bytes; so does a batch whose good statements
+ * hold different lfgpu_ligero_param.  lfgpu_zk_timings: [2] and [3] are the batch's phase times, the same values for every
+ * member, [1] the whole call's; [4] and [5] the batch's on the batched tail and the statement's own otherwise.  Errors in the
+ * tail, the batch object's memory (allocated once in _new, the witness-dependent slabs scrubbed on free, no hipMalloc / hipFree
+ * in the prove call beyond the context's pooled scratch) and the threading model: as above.
+ * Not batched for this field: the commit (lfgpu_zk_commit per prover: 1.1 ms of a 16 ms proof), the verifier, and there is no
+ * resident grid for the batch's sumcheck.
+ * 1 <= nb <= nb_max <= LFGPU_SC_BATCH_MAX.  LFGPU_ERR_ARG, found before anything is enqueued or any transcript is touched: a
+ * NULL argument, nb out of range, a prover of another context or circuit, one that has not committed, the same prover twice, a
+ * transcript without write_elt_sized / write_elt_array_sized, at _new a circuit over a 16-byte field (lfgpu_zk_batch_new serves
+ * those).  LFGPU_ERR_UNSUPPORTED: a prover with a communicator set.  LFGPU_ERR_NOMEM from _new when the slabs do not fit. */
+typedef struct lfgpu_zk_batch256 lfgpu_zk_batch256;
+int lfgpu_zk_batch256_new(lfgpu_ctx* ctx, const lfgpu_circuit* c, size_t nb_max, lfgpu_zk_batch256** out);
+int lfgpu_zk_prove_batch256(lfgpu_zk_batch256* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                            const lfgpu_transcript_ops* const* ts, int* ok /*[nb]*/);
+int lfgpu_zk_batch256_free(lfgpu_zk_batch256* batch);
 /* ---- ZkProver::commit for a batch of provers ----
  * lfgpu_zk_commit (its one-GPU branch) for nb provers of the batch's context and circuit in one chain of dispatches: per
  * statement, in index order, fill_pad from rng[b] (its draws come before its Ligero draws, as in lfgpu_zk_commit); then ONE

@@ -48,6 +48,7 @@ ABI_SYMBOLS = [
     "lfgpu_zk_batch_new", "lfgpu_zk_prove_batch", "lfgpu_zk_batch_free",
     "lfgpu_column_commit_batch", "lfgpu_ligero_commit_batch", "lfgpu_zk_commit_batch",
     "lfgpu_ligero_prove", "lfgpu_ligero_verify",
+    "lfgpu_zk_batch256_new", "lfgpu_zk_prove_batch256", "lfgpu_zk_batch256_free", "lfgpu_ligero_prove_batch256", "lfgpu_ligero_open_batch256",
 ]
 
 
@@ -240,6 +241,11 @@ def load_library():
         "lfgpu_ligero_commit_batch": [vp, ci, ci, C.POINTER(LigeroParam), sz, C.POINTER(vp), sz, vp, C.POINTER(RNG_FN), C.POINTER(vp), vp, C.POINTER(vp)],
         "lfgpu_ligero_prove_batch": [vp, C.POINTER(vp), sz, vp, C.POINTER(vp), sz, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), vp, vp, vp, vp, vp],
         "lfgpu_ligero_open_batch": [vp, C.POINTER(vp), sz, C.POINTER(sz), vp, vp, vp, sz, C.POINTER(sz)],
+        "lfgpu_zk_batch256_new": [vp, vp, sz, C.POINTER(vp)],
+        "lfgpu_zk_prove_batch256": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), C.POINTER(ci)],
+        "lfgpu_zk_batch256_free": [vp],
+        "lfgpu_ligero_prove_batch256": [vp, C.POINTER(vp), sz, vp, C.POINTER(vp), sz, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), vp, vp, vp, vp, vp],
+        "lfgpu_ligero_open_batch256": [vp, C.POINTER(vp), sz, C.POINTER(sz), vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_zk_commit_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(RNG_FN), C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), vp],
         "lfgpu_ligero_prove": [vp, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_ligero_verify": [vp, ci, ci, C.POINTER(LigeroParam), vp, vp, sz, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, C.POINTER(ci),
@@ -577,7 +583,8 @@ class LigeroProver:
     over the C ABI: the tableau lives in HBM; the caller owns the transcript and the RandomEngine.
     `rng_bytes(n) -> bytes` plays RandomEngine::bytes.  Elements are (n, 2) uint64 arrays for GF(2^128) and Fp128 and (n, 4) --
     32-byte Montgomery images -- for FIELD_P256, which commit, low_degree_proof, dot_proof, quadratic_proof, open and prove serve
-    (the batch, sharded, slab and sparse forms are for the 16-byte fields)."""
+    (the sharded, slab and sparse forms and commit_batch are for the 16-byte fields; prove_batch256 / open_batch256 are the batch
+    of FIELD_P256 provers)."""
 
     def __init__(self, gpu, field, param, subfield_log_bits=4):
         self.gpu, self.field, self.p, self.k = gpu, field, param, subfield_log_bits
@@ -636,7 +643,7 @@ class LigeroProver:
         return [raw[32 * b:32 * b + 32] for b in range(nb)], provers
 
     @staticmethod
-    def prove_batch(gpu, provers, u_ldt, d_dense, ndense, scales, idxs, vals, u_quad):
+    def prove_batch(gpu, provers, u_ldt, d_dense, ndense, scales, idxs, vals, u_quad, _ew=2):
         """lfgpu_ligero_prove_batch: the low-degree, dot (sparse form) and quadratic proofs of len(provers) committed provers of
         one LigeroParam in one chain of dispatches.  u_ldt: [nb][nwqrow] elements; d_dense: one device pointer per statement (or
         None when ndense == 0); scales: [nb] elements; idxs[b] / vals[b]: statement b's sparse list (may be empty); u_quad:
@@ -652,12 +659,13 @@ class LigeroProver:
         vl = [np.ascontiguousarray(v, dtype=np.uint64) for v in vals]
         if len(ix) != nb or len(vl) != nb:
             raise ValueError("LigeroProver.prove_batch: one sparse list per prover")
-        y_ldt = np.zeros((n, p.block, 2), dtype=np.uint64)
-        y_dot = np.zeros((n, p.dblock, 2), dtype=np.uint64)
-        y_q0 = np.zeros((n, p.r, 2), dtype=np.uint64)
-        y_q2 = np.zeros((n, p.dblock - p.block, 2), dtype=np.uint64)
+        y_ldt = np.zeros((n, p.block, _ew), dtype=np.uint64)
+        y_dot = np.zeros((n, p.dblock, _ew), dtype=np.uint64)
+        y_q0 = np.zeros((n, p.r, _ew), dtype=np.uint64)
+        y_q2 = np.zeros((n, p.dblock - p.block, _ew), dtype=np.uint64)
         dd = (C.c_void_p * n)(*(d_dense if d_dense is not None else [None] * nb))
-        gpu._ck(gpu.L.lfgpu_ligero_prove_batch(
+        fn = gpu.L.lfgpu_ligero_prove_batch256 if _ew == 4 else gpu.L.lfgpu_ligero_prove_batch
+        gpu._ck(fn(
             gpu.h, (C.c_void_p * n)(*[pr.h.value if pr.h else None for pr in provers]), nb, C.c_void_p(u.ctypes.data), dd, ndense,
             C.c_void_p(sc.ctypes.data), (C.c_void_p * n)(*[i.ctypes.data if i.size else None for i in ix]),
             (C.c_void_p * n)(*[v.ctypes.data if v.size else None for v in vl]), (C.c_size_t * n)(*[len(i) for i in ix]),
@@ -666,9 +674,10 @@ class LigeroProver:
         return y_ldt[:nb], y_dot[:nb], y_q0[:nb], y_q2[:nb]
 
     @staticmethod
-    def open_batch(gpu, provers, idxs):
+    def open_batch(gpu, provers, idxs, path_cap=None, _ew=2):
         """lfgpu_ligero_open_batch: open() of every prover with its own nreq indices idxs[b] in one column gather, one digest gather
-        and one read-back -> [(req[nrow][nreq], nonces[nreq], path digests)] per statement"""
+        and one read-back -> [(req[nrow][nreq], nonces[nreq], path digests)] per statement.  path_cap: digests of room per
+        statement (default: the most a statement can need)"""
         import numpy as np
         nb = len(provers)
         p = provers[0].p if nb else LigeroParam()
@@ -676,15 +685,27 @@ class LigeroProver:
         flat = [int(j) for i in idxs for j in i]
         if len(flat) != nb * p.nreq:
             raise ValueError("LigeroProver.open_batch: nreq indices per prover")
-        req = np.zeros((n, p.nrow, p.nreq, 2), dtype=np.uint64)
+        req = np.zeros((n, p.nrow, p.nreq, _ew), dtype=np.uint64)
         nonces = np.zeros((n, p.nreq, 32), dtype=np.uint8)
-        cap = p.nreq * p.mc_pathlen + 1
-        path = np.zeros((n, cap, 32), dtype=np.uint8)
+        cap = p.nreq * p.mc_pathlen + 1 if path_cap is None else path_cap
+        path = np.zeros((n, max(1, cap), 32), dtype=np.uint8)
         npath = (C.c_size_t * n)()
-        gpu._ck(gpu.L.lfgpu_ligero_open_batch(gpu.h, (C.c_void_p * n)(*[pr.h.value if pr.h else None for pr in provers]), nb,
-                                               (C.c_size_t * max(1, len(flat)))(*flat), C.c_void_p(req.ctypes.data), C.c_void_p(nonces.ctypes.data),
-                                               C.c_void_p(path.ctypes.data), cap, npath))
+        fn = gpu.L.lfgpu_ligero_open_batch256 if _ew == 4 else gpu.L.lfgpu_ligero_open_batch
+        gpu._ck(fn(gpu.h, (C.c_void_p * n)(*[pr.h.value if pr.h else None for pr in provers]), nb,
+                   (C.c_size_t * max(1, len(flat)))(*flat), C.c_void_p(req.ctypes.data), C.c_void_p(nonces.ctypes.data),
+                   C.c_void_p(path.ctypes.data), cap, npath))
         return [(req[b], nonces[b], [bytes(path[b, i]) for i in range(npath[b])]) for b in range(nb)]
+
+    @staticmethod
+    def prove_batch256(gpu, provers, u_ldt, d_dense, ndense, scales, idxs, vals, u_quad):
+        """lfgpu_ligero_prove_batch256: prove_batch for provers committed over FIELD_P256; every element is a row of 4 uint64 (a
+        32-byte Montgomery image), d_dense[b] points at 32-byte elements"""
+        return LigeroProver.prove_batch(gpu, provers, u_ldt, d_dense, ndense, scales, idxs, vals, u_quad, _ew=4)
+
+    @staticmethod
+    def open_batch256(gpu, provers, idxs, path_cap=None):
+        """lfgpu_ligero_open_batch256: open_batch for provers committed over FIELD_P256 (req: [nrow][nreq][4])"""
+        return LigeroProver.open_batch(gpu, provers, idxs, path_cap, _ew=4)
 
     def low_degree_proof(self, u_ldt):
         import numpy as np
@@ -1161,6 +1182,40 @@ class ZkBatch:
     def close(self):
         if self.h:
             self.gpu.L.lfgpu_zk_batch_free(self.h)
+            self.h = None
+
+
+class ZkBatch256:
+    """lfgpu_zk_batch256: ZkBatch for circuits over FIELD_P256 -- up to nb_max committed ZkProvers of one context and one Fp256Base
+    circuit proved in lock-step (batched eval_circuit and sumcheck; one EQ launch chain, one lfgpu_ligero_prove_batch256 and one
+    lfgpu_ligero_open_batch256 for the Ligero proofs of all statements; LFGPU_LIGERO_PROVE_BATCH256=0 runs that tail per
+    statement).  Every proof is byte-identical to ZkProver.prove's.  The provers commit one by one (ZkProver.commit)."""
+
+    def __init__(self, gpu, circuit, nb_max):
+        self.gpu, self.circuit, self.nb_max = gpu, circuit, nb_max
+        h = C.c_void_p()
+        gpu._ck(gpu.L.lfgpu_zk_batch256_new(gpu.h, circuit.h, nb_max, C.byref(h)))
+        self.h = h
+
+    def prove(self, provers, Ws, transcripts):
+        """-> [bool] per statement: True = provers[b] holds its proof, False = witness b does not satisfy the circuit"""
+        import numpy as np
+        nb = len(provers)
+        if not (len(Ws) == nb and len(transcripts) == nb):
+            raise ValueError("ZkBatch256.prove: one witness and one transcript per prover")
+        Ws = [np.ascontiguousarray(W) for W in Ws]
+        ops = [t.ops() for t in transcripts]
+        n = max(1, nb)
+        zk = (C.c_void_p * n)(*[p.h for p in provers])
+        hw = (C.c_void_p * n)(*[W.ctypes.data for W in Ws])
+        tp = (C.POINTER(TranscriptOps) * n)(*[C.pointer(o) for o in ops])
+        ok = (C.c_int * n)()
+        self.gpu._ck(self.gpu.L.lfgpu_zk_prove_batch256(self.h, zk, nb, hw, tp, ok))
+        return [bool(ok[b]) for b in range(nb)]
+
+    def close(self):
+        if self.h:
+            self.gpu.L.lfgpu_zk_batch256_free(self.h)
             self.h = None
 
 

@@ -1001,7 +1001,7 @@ static int ligero_batch_provers_ok(lfgpu_ctx* c, const char* who, lfgpu_ligero_p
       if (pr[a] == pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu appears twice", who, b);
   }
   if (pr[0]->field != LFGPU_FIELD_GF2_128 && pr[0]->field != LFGPU_FIELD_FP128)
-    return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: 16-byte fields only (Fp256Base provers run one statement at a time)", who);
+    return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: 16-byte fields only (Fp256Base provers take lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256)", who);
   for (size_t b = 0; b < nb; ++b)
     if (pr[b]->sharded || pr[b]->row_lo != 0 || pr[b]->row_hi != pr[b]->p.nrow || !pr[b]->d_T)
       return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: prover %zu is sharded or holds a slab (the batch runs whole tableaux on one GPU)", who, b);

@@ -22,7 +22,7 @@
 // The commit side: Slab::init / alloc build the record, extend_slab Reed-Solomon-encodes a fresh slab, commit_rows uploads a
 // slab's host image, encodes it and commits the columns (one GPU, or the sharded exchange).  What stays in the two files: the
 // entry points with their argument checks and their own layout call (ligero_layout.h; the sharded record / replay of the engine),
-// the batched entry points (16-byte only) and every kernel.
+// the batched entry points (each width its own: their chains differ in the Reed-Solomon step) and every kernel.
 #pragma once
 #include <algorithm>
 #include <chrono>

@@ -310,6 +310,11 @@ struct P16 : zkp::Wire16 {
   // ---- the batch axis (zkp::prove_batch): B statements of one layer per call
   typedef void (*round_batch_fn)(void* user, size_t hand, size_t rnd, size_t nb, const E (*ev)[3], E* chal);
   static constexpr const char* kProveBatchName = "zk_prove_batch";
+  // LFGPU_LIGERO_PROVE_BATCH [1] (read once per process): 0 = constraints, Ligero prove and opening per statement (prove_finish)
+  static int ligero_batch_switch() {
+    static const int on = getenv("LFGPU_LIGERO_PROVE_BATCH") ? atoi(getenv("LFGPU_LIGERO_PROVE_BATCH")) : 1;
+    return on;
+  }
   static int eval_layer_batch(lfgpu_quad* q, size_t nb, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail) {
     return lf_eval_quad_batch_async(q, nb, d_W, ldw, d_V, ldv, d_fail);
   }
@@ -731,7 +736,7 @@ struct lfgpu_zk_batch {
 extern "C" int lfgpu_zk_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, lfgpu_zk_batch** out) {
   if (!c || !C || !out || C->c != c) return LFGPU_ERR_ARG;
   if (nb_max == 0 || nb_max > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch_new: nb_max must be 1..%d", LFGPU_SC_BATCH_MAX);
-  if (C->info.field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_batch_new: Fp256Base circuits are proved one statement at a time");
+  if (C->info.field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_batch_new: an Fp256Base circuit (lfgpu_zk_batch256_new serves those)");
   std::unique_ptr<lfgpu_zk_batch> bt(new lfgpu_zk_batch());
   bt->c = c;
   bt->C = C;
@@ -866,6 +871,55 @@ extern "C" int lfgpu_zk_commit_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const*
 }
 
 extern "C" int lfgpu_zk_batch_free(lfgpu_zk_batch* bt) {
+  if (!bt) return LFGPU_ERR_ARG;
+  delete bt;
+  return LFGPU_OK;
+}
+
+// ------------------------------------------------------------------ ... over Fp256Base
+// The same contract with names of their own (lfgpu_zk_batch_new / lfgpu_zk_prove_batch keep refusing the field): the handles are
+// checked here, the batch and the proof are zk256.hip's (Zk256Batch, zk256_prove_batch).
+struct lfgpu_zk_batch256 {
+  lfgpu_ctx* c = nullptr;
+  const lfgpu_circuit* C = nullptr;
+  size_t nb_max = 0;
+  Zk256Batch* bt = nullptr;
+  ~lfgpu_zk_batch256() {
+    if (bt) zk256_batch_free(bt);
+  }
+};
+
+extern "C" int lfgpu_zk_batch256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, lfgpu_zk_batch256** out) {
+  if (!c || !C || !out || C->c != c) return LFGPU_ERR_ARG;
+  if (nb_max == 0 || nb_max > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch256_new: nb_max must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (C->info.field != LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch256_new: the circuit is over a 16-byte field (lfgpu_zk_batch_new serves those)");
+  std::unique_ptr<lfgpu_zk_batch256> bt(new lfgpu_zk_batch256());
+  bt->c = c;
+  bt->C = C;
+  bt->nb_max = nb_max;
+  LF_TRY(zk256_batch_new(c, C, nb_max, &bt->bt));
+  *out = bt.release();
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_zk_prove_batch256(lfgpu_zk_batch256* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                                       const lfgpu_transcript_ops* const* ts, int* ok) {
+  if (!bt || !zk || !h_W || !ts || !ok) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = bt->c;
+  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
+  std::vector<Zk256*> z(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!zk[b] || !h_W[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: null argument for statement %zu", b);
+    if (zk[b]->c != c || zk[b]->C != bt->C || !zk[b]->z256) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: prover %zu belongs to another context or circuit", b);
+    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_prove_batch256: prover %zu has a communicator (the batch runs on one GPU)", b);
+    for (size_t a = 0; a < b; ++a)
+      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: prover %zu appears twice", b);
+    z[b] = zk[b]->z256;
+  }
+  return zk256_prove_batch(bt->bt, z.data(), nb, h_W, ts, ok);  // (a prover that has not committed, a transcript without the sized hooks: found there, first)
+}
+
+extern "C" int lfgpu_zk_batch256_free(lfgpu_zk_batch256* bt) {
   if (!bt) return LFGPU_ERR_ARG;
   delete bt;
   return LFGPU_OK;

@@ -10,6 +10,8 @@
 //   Ligero                  LigeroProver::commit / prove       lib/ligero/ligero_prover.h:58-146,171-351
 //   driver                  ZkProver::commit (lib/zk/zk_prover.h:72-96) here; prove, verifier_constraints, ZkProof::write / read
 //                           and the verifier are csrc/zk_proto.h, instantiated with the policy P32 at the end of this file
+//   batch                   B provers in lock-step: zkp::prove_batch<P32> (zk_proto.h) over the *_batch kernels here, Zk256Batch,
+//                           lig256_prove_batch / lig256_open_batch (lfgpu_zk_prove_batch256, lfgpu_ligero_prove_batch256 / _open_batch256)
 // Sums over many terms (run sums of bind_g, the QW scatter) add the 32-bit limbs of canonical residues into 64-bit integer
 // accumulators with atomics and reduce once (fp256_reduce_limbs): exact and independent of arrival order, as for Fp128.
 // Row extension and column hashing are csrc/p256.hip.
@@ -1339,6 +1341,99 @@ __global__ __launch_bounds__(Z_THREADS) void gather_columns256_kernel(u32 nrow, 
   st32(&req[t], ld32(&T[(size_t)i * ld + col0 + idx[j]]));
 }
 
+// ---- the batch twins of the six kernels above (lig256_prove_batch / lig256_open_batch): statement blockIdx.y.  The B tableaux
+// are the provers' own buffers and the dense blocks the caller's, so their base pointers come as ONE by-value argument indexed by
+// the (wave-uniform) statement -- scalar loads from the kernarg segment (LfBatchPtrs, ctx.h); what the call owns (the A rows, the
+// challenge vectors, the y vectors, the gathered columns) stands at one stride per statement.  Tableau rows are given as element
+// offsets into a statement's tableau (o_*).  The arithmetic per entry is the single kernels', in their order.
+// rows of statement y at rows + y * s_rows: rows[i][r + j] = scale[y] * dense_y[i w + j]
+__global__ __launch_bounds__(Z_THREADS) void a_rows_dense256_batch_kernel(u32 r, u32 w, size_t ld, const E* __restrict__ scale, LfBatchPtrs dense, size_t n,
+                                                                          E* __restrict__ rows, size_t s_rows) {
+  const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+  if (t >= n) return;
+  const size_t b = blockIdx.y, i = t / w, j = t % w;
+  const E* __restrict__ d = (const E*)dense.p[b];
+  st32(&rows[b * s_rows + i * ld + r + j], fp256_mul(ld32(&scale[b]), ld32(&d[t])));
+}
+// ... += the sparse terms: ONE packed list for all statements, statement y's entries at [off[y], off[y + 1]) (ragged; a statement
+// may have none).  No bound on idx here either: the host has checked every list against nwqrow * w.
+__global__ __launch_bounds__(Z_THREADS) void a_rows_sparse256_batch_kernel(u32 r, u32 w, size_t ld, const u64* __restrict__ idx, const E* __restrict__ val,
+                                                                           const u64* __restrict__ off, E* __restrict__ rows, size_t s_rows) {
+  const size_t b = blockIdx.y, o = off[b], n = off[b + 1] - o;
+  const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+  if (t >= n) return;
+  const u64 f = idx[o + t];
+  E* dst = &rows[b * s_rows + (f / w) * ld + r + f % w];
+  st32(dst, fp256_add(ld32(dst), ld32(&val[o + t])));
+}
+// dot proof: y_b[j] = T_b[idot][j] + sum_i A_b[i][j] T_b[iw + i][j], j < n = dblock; 64 columns x 4 row slices per workgroup
+__global__ __launch_bounds__(256) void rows_vaxpy256_batch_kernel(u32 nrows, size_t n, LfBatchPtrs T, size_t ld, size_t o_dot, size_t o_w, const E* __restrict__ A,
+                                                                  size_t s_A, size_t lda, E* __restrict__ y, size_t s_y) {
+  __shared__ E part[4][64];
+  const u32 col = threadIdx.x & 63, slice = threadIdx.x >> 6;
+  const size_t j = (size_t)blockIdx.x * 64 + col, b = blockIdx.y;
+  const E* __restrict__ Tb = (const E*)T.p[b];
+  const E* __restrict__ Ab = A + b * s_A;
+  E acc = e32_zero();
+  if (j < n)
+    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&Tb[o_w + (size_t)i * ld + j]), ld32(&Ab[(size_t)i * lda + j])));
+  part[slice][col] = acc;
+  __syncthreads();
+  if (slice == 0 && j < n) {
+    acc = ld32(&Tb[o_dot + j]);
+    for (u32 k = 0; k < 4; ++k) acc = fp256_add(acc, part[k][col]);
+    st32(&y[b * s_y + j], acc);
+  }
+}
+// low-degree proof: y_b[j] = T_b[ildt][j] + sum_i u_b[i] T_b[iw + i][j], j < n = block (the single path copies the ILDT row into
+// y first and rows_axpy256_kernel adds to it: the same sum in the same order); u_b at u + b * s_u
+__global__ __launch_bounds__(256) void rows_axpy256_batch_kernel(u32 nrows, size_t n, LfBatchPtrs T, size_t ld, size_t o_ldt, size_t o_w, const E* __restrict__ u,
+                                                                 size_t s_u, E* __restrict__ y, size_t s_y) {
+  __shared__ E part[4][64];
+  const u32 col = threadIdx.x & 63, slice = threadIdx.x >> 6;
+  const size_t j = (size_t)blockIdx.x * 64 + col, b = blockIdx.y;
+  const E* __restrict__ Tb = (const E*)T.p[b];
+  const E* __restrict__ ub = u + b * s_u;
+  E acc = e32_zero();
+  if (j < n)
+    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&Tb[o_w + (size_t)i * ld + j]), ld32(&ub[i])));
+  part[slice][col] = acc;
+  __syncthreads();
+  if (slice == 0 && j < n) {
+    acc = ld32(&Tb[o_ldt + j]);
+    for (u32 k = 0; k < 4; ++k) acc = fp256_add(acc, part[k][col]);
+    st32(&y[b * s_y + j], acc);
+  }
+}
+// quadratic proof: y_b[j] = T_b[iquad][j] + sum_i u_b[i] (z_i[j] - x_i[j] y_i[j]); the triples' rows x | y | z stand nt rows apart from o_x on
+__global__ __launch_bounds__(Z_THREADS) void quad_combo256_batch_kernel(u32 nt, size_t n, LfBatchPtrs T, size_t ld, size_t o_quad, size_t o_x, const E* __restrict__ u,
+                                                                        size_t s_u, E* __restrict__ y, size_t s_y) {
+  const size_t j = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+  if (j >= n) return;
+  const size_t b = blockIdx.y;
+  const E* __restrict__ Tb = (const E*)T.p[b];
+  const E* __restrict__ X = Tb + o_x;
+  const E* __restrict__ Y = X + (size_t)nt * ld;
+  const E* __restrict__ Zr = Y + (size_t)nt * ld;
+  const E* __restrict__ ub = u + b * s_u;
+  E acc = ld32(&Tb[o_quad + j]);
+  for (u32 i = 0; i < nt; ++i) {
+    const E t = fp256_sub(ld32(&Zr[(size_t)i * ld + j]), fp256_mul(ld32(&X[(size_t)i * ld + j]), ld32(&Y[(size_t)i * ld + j])));
+    acc = fp256_add(acc, fp256_mul(ld32(&ub[i]), t));
+  }
+  st32(&y[b * s_y + j], acc);
+}
+// req_b[i][j] = T_b[i][col0 + idx_b[j]]: idx [nb][nreq], req [nb][nrow][nreq]
+__global__ __launch_bounds__(Z_THREADS) void gather_columns256_batch_kernel(u32 nrow, size_t ld, size_t col0, LfBatchPtrs T, const u64* __restrict__ idx, u32 nreq,
+                                                                            E* __restrict__ req) {
+  const u32 t = blockIdx.x * Z_THREADS + threadIdx.x;
+  if (t >= nrow * nreq) return;
+  const size_t b = blockIdx.y;
+  const u32 i = t / nreq, j = t % nreq;
+  const E* __restrict__ Tb = (const E*)T.p[b];
+  st32(&req[b * (size_t)nrow * nreq + t], ld32(&Tb[(size_t)i * ld + col0 + idx[b * nreq + j]]));
+}
+
 // Quad::bind_gh_all (lib/sumcheck/quad.h:188-210), the verifier's combined bind: the sum over all corners of
 // prep_v(v, beta) (EQ(G0,g) + alpha EQ(G1,g)) EQ(H0,h0) EQ(H1,h1); block sums go as limbs into 8 words
 __global__ __launch_bounds__(Z_THREADS) void bind_gh_all256_kernel(size_t n, const corner4* __restrict__ t, const E* __restrict__ kvec, const E* __restrict__ eqg,
@@ -2019,7 +2114,21 @@ int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail
 }
 
 // ProverLayers::eval_quad for nb statements of one quad: two launches whatever nb; 64 bytes of limb accumulators per output and
-// statement, so no two statements share one
+// statement, so no two statements share one.  Enqueue only: a violated assert-zero term of statement b ORs into d_fail[b], which
+// the caller has cleared and reads back when it wants the verdict (zkp::prove_batch: once, after the last layer).
+int lf256_eval_quad_batch_async(lfgpu_quad* q, size_t nb, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail) {
+  lfgpu_ctx* c = q->c;
+  if ((q->nv * 64) > ((size_t)1 << 40) / nb) return lf_fail(c, LFGPU_ERR_NOMEM, "eval_quad_batch256: %zu bytes of accumulators per statement", q->nv * 64);
+  void* acc = nullptr;
+  LF_TRY(lf_scratch2(c, nb * q->nv * 64 + 64, &acc));
+  LF_HIP(c, hipMemsetAsync(acc, 0, nb * q->nv * 64, c->stream));
+  hipLaunchKernelGGL(eval_quad256_batch_kernel, dim3(nblk(q->n), (u32)nb), dim3(Z_THREADS), 0, c->stream, q->n, (const corner4*)q->d_bygate, (const E*)q->d_kvec,
+                     (const E*)d_W, ldw, (u64*)acc, q->nv * 8, d_fail);
+  hipLaunchKernelGGL(limb_normalize256_batch_kernel, dim3(nblk(q->nv), (u32)nb), dim3(Z_THREADS), 0, c->stream, q->nv, (u64*)acc, q->nv * 8, h256_rsq(), (E*)d_V, ldv);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
 extern "C" int lfgpu_eval_quad_batch256(lfgpu_quad* q, size_t nb, size_t nw, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* ok_out) {
   if (!q) return LFGPU_ERR_ARG;
   lfgpu_ctx* c = q->c;
@@ -2030,15 +2139,9 @@ extern "C" int lfgpu_eval_quad_batch256(lfgpu_quad* q, size_t nb, size_t nw, con
     return lf_fail(c, LFGPU_ERR_ARG, "eval_quad_batch256: nw = %zu (a corner reads wire %zu), ldw = %zu, ldv = %zu (nv = %zu)", nw, q->hmax, ldw, ldv, q->nv);
   if ((q->nv * 64) > ((size_t)1 << 40) / nb) return lf_fail(c, LFGPU_ERR_NOMEM, "eval_quad_batch256: %zu bytes of accumulators per statement", q->nv * 64);
   LF_HIP(c, hipSetDevice(c->device));
-  void* acc = nullptr;
-  LF_TRY(lf_scratch2(c, nb * q->nv * 64 + 64, &acc));
   int* d_fail = (int*)((uint8_t*)c->mailbox_d + LF_EVALB_FAIL_OFF);
   LF_HIP(c, hipMemsetAsync(d_fail, 0, nb * 4, c->stream));
-  LF_HIP(c, hipMemsetAsync(acc, 0, nb * q->nv * 64, c->stream));
-  hipLaunchKernelGGL(eval_quad256_batch_kernel, dim3(nblk(q->n), (u32)nb), dim3(Z_THREADS), 0, c->stream, q->n, (const corner4*)q->d_bygate, (const E*)q->d_kvec,
-                     (const E*)d_W, ldw, (u64*)acc, q->nv * 8, d_fail);
-  hipLaunchKernelGGL(limb_normalize256_batch_kernel, dim3(nblk(q->nv), (u32)nb), dim3(Z_THREADS), 0, c->stream, q->nv, (u64*)acc, q->nv * 8, h256_rsq(), (E*)d_V, ldv);
-  LF_HIP(c, hipGetLastError());
+  LF_TRY(lf256_eval_quad_batch_async(q, nb, d_W, ldw, d_V, ldv, d_fail));
   LF_HIP(c, hipMemcpyAsync(c->mailbox_h, d_fail, nb * 4, hipMemcpyDeviceToHost, c->stream));
   LF_HIP(c, hipStreamSynchronize(c->stream));
   for (size_t b = 0; b < nb; ++b) ok_out[b] = ((const int*)c->mailbox_h)[b] ? 0 : 1;
@@ -2177,7 +2280,272 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
   return LFGPU_OK;
 }
 Lig32* lig32_of(Lig256* L) { return reinterpret_cast<Lig32*>(L); }
+
+// ---- LigeroProver::prove for nb committed provers of one shape in one chain (what lfgpu_ligero_prove_batch / _open_batch of
+// ligero.hip are for the 16-byte fields).  One pair of functions over Lig32* const* serves lfgpu_ligero_prove_batch256 /
+// lfgpu_ligero_open_batch256 (through Lig256) and the ZK driver (P32::ligero_prove_batch / ligero_open_batch, which holds Lig32
+// directly).  Host vectors come and go as bytes (the C ABI's arrays are 8-byte aligned words, the elements want 16).
+// what both calls ask of their provers, found before anything is enqueued
+int lig256_batch_ok(lfgpu_ctx* c, const char* who, Lig32* const* pr, size_t nb) {
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is NULL", who, b);
+    if (pr[b]->c != c) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu belongs to another context", who, b);
+    if (memcmp(&pr[b]->p, &pr[0]->p, sizeof(lfgpu_ligero_param)) != 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu has another lfgpu_ligero_param than prover 0", who, b);
+    for (size_t a = 0; a < b; ++a)
+      if (pr[a] == pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu appears twice", who, b);
+  }
+  for (size_t b = 0; b < nb; ++b) {
+    if (pr[b]->sharded || !pr[b]->owns || pr[b]->row_lo != 0 || pr[b]->row_hi != pr[b]->p.nrow)
+      return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: prover %zu is sharded or holds a slab (the batch runs whole tableaux on one GPU)", who, b);
+    if (!pr[b]->d_T) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu holds no commitment", who, b);
+  }
+  return LFGPU_OK;
+}
+// statements per launch chain: the chain's working set in scratch3 (`per` bytes a statement) and the convolution scratch of the A
+// rows' extension (rows in pairs, 64 bytes per point) stay below LF_CB_SCRATCH_CAP, and the row pairs of a chain fit one launch's
+// gridDim.y; LFGPU_LP_CHUNK overrides (read once)
+size_t lig256_chunk(const lfgpu_ligero_param& p, size_t nb, size_t per) {
+  static const long env = getenv("LFGPU_LP_CHUNK") ? atol(getenv("LFGPU_LP_CHUNK")) : 0;
+  size_t chunk = std::min(nb, std::max<size_t>(1, LF_CB_SCRATCH_CAP / std::max<size_t>(per, 1)));
+  if (p.nwqrow) {
+    size_t P = 1;
+    while (P < p.dblock) P <<= 1;
+    chunk = std::min(chunk, std::min<size_t>(2 * 65535 / p.nwqrow, LF_CB_SCRATCH_CAP / (((p.nwqrow + 1) / 2) * P * sizeof(fp2_t))));
+  }
+  if (env > 0) chunk = std::min(chunk, (size_t)env);
+  return std::max<size_t>(chunk, 1);
+}
+
+// low_degree_proof, dot_proof (A = scale * dense + the sparse terms, as lig::dot builds it) and quadratic_proof of nb provers: per
+// chain one upload, one memset, one dense and one sparse launch, ONE Reed-Solomon extension of the chain's A rows, the three
+// combinations, one read-back.  Arguments as lfgpu_ligero_prove_batch256 (lfgpu.h).
+int lig256_prove_batch(lfgpu_ctx* c, const char* who, Lig32* const* pr, size_t nb, const void* h_u_ldt, const void* const* d_dense, size_t ndense,
+                       const void* scale, const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse, const void* h_u_quad, void* h_y_ldt,
+                       void* h_y_dot, void* h_y_q0, void* h_y_q2) {
+  LF_TRY(lig256_batch_ok(c, who, pr, nb));
+  const lfgpu_ligero_param& p = pr[0]->p;
+  const size_t nwq = p.nwqrow, nqt = p.nqtriples, lda = p.dblock, ld = p.block_enc, nflat = nwq * p.w, ymid = p.dblock - p.block;
+  if ((nwq && !h_u_ldt) || (nqt && !h_u_quad) || ndense > nflat || (ndense && (!d_dense || !scale)))
+    return lf_fail(c, LFGPU_ERR_ARG, "%s: null challenge vector / dense block, or ndense > nwqrow * w", who);
+  if (nwq >> 31 || nqt >> 31 || p.w >> 32 || p.r >> 32) return lf_fail(c, LFGPU_ERR_ARG, "%s: too many rows", who);
+  for (size_t b = 0; b < nb; ++b) {
+    if (ndense && !d_dense[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: dense block of statement %zu is NULL", who, b);
+    if (nsparse[b] && (!h_idx || !h_val || !h_idx[b] || !h_val[b])) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse list of statement %zu is NULL", who, b);
+    for (size_t t = 0; t < nsparse[b]; ++t) {
+      if (h_idx[b][t] >= nflat) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse index out of range (statement %zu)", who, b);
+      if (t && h_idx[b][t] <= h_idx[b][t - 1]) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse indices must be strictly increasing (statement %zu)", who, b);
+    }
+  }
+  // the working set of a chain of cb statements in scratch3, in elements: Aext [cb][nwq][dblock] | y [cb][block + 2 dblock] (y_ldt | y_dot |
+  // y_quad) | one uploaded block: u_ldt [cb][nwq] | u_quad [cb][nqt] | scale [cb] | val [tot] | idx [tot] (u64) | off [cb + 1] (u64).
+  // The uploaded block stays in scratch3: scratch2 is the Reed-Solomon encoder's work space (L32::a_rows_sparse).
+  const size_t sA = nwq * lda, sy = p.block + 2 * p.dblock;
+  const size_t chunk = lig256_chunk(p, nb, (sA + sy + nwq + nqt + 1) * 32);
+  auto pack_elts = [&](size_t cb, size_t tot) { return cb * (nwq + nqt + 1) + tot + (tot + 3) / 4 + (cb + 1 + 3) / 4; };
+  size_t need = 0;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0);
+    size_t tot = 0;
+    for (size_t b = b0; b < b0 + cb; ++b) tot += nsparse[b];
+    need = std::max(need, (cb * (sA + sy) + pack_elts(cb, tot)) * 32 + 64);
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+  // A dense block must not live in the scratch this call is about to overwrite: checked against the buffer as it stands (growing it
+  // frees that memory) and against the buffer after lf_scratch3 has grown it, both before anything is enqueued or written.  The
+  // extension works through scratch2, but it runs after a_rows_dense256_batch_kernel, the only reader of the dense blocks.
+  auto aliases = [&]() {
+    const uint8_t* lo = (const uint8_t*)c->scratch3;
+    const size_t span = c->scratch3_bytes;
+    for (size_t b = 0; b < nb && ndense && lo; ++b) {
+      const uint8_t* d = (const uint8_t*)d_dense[b];
+      if (d + ndense * 32 > lo && d < lo + span) return true;
+    }
+    return false;
+  };
+  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "%s: a dense block aliases the call's scratch", who);
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, need, &sc));
+  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "%s: a dense block aliases the call's scratch", who);
+  std::vector<E> pack, y;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0);
+    size_t tot = 0, maxsp = 0;
+    for (size_t b = b0; b < b0 + cb; ++b) {
+      tot += nsparse[b];
+      maxsp = std::max(maxsp, nsparse[b]);
+    }
+    E* const dAext = (E*)sc;
+    E* const dy = dAext + cb * sA;
+    E* const d_pack = dy + cb * sy;
+    // the host image of the uploaded block (kept until the chain's read-back has synchronised)
+    pack.assign(pack_elts(cb, tot), e32_zero());
+    const size_t o_uq = cb * nwq, o_sc = o_uq + cb * nqt, o_val = o_sc + cb, o_idx = o_val + tot, o_off = o_idx + (tot + 3) / 4;
+    if (nwq) memcpy((void*)pack.data(), (const uint8_t*)h_u_ldt + b0 * nwq * 32, cb * nwq * 32);
+    if (nqt) memcpy((void*)(pack.data() + o_uq), (const uint8_t*)h_u_quad + b0 * nqt * 32, cb * nqt * 32);
+    if (ndense) memcpy((void*)(pack.data() + o_sc), (const uint8_t*)scale + b0 * 32, cb * 32);
+    u64* const pk_idx = (u64*)(pack.data() + o_idx);
+    u64* const pk_off = (u64*)(pack.data() + o_off);
+    LfBatchPtrs pt{}, pd{};
+    size_t run = 0;
+    for (size_t b = 0; b < cb; ++b) {
+      const size_t g = b0 + b;
+      pk_off[b] = run;
+      if (nsparse[g]) {
+        memcpy((void*)(pack.data() + o_val + run), h_val[g], nsparse[g] * 32);
+        memcpy(pk_idx + run, h_idx[g], nsparse[g] * 8);
+      }
+      run += nsparse[g];
+      pt.p[b] = pr[g]->d_T;
+      pd.p[b] = ndense ? const_cast<void*>(d_dense[g]) : nullptr;
+    }
+    pk_off[cb] = run;
+    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 32, hipMemcpyHostToDevice, c->stream));
+    const E* const d_ul = d_pack;
+    const E* const d_uq = d_pack + o_uq;
+    // inner_product_vector + layout_Aext of every statement: one memset, one dense and one sparse launch
+    if (cb * sA) LF_HIP(c, hipMemsetAsync(dAext, 0, cb * sA * 32, c->stream));
+    if (ndense)
+      hipLaunchKernelGGL(a_rows_dense256_batch_kernel, dim3(nblk(ndense), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, lda, (const E*)(d_pack + o_sc), pd,
+                         ndense, dAext, sA);
+    if (maxsp)
+      hipLaunchKernelGGL(a_rows_sparse256_batch_kernel, dim3(nblk(maxsp), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, lda, (const u64*)(d_pack + o_idx),
+                         (const E*)(d_pack + o_val), (const u64*)(d_pack + o_off), dAext, sA);
+    LF_HIP(c, hipGetLastError());
+    // the A rows from block to dblock values, in place: the rows of all statements of the chain stand contiguously at the stride
+    // dblock, so this is one extension of cb * nwq rows (exact arithmetic: how the encoder pairs the rows does not change a value)
+    if (nwq) LF_TRY(lfgpu_fp256_rs_encode_rows(c, cb * nwq, p.block, p.dblock, dAext, lda));
+    // dot proof (dblock columns), low-degree proof (block columns), quadratic proof
+    hipLaunchKernelGGL(rows_vaxpy256_batch_kernel, dim3(nblk(p.dblock, 64), (u32)cb), dim3(256), 0, c->stream, (u32)nwq, p.dblock, pt, ld, p.idot * ld, p.iw * ld,
+                       (const E*)dAext, sA, lda, dy + p.block, sy);
+    hipLaunchKernelGGL(rows_axpy256_batch_kernel, dim3(nblk(p.block, 64), (u32)cb), dim3(256), 0, c->stream, (u32)nwq, p.block, pt, ld, p.ildt * ld, p.iw * ld, d_ul,
+                       nwq, dy, sy);
+    hipLaunchKernelGGL(quad_combo256_batch_kernel, dim3(nblk(p.dblock), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)nqt, p.dblock, pt, ld, p.iquad * ld, p.iq * ld,
+                       d_uq, nqt, dy + p.block + p.dblock, sy);
+    LF_HIP(c, hipGetLastError());
+    y.resize(cb * sy);
+    LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, cb * sy * 32));  // all three y vectors of all statements of the chain
+    for (size_t b = 0; b < cb; ++b) {  // the reference's sanity check (:335-337), as lig::quadratic makes it
+      const E* yq = y.data() + b * sy + p.block + p.dblock;
+      for (size_t j = 0; j < p.w; ++j)
+        if (!e32_is_zero(yq[p.r + j])) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero (statement %zu)", b0 + b);
+    }
+    for (size_t b = 0; b < cb; ++b) {
+      const E* yb = y.data() + b * sy;
+      const size_t g = b0 + b;
+      memcpy((uint8_t*)h_y_ldt + g * p.block * 32, yb, p.block * 32);
+      memcpy((uint8_t*)h_y_dot + g * p.dblock * 32, yb + p.block, p.dblock * 32);
+      const E* yq = yb + p.block + p.dblock;
+      memcpy((uint8_t*)h_y_q0 + g * p.r * 32, yq, p.r * 32);
+      memcpy((uint8_t*)h_y_q2 + g * ymid * 32, yq + p.block, ymid * 32);
+    }
+  }
+  return LFGPU_OK;
+}
+
+// compute_req + MerkleCommitment::open for nb provers: per chain the index lists of all statements in one upload, one column
+// gather, one digest gather (merkle.hip's: digests do not know the field) and one read-back of the columns and the digests, which
+// stand behind one another.  idx [nb][nreq]; h_req [nb][nrow][nreq]; statement b's path at h_path + b * path_cap * 32.
+int lig256_open_batch(lfgpu_ctx* c, const char* who, Lig32* const* pr, size_t nb, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap,
+                      size_t* npath) {
+  LF_TRY(lig256_batch_ok(c, who, pr, nb));
+  const lfgpu_ligero_param& p = pr[0]->p;
+  const size_t nreq = p.nreq, nrow = p.nrow, ncols = p.block_ext;
+  if (nreq == 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: nreq = 0 (a proof with 0 leaves is not defined)", who);
+  if ((nrow * nreq) >> 32) return lf_fail(c, LFGPU_ERR_ARG, "%s: nrow * nreq does not fit 32 bits", who);
+  for (size_t b = 0; b < nb; ++b)
+    if (pr[b]->nonces.size() != 32 * ncols || !pr[b]->d_layers) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu holds no commitment", who, b);
+  // MerkleTree::generate_compressed_proof's walk per statement (it also rejects an index out of range or given twice)
+  std::vector<u64> nodes;
+  std::vector<size_t> off(nb + 1, 0);
+  for (size_t b = 0; b < nb; ++b) {
+    LF_TRY(lf_merkle_path_nodes(c, ncols, idx + b * nreq, nreq, nodes));
+    off[b + 1] = nodes.size();
+    if (off[b + 1] - off[b] > path_cap || (off[b + 1] > off[b] && !h_path)) return lf_fail(c, LFGPU_ERR_ARG, "%s: path buffer too small (statement %zu)", who, b);
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+  // a chain of cb statements in scratch3: req [cb][nrow][nreq] | digests [32 bytes per node] | idx [cb][nreq] (u64) | nodes (u64) | off [cb + 1] (u64)
+  const size_t chunk = lig256_chunk(p, nb, (nrow * nreq + nreq * (p.mc_pathlen + 1)) * 32);
+  auto words = [&](size_t cb, size_t tot) { return cb * nreq + tot + cb + 1; };
+  size_t need = 0;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
+    need = std::max(need, (cb * nrow * nreq + tot) * 32 + words(cb, tot) * 8 + 64);
+  }
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, need, &sc));
+  std::vector<u64> pack;
+  std::vector<uint8_t> back;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
+    E* const d_req = (E*)sc;
+    E* const d_dig = d_req + cb * nrow * nreq;
+    u64* const d_pack = (u64*)(d_dig + tot);
+    pack.assign(words(cb, tot), 0);
+    LfBatchPtrs pt{}, pl{};
+    size_t maxcnt = 0;
+    for (size_t b = 0; b < cb; ++b) {
+      const size_t g = b0 + b;
+      for (size_t j = 0; j < nreq; ++j) pack[b * nreq + j] = idx[g * nreq + j];
+      pack[cb * nreq + tot + b] = off[g] - off[b0];
+      maxcnt = std::max(maxcnt, off[g + 1] - off[g]);
+      pt.p[b] = pr[g]->d_T;
+      pl.p[b] = pr[g]->d_layers;
+    }
+    pack[cb * nreq + tot + cb] = tot;
+    for (size_t t = 0; t < tot; ++t) pack[cb * nreq + t] = nodes[off[b0] + t];
+    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(gather_columns256_batch_kernel, dim3(nblk(nrow * nreq), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)nrow, p.block_enc, p.dblock, pt,
+                       (const u64*)d_pack, (u32)nreq, d_req);
+    LF_HIP(c, hipGetLastError());
+    LF_TRY(lf_merkle_gather_batch(c, cb, ncols, pl, d_pack + cb * nreq, d_pack + cb * nreq + tot, maxcnt, d_dig));
+    back.resize((cb * nrow * nreq + tot) * 32);
+    LF_TRY(lfgpu_memcpy_d2h(c, back.data(), d_req, back.size()));
+    memcpy((uint8_t*)h_req + b0 * nrow * nreq * 32, back.data(), cb * nrow * nreq * 32);
+    const uint8_t* dig = back.data() + cb * nrow * nreq * 32;
+    for (size_t b = 0; b < cb; ++b) {
+      const size_t g = b0 + b, cnt = off[g + 1] - off[g];
+      if (cnt) memcpy(h_path + g * path_cap * 32, dig + (off[g] - off[b0]) * 32, cnt * 32);
+      npath[g] = cnt;
+      for (size_t j = 0; j < nreq; ++j) memcpy(h_nonces + (g * nreq + j) * 32, &pr[g]->nonces[32 * idx[g * nreq + j]], 32);
+    }
+  }
+  return LFGPU_OK;
+}
 }  // namespace
+
+// ---- lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256 (lfgpu.h): the provers of lfgpu_ligero_commit(field = P256)
+namespace {
+int lig256_handles(lfgpu_ctx* c, const char* who, lfgpu_ligero_prover* const* pr, size_t nb, Lig32** out) {
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is NULL", who, b);
+    LfLigeroView v;
+    lf_ligero_prover_view(pr[b], &v);
+    if (v.c != c) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu belongs to another context", who, b);
+    if (!v.lig256) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is over a 16-byte field (lfgpu_ligero_prove_batch / lfgpu_ligero_open_batch serve those)", who, b);
+    out[b] = lig32_of(v.lig256);
+  }
+  return LFGPU_OK;
+}
+}  // namespace
+extern "C" int lfgpu_ligero_prove_batch256(lfgpu_ctx* c, lfgpu_ligero_prover* const* pr, size_t nb, const void* h_u_ldt, const void* const* d_dense, size_t ndense,
+                                           const uint64_t* scale, const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse,
+                                           const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2) {
+  static const char* const who = "ligero_prove_batch256";
+  if (!c || !pr || !nsparse || !h_y_ldt || !h_y_dot || !h_y_q0 || !h_y_q2) return lf_fail(c, LFGPU_ERR_ARG, "%s: null argument", who);
+  Lig32* L[LFGPU_SC_BATCH_MAX];
+  LF_TRY(lig256_handles(c, who, pr, nb, L));
+  return lig256_prove_batch(c, who, L, nb, h_u_ldt, d_dense, ndense, scale, h_idx, h_val, nsparse, h_u_quad, h_y_ldt, h_y_dot, h_y_q0, h_y_q2);
+}
+extern "C" int lfgpu_ligero_open_batch256(lfgpu_ctx* c, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path,
+                                          size_t path_cap, size_t* npath) {
+  static const char* const who = "ligero_open_batch256";
+  if (!c || !pr || !idx || !h_req || !h_nonces || !npath) return lf_fail(c, LFGPU_ERR_ARG, "%s: null argument", who);
+  Lig32* L[LFGPU_SC_BATCH_MAX];
+  LF_TRY(lig256_handles(c, who, pr, nb, L));
+  return lig256_open_batch(c, who, L, nb, idx, h_req, h_nonces, h_path, path_cap, npath);
+}
 
 // ---- behind lfgpu_ligero_commit / low_degree_proof / dot_proof / quadratic_proof / open / tableau / free for field P256
 // (ligero.hip; declared in zkint.h): one GPU, all rows
@@ -2267,6 +2635,60 @@ struct P32 : zkp::Wire32 {
     LF_TRY(raw_eq2_256(c, F, logn, n, H0, H1, alpha, d_eq));
     if (npub) LF_TRY(lfgpu_memcpy_d2h(c, eq_in, d_eq, npub * 32));
     return LFGPU_OK;
+  }
+  // ---- the batch axis (zkp::prove_batch): B statements of one layer per call
+  typedef void (*round_batch_fn)(void* user, size_t hand, size_t rnd, size_t nb, const E (*ev)[3], E* chal);
+  static constexpr const char* kProveBatchName = "zk_prove_batch256";
+  // LFGPU_LIGERO_PROVE_BATCH256 [1] (read once per process): 0 = constraints, Ligero prove and opening per statement (prove_finish)
+  static int ligero_batch_switch() {
+    static const int on = getenv("LFGPU_LIGERO_PROVE_BATCH256") ? atoi(getenv("LFGPU_LIGERO_PROVE_BATCH256")) : 1;
+    return on;
+  }
+  static int eval_layer_batch(lfgpu_quad* q, size_t nb, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail) {
+    return lf256_eval_quad_batch_async(q, nb, d_W, ldw, d_V, ldv, d_fail);
+  }
+  // sumcheck_layer_batch256 spells its callback's elements as words: the template's callback is reached through a copy
+  struct TrampBatch {
+    round_batch_fn f;
+    void* user;
+    std::vector<E> ev, ch;
+  };
+  static void tramp_batch_cb(void* user, size_t hand, size_t rnd, size_t nb, const uint64_t (*ev)[3][4], uint64_t (*chal)[4]) {
+    TrampBatch* t = (TrampBatch*)user;
+    memcpy((void*)t->ev.data(), ev, nb * 96);
+    t->f(t->user, hand, rnd, nb, (const E(*)[3])t->ev.data(), t->ch.data());
+    memcpy(chal, t->ch.data(), nb * 32);
+  }
+  // G0 / G1: [nb][logv]; alpha, beta, bound_quad: [nb]; wc_in, wc_out: [nb][2]; g_out: [nb][2][logw]; d_W: statement b at b * ldw
+  static int sumcheck_layer_batch(lfgpu_quad* q, const F256& F, size_t nb, size_t logv, const E* G0, const E* G1, const E* alpha, const E* beta, size_t logw,
+                                  size_t nw, void* d_W, size_t ldw, const E* wc_in, round_batch_fn round, void* user, E* wc_out, E* g_out, E* bound_quad) {
+    lfgpu_ctx* c = q->c;
+    if (nw == 0 || logw > 40 || nw > ((size_t)1 << logw) || nw <= q->hmax || ldw < nw)  // (as sumcheck_layer256 and the kernel ABI check)
+      return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: nw must exceed the largest hand index and fit 2^logw and ldw");
+    if (logv > 40 || ((size_t)1 << logv) < q->nv) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: 2^logv < nv");
+    TrampBatch t{round, user, std::vector<E>(3 * nb), std::vector<E>(nb)};
+    return sumcheck_layer_batch256(q, F, nb, logv, G0, G1, alpha, beta, logw, nw, (const E*)d_W, ldw, wc_in, tramp_batch_cb, &t, wc_out, g_out, bound_quad);
+  }
+  // eq_table for nb statements in one upload and one launch chain: H0 / H1 [nb][logn], statement b's table at d_eq + b * n, its
+  // first npub entries to eq_in + b * npub in ONE read-back
+  static int eq_table_batch(lfgpu_ctx* c, const F256& F, size_t nb, size_t logn, size_t n, const E* H0, const E* H1, const E* alpha, E* d_eq, size_t npub,
+                            E* eq_in) {
+    const std::vector<E> no_beta(nb, e32_zero());  // the table's beta slot is bind_g's
+    const E* d_pts = nullptr;
+    LF_TRY(raw_eq2_256_batch(c, F, nb, logn, n, H0, H1, alpha, no_beta.data(), d_eq, &d_pts));
+    if (npub) {  // (without public inputs nothing is read: the tables are consumed in stream order by the dot proofs)
+      LF_HIP(c, hipMemcpy2DAsync(eq_in, npub * 32, d_eq, n * 32, npub * 32, nb, hipMemcpyDeviceToHost, c->stream));
+      LF_HIP(c, hipStreamSynchronize(c->stream));
+    }
+    return LFGPU_OK;
+  }
+  static int ligero_prove_batch(lfgpu_ctx* c, Lig* const* lp, size_t nb, const E* u_ldt, const E* const* d_dense, size_t ndense, const E* scale,
+                                const uint64_t* const* idx, const E* const* val, const size_t* nsparse, const E* u_quad, E* y_ldt, E* y_dot, E* y_q0, E* y_q2) {
+    return lig256_prove_batch(c, kProveBatchName, lp, nb, u_ldt, (const void* const*)d_dense, ndense, scale, idx, (const void* const*)val, nsparse, u_quad, y_ldt, y_dot,
+                              y_q0, y_q2);
+  }
+  static int ligero_open_batch(lfgpu_ctx* c, Lig* const* lp, size_t nb, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t cap, size_t* npath) {
+    return lig256_open_batch(c, kProveBatchName, lp, nb, idx, req, nonces, path, cap, npath);
   }
   static int low_degree(Lig* lp, const E* u, E* y) { return lig::low_degree(lp, L32(), u, y); }
   static int dot(Lig* lp, const E* d_dense, size_t ndense, const E& scale, const uint64_t* idx, const E* val, size_t nsparse, E* y) {
@@ -2441,6 +2863,108 @@ int zk256_prove(Zk256* z, const void* h_W, const lfgpu_transcript_ops* tso, int*
   return zkp::prove<P32>(z->c, z->C, P32(), z->st, z->lp, z->d_in.data(), z->d_V, z->h_V, eq_table, h_W, tso, ok);
 }
 int zk256_proof_write(const Zk256* z, uint8_t* buf, size_t cap, size_t* nbytes) { return zkp::proof_write_cached(z->c, P32(), z->C, z->st, buf, cap, nbytes); }
+
+// ------------------------------------------------------------------ ZkProver::prove for a batch of committed provers
+// What lfgpu_zk_batch (zk.hip) is for the 16-byte fields, over 32-byte elements: the batch owns what the lock-step needs nb_max
+// times -- the layers' input slabs (statement b of layer l at d_in[l] + b * ldw[l] elements), the outputs, one assert-zero flag
+// per statement, their pinned read-back and nb_max EQ tables over the inputs (the dense blocks of the batched dot proofs).  All
+// of it is allocated in zk256_batch_new and nothing is allocated or freed inside zk256_prove_batch (hipFree waits for every
+// stream of the device); the only device memory a call may allocate is the context's pooled scratch, which grows on the first
+// call at a shape.
+struct Zk256Batch {
+  lfgpu_ctx* c = nullptr;
+  const lfgpu_circuit* C = nullptr;
+  size_t nb_max = 0;
+  std::vector<void*> d_in;
+  std::vector<size_t> ldw;
+  // the sizes of the allocations, recorded here: the scrub at destruction does not look at the circuit handle (which the caller
+  // may have freed first)
+  std::vector<size_t> in_bytes;
+  void* d_V = nullptr;
+  size_t ldv = 0, v_bytes = 0;
+  int* d_fail = nullptr;
+  void* h_V = nullptr;
+  size_t h_bytes = 0;
+  void* d_eq = nullptr;  // [nb_max][ninputs]: functions of the challenges only, not scrubbed
+  ~Zk256Batch() {
+    // the slabs hold the wire values of every statement -- functions of the witnesses: scrubbed before the memory goes back
+    if (c) {
+      (void)hipSetDevice(c->device);
+      for (size_t l = 0; l < d_in.size(); ++l)
+        if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, in_bytes[l], c->stream);
+      if (d_V) (void)hipMemsetAsync(d_V, 0, v_bytes, c->stream);
+      (void)hipStreamSynchronize(c->stream);
+    }
+    for (void* p : d_in)
+      if (p) (void)hipFree(p);
+    if (d_V) (void)hipFree(d_V);
+    if (d_fail) (void)hipFree(d_fail);
+    if (d_eq) (void)hipFree(d_eq);
+    if (h_V) {
+      memset(h_V, 0, h_bytes);
+      (void)hipHostFree(h_V);
+    }
+  }
+};
+
+int zk256_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, Zk256Batch** out) {
+  std::unique_ptr<Zk256Batch> bt(new Zk256Batch());
+  bt->c = c;
+  bt->C = C;
+  bt->nb_max = nb_max;
+  LF_HIP(c, hipSetDevice(c->device));
+  auto pad2 = [](size_t n) { return (n + 1) & ~(size_t)1; };  // slabs start on 64-byte lines
+  const size_t nl = C->layers.size();
+  bt->d_in.assign(nl, nullptr);
+  bt->ldw.assign(nl, 0);
+  bt->in_bytes.assign(nl, 0);
+  auto alloc = [&](void** p, size_t bytes) {
+    if (hipMalloc(p, bytes) == hipSuccess) return true;
+    (void)hipGetLastError();
+    *p = nullptr;
+    return false;
+  };
+  for (size_t l = 0; l < nl; ++l) {
+    bt->ldw[l] = pad2(C->layers[l].nw);
+    bt->in_bytes[l] = nb_max * bt->ldw[l] * 32;
+    if (!alloc(&bt->d_in[l], bt->in_bytes[l])) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: %zu slabs of layer %zu (%zu bytes)", nb_max, l, bt->in_bytes[l]);
+  }
+  bt->ldv = pad2(C->info.nv);
+  bt->v_bytes = nb_max * bt->ldv * 32;
+  bt->h_bytes = bt->v_bytes + nb_max * sizeof(int);
+  if (!alloc(&bt->d_V, bt->v_bytes) || !alloc((void**)&bt->d_fail, nb_max * sizeof(int))) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: outputs");
+  if (hipHostMalloc(&bt->h_V, bt->h_bytes, hipHostMallocDefault) != hipSuccess) {
+    (void)hipGetLastError();
+    bt->h_V = nullptr;
+    return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: pinned outputs");
+  }
+  if (!alloc(&bt->d_eq, std::max<size_t>(nb_max * C->info.ninputs, 1) * 32)) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: %zu EQ tables over the inputs", nb_max);
+  LF_TRY(scb256_mailbox(c));  // the context's pinned mailbox of the batched sumcheck: here, not inside the first proof
+  *out = bt.release();
+  return LFGPU_OK;
+}
+void zk256_batch_free(Zk256Batch* bt) { delete bt; }
+
+int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_transcript_ops* const* ts, int* ok) {
+  lfgpu_ctx* c = bt->c;
+  for (size_t b = 0; b < nb; ++b) {
+    LF_TRY(ts256_ok(c, ts[b]));
+    if (!z[b]->lp) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: prover %zu must run commit before prove", b);
+  }
+  std::vector<P32> pol(nb);
+  std::vector<zkp::ProverState<P32>*> st(nb);
+  std::vector<Lig32*> lp(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    st[b] = &z[b]->st;
+    lp[b] = z[b]->lp;
+  }
+  auto eq_table = [&](E** d_eq) {  // the per-statement tail: the batch's first table, one statement after the other in stream order
+    *d_eq = (E*)bt->d_eq;
+    return (int)LFGPU_OK;
+  };
+  const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max, bt->d_eq};
+  return zkp::prove_batch<P32>(c, bt->C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
+}
 
 int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof, size_t proof_len, const void* h_pub,
                  const lfgpu_transcript_ops* tso, bool committed, int* ok, const char** why_out) {

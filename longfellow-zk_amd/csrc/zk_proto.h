@@ -21,8 +21,8 @@
 // build_constraints, prove and verify also call the device steps, which the .hip files add as static members:
 //   Lig, kProveName, host_field, kDeferGh, eval_layer, sumcheck_layer, bind_gh_all (+ gh_enqueue / gh_read when kDeferGh),
 //   eq_table, low_degree / dot / quadratic / open, verifier_ext.
-// prove_batch (B statements in lock-step; instantiated for the 16-byte policy only) also wants kProveBatchName, eval_layer_batch
-// and sumcheck_layer_batch.
+// prove_batch (B statements in lock-step; both policies) also wants kProveBatchName, eval_layer_batch, sumcheck_layer_batch,
+// eq_table_batch, ligero_prove_batch, ligero_open_batch and ligero_batch_switch (the A/B switch of the batched tail).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -1298,9 +1298,10 @@ int prove_batch(lfgpu_ctx* c, const lfgpu_circuit* C, const P* pol, ProverState<
   const double ms_sc = now_ms() - t0;
 
   // constraints, Ligero prove and open of the statements with a good witness: in three chains for all of them
-  // (prove_finish_batch), or with LFGPU_LIGERO_PROVE_BATCH=0 (read once per process; the A/B switch, the same bytes) per
-  // statement, one after the other, with the context's EQ table reused
-  static const int lig_batched = getenv("LFGPU_LIGERO_PROVE_BATCH") ? atoi(getenv("LFGPU_LIGERO_PROVE_BATCH")) : 1;
+  // (prove_finish_batch), or with the policy's switch at 0 (P::ligero_batch_switch: LFGPU_LIGERO_PROVE_BATCH for the 16-byte
+  // fields, LFGPU_LIGERO_PROVE_BATCH256 for Fp256Base, each read once per process; the A/B switch, the same bytes) per
+  // statement, one after the other, with the caller's EQ table reused
+  const int lig_batched = P::ligero_batch_switch();
   for (size_t b = 0; b < nb; ++b) {
     st[b]->ms[2] = ms_eval;
     st[b]->ms[3] = ms_sc;

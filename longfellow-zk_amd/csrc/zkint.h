@@ -84,3 +84,14 @@ struct LfLigeroView {
 void lf_ligero_prover_view(lfgpu_ligero_prover* pr, LfLigeroView* v);
 // K11 over 32-byte elements (quad.hip forwards field 1 here)
 int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail);
+// ... for nb statements in two launches (the asynchronous twin of lfgpu_eval_quad_batch256): statement b's wires at d_W + b * ldw,
+// its outputs at d_V + b * ldv (32-byte elements), its assert-zero failures ORed into d_fail[b]; arguments already checked
+int lf256_eval_quad_batch_async(lfgpu_quad* q, size_t nb, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail);
+// ---- zk256.hip: ZkProver::prove for a batch of committed Fp256Base provers (lfgpu_zk_batch256_new / lfgpu_zk_prove_batch256 /
+// lfgpu_zk_batch256_free of zk.hip, which checks the handles: non-null, one context and circuit, no communicator, no prover
+// twice).  zk256_prove_batch finds the remaining argument errors -- a prover that has not committed, a transcript without the
+// sized hooks -- before it enqueues anything or touches a transcript.
+struct Zk256Batch;
+int zk256_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, Zk256Batch** out);
+int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_transcript_ops* const* ts, int* ok);
+void zk256_batch_free(Zk256Batch* bt);
