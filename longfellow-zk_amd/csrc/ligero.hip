@@ -654,6 +654,76 @@ struct L16 : lig::Host16 {
   int column_leaves(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out) const {
     return lfgpu_column_leaves(c, field, nrow, ld, col0, ncols, d_T, d_nonces, d_out);
   }
+  // ---- the steps of lig::prove_batch / open_batch over cb statements (statement blockIdx.y of the batch kernels above)
+  // what the batch asks of 16-byte provers beyond lig::batch_core; a borrowed full-range slab will do
+  static int batch_ok(lfgpu_ctx* c, const char* who, lfgpu_ligero_prover* const* pr, size_t nb, L16* pol) {
+    for (size_t b = 0; b < nb; ++b)
+      if (pr[b]->field != pr[0]->field || pr[b]->k != pr[0]->k) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu has another field than prover 0", who, b);
+    if (pr[0]->field != LFGPU_FIELD_GF2_128 && pr[0]->field != LFGPU_FIELD_FP128)
+      return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: 16-byte fields only (Fp256Base provers take lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256)", who);
+    for (size_t b = 0; b < nb; ++b)
+      if (pr[b]->sharded || pr[b]->row_lo != 0 || pr[b]->row_hi != pr[b]->p.nrow || !pr[b]->d_T)
+        return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: prover %zu is sharded or holds a slab (the batch runs whole tableaux on one GPU)", who, b);
+    *pol = L16{{pr[0]->field, pr[0]->k, nullptr}};
+    return LFGPU_OK;
+  }
+  // Fp128: the rows of a chain's extension fit one launch (lf_fp_rs_rows_batch) and its convolution scratch stays below the cap
+  size_t batch_rs_cap(const lfgpu_ligero_param& p) const {
+    if (field != LFGPU_FIELD_FP128 || !p.nwqrow) return SIZE_MAX;
+    size_t P = 1;
+    while (P < p.dblock) P <<= 1;
+    return std::min<size_t>(65535 / p.nwqrow, LF_CB_SCRATCH_CAP / (p.nwqrow * P * 16));
+  }
+  int a_rows_dense_batch(lfgpu_ctx* c, size_t cb, size_t r, size_t w, size_t ld, const E* d_scale, const LfBatchPtrs& dense, size_t n, E* d_rows, size_t srows) const {
+    LIG_DISPATCH(field, a_rows_dense_batch_kernel, dim3((u32)((n + 255) / 256), (u32)cb), dim3(256), (u32)r, (u32)w, ld, d_scale, dense, n, d_rows, srows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  int a_rows_sparse_batch(lfgpu_ctx* c, size_t cb, size_t r, size_t w, size_t ld, const u64* d_idx, const E* d_val, const u64* d_off, size_t maxn, size_t nflat,
+                          E* d_rows, size_t srows) const {
+    LIG_DISPATCH(field, a_rows_sparse_batch_kernel, dim3((u32)((maxn + 255) / 256), (u32)cb), dim3(256), (u32)r, (u32)w, ld, d_idx, d_val, d_off, nflat, d_rows, srows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  // one launch for the chain; rows longer than the LDS-resident kernel / more rows than a launch takes: statement by statement
+  int rs_rows_batch(lfgpu_ctx* c, size_t cb, E* d_rows, size_t srows, size_t nrow, size_t n, size_t m, size_t ld) const {
+    E* rows[LFGPU_SC_BATCH_MAX];
+    for (size_t b = 0; b < cb; ++b) rows[b] = d_rows + b * srows;
+    int rc = LFGPU_ERR_UNSUPPORTED;
+    if (field == LFGPU_FIELD_GF2_128) rc = lf_gf_rs_rows_mixed_batch(c, k, cb, rows, nrow, n, n, 0, 0, m, ld);
+    else if (cb * nrow <= 65535) rc = lf_fp_rs_rows_batch(c, cb, rows, 0, nrow, n, m, ld);
+    if (rc != LFGPU_ERR_UNSUPPORTED) return rc;
+    for (size_t b = 0; b < cb; ++b) LF_TRY(rs_rows(c, nrow, n, m, rows[b], ld));
+    return LFGPU_OK;
+  }
+  // the dot proof and the low-degree proof as two launches: see rows_combo_batch_kernel
+  template <bool DOT, bool LDT>
+  void rows_combo_launch(lfgpu_ctx* c, size_t cb, const lfgpu_ligero_param& p, const LfBatchPtrs& T, const E* A, size_t sA, const E* u, E* y, size_t sy) const {
+    const size_t ld = p.block_enc;
+    const dim3 grid((u32)(((DOT ? p.dblock : p.block) + 63) / 64), (u32)cb);
+    if (field == LFGPU_FIELD_GF2_128)
+      hipLaunchKernelGGL((rows_combo_batch_kernel<FIELD_GF2_128, DOT, LDT>), grid, dim3(1024), 0, c->stream, (u32)p.nwqrow, p.dblock, p.block, T, ld, p.idot * ld,
+                         p.ildt * ld, p.iw * ld, A, sA, p.dblock, u, p.nwqrow, y, sy);
+    else
+      hipLaunchKernelGGL((rows_combo_batch_kernel<FIELD_FP128, DOT, LDT>), grid, dim3(1024), 0, c->stream, (u32)p.nwqrow, p.dblock, p.block, T, ld, p.idot * ld,
+                         p.ildt * ld, p.iw * ld, A, sA, p.dblock, u, p.nwqrow, y, sy);
+  }
+  int rows_combo_batch(lfgpu_ctx* c, size_t cb, const lfgpu_ligero_param& p, const LfBatchPtrs& T, const E* A, size_t sA, const E* u, E* y, size_t sy) const {
+    rows_combo_launch<true, false>(c, cb, p, T, A, sA, u, y, sy);
+    rows_combo_launch<false, true>(c, cb, p, T, A, sA, u, y, sy);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  int quad_combo_batch(lfgpu_ctx* c, size_t cb, const lfgpu_ligero_param& p, const LfBatchPtrs& T, const E* u, E* y, size_t sy) const {
+    const size_t ld = p.block_enc;
+    LIG_DISPATCH(field, quad_combo_batch_kernel, dim3((u32)((p.dblock + 255) / 256), (u32)cb), dim3(256), (u32)p.nqtriples, p.dblock, T, ld, p.iquad * ld, p.iq * ld, u,
+                 p.nqtriples, y, sy);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  int gather_columns_batch(lfgpu_ctx* c, size_t cb, size_t nrow, size_t ld, size_t col0, const LfBatchPtrs& T, const u64* d_idx, size_t nreq, E* d_req) const {
+    return lf_gather_columns_batch(c, cb, nrow, ld, col0, T, d_idx, nreq, d_req);
+  }
 };
 static L16 policy16(const lfgpu_ligero_prover* pr) { return L16{{pr->field, pr->k, nullptr}}; }
 // ... for a commit: with the subfield tables of the host layout (null for an unknown k)
@@ -975,249 +1045,15 @@ extern "C" int lfgpu_ligero_open(lfgpu_ligero_prover* pr, const size_t* idx, voi
 }
 
 // ------------------------------------------------------------------ LigeroProver::prove for nb committed provers of one shape
-// statements per launch chain: the chain's working set in scratch3 (Aext, the u vectors, the y vectors: `per` bytes a statement)
-// and the Fp128 convolution scratch of the A rows' extension stay below LF_CB_SCRATCH_CAP, the rows of a chain's Fp128 extension
-// fit one launch (lf_fp_rs_rows_batch); LFGPU_LP_CHUNK overrides (read once)
-static size_t ligero_prove_chunk(int field, const lfgpu_ligero_param& p, size_t nb, size_t per) {
-  static const long env = getenv("LFGPU_LP_CHUNK") ? atol(getenv("LFGPU_LP_CHUNK")) : 0;
-  size_t chunk = std::min(nb, std::max<size_t>(1, LF_CB_SCRATCH_CAP / std::max<size_t>(per, 1)));
-  if (field == LFGPU_FIELD_FP128 && p.nwqrow) {
-    size_t P = 1;
-    while (P < p.dblock) P <<= 1;
-    chunk = std::min(chunk, std::min<size_t>(65535 / p.nwqrow, LF_CB_SCRATCH_CAP / (p.nwqrow * P * 16)));
-  }
-  if (env > 0) chunk = std::min(chunk, (size_t)env);
-  return std::max<size_t>(chunk, 1);
-}
-// what both batched entry points ask of their provers
-static int ligero_batch_provers_ok(lfgpu_ctx* c, const char* who, lfgpu_ligero_prover* const* pr, size_t nb) {
-  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is NULL", who, b);
-    if (pr[b]->c != c) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu belongs to another context", who, b);
-    if (pr[b]->field != pr[0]->field || pr[b]->k != pr[0]->k || memcmp(&pr[b]->p, &pr[0]->p, sizeof(lfgpu_ligero_param)) != 0)
-      return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu has another field or lfgpu_ligero_param than prover 0", who, b);
-    for (size_t a = 0; a < b; ++a)
-      if (pr[a] == pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu appears twice", who, b);
-  }
-  if (pr[0]->field != LFGPU_FIELD_GF2_128 && pr[0]->field != LFGPU_FIELD_FP128)
-    return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: 16-byte fields only (Fp256Base provers take lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256)", who);
-  for (size_t b = 0; b < nb; ++b)
-    if (pr[b]->sharded || pr[b]->row_lo != 0 || pr[b]->row_hi != pr[b]->p.nrow || !pr[b]->d_T)
-      return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: prover %zu is sharded or holds a slab (the batch runs whole tableaux on one GPU)", who, b);
-  return LFGPU_OK;
-}
-
+// (lig::prove_batch / lig::open_batch, ligero_slab.h, over L16)
 extern "C" int lfgpu_ligero_prove_batch(lfgpu_ctx* c, lfgpu_ligero_prover* const* pr, size_t nb, const void* h_u_ldt, const void* const* d_dense,
                                         size_t ndense, const uint64_t* scale, const uint64_t* const* h_idx, const void* const* h_val,
                                         const size_t* nsparse, const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2) {
   if (!c || !pr || !nsparse || !h_y_ldt || !h_y_dot || !h_y_q0 || !h_y_q2) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: null argument");
-  LF_TRY(ligero_batch_provers_ok(c, "ligero_prove_batch", pr, nb));
-  const int field = pr[0]->field, k = pr[0]->k;
-  const lfgpu_ligero_param& p = pr[0]->p;
-  const size_t nwq = p.nwqrow, nqt = p.nqtriples, lda = p.dblock, ld = p.block_enc, nflat = nwq * p.w;
-  if ((nwq && !h_u_ldt) || (nqt && !h_u_quad) || ndense > nflat || (ndense && (!d_dense || !scale)))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: null challenge vector / dense block, or ndense > nwqrow * w");
-  if (nwq >> 31 || nqt >> 31) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: too many rows");
-  for (size_t b = 0; b < nb; ++b) {
-    if (ndense && !d_dense[b]) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: dense block of statement %zu is NULL", b);
-    if (nsparse[b] && (!h_idx || !h_val || !h_idx[b] || !h_val[b])) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: sparse list of statement %zu is NULL", b);
-    for (size_t t = 0; t < nsparse[b]; ++t) {
-      if (h_idx[b][t] >= nflat) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: sparse index out of range (statement %zu)", b);
-      if (t && h_idx[b][t] <= h_idx[b][t - 1]) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: sparse indices must be strictly increasing (statement %zu)", b);
-    }
-  }
-  // the working set of a chain of cb statements in scratch3, in elements: Aext [cb][nwq][dblock] | y [cb][block + 2 dblock] (y_ldt | y_dot |
-  // y_quad) | one uploaded block: u_ldt [cb][nwq] | u_quad [cb][nqt] | scale [cb] | val [tot] | idx [tot] (u64) | off [cb + 1] (u64)
-  const size_t sA = nwq * lda, sy = p.block + 2 * p.dblock;
-  const size_t chunk = ligero_prove_chunk(field, p, nb, (sA + sy + nwq + nqt + 1) * 16);
-  auto pack_elts = [&](size_t cb, size_t tot) { return cb * (nwq + nqt + 1) + tot + (tot + 1) / 2 + (cb + 2) / 2; };
-  size_t need = 0;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0);
-    size_t tot = 0;
-    for (size_t b = b0; b < b0 + cb; ++b) tot += nsparse[b];
-    need = std::max(need, (cb * (sA + sy) + pack_elts(cb, tot)) * 16 + 64);
-  }
-  LF_HIP(c, hipSetDevice(c->device));
-  // A dense block must not live in the scratch this call is about to overwrite.  Checked twice: against the buffer as it stands
-  // (growing it frees that memory, so a block inside it would dangle), and against the buffer after lf_scratch3 has grown it --
-  // the second refusal comes after an allocation, but still before anything is enqueued or written.  Only scratch3 is checked:
-  // the RS extension below also works through scratch and scratch2, but it runs after a_rows_dense_batch_kernel, the only reader
-  // of the dense blocks, in stream order -- as in lfgpu_ligero_dot_proof_sparse.
-  auto aliases = [&]() {
-    const uint8_t* lo = (const uint8_t*)c->scratch3;
-    const size_t span = c->scratch3_bytes;
-    for (size_t b = 0; b < nb && ndense && lo; ++b) {
-      const uint8_t* d = (const uint8_t*)d_dense[b];
-      if (d + ndense * 16 > lo && d < lo + span) return true;
-    }
-    return false;
-  };
-  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: a dense block aliases the call's scratch");
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, need, &sc));
-  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove_batch: a dense block aliases the call's scratch");
-  const elt_t* u_ldt = (const elt_t*)h_u_ldt;
-  const elt_t* u_quad = (const elt_t*)h_u_quad;
-  std::vector<elt_t> pack, y;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0);
-    size_t tot = 0, maxsp = 0;
-    for (size_t b = b0; b < b0 + cb; ++b) {
-      tot += nsparse[b];
-      maxsp = std::max(maxsp, nsparse[b]);
-    }
-    elt_t* const dAext = (elt_t*)sc;
-    elt_t* const dy = dAext + cb * sA;
-    elt_t* const d_pack = dy + cb * sy;
-    // the host image of the uploaded block (kept until the chain's read-back has synchronised)
-    pack.assign(pack_elts(cb, tot), elt_t{0, 0});
-    const size_t o_uq = cb * nwq, o_sc = o_uq + cb * nqt, o_val = o_sc + cb, o_idx = o_val + tot, o_off = o_idx + (tot + 1) / 2;
-    if (nwq) memcpy(pack.data(), u_ldt + b0 * nwq, cb * nwq * 16);
-    if (nqt) memcpy(pack.data() + o_uq, u_quad + b0 * nqt, cb * nqt * 16);
-    u64* const pk_idx = (u64*)(pack.data() + o_idx);
-    u64* const pk_off = (u64*)(pack.data() + o_off);
-    LfBatchPtrs pt{}, pd{};
-    size_t run = 0;
-    for (size_t b = 0; b < cb; ++b) {
-      const size_t g = b0 + b;
-      if (ndense) pack[o_sc + b] = elt_t{scale[2 * g], scale[2 * g + 1]};
-      pk_off[b] = run;
-      if (nsparse[g]) {
-        memcpy(pack.data() + o_val + run, h_val[g], nsparse[g] * 16);
-        memcpy(pk_idx + run, h_idx[g], nsparse[g] * 8);
-      }
-      run += nsparse[g];
-      pt.p[b] = pr[g]->d_T;
-      pd.p[b] = ndense ? const_cast<void*>(d_dense[g]) : nullptr;
-    }
-    pk_off[cb] = run;
-    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 16, hipMemcpyHostToDevice, c->stream));
-    const elt_t* const d_ul = d_pack;
-    const elt_t* const d_uq = d_pack + o_uq;
-    // inner_product_vector + layout_Aext of every statement: one memset, one dense and one sparse launch
-    if (cb * sA) LF_HIP(c, hipMemsetAsync(dAext, 0, cb * sA * 16, c->stream));
-    if (ndense)
-      LIG_DISPATCH(field, a_rows_dense_batch_kernel, dim3((u32)((ndense + 255) / 256), (u32)cb), dim3(256), (u32)p.r, (u32)p.w, lda,
-                   (const elt_t*)(d_pack + o_sc), pd, ndense, dAext, sA);
-    if (maxsp)
-      LIG_DISPATCH(field, a_rows_sparse_batch_kernel, dim3((u32)((maxsp + 255) / 256), (u32)cb), dim3(256), (u32)p.r, (u32)p.w, lda,
-                   (const u64*)(d_pack + o_idx), (const elt_t*)(d_pack + o_val), (const u64*)(d_pack + o_off), nflat, dAext, sA);
-    LF_HIP(c, hipGetLastError());
-    // the A rows from block to dblock values, in place (ld = dblock)
-    if (nwq) {
-      elt_t* rows[LFGPU_SC_BATCH_MAX];
-      for (size_t b = 0; b < cb; ++b) rows[b] = dAext + b * sA;
-      int rc = LFGPU_ERR_UNSUPPORTED;
-      if (field == LFGPU_FIELD_GF2_128) rc = lf_gf_rs_rows_mixed_batch(c, k, cb, rows, nwq, p.block, p.block, 0, 0, p.dblock, lda);
-      else if (cb * nwq <= 65535) rc = lf_fp_rs_rows_batch(c, cb, rows, 0, nwq, p.block, p.dblock, lda);
-      if (rc == LFGPU_ERR_UNSUPPORTED) {  // rows longer than the LDS-resident kernel / more rows than a launch takes: statement by statement
-        for (size_t b = 0; b < cb; ++b) LF_TRY(lf_rs_rows(c, field, k, nwq, p.block, p.dblock, rows[b], lda));
-        rc = LFGPU_OK;
-      }
-      LF_TRY(rc);
-    }
-    // dot proof, low-degree proof, quadratic proof (the first two as two launches: see rows_combo_batch_kernel)
-#define LIG_COMBO_DISPATCH(DOT, LDT, ncol)                                                                                                      \
-  do {                                                                                                                                          \
-    if (field == LFGPU_FIELD_GF2_128)                                                                                                           \
-      hipLaunchKernelGGL((rows_combo_batch_kernel<FIELD_GF2_128, DOT, LDT>), dim3((u32)(((ncol) + 63) / 64), (u32)cb), dim3(1024), 0, c->stream, \
-                         (u32)nwq, p.dblock, p.block, pt, ld, p.idot * ld, p.ildt * ld, p.iw * ld, (const elt_t*)dAext, sA, lda, d_ul, nwq, dy, sy); \
-    else                                                                                                                                        \
-      hipLaunchKernelGGL((rows_combo_batch_kernel<FIELD_FP128, DOT, LDT>), dim3((u32)(((ncol) + 63) / 64), (u32)cb), dim3(1024), 0, c->stream,   \
-                         (u32)nwq, p.dblock, p.block, pt, ld, p.idot * ld, p.ildt * ld, p.iw * ld, (const elt_t*)dAext, sA, lda, d_ul, nwq, dy, sy); \
-  } while (0)
-    LIG_COMBO_DISPATCH(true, false, p.dblock);
-    LIG_COMBO_DISPATCH(false, true, p.block);
-#undef LIG_COMBO_DISPATCH
-    LIG_DISPATCH(field, quad_combo_batch_kernel, dim3((u32)((p.dblock + 255) / 256), (u32)cb), dim3(256), (u32)nqt, p.dblock, pt, ld, p.iquad * ld, p.iq * ld,
-                 d_uq, nqt, dy + p.block + p.dblock, sy);
-    LF_HIP(c, hipGetLastError());
-    y.resize(cb * sy);
-    LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, cb * sy * 16));
-    for (size_t b = 0; b < cb; ++b) {  // the reference's sanity check (:335-337), as lfgpu_ligero_quadratic_proof makes it
-      const elt_t* yq = y.data() + b * sy + p.block + p.dblock;
-      for (size_t j = 0; j < p.w; ++j)
-        if (yq[p.r + j].lo | yq[p.r + j].hi) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero (statement %zu)", b0 + b);
-    }
-    for (size_t b = 0; b < cb; ++b) {
-      const elt_t* yb = y.data() + b * sy;
-      const size_t g = b0 + b;
-      memcpy((elt_t*)h_y_ldt + g * p.block, yb, p.block * 16);
-      memcpy((elt_t*)h_y_dot + g * p.dblock, yb + p.block, p.dblock * 16);
-      const elt_t* yq = yb + p.block + p.dblock;
-      memcpy((elt_t*)h_y_q0 + g * p.r, yq, p.r * 16);
-      memcpy((elt_t*)h_y_q2 + g * (p.dblock - p.block), yq + p.block, (p.dblock - p.block) * 16);
-    }
-  }
-  return LFGPU_OK;
+  return lig::prove_batch<L16>(c, "ligero_prove_batch", pr, nb, h_u_ldt, d_dense, ndense, scale, h_idx, h_val, nsparse, h_u_quad, h_y_ldt, h_y_dot, h_y_q0, h_y_q2);
 }
-
-// compute_req + MerkleCommitment::open for nb provers: the index lists of all statements in one upload, one column gather, one
-// digest gather, one read-back per chain
 extern "C" int lfgpu_ligero_open_batch(lfgpu_ctx* c, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx, void* h_req, uint8_t* h_nonces,
                                        uint8_t* h_path, size_t path_cap, size_t* npath) {
   if (!c || !pr || !idx || !h_req || !h_nonces || !npath) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open_batch: null argument");
-  LF_TRY(ligero_batch_provers_ok(c, "ligero_open_batch", pr, nb));
-  const int field = pr[0]->field;
-  const lfgpu_ligero_param& p = pr[0]->p;
-  const size_t nreq = p.nreq, nrow = p.nrow, ncols = p.block_ext;
-  if (nreq == 0) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open_batch: nreq = 0 (a proof with 0 leaves is not defined)");
-  for (size_t b = 0; b < nb; ++b)
-    if (pr[b]->nonces.size() != 32 * ncols || !pr[b]->d_layers) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open_batch: prover %zu holds no commitment", b);
-  // MerkleTree::generate_compressed_proof's walk per statement (it also rejects an index out of range or given twice)
-  std::vector<u64> nodes;
-  std::vector<size_t> off(nb + 1, 0);
-  for (size_t b = 0; b < nb; ++b) {
-    LF_TRY(lf_merkle_path_nodes(c, ncols, idx + b * nreq, nreq, nodes));
-    off[b + 1] = nodes.size();
-    if (off[b + 1] - off[b] > path_cap || (off[b + 1] > off[b] && !h_path)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_open_batch: path buffer too small (statement %zu)", b);
-  }
-  LF_HIP(c, hipSetDevice(c->device));
-  // a chain of cb statements in scratch3, in elements: req [cb][nrow][nreq] | digests [2 per node] | idx [cb][nreq] (u64) | nodes (u64) | off [cb + 1] (u64)
-  const size_t chunk = ligero_prove_chunk(field, p, nb, (nrow * nreq + nreq * (2 * p.mc_pathlen + 2)) * 16);
-  auto words = [&](size_t cb, size_t tot) { return cb * nreq + tot + cb + 1; };
-  size_t need = 0;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
-    need = std::max(need, (cb * nrow * nreq + 2 * tot + (words(cb, tot) + 1) / 2) * 16 + 64);
-  }
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, need, &sc));
-  std::vector<u64> pack;
-  std::vector<uint8_t> back;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
-    elt_t* const d_req = (elt_t*)sc;
-    elt_t* const d_dig = d_req + cb * nrow * nreq;
-    u64* const d_pack = (u64*)(d_dig + 2 * tot);
-    pack.assign(words(cb, tot), 0);
-    LfBatchPtrs pt{}, pl{};
-    size_t maxcnt = 0;
-    for (size_t b = 0; b < cb; ++b) {
-      const size_t g = b0 + b;
-      for (size_t j = 0; j < nreq; ++j) pack[b * nreq + j] = idx[g * nreq + j];
-      pack[cb * nreq + tot + b] = off[g] - off[b0];
-      maxcnt = std::max(maxcnt, off[g + 1] - off[g]);
-      pt.p[b] = pr[g]->d_T;
-      pl.p[b] = pr[g]->d_layers;
-    }
-    pack[cb * nreq + tot + cb] = tot;
-    for (size_t t = 0; t < tot; ++t) pack[cb * nreq + t] = nodes[off[b0] + t];
-    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
-    LF_TRY(lf_gather_columns_batch(c, cb, nrow, p.block_enc, p.dblock, pt, d_pack, nreq, d_req));
-    LF_TRY(lf_merkle_gather_batch(c, cb, ncols, pl, d_pack + cb * nreq, d_pack + cb * nreq + tot, maxcnt, d_dig));
-    back.resize((cb * nrow * nreq + 2 * tot) * 16);
-    LF_TRY(lfgpu_memcpy_d2h(c, back.data(), d_req, back.size()));
-    memcpy((uint8_t*)h_req + b0 * nrow * nreq * 16, back.data(), cb * nrow * nreq * 16);
-    const uint8_t* dig = back.data() + cb * nrow * nreq * 16;
-    for (size_t b = 0; b < cb; ++b) {
-      const size_t g = b0 + b, cnt = off[g + 1] - off[g];
-      if (cnt) memcpy(h_path + g * path_cap * 32, dig + (off[g] - off[b0]) * 32, cnt * 32);
-      npath[g] = cnt;
-      for (size_t j = 0; j < nreq; ++j) memcpy(h_nonces + (g * nreq + j) * 32, &pr[g]->nonces[32 * idx[g * nreq + j]], 32);
-    }
-  }
-  return LFGPU_OK;
+  return lig::open_batch<L16>(c, "ligero_open_batch", pr, nb, idx, h_req, h_nonces, h_path, path_cap, npath);
 }

@@ -19,10 +19,19 @@
 //   rs_rows        nrow rows of n values extended to m, in place
 //   rs_rows_mixed  a slab's three row groups in one launch where the width has such a kernel, else LFGPU_ERR_UNSUPPORTED
 //   column_leaves  the leaf digests of ncols columns
+// and for the batched prove and open of nb whole-tableau provers of one shape (prove_batch / open_batch; every vector is on the
+// device, cb statements of a chain at one stride each, tableaux and dense blocks as LfBatchPtrs; these only enqueue):
+//   batch_ok             what the width asks of the provers beyond batch_core; yields the policy
+//   batch_rs_cap         the most statements the encoder of a chain's A rows takes
+//   a_rows_dense_batch / a_rows_sparse_batch   a_rows of every statement, the sparse lists packed behind one another
+//   rs_rows_batch        the A rows of every statement extended in place
+//   rows_combo_batch     y_b = T_b[ildt] + sum_i u_b[i] T_b[iw + i] over block columns | T_b[idot] + sum_i A_b[i] T_b[iw + i] over dblock
+//   quad_combo_batch     quad_combo of every statement
+//   gather_columns_batch gather_columns of every statement, idx [cb][nreq]
 // The commit side: Slab::init / alloc build the record, extend_slab Reed-Solomon-encodes a fresh slab, commit_rows uploads a
 // slab's host image, encodes it and commits the columns (one GPU, or the sharded exchange).  What stays in the two files: the
-// entry points with their argument checks and their own layout call (ligero_layout.h; the sharded record / replay of the engine),
-// the batched entry points (each width its own: their chains differ in the Reed-Solomon step) and every kernel.
+// entry points with their null-argument checks and their own layout call (ligero_layout.h; the sharded record / replay of the
+// engine), each width's own demands on the provers of a batch, and every kernel.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -460,6 +469,230 @@ int commit_rows(Slab<typename L::E>* pr, const L& pol, const typename L::E* H, d
   const int rc = run();
   if (rc) (void)hipStreamSynchronize(c->stream);  // a copy out of H may still be pending
   return rc;
+}
+
+// ---- LigeroProver::prove for nb committed provers of one shape in one chain of dispatches (lfgpu_ligero_prove_batch / _open_batch
+// and their 256 twins, and the ZK drivers).  P is the prover record: Slab<E> or a type derived from it.  Host vectors come and go as
+// bytes (the C ABI's arrays are 8-byte aligned words, 32-byte elements want 16).
+// What both calls ask of their provers whatever the width, found before anything is enqueued; the width's own demands follow
+// (L::batch_ok, which also yields the policy: the 16-byte one carries the provers' field).
+template <class P>
+int batch_core(lfgpu_ctx* c, const char* who, P* const* pr, size_t nb) {
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is NULL", who, b);
+    if (pr[b]->c != c) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu belongs to another context", who, b);
+    if (memcmp(&pr[b]->p, &pr[0]->p, sizeof(lfgpu_ligero_param)) != 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu has another lfgpu_ligero_param than prover 0", who, b);
+    for (size_t a = 0; a < b; ++a)
+      if (pr[a] == pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu appears twice", who, b);
+  }
+  return LFGPU_OK;
+}
+// statements per launch chain: the chain's working set in scratch3 (`per` bytes a statement) stays below LF_CB_SCRATCH_CAP, and the
+// chain within what the encoder of its A rows takes (rs_cap = L::batch_rs_cap); LFGPU_LP_CHUNK overrides (read once)
+inline size_t batch_chunk(size_t nb, size_t per, size_t rs_cap) {
+  static const long env = getenv("LFGPU_LP_CHUNK") ? atol(getenv("LFGPU_LP_CHUNK")) : 0;
+  size_t chunk = std::min(std::min(nb, rs_cap), std::max<size_t>(1, LF_CB_SCRATCH_CAP / std::max<size_t>(per, 1)));
+  if (env > 0) chunk = std::min(chunk, (size_t)env);
+  return std::max<size_t>(chunk, 1);
+}
+// elements that hold n u64 words behind one another (the index lists and offset tables of the uploaded blocks)
+template <class E>
+constexpr size_t u64_elts(size_t n) {
+  return (n * 8 + sizeof(E) - 1) / sizeof(E);
+}
+
+// low_degree_proof, dot_proof (A = scale * dense + the sparse terms, as dot builds it) and quadratic_proof of nb provers: per chain
+// one upload, one memset, one dense and one sparse launch, the Reed-Solomon extension of the chain's A rows, the three
+// combinations, one read-back.  Arguments as lfgpu_ligero_prove_batch (lfgpu.h).
+template <class L, class P>
+int prove_batch(lfgpu_ctx* c, const char* who, P* const* pr, size_t nb, const void* h_u_ldt, const void* const* d_dense, size_t ndense, const void* scale,
+                const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse, const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0,
+                void* h_y_q2) {
+  using E = typename L::E;
+  constexpr size_t esz = sizeof(E);
+  L pol{};
+  LF_TRY(batch_core(c, who, pr, nb));
+  LF_TRY(L::batch_ok(c, who, pr, nb, &pol));
+  const lfgpu_ligero_param& p = pr[0]->p;
+  const size_t nwq = p.nwqrow, nqt = p.nqtriples, lda = p.dblock, nflat = nwq * p.w, ymid = p.dblock - p.block;
+  if ((nwq && !h_u_ldt) || (nqt && !h_u_quad) || ndense > nflat || (ndense && (!d_dense || !scale)))
+    return lf_fail(c, LFGPU_ERR_ARG, "%s: null challenge vector / dense block, or ndense > nwqrow * w", who);
+  if (nwq >> 31 || nqt >> 31 || p.w >> 32 || p.r >> 32) return lf_fail(c, LFGPU_ERR_ARG, "%s: too many rows", who);  // the kernels take them as u32
+  for (size_t b = 0; b < nb; ++b) {
+    if (ndense && !d_dense[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: dense block of statement %zu is NULL", who, b);
+    if (nsparse[b] && (!h_idx || !h_val || !h_idx[b] || !h_val[b])) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse list of statement %zu is NULL", who, b);
+    for (size_t t = 0; t < nsparse[b]; ++t) {
+      if (h_idx[b][t] >= nflat) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse index out of range (statement %zu)", who, b);
+      if (t && h_idx[b][t] <= h_idx[b][t - 1]) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse indices must be strictly increasing (statement %zu)", who, b);
+    }
+  }
+  // the working set of a chain of cb statements in scratch3, in elements: Aext [cb][nwq][dblock] | y [cb][block + 2 dblock] (y_ldt | y_dot |
+  // y_quad) | one uploaded block: u_ldt [cb][nwq] | u_quad [cb][nqt] | scale [cb] | val [tot] | idx [tot] (u64) | off [cb + 1] (u64).
+  // The uploaded block stays in scratch3: scratch2 is the Reed-Solomon encoder's work space.
+  const size_t sA = nwq * lda, sy = p.block + 2 * p.dblock;
+  const size_t chunk = batch_chunk(nb, (sA + sy + nwq + nqt + 1) * esz, pol.batch_rs_cap(p));
+  auto pack_elts = [&](size_t cb, size_t tot) { return cb * (nwq + nqt + 1) + tot + u64_elts<E>(tot) + u64_elts<E>(cb + 1); };
+  size_t need = 0;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0);
+    size_t tot = 0;
+    for (size_t b = b0; b < b0 + cb; ++b) tot += nsparse[b];
+    need = std::max(need, (cb * (sA + sy) + pack_elts(cb, tot)) * esz + 64);
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+  // A dense block must not live in the scratch this call is about to overwrite.  Checked twice: against the buffer as it stands
+  // (growing it frees that memory, so a block inside it would dangle), and against the buffer after lf_scratch3 has grown it --
+  // the second refusal comes after an allocation, but still before anything is enqueued or written.  Only scratch3 is checked:
+  // the RS extension below also works through scratch and scratch2, but it runs after a_rows_dense_batch, the only reader of the
+  // dense blocks, in stream order -- as in dot.
+  auto aliases = [&]() {
+    const uint8_t* lo = (const uint8_t*)c->scratch3;
+    const size_t span = c->scratch3_bytes;
+    for (size_t b = 0; b < nb && ndense && lo; ++b) {
+      const uint8_t* d = (const uint8_t*)d_dense[b];
+      if (d + ndense * esz > lo && d < lo + span) return true;
+    }
+    return false;
+  };
+  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "%s: a dense block aliases the call's scratch", who);
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, need, &sc));
+  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "%s: a dense block aliases the call's scratch", who);
+  std::vector<E> pack, y;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0);
+    size_t tot = 0, maxsp = 0;
+    for (size_t b = b0; b < b0 + cb; ++b) {
+      tot += nsparse[b];
+      maxsp = std::max(maxsp, nsparse[b]);
+    }
+    E* const dAext = (E*)sc;
+    E* const dy = dAext + cb * sA;
+    E* const d_pack = dy + cb * sy;
+    // the host image of the uploaded block (kept until the chain's read-back has synchronised)
+    pack.assign(pack_elts(cb, tot), E{});
+    const size_t o_uq = cb * nwq, o_sc = o_uq + cb * nqt, o_val = o_sc + cb, o_idx = o_val + tot, o_off = o_idx + u64_elts<E>(tot);
+    if (nwq) memcpy((void*)pack.data(), (const uint8_t*)h_u_ldt + b0 * nwq * esz, cb * nwq * esz);
+    if (nqt) memcpy((void*)(pack.data() + o_uq), (const uint8_t*)h_u_quad + b0 * nqt * esz, cb * nqt * esz);
+    if (ndense) memcpy((void*)(pack.data() + o_sc), (const uint8_t*)scale + b0 * esz, cb * esz);
+    u64* const pk_idx = (u64*)(pack.data() + o_idx);
+    u64* const pk_off = (u64*)(pack.data() + o_off);
+    LfBatchPtrs pt{}, pd{};
+    size_t run = 0;
+    for (size_t b = 0; b < cb; ++b) {
+      const size_t g = b0 + b;
+      pk_off[b] = run;
+      if (nsparse[g]) {
+        memcpy((void*)(pack.data() + o_val + run), h_val[g], nsparse[g] * esz);
+        memcpy(pk_idx + run, h_idx[g], nsparse[g] * 8);
+      }
+      run += nsparse[g];
+      pt.p[b] = pr[g]->d_T;
+      pd.p[b] = ndense ? const_cast<void*>(d_dense[g]) : nullptr;
+    }
+    pk_off[cb] = run;
+    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * esz, hipMemcpyHostToDevice, c->stream));
+    // inner_product_vector + layout_Aext of every statement: one memset, one dense and one sparse launch
+    if (cb * sA) LF_HIP(c, hipMemsetAsync(dAext, 0, cb * sA * esz, c->stream));
+    if (ndense) LF_TRY(pol.a_rows_dense_batch(c, cb, p.r, p.w, lda, d_pack + o_sc, pd, ndense, dAext, sA));
+    if (maxsp) LF_TRY(pol.a_rows_sparse_batch(c, cb, p.r, p.w, lda, (const u64*)(d_pack + o_idx), d_pack + o_val, (const u64*)(d_pack + o_off), maxsp, nflat, dAext, sA));
+    // the A rows from block to dblock values, in place (ld = dblock)
+    if (nwq) LF_TRY(pol.rs_rows_batch(c, cb, dAext, sA, nwq, p.block, p.dblock, lda));
+    // dot proof and low-degree proof (y_ldt | y_dot of a statement), quadratic proof
+    LF_TRY(pol.rows_combo_batch(c, cb, p, pt, dAext, sA, d_pack, dy, sy));
+    LF_TRY(pol.quad_combo_batch(c, cb, p, pt, d_pack + o_uq, dy + p.block + p.dblock, sy));
+    y.resize(cb * sy);
+    LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, cb * sy * esz));  // all three y vectors of all statements of the chain
+    for (size_t b = 0; b < cb; ++b) {  // the reference's sanity check (:335-337), as quadratic makes it
+      const E* yq = y.data() + b * sy + p.block + p.dblock;
+      for (size_t j = 0; j < p.w; ++j)
+        if (!pol.is_zero(yq[p.r + j])) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero (statement %zu)", b0 + b);
+    }
+    for (size_t b = 0; b < cb; ++b) {
+      const E* yb = y.data() + b * sy;
+      const size_t g = b0 + b;
+      memcpy((uint8_t*)h_y_ldt + g * p.block * esz, yb, p.block * esz);
+      memcpy((uint8_t*)h_y_dot + g * p.dblock * esz, yb + p.block, p.dblock * esz);
+      const E* yq = yb + p.block + p.dblock;
+      memcpy((uint8_t*)h_y_q0 + g * p.r * esz, yq, p.r * esz);
+      memcpy((uint8_t*)h_y_q2 + g * ymid * esz, yq + p.block, ymid * esz);
+    }
+  }
+  return LFGPU_OK;
+}
+
+// compute_req + MerkleCommitment::open for nb provers: per chain the index lists of all statements in one upload, one column
+// gather, one digest gather (merkle.hip's: digests do not know the field) and one read-back of the columns and the digests, which
+// stand behind one another.  idx [nb][nreq]; h_req [nb][nrow][nreq]; statement b's path at h_path + b * path_cap * 32.
+template <class L, class P>
+int open_batch(lfgpu_ctx* c, const char* who, P* const* pr, size_t nb, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap,
+               size_t* npath) {
+  using E = typename L::E;
+  constexpr size_t esz = sizeof(E), dig = 32 / esz;  // elements per digest
+  L pol{};
+  LF_TRY(batch_core(c, who, pr, nb));
+  LF_TRY(L::batch_ok(c, who, pr, nb, &pol));
+  const lfgpu_ligero_param& p = pr[0]->p;
+  const size_t nreq = p.nreq, nrow = p.nrow, ncols = p.block_ext;
+  if (nreq == 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: nreq = 0 (a proof with 0 leaves is not defined)", who);
+  if ((nrow * nreq) >> 32) return lf_fail(c, LFGPU_ERR_ARG, "%s: nrow * nreq does not fit 32 bits", who);
+  for (size_t b = 0; b < nb; ++b)
+    if (pr[b]->nonces.size() != 32 * ncols || !pr[b]->d_layers) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu holds no commitment", who, b);
+  // MerkleTree::generate_compressed_proof's walk per statement (it also rejects an index out of range or given twice)
+  std::vector<u64> nodes;
+  std::vector<size_t> off(nb + 1, 0);
+  for (size_t b = 0; b < nb; ++b) {
+    LF_TRY(lf_merkle_path_nodes(c, ncols, idx + b * nreq, nreq, nodes));
+    off[b + 1] = nodes.size();
+    if (off[b + 1] - off[b] > path_cap || (off[b + 1] > off[b] && !h_path)) return lf_fail(c, LFGPU_ERR_ARG, "%s: path buffer too small (statement %zu)", who, b);
+  }
+  LF_HIP(c, hipSetDevice(c->device));
+  // a chain of cb statements in scratch3: req [cb][nrow][nreq] | digests [32 bytes per node] | idx [cb][nreq] (u64) | nodes (u64) | off [cb + 1] (u64)
+  const size_t chunk = batch_chunk(nb, nrow * nreq * esz + nreq * (p.mc_pathlen + 1) * 32, pol.batch_rs_cap(p));
+  auto words = [&](size_t cb, size_t tot) { return cb * nreq + tot + cb + 1; };
+  size_t need = 0;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
+    need = std::max(need, (cb * nrow * nreq + dig * tot + u64_elts<E>(words(cb, tot))) * esz + 64);
+  }
+  void* sc = nullptr;
+  LF_TRY(lf_scratch3(c, need, &sc));
+  std::vector<u64> pack;
+  std::vector<uint8_t> back;
+  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
+    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
+    E* const d_req = (E*)sc;
+    E* const d_dig = d_req + cb * nrow * nreq;
+    u64* const d_pack = (u64*)(d_dig + dig * tot);
+    pack.assign(words(cb, tot), 0);
+    LfBatchPtrs pt{}, pl{};
+    size_t maxcnt = 0;
+    for (size_t b = 0; b < cb; ++b) {
+      const size_t g = b0 + b;
+      for (size_t j = 0; j < nreq; ++j) pack[b * nreq + j] = idx[g * nreq + j];
+      pack[cb * nreq + tot + b] = off[g] - off[b0];
+      maxcnt = std::max(maxcnt, off[g + 1] - off[g]);
+      pt.p[b] = pr[g]->d_T;
+      pl.p[b] = pr[g]->d_layers;
+    }
+    pack[cb * nreq + tot + cb] = tot;
+    for (size_t t = 0; t < tot; ++t) pack[cb * nreq + t] = nodes[off[b0] + t];
+    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
+    LF_TRY(pol.gather_columns_batch(c, cb, nrow, p.block_enc, p.dblock, pt, d_pack, nreq, d_req));
+    LF_TRY(lf_merkle_gather_batch(c, cb, ncols, pl, d_pack + cb * nreq, d_pack + cb * nreq + tot, maxcnt, d_dig));
+    back.resize(cb * nrow * nreq * esz + tot * 32);
+    LF_TRY(lfgpu_memcpy_d2h(c, back.data(), d_req, back.size()));
+    memcpy((uint8_t*)h_req + b0 * nrow * nreq * esz, back.data(), cb * nrow * nreq * esz);
+    const uint8_t* digests = back.data() + cb * nrow * nreq * esz;
+    for (size_t b = 0; b < cb; ++b) {
+      const size_t g = b0 + b, cnt = off[g + 1] - off[g];
+      if (cnt) memcpy(h_path + g * path_cap * 32, digests + (off[g] - off[b0]) * 32, cnt * 32);
+      npath[g] = cnt;
+      for (size_t j = 0; j < nreq; ++j) memcpy(h_nonces + (g * nreq + j) * 32, &pr[g]->nonces[32 * idx[g * nreq + j]], 32);
+    }
+  }
+  return LFGPU_OK;
 }
 }  // namespace
 }  // namespace lig

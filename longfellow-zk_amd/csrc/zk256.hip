@@ -11,7 +11,7 @@
 //   driver                  ZkProver::commit (lib/zk/zk_prover.h:72-96) here; prove, verifier_constraints, ZkProof::write / read
 //                           and the verifier are csrc/zk_proto.h, instantiated with the policy P32 at the end of this file
 //   batch                   B provers in lock-step: zkp::prove_batch<P32> (zk_proto.h) over the *_batch kernels here, Zk256Batch,
-//                           lig256_prove_batch / lig256_open_batch (lfgpu_zk_prove_batch256, lfgpu_ligero_prove_batch256 / _open_batch256)
+//                           lig::prove_batch / open_batch over L32 (lfgpu_zk_prove_batch256, lfgpu_ligero_prove_batch256 / _open_batch256)
 // Sums over many terms (run sums of bind_g, the QW scatter) add the 32-bit limbs of canonical residues into 64-bit integer
 // accumulators with atomics and reduce once (fp256_reduce_limbs): exact and independent of arrival order, as for Fp128.
 // Row extension and column hashing are csrc/p256.hip.
@@ -1272,43 +1272,61 @@ __global__ __launch_bounds__(G256_THREADS) void grid256_layer_kernel(Grid256 a) 
   }
 }
 
-// ---- Ligero row combinations (ligero.hip / sumcheck.hip, over 32-byte elements)
-// y[j] += sum_i u[i] T[i][j]: 64 columns x 4 row slices per workgroup
-__global__ __launch_bounds__(256) void rows_axpy256_kernel(u32 nrows, size_t n, E* __restrict__ y, const E* __restrict__ u, const E* __restrict__ T, size_t ld) {
-  __shared__ E part[4][64];
+// ---- Ligero row combinations (ligero.hip / sumcheck.hip, over 32-byte elements).  Every kernel has a batch twin (lig::prove_batch /
+// open_batch through L32): statement blockIdx.y.  The B tableaux are the provers' own buffers and the dense blocks the caller's,
+// so their base pointers come as ONE by-value argument indexed by the (wave-uniform) statement -- scalar loads from the kernarg
+// segment (LfBatchPtrs, ctx.h); what the call owns (the A rows, the challenge vectors, the y vectors, the gathered columns) stands
+// at one stride per statement.  Tableau rows are given as element offsets into a statement's tableau (o_*).  A pair shares one
+// body, so the arithmetic per entry is the same in the same order.
+// y[j] = y0[j] + sum_i f_i[j] T[i][j] with f_i[j] = A[i][j] (VEC: dot_proof, Blas::vaxpy blas.h:71-78) or u[i] (low_degree_proof):
+// 64 columns x 4 row slices per workgroup, folded through LDS.  y0 may be y itself (rows_axpy256_kernel), so neither is __restrict__.
+template <bool VEC>
+__device__ __forceinline__ void rows_combo256_body(u32 nrows, size_t n, const E* y0, const E* __restrict__ f, size_t ldf, const E* __restrict__ T, size_t ld, E* y,
+                                                   E (*part)[64]) {
   const u32 col = threadIdx.x & 63, slice = threadIdx.x >> 6;
   const size_t j = (size_t)blockIdx.x * 64 + col;
   E acc = e32_zero();
   if (j < n)
-    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&T[(size_t)i * ld + j]), ld32(&u[i])));
+    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&T[(size_t)i * ld + j]), ld32(VEC ? &f[(size_t)i * ldf + j] : &f[i])));
   part[slice][col] = acc;
   __syncthreads();
   if (slice == 0 && j < n) {
-    acc = ld32(&y[j]);
+    acc = ld32(&y0[j]);
     for (u32 k = 0; k < 4; ++k) acc = fp256_add(acc, part[k][col]);
     st32(&y[j], acc);
   }
 }
-// y[j] = T0[j] + sum_i A[i][j] T[i][j]   (dot_proof, Blas::vaxpy blas.h:71-78)
+// y[j] += sum_i u[i] T[i][j]
+__global__ __launch_bounds__(256) void rows_axpy256_kernel(u32 nrows, size_t n, E* __restrict__ y, const E* __restrict__ u, const E* __restrict__ T, size_t ld) {
+  __shared__ E part[4][64];
+  rows_combo256_body<false>(nrows, n, y, u, 0, T, ld, y, part);
+}
+// y[j] = T0[j] + sum_i A[i][j] T[i][j]
 __global__ __launch_bounds__(256) void rows_vaxpy256_kernel(u32 nrows, size_t n, const E* __restrict__ T0, const E* __restrict__ A, size_t lda,
                                                             const E* __restrict__ T, size_t ld, E* __restrict__ y) {
   __shared__ E part[4][64];
-  const u32 col = threadIdx.x & 63, slice = threadIdx.x >> 6;
-  const size_t j = (size_t)blockIdx.x * 64 + col;
-  E acc = e32_zero();
-  if (j < n)
-    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&T[(size_t)i * ld + j]), ld32(&A[(size_t)i * lda + j])));
-  part[slice][col] = acc;
-  __syncthreads();
-  if (slice == 0 && j < n) {
-    acc = ld32(&T0[j]);
-    for (u32 k = 0; k < 4; ++k) acc = fp256_add(acc, part[k][col]);
-    st32(&y[j], acc);
-  }
+  rows_combo256_body<true>(nrows, n, T0, A, lda, T, ld, y, part);
+}
+// dot proof: y_b[j] = T_b[idot][j] + sum_i A_b[i][j] T_b[iw + i][j], j < n = dblock
+__global__ __launch_bounds__(256) void rows_vaxpy256_batch_kernel(u32 nrows, size_t n, LfBatchPtrs T, size_t ld, size_t o_dot, size_t o_w, const E* __restrict__ A,
+                                                                  size_t s_A, size_t lda, E* __restrict__ y, size_t s_y) {
+  __shared__ E part[4][64];
+  const size_t b = blockIdx.y;
+  const E* Tb = (const E*)T.p[b];
+  rows_combo256_body<true>(nrows, n, Tb + o_dot, A + b * s_A, lda, Tb + o_w, ld, y + b * s_y, part);
+}
+// low-degree proof: y_b[j] = T_b[ildt][j] + sum_i u_b[i] T_b[iw + i][j], j < n = block (the single path copies the ILDT row into
+// y first and rows_axpy256_kernel adds to it: the same sum in the same order); u_b at u + b * s_u
+__global__ __launch_bounds__(256) void rows_axpy256_batch_kernel(u32 nrows, size_t n, LfBatchPtrs T, size_t ld, size_t o_ldt, size_t o_w, const E* __restrict__ u,
+                                                                 size_t s_u, E* __restrict__ y, size_t s_y) {
+  __shared__ E part[4][64];
+  const size_t b = blockIdx.y;
+  const E* Tb = (const E*)T.p[b];
+  rows_combo256_body<false>(nrows, n, Tb + o_ldt, u + b * s_u, 0, Tb + o_w, ld, y + b * s_y, part);
 }
 // y[j] = Tq[j] + sum_i u[i] (z_i[j] - x_i[j] y_i[j])   (quadratic_proof :311-333)
-__global__ __launch_bounds__(Z_THREADS) void quad_combo256_kernel(u32 nt, size_t n, const E* __restrict__ Tq, const E* __restrict__ u, const E* __restrict__ X,
-                                                                  const E* __restrict__ Y, const E* __restrict__ Zr, size_t ld, E* __restrict__ y) {
+__device__ __forceinline__ void quad_combo256_body(u32 nt, size_t n, const E* __restrict__ Tq, const E* __restrict__ u, const E* __restrict__ X, const E* __restrict__ Y,
+                                                   const E* __restrict__ Zr, size_t ld, E* __restrict__ y) {
   const size_t j = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
   if (j >= n) return;
   E acc = ld32(&Tq[j]);
@@ -1318,7 +1336,29 @@ __global__ __launch_bounds__(Z_THREADS) void quad_combo256_kernel(u32 nt, size_t
   }
   st32(&y[j], acc);
 }
-// rows[i][r + j] = scale * dense[i w + j]; then rows[pos(idx)] += val (inner_product_vector + layout_Aext, ligero_param.h:382-430)
+__global__ __launch_bounds__(Z_THREADS) void quad_combo256_kernel(u32 nt, size_t n, const E* __restrict__ Tq, const E* __restrict__ u, const E* __restrict__ X,
+                                                                  const E* __restrict__ Y, const E* __restrict__ Zr, size_t ld, E* __restrict__ y) {
+  quad_combo256_body(nt, n, Tq, u, X, Y, Zr, ld, y);
+}
+// statement blockIdx.y: row IQUAD (o_quad) and the triples' rows x | y | z, nt rows apart from o_x on, of its own tableau; u_b = u + b * s_u
+__global__ __launch_bounds__(Z_THREADS) void quad_combo256_batch_kernel(u32 nt, size_t n, LfBatchPtrs T, size_t ld, size_t o_quad, size_t o_x, const E* __restrict__ u,
+                                                                        size_t s_u, E* __restrict__ y, size_t s_y) {
+  const size_t b = blockIdx.y;
+  const E* Tb = (const E*)T.p[b];
+  const E* X = Tb + o_x;
+  const E* Y = X + (size_t)nt * ld;
+  quad_combo256_body(nt, n, Tb + o_quad, u + b * s_u, X, Y, Y + (size_t)nt * ld, ld, y + b * s_y);
+}
+// rows[i][r + j] = scale * dense[i w + j]; then rows[pos(idx)] += val (inner_product_vector + layout_Aext, ligero_param.h:382-430).
+// No bound on idx in the kernels: the host has checked every list against nwqrow * w (lig::a_rows, lig::prove_batch).
+__device__ __forceinline__ void a_rows_sparse256_body(u32 r, u32 w, size_t ld, const u64* __restrict__ idx, const E* __restrict__ val, size_t o, size_t n,
+                                                      E* __restrict__ rows) {  // entries [o, o + n) of the lists
+  const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
+  if (t >= n) return;
+  const u64 f = idx[o + t];
+  E* dst = &rows[(f / w) * ld + r + f % w];
+  st32(dst, fp256_add(ld32(dst), ld32(&val[o + t])));
+}
 __global__ __launch_bounds__(Z_THREADS) void a_rows_dense256_kernel(u32 r, u32 w, size_t ld, E scale, const E* __restrict__ dense, size_t n, E* __restrict__ rows) {
   const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
   if (t >= n) return;
@@ -1327,26 +1367,10 @@ __global__ __launch_bounds__(Z_THREADS) void a_rows_dense256_kernel(u32 r, u32 w
 }
 __global__ __launch_bounds__(Z_THREADS) void a_rows_sparse256_kernel(u32 r, u32 w, size_t ld, const u64* __restrict__ idx, const E* __restrict__ val, size_t n,
                                                                      E* __restrict__ rows) {
-  const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
-  if (t >= n) return;
-  const size_t i = idx[t] / w, j = idx[t] % w;
-  E* dst = &rows[i * ld + r + j];
-  st32(dst, fp256_add(ld32(dst), ld32(&val[t])));
+  a_rows_sparse256_body(r, w, ld, idx, val, 0, n, rows);
 }
-__global__ __launch_bounds__(Z_THREADS) void gather_columns256_kernel(u32 nrow, size_t ld, size_t col0, const E* __restrict__ T, const u64* __restrict__ idx,
-                                                                      u32 nreq, E* __restrict__ req) {
-  const u32 t = blockIdx.x * Z_THREADS + threadIdx.x;
-  if (t >= nrow * nreq) return;
-  const u32 i = t / nreq, j = t % nreq;
-  st32(&req[t], ld32(&T[(size_t)i * ld + col0 + idx[j]]));
-}
-
-// ---- the batch twins of the six kernels above (lig256_prove_batch / lig256_open_batch): statement blockIdx.y.  The B tableaux
-// are the provers' own buffers and the dense blocks the caller's, so their base pointers come as ONE by-value argument indexed by
-// the (wave-uniform) statement -- scalar loads from the kernarg segment (LfBatchPtrs, ctx.h); what the call owns (the A rows, the
-// challenge vectors, the y vectors, the gathered columns) stands at one stride per statement.  Tableau rows are given as element
-// offsets into a statement's tableau (o_*).  The arithmetic per entry is the single kernels', in their order.
-// rows of statement y at rows + y * s_rows: rows[i][r + j] = scale[y] * dense_y[i w + j]
+// rows of statement b at rows + b * s_rows: dense_b is a per-statement pointer, scaled by scale[b].  (Written out: through a shared
+// body both dense kernels need more SGPRs, profiles/ligero_slab/README.md.)
 __global__ __launch_bounds__(Z_THREADS) void a_rows_dense256_batch_kernel(u32 r, u32 w, size_t ld, const E* __restrict__ scale, LfBatchPtrs dense, size_t n,
                                                                           E* __restrict__ rows, size_t s_rows) {
   const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
@@ -1355,83 +1379,29 @@ __global__ __launch_bounds__(Z_THREADS) void a_rows_dense256_batch_kernel(u32 r,
   const E* __restrict__ d = (const E*)dense.p[b];
   st32(&rows[b * s_rows + i * ld + r + j], fp256_mul(ld32(&scale[b]), ld32(&d[t])));
 }
-// ... += the sparse terms: ONE packed list for all statements, statement y's entries at [off[y], off[y + 1]) (ragged; a statement
-// may have none).  No bound on idx here either: the host has checked every list against nwqrow * w.
+// ONE packed (idx, val) list for all statements, statement b's entries at [off[b], off[b + 1]) (ragged; a statement may have none)
 __global__ __launch_bounds__(Z_THREADS) void a_rows_sparse256_batch_kernel(u32 r, u32 w, size_t ld, const u64* __restrict__ idx, const E* __restrict__ val,
                                                                            const u64* __restrict__ off, E* __restrict__ rows, size_t s_rows) {
-  const size_t b = blockIdx.y, o = off[b], n = off[b + 1] - o;
-  const size_t t = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
-  if (t >= n) return;
-  const u64 f = idx[o + t];
-  E* dst = &rows[b * s_rows + (f / w) * ld + r + f % w];
-  st32(dst, fp256_add(ld32(dst), ld32(&val[o + t])));
+  const size_t b = blockIdx.y, o = off[b];
+  a_rows_sparse256_body(r, w, ld, idx, val, o, off[b + 1] - o, rows + b * s_rows);
 }
-// dot proof: y_b[j] = T_b[idot][j] + sum_i A_b[i][j] T_b[iw + i][j], j < n = dblock; 64 columns x 4 row slices per workgroup
-__global__ __launch_bounds__(256) void rows_vaxpy256_batch_kernel(u32 nrows, size_t n, LfBatchPtrs T, size_t ld, size_t o_dot, size_t o_w, const E* __restrict__ A,
-                                                                  size_t s_A, size_t lda, E* __restrict__ y, size_t s_y) {
-  __shared__ E part[4][64];
-  const u32 col = threadIdx.x & 63, slice = threadIdx.x >> 6;
-  const size_t j = (size_t)blockIdx.x * 64 + col, b = blockIdx.y;
-  const E* __restrict__ Tb = (const E*)T.p[b];
-  const E* __restrict__ Ab = A + b * s_A;
-  E acc = e32_zero();
-  if (j < n)
-    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&Tb[o_w + (size_t)i * ld + j]), ld32(&Ab[(size_t)i * lda + j])));
-  part[slice][col] = acc;
-  __syncthreads();
-  if (slice == 0 && j < n) {
-    acc = ld32(&Tb[o_dot + j]);
-    for (u32 k = 0; k < 4; ++k) acc = fp256_add(acc, part[k][col]);
-    st32(&y[b * s_y + j], acc);
-  }
-}
-// low-degree proof: y_b[j] = T_b[ildt][j] + sum_i u_b[i] T_b[iw + i][j], j < n = block (the single path copies the ILDT row into
-// y first and rows_axpy256_kernel adds to it: the same sum in the same order); u_b at u + b * s_u
-__global__ __launch_bounds__(256) void rows_axpy256_batch_kernel(u32 nrows, size_t n, LfBatchPtrs T, size_t ld, size_t o_ldt, size_t o_w, const E* __restrict__ u,
-                                                                 size_t s_u, E* __restrict__ y, size_t s_y) {
-  __shared__ E part[4][64];
-  const u32 col = threadIdx.x & 63, slice = threadIdx.x >> 6;
-  const size_t j = (size_t)blockIdx.x * 64 + col, b = blockIdx.y;
-  const E* __restrict__ Tb = (const E*)T.p[b];
-  const E* __restrict__ ub = u + b * s_u;
-  E acc = e32_zero();
-  if (j < n)
-    for (u32 i = slice; i < nrows; i += 4) acc = fp256_add(acc, fp256_mul(ld32(&Tb[o_w + (size_t)i * ld + j]), ld32(&ub[i])));
-  part[slice][col] = acc;
-  __syncthreads();
-  if (slice == 0 && j < n) {
-    acc = ld32(&Tb[o_ldt + j]);
-    for (u32 k = 0; k < 4; ++k) acc = fp256_add(acc, part[k][col]);
-    st32(&y[b * s_y + j], acc);
-  }
-}
-// quadratic proof: y_b[j] = T_b[iquad][j] + sum_i u_b[i] (z_i[j] - x_i[j] y_i[j]); the triples' rows x | y | z stand nt rows apart from o_x on
-__global__ __launch_bounds__(Z_THREADS) void quad_combo256_batch_kernel(u32 nt, size_t n, LfBatchPtrs T, size_t ld, size_t o_quad, size_t o_x, const E* __restrict__ u,
-                                                                        size_t s_u, E* __restrict__ y, size_t s_y) {
-  const size_t j = (size_t)blockIdx.x * Z_THREADS + threadIdx.x;
-  if (j >= n) return;
-  const size_t b = blockIdx.y;
-  const E* __restrict__ Tb = (const E*)T.p[b];
-  const E* __restrict__ X = Tb + o_x;
-  const E* __restrict__ Y = X + (size_t)nt * ld;
-  const E* __restrict__ Zr = Y + (size_t)nt * ld;
-  const E* __restrict__ ub = u + b * s_u;
-  E acc = ld32(&Tb[o_quad + j]);
-  for (u32 i = 0; i < nt; ++i) {
-    const E t = fp256_sub(ld32(&Zr[(size_t)i * ld + j]), fp256_mul(ld32(&X[(size_t)i * ld + j]), ld32(&Y[(size_t)i * ld + j])));
-    acc = fp256_add(acc, fp256_mul(ld32(&ub[i]), t));
-  }
-  st32(&y[b * s_y + j], acc);
-}
-// req_b[i][j] = T_b[i][col0 + idx_b[j]]: idx [nb][nreq], req [nb][nrow][nreq]
-__global__ __launch_bounds__(Z_THREADS) void gather_columns256_batch_kernel(u32 nrow, size_t ld, size_t col0, LfBatchPtrs T, const u64* __restrict__ idx, u32 nreq,
-                                                                            E* __restrict__ req) {
+// req[i][j] = T[i][col0 + idx[j]]
+__device__ __forceinline__ void gather_columns256_body(u32 nrow, size_t ld, size_t col0, const E* __restrict__ T, const u64* __restrict__ idx, u32 nreq,
+                                                       E* __restrict__ req) {
   const u32 t = blockIdx.x * Z_THREADS + threadIdx.x;
   if (t >= nrow * nreq) return;
-  const size_t b = blockIdx.y;
   const u32 i = t / nreq, j = t % nreq;
-  const E* __restrict__ Tb = (const E*)T.p[b];
-  st32(&req[b * (size_t)nrow * nreq + t], ld32(&Tb[(size_t)i * ld + col0 + idx[b * nreq + j]]));
+  st32(&req[t], ld32(&T[(size_t)i * ld + col0 + idx[j]]));
+}
+__global__ __launch_bounds__(Z_THREADS) void gather_columns256_kernel(u32 nrow, size_t ld, size_t col0, const E* __restrict__ T, const u64* __restrict__ idx,
+                                                                      u32 nreq, E* __restrict__ req) {
+  gather_columns256_body(nrow, ld, col0, T, idx, nreq, req);
+}
+// statement blockIdx.y: idx [nb][nreq], req [nb][nrow][nreq]
+__global__ __launch_bounds__(Z_THREADS) void gather_columns256_batch_kernel(u32 nrow, size_t ld, size_t col0, LfBatchPtrs T, const u64* __restrict__ idx, u32 nreq,
+                                                                            E* __restrict__ req) {
+  const size_t b = blockIdx.y;
+  gather_columns256_body(nrow, ld, col0, (const E*)T.p[b], idx + b * nreq, nreq, req + b * (size_t)nrow * nreq);
 }
 
 // Quad::bind_gh_all (lib/sumcheck/quad.h:188-210), the verifier's combined bind: the sum over all corners of
@@ -2258,6 +2228,63 @@ struct L32 : lig::Host32 {
   static int column_leaves(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out) {
     return lf_column_leaves32(c, nrow, ld, col0, ncols, d_T, d_nonces, d_out, 0);
   }
+  // ---- the steps of lig::prove_batch / open_batch over cb statements (the batch twins of the row kernels: statement blockIdx.y)
+  // what the batch asks of 32-byte provers beyond lig::batch_core
+  static int batch_ok(lfgpu_ctx* c, const char* who, lig::Slab<E>* const* pr, size_t nb, L32*) {
+    for (size_t b = 0; b < nb; ++b) {
+      if (pr[b]->sharded || !pr[b]->owns || pr[b]->row_lo != 0 || pr[b]->row_hi != pr[b]->p.nrow)
+        return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: prover %zu is sharded or holds a slab (the batch runs whole tableaux on one GPU)", who, b);
+      if (!pr[b]->d_T) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu holds no commitment", who, b);
+    }
+    return LFGPU_OK;
+  }
+  // the encoder takes the rows of a chain in pairs: the pairs fit one launch's gridDim.y and their convolution scratch (64 bytes
+  // per point) stays below the cap
+  static size_t batch_rs_cap(const lfgpu_ligero_param& p) {
+    if (!p.nwqrow) return SIZE_MAX;
+    size_t P = 1;
+    while (P < p.dblock) P <<= 1;
+    return std::min<size_t>(2 * 65535 / p.nwqrow, LF_CB_SCRATCH_CAP / (((p.nwqrow + 1) / 2) * P * sizeof(fp2_t)));
+  }
+  static int a_rows_dense_batch(lfgpu_ctx* c, size_t cb, size_t r, size_t w, size_t ld, const E* d_scale, const LfBatchPtrs& dense, size_t n, E* d_rows, size_t srows) {
+    hipLaunchKernelGGL(a_rows_dense256_batch_kernel, dim3(nblk(n), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)r, (u32)w, ld, d_scale, dense, n, d_rows, srows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  // (no bound on idx in the kernel: lig::prove_batch has checked every list against nflat on the host)
+  static int a_rows_sparse_batch(lfgpu_ctx* c, size_t cb, size_t r, size_t w, size_t ld, const u64* d_idx, const E* d_val, const u64* d_off, size_t maxn,
+                                 size_t /*nflat*/, E* d_rows, size_t srows) {
+    hipLaunchKernelGGL(a_rows_sparse256_batch_kernel, dim3(nblk(maxn), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)r, (u32)w, ld, d_idx, d_val, d_off, d_rows, srows);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  // the rows of all statements of the chain stand contiguously at the stride ld (srows = nrow * ld), so this is ONE extension of
+  // cb * nrow rows (exact arithmetic: how the encoder pairs the rows does not change a value)
+  static int rs_rows_batch(lfgpu_ctx* c, size_t cb, E* d_rows, size_t /*srows*/, size_t nrow, size_t n, size_t m, size_t ld) {
+    return lfgpu_fp256_rs_encode_rows(c, cb * nrow, n, m, d_rows, ld);
+  }
+  // dot proof (dblock columns) into y_b + block, low-degree proof (block columns) into y_b
+  static int rows_combo_batch(lfgpu_ctx* c, size_t cb, const lfgpu_ligero_param& p, const LfBatchPtrs& T, const E* A, size_t sA, const E* u, E* y, size_t sy) {
+    const size_t ld = p.block_enc;
+    hipLaunchKernelGGL(rows_vaxpy256_batch_kernel, dim3(nblk(p.dblock, 64), (u32)cb), dim3(256), 0, c->stream, (u32)p.nwqrow, p.dblock, T, ld, p.idot * ld, p.iw * ld, A, sA,
+                       p.dblock, y + p.block, sy);
+    hipLaunchKernelGGL(rows_axpy256_batch_kernel, dim3(nblk(p.block, 64), (u32)cb), dim3(256), 0, c->stream, (u32)p.nwqrow, p.block, T, ld, p.ildt * ld, p.iw * ld, u,
+                       p.nwqrow, y, sy);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  static int quad_combo_batch(lfgpu_ctx* c, size_t cb, const lfgpu_ligero_param& p, const LfBatchPtrs& T, const E* u, E* y, size_t sy) {
+    const size_t ld = p.block_enc;
+    hipLaunchKernelGGL(quad_combo256_batch_kernel, dim3(nblk(p.dblock), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)p.nqtriples, p.dblock, T, ld, p.iquad * ld, p.iq * ld,
+                       u, p.nqtriples, y, sy);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
+  static int gather_columns_batch(lfgpu_ctx* c, size_t cb, size_t nrow, size_t ld, size_t col0, const LfBatchPtrs& T, const u64* d_idx, size_t nreq, E* d_req) {
+    hipLaunchKernelGGL(gather_columns256_batch_kernel, dim3(nblk(nrow * nreq), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)nrow, ld, col0, T, d_idx, (u32)nreq, d_req);
+    LF_HIP(c, hipGetLastError());
+    return LFGPU_OK;
+  }
 };
 using Lig32 = lig::Slab<E>;  // the prover record: all rows on one GPU, or a slab with a communicator (lfgpu_zk_prover_set_comm above the size threshold)
 
@@ -2281,245 +2308,11 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
 }
 Lig32* lig32_of(Lig256* L) { return reinterpret_cast<Lig32*>(L); }
 
-// ---- LigeroProver::prove for nb committed provers of one shape in one chain (what lfgpu_ligero_prove_batch / _open_batch of
-// ligero.hip are for the 16-byte fields).  One pair of functions over Lig32* const* serves lfgpu_ligero_prove_batch256 /
-// lfgpu_ligero_open_batch256 (through Lig256) and the ZK driver (P32::ligero_prove_batch / ligero_open_batch, which holds Lig32
-// directly).  Host vectors come and go as bytes (the C ABI's arrays are 8-byte aligned words, the elements want 16).
-// what both calls ask of their provers, found before anything is enqueued
-int lig256_batch_ok(lfgpu_ctx* c, const char* who, Lig32* const* pr, size_t nb) {
-  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is NULL", who, b);
-    if (pr[b]->c != c) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu belongs to another context", who, b);
-    if (memcmp(&pr[b]->p, &pr[0]->p, sizeof(lfgpu_ligero_param)) != 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu has another lfgpu_ligero_param than prover 0", who, b);
-    for (size_t a = 0; a < b; ++a)
-      if (pr[a] == pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu appears twice", who, b);
-  }
-  for (size_t b = 0; b < nb; ++b) {
-    if (pr[b]->sharded || !pr[b]->owns || pr[b]->row_lo != 0 || pr[b]->row_hi != pr[b]->p.nrow)
-      return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: prover %zu is sharded or holds a slab (the batch runs whole tableaux on one GPU)", who, b);
-    if (!pr[b]->d_T) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu holds no commitment", who, b);
-  }
-  return LFGPU_OK;
-}
-// statements per launch chain: the chain's working set in scratch3 (`per` bytes a statement) and the convolution scratch of the A
-// rows' extension (rows in pairs, 64 bytes per point) stay below LF_CB_SCRATCH_CAP, and the row pairs of a chain fit one launch's
-// gridDim.y; LFGPU_LP_CHUNK overrides (read once)
-size_t lig256_chunk(const lfgpu_ligero_param& p, size_t nb, size_t per) {
-  static const long env = getenv("LFGPU_LP_CHUNK") ? atol(getenv("LFGPU_LP_CHUNK")) : 0;
-  size_t chunk = std::min(nb, std::max<size_t>(1, LF_CB_SCRATCH_CAP / std::max<size_t>(per, 1)));
-  if (p.nwqrow) {
-    size_t P = 1;
-    while (P < p.dblock) P <<= 1;
-    chunk = std::min(chunk, std::min<size_t>(2 * 65535 / p.nwqrow, LF_CB_SCRATCH_CAP / (((p.nwqrow + 1) / 2) * P * sizeof(fp2_t))));
-  }
-  if (env > 0) chunk = std::min(chunk, (size_t)env);
-  return std::max<size_t>(chunk, 1);
-}
-
-// low_degree_proof, dot_proof (A = scale * dense + the sparse terms, as lig::dot builds it) and quadratic_proof of nb provers: per
-// chain one upload, one memset, one dense and one sparse launch, ONE Reed-Solomon extension of the chain's A rows, the three
-// combinations, one read-back.  Arguments as lfgpu_ligero_prove_batch256 (lfgpu.h).
-int lig256_prove_batch(lfgpu_ctx* c, const char* who, Lig32* const* pr, size_t nb, const void* h_u_ldt, const void* const* d_dense, size_t ndense,
-                       const void* scale, const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse, const void* h_u_quad, void* h_y_ldt,
-                       void* h_y_dot, void* h_y_q0, void* h_y_q2) {
-  LF_TRY(lig256_batch_ok(c, who, pr, nb));
-  const lfgpu_ligero_param& p = pr[0]->p;
-  const size_t nwq = p.nwqrow, nqt = p.nqtriples, lda = p.dblock, ld = p.block_enc, nflat = nwq * p.w, ymid = p.dblock - p.block;
-  if ((nwq && !h_u_ldt) || (nqt && !h_u_quad) || ndense > nflat || (ndense && (!d_dense || !scale)))
-    return lf_fail(c, LFGPU_ERR_ARG, "%s: null challenge vector / dense block, or ndense > nwqrow * w", who);
-  if (nwq >> 31 || nqt >> 31 || p.w >> 32 || p.r >> 32) return lf_fail(c, LFGPU_ERR_ARG, "%s: too many rows", who);
-  for (size_t b = 0; b < nb; ++b) {
-    if (ndense && !d_dense[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: dense block of statement %zu is NULL", who, b);
-    if (nsparse[b] && (!h_idx || !h_val || !h_idx[b] || !h_val[b])) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse list of statement %zu is NULL", who, b);
-    for (size_t t = 0; t < nsparse[b]; ++t) {
-      if (h_idx[b][t] >= nflat) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse index out of range (statement %zu)", who, b);
-      if (t && h_idx[b][t] <= h_idx[b][t - 1]) return lf_fail(c, LFGPU_ERR_ARG, "%s: sparse indices must be strictly increasing (statement %zu)", who, b);
-    }
-  }
-  // the working set of a chain of cb statements in scratch3, in elements: Aext [cb][nwq][dblock] | y [cb][block + 2 dblock] (y_ldt | y_dot |
-  // y_quad) | one uploaded block: u_ldt [cb][nwq] | u_quad [cb][nqt] | scale [cb] | val [tot] | idx [tot] (u64) | off [cb + 1] (u64).
-  // The uploaded block stays in scratch3: scratch2 is the Reed-Solomon encoder's work space (L32::a_rows_sparse).
-  const size_t sA = nwq * lda, sy = p.block + 2 * p.dblock;
-  const size_t chunk = lig256_chunk(p, nb, (sA + sy + nwq + nqt + 1) * 32);
-  auto pack_elts = [&](size_t cb, size_t tot) { return cb * (nwq + nqt + 1) + tot + (tot + 3) / 4 + (cb + 1 + 3) / 4; };
-  size_t need = 0;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0);
-    size_t tot = 0;
-    for (size_t b = b0; b < b0 + cb; ++b) tot += nsparse[b];
-    need = std::max(need, (cb * (sA + sy) + pack_elts(cb, tot)) * 32 + 64);
-  }
-  LF_HIP(c, hipSetDevice(c->device));
-  // A dense block must not live in the scratch this call is about to overwrite: checked against the buffer as it stands (growing it
-  // frees that memory) and against the buffer after lf_scratch3 has grown it, both before anything is enqueued or written.  The
-  // extension works through scratch2, but it runs after a_rows_dense256_batch_kernel, the only reader of the dense blocks.
-  auto aliases = [&]() {
-    const uint8_t* lo = (const uint8_t*)c->scratch3;
-    const size_t span = c->scratch3_bytes;
-    for (size_t b = 0; b < nb && ndense && lo; ++b) {
-      const uint8_t* d = (const uint8_t*)d_dense[b];
-      if (d + ndense * 32 > lo && d < lo + span) return true;
-    }
-    return false;
-  };
-  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "%s: a dense block aliases the call's scratch", who);
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, need, &sc));
-  if (aliases()) return lf_fail(c, LFGPU_ERR_ARG, "%s: a dense block aliases the call's scratch", who);
-  std::vector<E> pack, y;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0);
-    size_t tot = 0, maxsp = 0;
-    for (size_t b = b0; b < b0 + cb; ++b) {
-      tot += nsparse[b];
-      maxsp = std::max(maxsp, nsparse[b]);
-    }
-    E* const dAext = (E*)sc;
-    E* const dy = dAext + cb * sA;
-    E* const d_pack = dy + cb * sy;
-    // the host image of the uploaded block (kept until the chain's read-back has synchronised)
-    pack.assign(pack_elts(cb, tot), e32_zero());
-    const size_t o_uq = cb * nwq, o_sc = o_uq + cb * nqt, o_val = o_sc + cb, o_idx = o_val + tot, o_off = o_idx + (tot + 3) / 4;
-    if (nwq) memcpy((void*)pack.data(), (const uint8_t*)h_u_ldt + b0 * nwq * 32, cb * nwq * 32);
-    if (nqt) memcpy((void*)(pack.data() + o_uq), (const uint8_t*)h_u_quad + b0 * nqt * 32, cb * nqt * 32);
-    if (ndense) memcpy((void*)(pack.data() + o_sc), (const uint8_t*)scale + b0 * 32, cb * 32);
-    u64* const pk_idx = (u64*)(pack.data() + o_idx);
-    u64* const pk_off = (u64*)(pack.data() + o_off);
-    LfBatchPtrs pt{}, pd{};
-    size_t run = 0;
-    for (size_t b = 0; b < cb; ++b) {
-      const size_t g = b0 + b;
-      pk_off[b] = run;
-      if (nsparse[g]) {
-        memcpy((void*)(pack.data() + o_val + run), h_val[g], nsparse[g] * 32);
-        memcpy(pk_idx + run, h_idx[g], nsparse[g] * 8);
-      }
-      run += nsparse[g];
-      pt.p[b] = pr[g]->d_T;
-      pd.p[b] = ndense ? const_cast<void*>(d_dense[g]) : nullptr;
-    }
-    pk_off[cb] = run;
-    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 32, hipMemcpyHostToDevice, c->stream));
-    const E* const d_ul = d_pack;
-    const E* const d_uq = d_pack + o_uq;
-    // inner_product_vector + layout_Aext of every statement: one memset, one dense and one sparse launch
-    if (cb * sA) LF_HIP(c, hipMemsetAsync(dAext, 0, cb * sA * 32, c->stream));
-    if (ndense)
-      hipLaunchKernelGGL(a_rows_dense256_batch_kernel, dim3(nblk(ndense), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, lda, (const E*)(d_pack + o_sc), pd,
-                         ndense, dAext, sA);
-    if (maxsp)
-      hipLaunchKernelGGL(a_rows_sparse256_batch_kernel, dim3(nblk(maxsp), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)p.r, (u32)p.w, lda, (const u64*)(d_pack + o_idx),
-                         (const E*)(d_pack + o_val), (const u64*)(d_pack + o_off), dAext, sA);
-    LF_HIP(c, hipGetLastError());
-    // the A rows from block to dblock values, in place: the rows of all statements of the chain stand contiguously at the stride
-    // dblock, so this is one extension of cb * nwq rows (exact arithmetic: how the encoder pairs the rows does not change a value)
-    if (nwq) LF_TRY(lfgpu_fp256_rs_encode_rows(c, cb * nwq, p.block, p.dblock, dAext, lda));
-    // dot proof (dblock columns), low-degree proof (block columns), quadratic proof
-    hipLaunchKernelGGL(rows_vaxpy256_batch_kernel, dim3(nblk(p.dblock, 64), (u32)cb), dim3(256), 0, c->stream, (u32)nwq, p.dblock, pt, ld, p.idot * ld, p.iw * ld,
-                       (const E*)dAext, sA, lda, dy + p.block, sy);
-    hipLaunchKernelGGL(rows_axpy256_batch_kernel, dim3(nblk(p.block, 64), (u32)cb), dim3(256), 0, c->stream, (u32)nwq, p.block, pt, ld, p.ildt * ld, p.iw * ld, d_ul,
-                       nwq, dy, sy);
-    hipLaunchKernelGGL(quad_combo256_batch_kernel, dim3(nblk(p.dblock), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)nqt, p.dblock, pt, ld, p.iquad * ld, p.iq * ld,
-                       d_uq, nqt, dy + p.block + p.dblock, sy);
-    LF_HIP(c, hipGetLastError());
-    y.resize(cb * sy);
-    LF_TRY(lfgpu_memcpy_d2h(c, y.data(), dy, cb * sy * 32));  // all three y vectors of all statements of the chain
-    for (size_t b = 0; b < cb; ++b) {  // the reference's sanity check (:335-337), as lig::quadratic makes it
-      const E* yq = y.data() + b * sy + p.block + p.dblock;
-      for (size_t j = 0; j < p.w; ++j)
-        if (!e32_is_zero(yq[p.r + j])) return lf_fail(c, LFGPU_ERR_ASSERT, "quadratic_proof: W part is nonzero (statement %zu)", b0 + b);
-    }
-    for (size_t b = 0; b < cb; ++b) {
-      const E* yb = y.data() + b * sy;
-      const size_t g = b0 + b;
-      memcpy((uint8_t*)h_y_ldt + g * p.block * 32, yb, p.block * 32);
-      memcpy((uint8_t*)h_y_dot + g * p.dblock * 32, yb + p.block, p.dblock * 32);
-      const E* yq = yb + p.block + p.dblock;
-      memcpy((uint8_t*)h_y_q0 + g * p.r * 32, yq, p.r * 32);
-      memcpy((uint8_t*)h_y_q2 + g * ymid * 32, yq + p.block, ymid * 32);
-    }
-  }
-  return LFGPU_OK;
-}
-
-// compute_req + MerkleCommitment::open for nb provers: per chain the index lists of all statements in one upload, one column
-// gather, one digest gather (merkle.hip's: digests do not know the field) and one read-back of the columns and the digests, which
-// stand behind one another.  idx [nb][nreq]; h_req [nb][nrow][nreq]; statement b's path at h_path + b * path_cap * 32.
-int lig256_open_batch(lfgpu_ctx* c, const char* who, Lig32* const* pr, size_t nb, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path, size_t path_cap,
-                      size_t* npath) {
-  LF_TRY(lig256_batch_ok(c, who, pr, nb));
-  const lfgpu_ligero_param& p = pr[0]->p;
-  const size_t nreq = p.nreq, nrow = p.nrow, ncols = p.block_ext;
-  if (nreq == 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: nreq = 0 (a proof with 0 leaves is not defined)", who);
-  if ((nrow * nreq) >> 32) return lf_fail(c, LFGPU_ERR_ARG, "%s: nrow * nreq does not fit 32 bits", who);
-  for (size_t b = 0; b < nb; ++b)
-    if (pr[b]->nonces.size() != 32 * ncols || !pr[b]->d_layers) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu holds no commitment", who, b);
-  // MerkleTree::generate_compressed_proof's walk per statement (it also rejects an index out of range or given twice)
-  std::vector<u64> nodes;
-  std::vector<size_t> off(nb + 1, 0);
-  for (size_t b = 0; b < nb; ++b) {
-    LF_TRY(lf_merkle_path_nodes(c, ncols, idx + b * nreq, nreq, nodes));
-    off[b + 1] = nodes.size();
-    if (off[b + 1] - off[b] > path_cap || (off[b + 1] > off[b] && !h_path)) return lf_fail(c, LFGPU_ERR_ARG, "%s: path buffer too small (statement %zu)", who, b);
-  }
-  LF_HIP(c, hipSetDevice(c->device));
-  // a chain of cb statements in scratch3: req [cb][nrow][nreq] | digests [32 bytes per node] | idx [cb][nreq] (u64) | nodes (u64) | off [cb + 1] (u64)
-  const size_t chunk = lig256_chunk(p, nb, (nrow * nreq + nreq * (p.mc_pathlen + 1)) * 32);
-  auto words = [&](size_t cb, size_t tot) { return cb * nreq + tot + cb + 1; };
-  size_t need = 0;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
-    need = std::max(need, (cb * nrow * nreq + tot) * 32 + words(cb, tot) * 8 + 64);
-  }
-  void* sc = nullptr;
-  LF_TRY(lf_scratch3(c, need, &sc));
-  std::vector<u64> pack;
-  std::vector<uint8_t> back;
-  for (size_t b0 = 0; b0 < nb; b0 += chunk) {
-    const size_t cb = std::min(chunk, nb - b0), tot = off[b0 + cb] - off[b0];
-    E* const d_req = (E*)sc;
-    E* const d_dig = d_req + cb * nrow * nreq;
-    u64* const d_pack = (u64*)(d_dig + tot);
-    pack.assign(words(cb, tot), 0);
-    LfBatchPtrs pt{}, pl{};
-    size_t maxcnt = 0;
-    for (size_t b = 0; b < cb; ++b) {
-      const size_t g = b0 + b;
-      for (size_t j = 0; j < nreq; ++j) pack[b * nreq + j] = idx[g * nreq + j];
-      pack[cb * nreq + tot + b] = off[g] - off[b0];
-      maxcnt = std::max(maxcnt, off[g + 1] - off[g]);
-      pt.p[b] = pr[g]->d_T;
-      pl.p[b] = pr[g]->d_layers;
-    }
-    pack[cb * nreq + tot + cb] = tot;
-    for (size_t t = 0; t < tot; ++t) pack[cb * nreq + t] = nodes[off[b0] + t];
-    LF_HIP(c, hipMemcpyAsync(d_pack, pack.data(), pack.size() * 8, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(gather_columns256_batch_kernel, dim3(nblk(nrow * nreq), (u32)cb), dim3(Z_THREADS), 0, c->stream, (u32)nrow, p.block_enc, p.dblock, pt,
-                       (const u64*)d_pack, (u32)nreq, d_req);
-    LF_HIP(c, hipGetLastError());
-    LF_TRY(lf_merkle_gather_batch(c, cb, ncols, pl, d_pack + cb * nreq, d_pack + cb * nreq + tot, maxcnt, d_dig));
-    back.resize((cb * nrow * nreq + tot) * 32);
-    LF_TRY(lfgpu_memcpy_d2h(c, back.data(), d_req, back.size()));
-    memcpy((uint8_t*)h_req + b0 * nrow * nreq * 32, back.data(), cb * nrow * nreq * 32);
-    const uint8_t* dig = back.data() + cb * nrow * nreq * 32;
-    for (size_t b = 0; b < cb; ++b) {
-      const size_t g = b0 + b, cnt = off[g + 1] - off[g];
-      if (cnt) memcpy(h_path + g * path_cap * 32, dig + (off[g] - off[b0]) * 32, cnt * 32);
-      npath[g] = cnt;
-      for (size_t j = 0; j < nreq; ++j) memcpy(h_nonces + (g * nreq + j) * 32, &pr[g]->nonces[32 * idx[g * nreq + j]], 32);
-    }
-  }
-  return LFGPU_OK;
-}
-}  // namespace
-
-// ---- lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256 (lfgpu.h): the provers of lfgpu_ligero_commit(field = P256)
-namespace {
+// ---- lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256 (lfgpu.h): the provers of lfgpu_ligero_commit(field = P256) through
+// lig::prove_batch / lig::open_batch (ligero_slab.h), which the ZK driver calls on its Lig32 directly (P32).
+// The records behind the handles.  The range of nb and a NULL entry are lig::batch_core's to refuse: the conversion stops there.
 int lig256_handles(lfgpu_ctx* c, const char* who, lfgpu_ligero_prover* const* pr, size_t nb, Lig32** out) {
-  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!pr[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu is NULL", who, b);
+  for (size_t b = 0; b < (nb <= LFGPU_SC_BATCH_MAX ? nb : 0) && pr[b]; ++b) {
     LfLigeroView v;
     lf_ligero_prover_view(pr[b], &v);
     if (v.c != c) return lf_fail(c, LFGPU_ERR_ARG, "%s: prover %zu belongs to another context", who, b);
@@ -2534,17 +2327,17 @@ extern "C" int lfgpu_ligero_prove_batch256(lfgpu_ctx* c, lfgpu_ligero_prover* co
                                            const void* h_u_quad, void* h_y_ldt, void* h_y_dot, void* h_y_q0, void* h_y_q2) {
   static const char* const who = "ligero_prove_batch256";
   if (!c || !pr || !nsparse || !h_y_ldt || !h_y_dot || !h_y_q0 || !h_y_q2) return lf_fail(c, LFGPU_ERR_ARG, "%s: null argument", who);
-  Lig32* L[LFGPU_SC_BATCH_MAX];
+  Lig32* L[LFGPU_SC_BATCH_MAX] = {};
   LF_TRY(lig256_handles(c, who, pr, nb, L));
-  return lig256_prove_batch(c, who, L, nb, h_u_ldt, d_dense, ndense, scale, h_idx, h_val, nsparse, h_u_quad, h_y_ldt, h_y_dot, h_y_q0, h_y_q2);
+  return lig::prove_batch<L32>(c, who, L, nb, h_u_ldt, d_dense, ndense, scale, h_idx, h_val, nsparse, h_u_quad, h_y_ldt, h_y_dot, h_y_q0, h_y_q2);
 }
 extern "C" int lfgpu_ligero_open_batch256(lfgpu_ctx* c, lfgpu_ligero_prover* const* pr, size_t nb, const size_t* idx, void* h_req, uint8_t* h_nonces, uint8_t* h_path,
                                           size_t path_cap, size_t* npath) {
   static const char* const who = "ligero_open_batch256";
   if (!c || !pr || !idx || !h_req || !h_nonces || !npath) return lf_fail(c, LFGPU_ERR_ARG, "%s: null argument", who);
-  Lig32* L[LFGPU_SC_BATCH_MAX];
+  Lig32* L[LFGPU_SC_BATCH_MAX] = {};
   LF_TRY(lig256_handles(c, who, pr, nb, L));
-  return lig256_open_batch(c, who, L, nb, idx, h_req, h_nonces, h_path, path_cap, npath);
+  return lig::open_batch<L32>(c, who, L, nb, idx, h_req, h_nonces, h_path, path_cap, npath);
 }
 
 // ---- behind lfgpu_ligero_commit / low_degree_proof / dot_proof / quadratic_proof / open / tableau / free for field P256
@@ -2684,11 +2477,11 @@ struct P32 : zkp::Wire32 {
   }
   static int ligero_prove_batch(lfgpu_ctx* c, Lig* const* lp, size_t nb, const E* u_ldt, const E* const* d_dense, size_t ndense, const E* scale,
                                 const uint64_t* const* idx, const E* const* val, const size_t* nsparse, const E* u_quad, E* y_ldt, E* y_dot, E* y_q0, E* y_q2) {
-    return lig256_prove_batch(c, kProveBatchName, lp, nb, u_ldt, (const void* const*)d_dense, ndense, scale, idx, (const void* const*)val, nsparse, u_quad, y_ldt, y_dot,
-                              y_q0, y_q2);
+    return lig::prove_batch<L32>(c, kProveBatchName, lp, nb, u_ldt, (const void* const*)d_dense, ndense, scale, idx, (const void* const*)val, nsparse, u_quad, y_ldt,
+                                 y_dot, y_q0, y_q2);
   }
   static int ligero_open_batch(lfgpu_ctx* c, Lig* const* lp, size_t nb, const size_t* idx, E* req, uint8_t* nonces, uint8_t* path, size_t cap, size_t* npath) {
-    return lig256_open_batch(c, kProveBatchName, lp, nb, idx, req, nonces, path, cap, npath);
+    return lig::open_batch<L32>(c, kProveBatchName, lp, nb, idx, req, nonces, path, cap, npath);
   }
   static int low_degree(Lig* lp, const E* u, E* y) { return lig::low_degree(lp, L32(), u, y); }
   static int dot(Lig* lp, const E* d_dense, size_t ndense, const E& scale, const uint64_t* idx, const E* val, size_t nsparse, E* y) {

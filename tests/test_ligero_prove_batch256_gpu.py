@@ -195,6 +195,35 @@ def test_batch_equals_single_calls_and_model(nq):
     check_shape(G, nq, 7000 + nq)
 
 
+# ---------------------------------------------------------------- where the index list and the offset table land in the uploaded block
+@pytest.fixture(scope="module")
+def four_statements():
+    import gpu_util as G
+    st = Statements(G, NQS[0], 7800, nb=4)
+    yield st
+    st.close()
+
+
+@pytest.mark.parametrize("r", [0, 1, 2, 3])
+@pytest.mark.parametrize("nb", [3, 4])
+def test_packed_lists_at_every_residue_of_the_sparse_total(four_statements, nb, r):
+    """The chain's uploaded block holds u_ldt | u_quad | scale | val [tot] | idx [tot] (u64) | off [nb + 1] (u64) in 32-byte elements,
+    so the index list ends, and the offset table begins, on an element boundary only where tot is a multiple of 4.  Sparse lists of
+    lengths (0, 1, r[, 2]): tot = 1 .. 6 takes every residue, one statement has no term, and nb + 1 is even and odd.  No dense block;
+    the one-term list sits on the last flat position.  y_dot against the single call on the same prover, byte for byte."""
+    st = four_statements
+    p, provers = st.p, st.provers[:nb]
+    nflat = p.nwqrow * p.w
+    lens = (0, 1, r, 2)[:nb]
+    rng = np.random.default_rng(7810 + 10 * nb + r)
+    inp = dict(u_ldt=[lm.rand_ints(rng, p.nwqrow) for _ in range(nb)], u_quad=[lm.rand_ints(rng, p.nqtriples) for _ in range(nb)], scales=lm.rand_ints(rng, nb),
+               ndense=0, idxs=[np.array([nflat - 1], dtype=np.uint64) if b == 1 else np.arange(n, dtype=np.uint64) for b, n in enumerate(lens)],
+               vals=[lm.rand_ints(rng, n) for n in lens])
+    got = batch_proofs(st.G.pkg, st.gpu, p, provers, inp, None)
+    for b, pr in enumerate(provers):
+        assert got[b][1] == pr.dot_proof(lm.elts(matrix_of(p, inp, b))).tobytes(), "y_dot of statement %d (lengths %s)" % (b, lens)
+
+
 # ---------------------------------------------------------------- chunking (the environment is read once per process)
 def test_chunks_of_two_statements_give_the_same_bytes():
     env = {k: v for k, v in os.environ.items() if k != "LFGPU_LP_CHUNK"}

@@ -182,6 +182,47 @@ def test_fp128_two_pass_fft_plan_inside_the_batched_extension():
     check_shape(FP, p, 2, [], 3200, [1501])
 
 
+# ---------------------------------------------------------------- where the index list and the offset table land in the uploaded block
+@pytest.fixture(scope="module")
+def small_provers():
+    """four provers of the 40-element shape per field, committed once for the module"""
+    import gpu_util as G
+    made = {}
+
+    def get(field):
+        if field not in made:
+            p = G.pkg.ligero_param(field, 40, 7, 4, 3, 64)
+            made[field] = p, commit(field, p, 4, _lqc(40, 7, 31), 6000 + field)
+        return made[field]
+
+    yield get
+    for _, provers in made.values():
+        for pr in provers:
+            pr.close()
+
+
+@pytest.mark.parametrize("r", [0, 1])
+@pytest.mark.parametrize("B", [3, 4])
+@pytest.mark.parametrize("field", [GF, FP])
+def test_packed_lists_at_every_residue_of_the_sparse_total(small_provers, field, B, r):
+    """The chain's uploaded block holds u_ldt | u_quad | scale | val [tot] | idx [tot] (u64) | off [B + 1] (u64) in 16-byte elements,
+    so the index list ends, and the offset table begins, on an element boundary only for an even tot.  Sparse lists of lengths
+    (0, 1, r[, 2]): tot = 1 .. 4 takes both residues, one statement has no term, and B + 1 is even and odd.  No dense block; the
+    one-term list sits on the last flat position.  y_dot against the single call on the same prover, byte for byte."""
+    import gpu_util as G
+    p, provers = small_provers(field)
+    provers = provers[:B]
+    nflat = p.nwqrow * p.w
+    lens = (0, 1, r, 2)[:B]
+    inp = prove_inputs(field, p, B, 0, 6100 + 10 * B + r)
+    inp["idxs"] = [np.array([nflat - 1], dtype=np.uint64) if b == 1 else np.arange(n, dtype=np.uint64) for b, n in enumerate(lens)]
+    inp["vals"] = [ol.rand_elts(np.random.default_rng(6200 + b), n, field).reshape(-1, 2) for b, n in enumerate(lens)]
+    got = batch_proofs(G.gpu(), provers, inp, [])
+    for b, pr in enumerate(provers):
+        want = pr.dot_proof_sparse(None, 0, inp["scales"][b], inp["idxs"][b], inp["vals"][b])
+        assert got[b][1] == want.tobytes(), "y_dot of statement %d (lengths %s)" % (b, lens)
+
+
 # ---------------------------------------------------------------- chunking (the environment is read once per process)
 @pytest.mark.parametrize("field", [GF, FP])
 def test_chunks_of_two_statements_give_the_same_bytes(field):
