@@ -57,8 +57,9 @@ extern "C" {
                               before any launch: commit_batch, commit_sharded, layout_rows_sharded, encode_rows,
                               prover_from_slab, dot_proof_sparse (LFGPU_ERR_ARG); inner_product_rows, prove_batch, open_batch
                               (LFGPU_ERR_UNSUPPORTED; an Fp256Base prover takes lfgpu_ligero_prove_batch256 /
-                              lfgpu_ligero_open_batch256, and lfgpu_zk_batch256_new / lfgpu_zk_prove_batch256 in lfgpu_zk.h
-                              are the batched prover of such a circuit).  The per-step
+                              lfgpu_ligero_open_batch256; the batched commit of the field is lfgpu_column_commit_batch256 /
+                              lfgpu_ligero_commit_batch256, and lfgpu_zk_batch256_new / lfgpu_zk_commit_batch256 /
+                              lfgpu_zk_prove_batch256 in lfgpu_zk.h are the batched prover of such a circuit).  The per-step
                               sumcheck entry points below (partials, scatter, binds, bind_g, sumcheck_layer) take the
                               16-byte fields only: for Fp256Base those steps run inside lfgpu_zk_prove / lfgpu_zk_verify, and
                               the whole layer has entry points of its own: lfgpu_sumcheck_layer256,
@@ -162,9 +163,14 @@ int lfgpu_column_commit(lfgpu_ctx* ctx, int field, size_t nrow, size_t ld, size_
  * all roots in one read-back.  d_T[b], d_layers[b]: device pointers per statement (host arrays of nb pointers; the kernels
  * take them as one by-value argument, nothing is uploaded); d_nonces: [nb][ncols][32] contiguous on the device.
  * Heap b and root b are byte-identical to lfgpu_column_commit on statement b alone.  1 <= nb <= LFGPU_SC_BATCH_MAX.
- * Fields: GF2_128 and Fp128; LFGPU_ERR_UNSUPPORTED for P256. */
+ * Fields: GF2_128 and Fp128; LFGPU_ERR_UNSUPPORTED for P256 (lfgpu_column_commit_batch256 serves that field). */
 int lfgpu_column_commit_batch(lfgpu_ctx* ctx, int field, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb,
                               const void* const* d_T, const void* d_nonces, void* const* d_layers, uint8_t* roots_out /*[nb][32]*/);
+/* ... for tableaux of 32-byte elements (Fp256Base): the same contract -- pointer tables by value, nonces [nb][ncols][32], heap b
+ * and root b byte-identical to lfgpu_column_commit(field = LFGPU_FIELD_P256) on statement b alone, the roots in one read-back,
+ * and the call's one stream synchronise at its end.  ld, col0 and ncols count 32-byte elements. */
+int lfgpu_column_commit_batch256(lfgpu_ctx* ctx, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb,
+                                 const void* const* d_T, const void* d_nonces, void* const* d_layers, uint8_t* roots_out /*[nb][32]*/);
 /* The leaf half of the above alone (enqueue only, nothing read back): d_leaves[j] = leaf digest of column col0 + j,
  * j < ncols, 32 bytes each.  Multi-GPU commit: after the column re-partition a rank hashes the columns it
  * owns, the digests are all-gathered into the leaf level of d_layers and lfgpu_merkle_build_tree finishes on every rank. */
@@ -418,6 +424,27 @@ int lfgpu_ligero_commit_batch(lfgpu_ctx* ctx, int field, int subfield_log_bits, 
                               const void* const* h_W, size_t subfield_boundary, const size_t* h_lqc,
                               const lfgpu_rng_fn* rng, void* const* rng_user, uint8_t* roots_out /*[nb][32]*/,
                               lfgpu_ligero_prover** out /*[nb]*/);
+/* lfgpu_ligero_commit_batch over Fp256Base: nb x lfgpu_ligero_commit(field = LFGPU_FIELD_P256) of ONE lfgpu_ligero_param and one
+ * h_lqc (h_W[b]: nw 32-byte Montgomery elements).  The contract is the one above: the host layout per statement in index order,
+ * every draw of statement b from rng[b] in lfgpu_ligero_commit's order with lfgpu_set_rng_exact_calls honoured, so one engine
+ * handed to several statements sees the draw order of sequential calls; pinned staging kept by the context and scrubbed after
+ * every call; ONE stream synchronise; on any error out[0 .. nb) are NULL, and the stream is synchronised before the staging is
+ * scrubbed.  The device half per chain of statements: the rows that carry `block` values ([0, IDOT) and (IQUAD, nrow)) of ALL
+ * statements go through one convolution, the IDOT / IQUAD rows of all statements through a second -- two rows share one complex
+ * transform, across statements too (exact arithmetic: the pairing does not change a byte) -- then one leaf-hash launch and the
+ * Merkle levels with the statement on a grid axis (lfgpu_column_commit_batch256).  The encoder's tables of both shapes are made
+ * sure of before anything is enqueued, so a warm call does not synchronise in the middle.  Statements are chunked so that a
+ * chain's row pairs fit one launch (65535) and its convolution scratch (64 bytes per point) stays under 256 MiB;
+ * LFGPU_CB_CHUNK overrides as above.  A shape of which not even one statement fits is encoded per statement with
+ * lfgpu_ligero_commit's own encoder inside the call; block_enc above 2^24 is LFGPU_ERR_UNSUPPORTED, as in lfgpu_ligero_commit.
+ * Roots, tableaux, Merkle heaps and nonces are byte-identical to nb lfgpu_ligero_commit calls; each out[b] is a prover of the kind
+ * lfgpu_ligero_commit(field = LFGPU_FIELD_P256) returns (low_degree_proof, dot_proof, quadratic_proof, open, tableau, free,
+ * lfgpu_ligero_prove256, lfgpu_ligero_prove_batch256, lfgpu_ligero_open_batch256).  LFGPU_COMMIT_BATCH256=0 (read once per
+ * process) keeps these semantics and runs the single-statement device path per statement: the same bytes.
+ * 1 <= nb <= LFGPU_SC_BATCH_MAX, else LFGPU_ERR_ARG; argument errors are found before the first draw. */
+int lfgpu_ligero_commit_batch256(lfgpu_ctx* ctx, const lfgpu_ligero_param* p, size_t nb, const void* const* h_W,
+                                 const size_t* h_lqc, const lfgpu_rng_fn* rng, void* const* rng_user,
+                                 uint8_t* roots_out /*[nb][32]*/, lfgpu_ligero_prover** out /*[nb]*/);
 /* LigeroProver::commit split for a row slab [row_lo, row_hi) of the tableau -- the multi-GPU form (rows are independent
  * up to the RandomEngine's draw order, lib/ligero/ligero_prover.h:171-270).
  *  lfgpu_ligero_layout_rows: HOST ONLY (no context, no device).  Performs every RandomEngine draw of commit in the
@@ -549,7 +576,8 @@ int lfgpu_ligero_open_batch(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size
  * or of another context, provers whose lfgpu_ligero_param differ, the same prover twice, a prover without a commitment, a
  * sparse index out of range or not strictly increasing, an opened index out of range or given twice, a path buffer too small,
  * a dense block inside the call's scratch.  LFGPU_ERR_UNSUPPORTED: a sharded prover or one that holds a slab.
- * Not batched for this field: the commit (lfgpu_column_commit_batch / lfgpu_ligero_commit_batch keep refusing it). */
+ * The commit of nb such provers in one chain is lfgpu_ligero_commit_batch256 above (lfgpu_column_commit_batch /
+ * lfgpu_ligero_commit_batch keep refusing the field). */
 int lfgpu_ligero_prove_batch256(lfgpu_ctx* ctx, lfgpu_ligero_prover* const* pr, size_t nb, const void* h_u_ldt,
                                 const void* const* d_dense, size_t ndense, const uint64_t* scale /*[nb][4]*/,
                                 const uint64_t* const* h_idx, const void* const* h_val, const size_t* nsparse /*[nb]*/,

@@ -176,8 +176,8 @@ int lfgpu_zk_batch_free(lfgpu_zk_batch* batch);
  * member, [1] the whole call's; [4] and [5] the batch's on the batched tail and the statement's own otherwise.  Errors in the
  * tail, the batch object's memory (allocated once in _new, the witness-dependent slabs scrubbed on free, no hipMalloc / hipFree
  * in the prove call beyond the context's pooled scratch) and the threading model: as above.
- * Not batched for this field: the commit (lfgpu_zk_commit per prover: 1.1 ms of a 16 ms proof), the verifier, and there is no
- * resident grid for the batch's sumcheck.
+ * The commit of the batch's provers in one chain is lfgpu_zk_commit_batch256 below.  Not batched for this field: the verifier,
+ * and there is no resident grid for the batch's sumcheck.
  * 1 <= nb <= nb_max <= LFGPU_SC_BATCH_MAX.  LFGPU_ERR_ARG, found before anything is enqueued or any transcript is touched: a
  * NULL argument, nb out of range, a prover of another context or circuit, one that has not committed, the same prover twice, a
  * transcript without write_elt_sized / write_elt_array_sized, at _new a circuit over a 16-byte field (lfgpu_zk_batch_new serves
@@ -205,6 +205,22 @@ int lfgpu_zk_batch256_free(lfgpu_zk_batch256* batch);
 int lfgpu_zk_commit_batch(lfgpu_zk_batch* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
                           const lfgpu_rng_fn* rng, void* const* rng_user,
                           const lfgpu_transcript_ops* const* ts, uint8_t* roots_out /*[nb][32], may be NULL*/);
+/* ... over Fp256Base: lfgpu_zk_commit's one-GPU branch for nb provers of the batch's context and (Fp256Base) circuit.  The same
+ * contract with 32-byte Montgomery images: per statement, in index order, the pads from rng[b] (in bulk, or one call per draw
+ * under lfgpu_set_rng_exact_calls) and the witness layout; then ONE lfgpu_ligero_commit_batch256 (lfgpu.h); then, once every
+ * root is back, ts[b]->write_bytes(root b).  Prover b is then in exactly the state lfgpu_zk_commit leaves it in (an earlier
+ * commitment and proof are dropped): lfgpu_zk_prove or lfgpu_zk_prove_batch256 may follow, and roots and proofs are
+ * byte-identical to the single path's.  lfgpu_zk_timings()[0] is the whole call's time, the same value for every member.
+ * Every statement needs a RandomEngine of its own, as above.  roots_out: [nb][32] or NULL.  LFGPU_COMMIT_BATCH256=0 (read once
+ * per process) runs the single-statement device path per statement instead: the same bytes.
+ * LFGPU_ERR_ARG (found before the first draw, nothing touched): a NULL entry, nb out of 1 .. nb_max, a prover of another
+ * context or circuit or of a 16-byte field, the same prover twice, provers whose lfgpu_ligero_param differ, a transcript
+ * without write_elt_sized / write_elt_array_sized (lfgpu_zk_commit refuses that too).  LFGPU_ERR_UNSUPPORTED: a prover with a
+ * communicator set.  On an error after the draws began no transcript has been written to and every prover of the call holds no
+ * commitment. */
+int lfgpu_zk_commit_batch256(lfgpu_zk_batch256* batch, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                             const lfgpu_rng_fn* rng, void* const* rng_user,
+                             const lfgpu_transcript_ops* const* ts, uint8_t* roots_out /*[nb][32], may be NULL*/);
 
 /* ---- ZkVerifier ----
  * ZkVerifier::recv_commitment + verify (lib/zk/zk_verifier.h:68-94) on the wire bytes of ZkProof::write

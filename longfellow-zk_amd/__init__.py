@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "lfgpu_column_commit_batch", "lfgpu_ligero_commit_batch", "lfgpu_zk_commit_batch",
     "lfgpu_ligero_prove", "lfgpu_ligero_verify",
     "lfgpu_zk_batch256_new", "lfgpu_zk_prove_batch256", "lfgpu_zk_batch256_free", "lfgpu_ligero_prove_batch256", "lfgpu_ligero_open_batch256",
+    "lfgpu_column_commit_batch256", "lfgpu_ligero_commit_batch256", "lfgpu_zk_commit_batch256",
 ]
 
 
@@ -247,6 +248,9 @@ def load_library():
         "lfgpu_ligero_prove_batch256": [vp, C.POINTER(vp), sz, vp, C.POINTER(vp), sz, vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(sz), vp, vp, vp, vp, vp],
         "lfgpu_ligero_open_batch256": [vp, C.POINTER(vp), sz, C.POINTER(sz), vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_zk_commit_batch": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(RNG_FN), C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), vp],
+        "lfgpu_column_commit_batch256": [vp, sz, sz, sz, sz, sz, C.POINTER(vp), vp, C.POINTER(vp), vp],
+        "lfgpu_ligero_commit_batch256": [vp, C.POINTER(LigeroParam), sz, C.POINTER(vp), vp, C.POINTER(RNG_FN), C.POINTER(vp), vp, C.POINTER(vp)],
+        "lfgpu_zk_commit_batch256": [vp, C.POINTER(vp), sz, C.POINTER(vp), C.POINTER(RNG_FN), C.POINTER(vp), C.POINTER(C.POINTER(TranscriptOps)), vp],
         "lfgpu_ligero_prove": [vp, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, sz, C.POINTER(sz)],
         "lfgpu_ligero_verify": [vp, ci, ci, C.POINTER(LigeroParam), vp, vp, sz, C.POINTER(TranscriptOps), sz, sz, vp, vp, vp, vp, C.POINTER(ci),
                                 C.POINTER(C.c_char_p)],
@@ -442,6 +446,18 @@ class LfGpu:
         raw = bytes(roots)
         return [raw[32 * b:32 * b + 32] for b in range(nb)]
 
+    def column_commit_batch256(self, nrow, ld, col0, ncols, d_Ts, d_nonces, d_layers):
+        """lfgpu_column_commit_batch256: column_commit_batch for tableaux of 32-byte elements (FIELD_P256) -> [root] per statement"""
+        nb = len(d_Ts)
+        if len(d_layers) != nb:
+            raise ValueError("column_commit_batch256: one heap per tableau")
+        n = max(1, nb)
+        roots = (C.c_uint8 * (32 * n))()
+        self._ck(self.L.lfgpu_column_commit_batch256(self.h, nrow, ld, col0, ncols, nb, (C.c_void_p * n)(*d_Ts), C.c_void_p(d_nonces),
+                                                     (C.c_void_p * n)(*d_layers), roots))
+        raw = bytes(roots)
+        return [raw[32 * b:32 * b + 32] for b in range(nb)]
+
     def merkle_build_tree(self, n, d_layers):
         root = (C.c_uint8 * 32)()
         self._ck(self.L.lfgpu_merkle_build_tree(self.h, n, C.c_void_p(d_layers), root))
@@ -583,8 +599,8 @@ class LigeroProver:
     over the C ABI: the tableau lives in HBM; the caller owns the transcript and the RandomEngine.
     `rng_bytes(n) -> bytes` plays RandomEngine::bytes.  Elements are (n, 2) uint64 arrays for GF(2^128) and Fp128 and (n, 4) --
     32-byte Montgomery images -- for FIELD_P256, which commit, low_degree_proof, dot_proof, quadratic_proof, open and prove serve
-    (the sharded, slab and sparse forms and commit_batch are for the 16-byte fields; prove_batch256 / open_batch256 are the batch
-    of FIELD_P256 provers)."""
+    (the sharded, slab and sparse forms and commit_batch are for the 16-byte fields; commit_batch256, prove_batch256 and
+    open_batch256 are the batch of FIELD_P256 provers)."""
 
     def __init__(self, gpu, field, param, subfield_log_bits=4):
         self.gpu, self.field, self.p, self.k = gpu, field, param, subfield_log_bits
@@ -638,6 +654,36 @@ class LigeroProver:
         provers = []
         for b in range(nb):
             pr = LigeroProver(gpu, field, param, subfield_log_bits)
+            pr.h, pr._cb = C.c_void_p(hs[b]), cbs[b]
+            provers.append(pr)
+        return [raw[32 * b:32 * b + 32] for b in range(nb)], provers
+
+    @staticmethod
+    def commit_batch256(gpu, param, Ws, lqc, rng_bytes_list):
+        """lfgpu_ligero_commit_batch256: commit_batch over FIELD_P256 (Ws[b]: (nw, 4) Montgomery images) -> ([root], [LigeroProver]);
+        the provers are of the kind commit(FIELD_P256) returns"""
+        import numpy as np
+        nb = len(Ws)
+        if len(rng_bytes_list) != nb:
+            raise ValueError("LigeroProver.commit_batch256: one RandomEngine per witness")
+
+        def mk(rng_bytes):
+            def cb(_user, buf, n):
+                C.memmove(buf, rng_bytes(n), n)
+            return RNG_FN(cb)
+
+        cbs = [mk(r) for r in rng_bytes_list]
+        lq = np.ascontiguousarray(np.asarray(lqc, dtype=np.uint64).reshape(-1))
+        Ws = [np.ascontiguousarray(W) for W in Ws]
+        n = max(1, nb)
+        roots = (C.c_uint8 * (32 * n))()
+        hs = (C.c_void_p * n)()
+        gpu._ck(gpu.L.lfgpu_ligero_commit_batch256(gpu.h, C.byref(param), nb, (C.c_void_p * n)(*[W.ctypes.data for W in Ws]),
+                                                    C.c_void_p(lq.ctypes.data) if lq.size else None, (RNG_FN * n)(*cbs), None, roots, hs))
+        raw = bytes(roots)
+        provers = []
+        for b in range(nb):
+            pr = LigeroProver(gpu, FIELD_P256, param)
             pr.h, pr._cb = C.c_void_p(hs[b]), cbs[b]
             provers.append(pr)
         return [raw[32 * b:32 * b + 32] for b in range(nb)], provers
@@ -1189,13 +1235,37 @@ class ZkBatch256:
     """lfgpu_zk_batch256: ZkBatch for circuits over FIELD_P256 -- up to nb_max committed ZkProvers of one context and one Fp256Base
     circuit proved in lock-step (batched eval_circuit and sumcheck; one EQ launch chain, one lfgpu_ligero_prove_batch256 and one
     lfgpu_ligero_open_batch256 for the Ligero proofs of all statements; LFGPU_LIGERO_PROVE_BATCH256=0 runs that tail per
-    statement).  Every proof is byte-identical to ZkProver.prove's.  The provers commit one by one (ZkProver.commit)."""
+    statement).  Every proof is byte-identical to ZkProver.prove's.  The provers commit one by one (ZkProver.commit) or all in one
+    chain (commit: lfgpu_zk_commit_batch256, one lfgpu_ligero_commit_batch256; LFGPU_COMMIT_BATCH256=0 runs it per statement)."""
 
     def __init__(self, gpu, circuit, nb_max):
         self.gpu, self.circuit, self.nb_max = gpu, circuit, nb_max
         h = C.c_void_p()
         gpu._ck(gpu.L.lfgpu_zk_batch256_new(gpu.h, circuit.h, nb_max, C.byref(h)))
         self.h = h
+
+    def commit(self, provers, Ws, rng_bytes_list, transcripts):
+        """lfgpu_zk_commit_batch256: ZkProver.commit for every prover through one chain of dispatches (one batched Ligero commit),
+        statement b with its own witness, RandomEngine `rng_bytes_list[b](n) -> bytes` and transcript -> [root]"""
+        import numpy as np
+        nb = len(provers)
+        if not (len(Ws) == nb and len(rng_bytes_list) == nb and len(transcripts) == nb):
+            raise ValueError("ZkBatch256.commit: one witness, one RandomEngine and one transcript per prover")
+
+        def mk(rng_bytes):
+            def cb(_user, buf, n):
+                C.memmove(buf, rng_bytes(n), n)
+            return RNG_FN(cb)
+
+        cbs = [mk(r) for r in rng_bytes_list]
+        Ws = [np.ascontiguousarray(W) for W in Ws]
+        ops = [t.ops() for t in transcripts]
+        n = max(1, nb)
+        roots = (C.c_uint8 * (32 * n))()
+        self.gpu._ck(self.gpu.L.lfgpu_zk_commit_batch256(self.h, (C.c_void_p * n)(*[p.h for p in provers]), nb, (C.c_void_p * n)(*[W.ctypes.data for W in Ws]),
+                                                         (RNG_FN * n)(*cbs), None, (C.POINTER(TranscriptOps) * n)(*[C.pointer(o) for o in ops]), roots))
+        raw = bytes(roots)
+        return [raw[32 * b:32 * b + 32] for b in range(nb)]
 
     def prove(self, provers, Ws, transcripts):
         """-> [bool] per statement: True = provers[b] holds its proof, False = witness b does not satisfy the circuit"""

@@ -275,6 +275,17 @@ int lf_eval_quad_batch_async(lfgpu_quad* q, size_t B, const void* d_W, size_t ld
 // p256.hip (field id 1, 32-byte elements)
 int lf_column_leaves32(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out, size_t out0);
 int lf_p256_binop(lfgpu_ctx* c, int op, size_t n, const void* d_a, const void* d_b, void* d_out);
+// ... the batched commit over 32-byte elements (lfgpu_ligero_commit_batch256).  lf_p256_rs_prepare builds the encoder's tables of
+// the extension n -> m on first use (synchronous copies, a synchronise) and is called before a chain enqueues anything; the two
+// _batch calls only enqueue.  lf_p256_rs_rows_batch: one row group (gr rows a statement: tableau row base + r, from r = seg on
+// base + r + skip) of cb tableaux through ONE convolution in d_Z, lf_p256_rs_batch_scratch(cb * gr, m) bytes (0: the row pairs do
+// not fit one launch).  lf_column_leaves32_batch: statement b's nonces at d_nonces + b * ncols * 32, its leaves into level ncols
+// of its heap.
+int lf_p256_rs_prepare(lfgpu_ctx* c, size_t n, size_t m);
+size_t lf_p256_rs_batch_scratch(size_t rows, size_t m);
+int lf_p256_rs_rows_batch(lfgpu_ctx* c, size_t cb, const LfBatchPtrs& T, size_t base, size_t seg, size_t skip, size_t gr, size_t n, size_t m, size_t ld, void* d_Z);
+int lf_column_leaves32_batch(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb, const LfBatchPtrs& T, const void* d_nonces,
+                             const LfBatchPtrs& layers);
 
 static inline unsigned lf_log2(size_t n) {
   unsigned l = 0;

@@ -861,24 +861,10 @@ extern "C" int lfgpu_ligero_commit_batch(lfgpu_ctx* c, int field, int k, const l
   // pinned staging: [nb][nrow][dblock] un-encoded images, then [nb][ncols][32] nonces.  The uploads of the previous call are
   // over (every call ends with a stream synchronise), so the memory may be rewritten at once.
   const size_t img = p.nrow * hw * 16, used = nb * (img + ncols * 32);
-  if (c->cb_stage_bytes < used) {
-    if (c->cb_stage_h) (void)hipHostFree(c->cb_stage_h);  // (scrubbed after the call that filled it)
-    c->cb_stage_h = nullptr;
-    c->cb_stage_bytes = 0;
-    if (hipHostMalloc(&c->cb_stage_h, used, hipHostMallocDefault) != hipSuccess) {
-      (void)hipGetLastError();
-      c->cb_stage_h = nullptr;
-      return lf_fail(c, LFGPU_ERR_NOMEM, "ligero_commit_batch: %zu bytes of pinned staging", used);
-    }
-    c->cb_stage_bytes = used;
-  }
-  uint8_t* const stage = (uint8_t*)c->cb_stage_h;
+  uint8_t* stage = nullptr;
+  LF_TRY(lig::cb_stage(c, "ligero_commit_batch", used, &stage));
   uint8_t* const h_non = stage + nb * img;
-  struct Scrub {  // the images hold the witnesses, the pads and the blinding rows
-    uint8_t* p;
-    size_t n;
-    ~Scrub() { explicit_bzero(p, n); }
-  } scrub{stage, used};
+  const lig::CbScrub scrub{stage, used};
   // the host half, statement by statement in index order: all draws of statement b from rng[b]
   for (size_t b = 0; b < nb; ++b) {
     char err[256] = {0};
@@ -920,6 +906,27 @@ extern "C" int lfgpu_ligero_commit_batch(lfgpu_ctx* c, int field, int k, const l
   if (verbose)
     fprintf(stderr, "lfgpu ligero_commit_batch: %zu x %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
             nb, p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, lig::clock_ms() - tv2);
+  return LFGPU_OK;
+}
+
+// ... over Fp256Base: the provers lfgpu_ligero_commit(field = P256) returns, their records from ONE chain of zk256.hip
+extern "C" int lfgpu_ligero_commit_batch256(lfgpu_ctx* c, const lfgpu_ligero_param* pp, size_t nb, const void* const* h_W, const size_t* h_lqc,
+                                            const lfgpu_rng_fn* rng, void* const* rng_user, uint8_t* roots_out, lfgpu_ligero_prover** out) {
+  if (!c || !pp || !h_W || !rng || !roots_out || !out) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch256: null argument");
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch256: nb = %zu, a batch holds 1..%d statements", nb, LFGPU_SC_BATCH_MAX);
+  for (size_t b = 0; b < nb; ++b)
+    if (!ligero_args_ok(LFGPU_FIELD_P256, 0, pp, h_W[b], h_lqc, rng[b], true))
+      return lf_fail(c, LFGPU_ERR_ARG, "ligero_commit_batch256: bad argument for statement %zu (null pointer)", b);
+  for (size_t b = 0; b < nb; ++b) out[b] = nullptr;
+  Lig256* L[LFGPU_SC_BATCH_MAX] = {};
+  LF_TRY(lf_lig256_commit_batch(c, pp, nb, h_W, h_lqc, rng, rng_user, roots_out, L));
+  for (size_t b = 0; b < nb; ++b) {
+    lfgpu_ligero_prover* pr = out[b] = new lfgpu_ligero_prover();
+    pr->c = c;
+    pr->p = *pp;
+    pr->field = LFGPU_FIELD_P256;
+    pr->p256 = L[b];
+  }
   return LFGPU_OK;
 }
 

@@ -122,6 +122,30 @@ struct Slab {
 
 inline double clock_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
+// The context's pinned staging of a batched commit (ctx.h: cb_stage_h), at least `used` bytes: kept from call to call, replaced by
+// a larger one when a call needs more.  The uploads of the previous call are over (every call ends with a stream synchronise), so
+// the memory may be rewritten at once.  The caller scrubs what it wrote before it returns (CbScrub).
+inline int cb_stage(lfgpu_ctx* c, const char* who, size_t used, uint8_t** out) {
+  if (c->cb_stage_bytes < used) {
+    if (c->cb_stage_h) (void)hipHostFree(c->cb_stage_h);  // (scrubbed after the call that filled it)
+    c->cb_stage_h = nullptr;
+    c->cb_stage_bytes = 0;
+    if (hipHostMalloc(&c->cb_stage_h, used, hipHostMallocDefault) != hipSuccess) {
+      (void)hipGetLastError();
+      c->cb_stage_h = nullptr;
+      return lf_fail(c, LFGPU_ERR_NOMEM, "%s: %zu bytes of pinned staging", who, used);
+    }
+    c->cb_stage_bytes = used;
+  }
+  *out = (uint8_t*)c->cb_stage_h;
+  return LFGPU_OK;
+}
+struct CbScrub {  // the images hold the witnesses, the pads and the blinding rows
+  uint8_t* p;
+  size_t n;
+  ~CbScrub() { explicit_bzero(p, n); }
+};
+
 inline void shard_split(size_t n, int rank, int world, size_t* start, size_t* count) {  // contiguous, sizes differ by at most 1
   const size_t base = n / (size_t)world, rem = n % (size_t)world, r = (size_t)rank;
   *start = r * base + std::min(r, rem);

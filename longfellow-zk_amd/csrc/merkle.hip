@@ -217,33 +217,30 @@ extern "C" int lfgpu_column_commit(lfgpu_ctx* c, int field, size_t nrow, size_t 
   return read_root(c, ncols, d_layers, root_out);
 }
 
-extern "C" int lfgpu_column_commit_batch(lfgpu_ctx* c, int field, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb,
-                                         const void* const* d_T, const void* d_nonces, void* const* d_layers, uint8_t* roots_out) {
-  if (!c || !d_T || !d_nonces || !d_layers || !roots_out || ncols == 0) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: bad argument");
-  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: nb = %zu, a batch holds 1..%d statements", nb, LFGPU_SC_BATCH_MAX);
-  if (col0 + ncols > ld) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: col0 + ncols > ld");
-  if (nrow > 0x0fffffffu || ncols > 0x7fffffffu) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: too large");
-  if (field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "column_commit_batch: Fp256Base columns are committed one statement at a time");
-  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: unknown field %d", field);
-  LfBatchPtrs pt{}, pl{};
+// what both batched column commits ask of their shape ...
+static int column_commit_batch_shape(lfgpu_ctx* c, const char* who, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb, const void* const* d_T,
+                                     const void* d_nonces, void* const* d_layers, const uint8_t* roots_out) {
+  if (!c || !d_T || !d_nonces || !d_layers || !roots_out || ncols == 0) return lf_fail(c, LFGPU_ERR_ARG, "%s: bad argument", who);
+  if (nb == 0 || nb > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "%s: nb = %zu, a batch holds 1..%d statements", who, nb, LFGPU_SC_BATCH_MAX);
+  if (col0 + ncols > ld) return lf_fail(c, LFGPU_ERR_ARG, "%s: col0 + ncols > ld", who);
+  if (nrow > 0x0fffffffu || ncols > 0x7fffffffu) return lf_fail(c, LFGPU_ERR_ARG, "%s: too large", who);
+  return LFGPU_OK;
+}
+// ... and the pointer tables of their statements
+static int column_commit_batch_ptrs(lfgpu_ctx* c, const char* who, size_t nb, const void* const* d_T, void* const* d_layers, LfBatchPtrs* pt, LfBatchPtrs* pl) {
   for (size_t b = 0; b < nb; ++b) {
-    if (!d_T[b] || !d_layers[b]) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: null pointer for statement %zu", b);
-    pt.p[b] = const_cast<void*>(d_T[b]);
-    pl.p[b] = d_layers[b];
+    if (!d_T[b] || !d_layers[b]) return lf_fail(c, LFGPU_ERR_ARG, "%s: null pointer for statement %zu", who, b);
+    pt->p[b] = const_cast<void*>(d_T[b]);
+    pl->p[b] = d_layers[b];
   }
-  LF_HIP(c, hipSetDevice(c->device));
-  void* d_roots = nullptr;
-  LF_TRY(lf_scratch(c, LFGPU_SC_BATCH_MAX * 32, &d_roots));
-  const dim3 gl((u32)((ncols + SHA_THREADS - 1) / SHA_THREADS), (u32)nb);
-  if (field == LFGPU_FIELD_GF2_128)
-    hipLaunchKernelGGL(column_leaves_batch_kernel<FIELD_GF2_128>, gl, dim3(SHA_THREADS), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, pt,
-                       (const uint4*)d_nonces, pl);
-  else
-    hipLaunchKernelGGL(column_leaves_batch_kernel<FIELD_FP128>, gl, dim3(SHA_THREADS), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, pt,
-                       (const uint4*)d_nonces, pl);
+  return LFGPU_OK;
+}
+// the trees above nb leaf levels (build_tree with the statement on a grid axis), the roots in one contiguous device array and
+// back in one copy; ends with a stream synchronise
+static int tree_batch(lfgpu_ctx* c, size_t ncols, size_t nb, const LfBatchPtrs& pl, void* d_roots, uint8_t* roots_out) {
   if (ncols < 2) {
     hipLaunchKernelGGL(merkle_root_is_leaf_batch_kernel, dim3((u32)nb), dim3(64), 0, c->stream, pl, (uint4*)d_roots);
-  } else {  // build_tree with the statement on a grid axis
+  } else {
     int d = 0;
     while (((size_t)2 << d) <= ncols - 1) ++d;
     for (; d > 10; --d) {
@@ -258,6 +255,42 @@ extern "C" int lfgpu_column_commit_batch(lfgpu_ctx* c, int field, size_t nrow, s
   LF_HIP(c, hipStreamSynchronize(c->stream));
   memcpy(roots_out, c->mailbox_h, nb * 32);
   return LFGPU_OK;
+}
+
+extern "C" int lfgpu_column_commit_batch(lfgpu_ctx* c, int field, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb,
+                                         const void* const* d_T, const void* d_nonces, void* const* d_layers, uint8_t* roots_out) {
+  static const char* const who = "column_commit_batch";
+  LF_TRY(column_commit_batch_shape(c, who, nrow, ld, col0, ncols, nb, d_T, d_nonces, d_layers, roots_out));
+  if (field == LFGPU_FIELD_P256)
+    return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "column_commit_batch: 16-byte fields only (Fp256Base columns take lfgpu_column_commit_batch256)");
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "column_commit_batch: unknown field %d", field);
+  LfBatchPtrs pt{}, pl{};
+  LF_TRY(column_commit_batch_ptrs(c, who, nb, d_T, d_layers, &pt, &pl));
+  LF_HIP(c, hipSetDevice(c->device));
+  void* d_roots = nullptr;
+  LF_TRY(lf_scratch(c, LFGPU_SC_BATCH_MAX * 32, &d_roots));
+  const dim3 gl((u32)((ncols + SHA_THREADS - 1) / SHA_THREADS), (u32)nb);
+  if (field == LFGPU_FIELD_GF2_128)
+    hipLaunchKernelGGL(column_leaves_batch_kernel<FIELD_GF2_128>, gl, dim3(SHA_THREADS), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, pt,
+                       (const uint4*)d_nonces, pl);
+  else
+    hipLaunchKernelGGL(column_leaves_batch_kernel<FIELD_FP128>, gl, dim3(SHA_THREADS), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, pt,
+                       (const uint4*)d_nonces, pl);
+  return tree_batch(c, ncols, nb, pl, d_roots, roots_out);
+}
+
+// ... over 32-byte elements (Fp256Base): column_leaves32_batch_kernel (p256.hip) under the same trees
+extern "C" int lfgpu_column_commit_batch256(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb, const void* const* d_T,
+                                            const void* d_nonces, void* const* d_layers, uint8_t* roots_out) {
+  static const char* const who = "column_commit_batch256";
+  LF_TRY(column_commit_batch_shape(c, who, nrow, ld, col0, ncols, nb, d_T, d_nonces, d_layers, roots_out));
+  LfBatchPtrs pt{}, pl{};
+  LF_TRY(column_commit_batch_ptrs(c, who, nb, d_T, d_layers, &pt, &pl));
+  LF_HIP(c, hipSetDevice(c->device));
+  void* d_roots = nullptr;
+  LF_TRY(lf_scratch(c, LFGPU_SC_BATCH_MAX * 32, &d_roots));
+  LF_TRY(lf_column_leaves32_batch(c, nrow, ld, col0, ncols, nb, pt, d_nonces, pl));
+  return tree_batch(c, ncols, nb, pl, d_roots, roots_out);
 }
 
 // the leaf half alone (multi-GPU commit: a rank hashes the columns it owns); enqueue only

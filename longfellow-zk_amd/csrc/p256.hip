@@ -94,19 +94,34 @@ static int fp2_fft(lfgpu_ctx* c, bool fwd, size_t batch, u32 P, fp2_t* Z, const 
 }
 
 // ------------------------------------------------------------------ Reed-Solomon rows
-// Z[pair][i] = binom[i] * (T[2 pair][i] + i T[2 pair + 1][i]) for i < n, 0 up to P  (reed_solomon.h:101-104)
+// One complex row of the convolution's input: z[i] = binom[i] * (row0[i] + i row1[i]) for i < n, 0 up to P (reed_solomon.h:101-104);
+// row1 == nullptr: the odd last row, its imaginary part stays zero.  The body of p256_rs_pre_kernel and of its batched twin.
+__device__ __forceinline__ void p256_rs_pre_row(u32 i, u32 n, const elt32_t* __restrict__ binom, const elt32_t* __restrict__ row0,
+                                                const elt32_t* __restrict__ row1, fp2_t* __restrict__ z) {
+  fp2_t v{e32_zero(), e32_zero()};
+  if (i < n) {
+    const elt32_t b = ld32(&binom[i]);
+    v.re = fp256_mul(b, ld32(&row0[i]));
+    if (row1) v.im = fp256_mul(b, ld32(&row1[i]));
+  }
+  stc(&z[i], v);
+}
+// ... and of its output: row[k] = lead[k - (n-1)] * conv[k] for n <= k < m (reed_solomon.h:106-109); row1 == nullptr: nothing is
+// written for the imaginary part
+__device__ __forceinline__ void p256_rs_post_row(u32 i, u32 n, const elt32_t* __restrict__ lead, const fp2_t* __restrict__ z,
+                                                 elt32_t* __restrict__ row0, elt32_t* __restrict__ row1) {
+  const elt32_t l = ld32(&lead[i - (n - 1)]);
+  const fp2_t v = ldc(&z[i]);
+  st32(&row0[i], fp256_mul(l, v.re));
+  if (row1) st32(&row1[i], fp256_mul(l, v.im));
+}
+// Z[pair] from rows 2 pair, 2 pair + 1 of one tableau
 __global__ void p256_rs_pre_kernel(u32 n, u32 P, u32 nrow, const elt32_t* __restrict__ binom, const elt32_t* __restrict__ T, size_t ld,
                                    fp2_t* __restrict__ Z) {
   const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= P) return;
   const u32 r0 = 2 * blockIdx.y, r1 = r0 + 1;
-  fp2_t v{e32_zero(), e32_zero()};
-  if (i < n) {
-    const elt32_t b = ld32(&binom[i]);
-    v.re = fp256_mul(b, ld32(&T[(size_t)r0 * ld + i]));
-    if (r1 < nrow) v.im = fp256_mul(b, ld32(&T[(size_t)r1 * ld + i]));
-  }
-  stc(&Z[(size_t)blockIdx.y * P + i], v);
+  p256_rs_pre_row(i, n, binom, T + (size_t)r0 * ld, r1 < nrow ? T + (size_t)r1 * ld : nullptr, Z + (size_t)blockIdx.y * P);
 }
 // Z[k] *= yhat[k] (both in the forward transform's bit-reversed order)
 __global__ void p256_rs_pointwise_kernel(u32 P, const fp2_t* __restrict__ yhat, fp2_t* __restrict__ Z) {
@@ -115,16 +130,40 @@ __global__ void p256_rs_pointwise_kernel(u32 P, const fp2_t* __restrict__ yhat, 
   fp2_t* z = &Z[(size_t)blockIdx.y * P + i];
   stc(z, fp2_mul(ldc(z), ldc(&yhat[i])));
 }
-// y[k] = lead[k - (n-1)] * conv[k] for n <= k < m  (reed_solomon.h:106-109)
+// rows 2 pair, 2 pair + 1 of one tableau from Z[pair]
 __global__ void p256_rs_post_kernel(u32 n, u32 m, u32 P, u32 nrow, const elt32_t* __restrict__ lead, const fp2_t* __restrict__ Z,
                                     elt32_t* __restrict__ T, size_t ld) {
   const u32 i = n + blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= m) return;
   const u32 r0 = 2 * blockIdx.y, r1 = r0 + 1;
-  const elt32_t l = ld32(&lead[i - (n - 1)]);
-  const fp2_t z = ldc(&Z[(size_t)blockIdx.y * P + i]);
-  st32(&T[(size_t)r0 * ld + i], fp256_mul(l, z.re));
-  if (r1 < nrow) st32(&T[(size_t)r1 * ld + i], fp256_mul(l, z.im));
+  p256_rs_post_row(i, n, lead, Z + (size_t)blockIdx.y * P, T + (size_t)r0 * ld, r1 < nrow ? T + (size_t)r1 * ld : nullptr);
+}
+
+// The batched twins: one row group of cb tableaux of one shape through ONE convolution.  The group's rows are numbered through all
+// statements, q = b * gr + r (statement b, r-th row of the group), and rows 2 pair, 2 pair + 1 of that numbering share a complex
+// transform -- across statements too, so a one-row group does not leave every imaginary half empty (the arithmetic is exact:
+// the pairing does not change a value).  Row r of the group is tableau row base + r, or base + r + skip from r = seg on (the
+// group [0, idot) + [iquad + 1, nrow) is base 0, seg idot, skip 2).  Statement and row follow from blockIdx.y alone: the base
+// pointers are scalar loads from the kernarg segment.
+struct P256RowGroup {
+  u32 total, gr, base, seg, skip;  // total = cb * gr rows
+};
+__device__ __forceinline__ elt32_t* p256_group_row(const LfBatchPtrs& T, size_t ld, const P256RowGroup& g, u32 q) {
+  const u32 b = q / g.gr, r = q - b * g.gr;
+  return (elt32_t*)T.p[b] + (size_t)(g.base + r + (r >= g.seg ? g.skip : 0u)) * ld;
+}
+__global__ void p256_rs_pre_batch_kernel(u32 n, u32 P, P256RowGroup g, const elt32_t* __restrict__ binom, LfBatchPtrs T, size_t ld, fp2_t* __restrict__ Z) {
+  const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  const u32 q0 = 2 * blockIdx.y, q1 = q0 + 1;
+  p256_rs_pre_row(i, n, binom, p256_group_row(T, ld, g, q0), q1 < g.total ? p256_group_row(T, ld, g, q1) : nullptr, Z + (size_t)blockIdx.y * P);
+}
+__global__ void p256_rs_post_batch_kernel(u32 n, u32 m, u32 P, P256RowGroup g, const elt32_t* __restrict__ lead, const fp2_t* __restrict__ Z, LfBatchPtrs T,
+                                          size_t ld) {
+  const u32 i = n + blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  const u32 q0 = 2 * blockIdx.y, q1 = q0 + 1;
+  p256_rs_post_row(i, n, lead, Z + (size_t)blockIdx.y * P, p256_group_row(T, ld, g, q0), q1 < g.total ? p256_group_row(T, ld, g, q1) : nullptr);
 }
 
 // host-side field helpers: fp256.h
@@ -156,14 +195,17 @@ static int p256_twiddles(lfgpu_ctx* c, u32 P, const fp2_t** out) {
   return LFGPU_OK;
 }
 
-extern "C" int lfgpu_fp256_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, void* d_T, size_t ld) {
-  if (!c || (!d_T && nrow)) return lf_fail(c, LFGPU_ERR_ARG, "fp256_rs_encode_rows: null argument");
-  if (n == 0 || m < n || ld < m) return lf_fail(c, LFGPU_ERR_ARG, "fp256_rs_encode_rows: need 0 < n <= m <= ld");
-  if (nrow == 0 || m == n) return LFGPU_OK;
+// The device tables of the extension n -> m (0 < n < m): the twiddles of its transform size P and the constants of the ReedSolomon
+// ctor.  Built on first use, with synchronous copies and a stream synchronise; a later call only looks them up.
+struct P256RsTables {
+  size_t P;
+  const fp2_t *W, *yhat;
+  const elt32_t *binom, *lead;
+};
+static int p256_rs_tables(lfgpu_ctx* c, const char* who, size_t n, size_t m, P256RsTables* out) {
   size_t P = 1;
   while (P < m) P <<= 1;
-  if (P > ((size_t)1 << 24)) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "fp256_rs_encode_rows: m > 2^24");
-  LF_HIP(c, hipSetDevice(c->device));
+  if (P > ((size_t)1 << 24)) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "%s: m > 2^24", who);
   const fp2_t* W = nullptr;
   LF_TRY(p256_twiddles(c, (u32)P, &W));
   const size_t d = n - 1;
@@ -216,18 +258,68 @@ extern "C" int lfgpu_fp256_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, s
     lf_table_lookup(c, key + ":binom", &dbinom);
     lf_table_lookup(c, key + ":lead", &dlead);
   }
-  const size_t npair = (nrow + 1) / 2;
+  *out = P256RsTables{P, W, (const fp2_t*)dyhat, (const elt32_t*)dbinom, (const elt32_t*)dlead};
+  return LFGPU_OK;
+}
+
+extern "C" int lfgpu_fp256_rs_encode_rows(lfgpu_ctx* c, size_t nrow, size_t n, size_t m, void* d_T, size_t ld) {
+  if (!c || (!d_T && nrow)) return lf_fail(c, LFGPU_ERR_ARG, "fp256_rs_encode_rows: null argument");
+  if (n == 0 || m < n || ld < m) return lf_fail(c, LFGPU_ERR_ARG, "fp256_rs_encode_rows: need 0 < n <= m <= ld");
+  if (nrow == 0 || m == n) return LFGPU_OK;
+  LF_HIP(c, hipSetDevice(c->device));
+  P256RsTables t;
+  LF_TRY(p256_rs_tables(c, "fp256_rs_encode_rows", n, m, &t));
+  const size_t P = t.P, npair = (nrow + 1) / 2;
   void* Zv = nullptr;
   LF_TRY(lf_scratch2(c, npair * P * sizeof(fp2_t), &Zv));
   fp2_t* Z = (fp2_t*)Zv;
   const dim3 gp((u32)((P + 255) / 256), (u32)npair);
-  hipLaunchKernelGGL(p256_rs_pre_kernel, gp, dim3(256), 0, c->stream, (u32)n, (u32)P, (u32)nrow, (const elt32_t*)dbinom, (const elt32_t*)d_T, ld, Z);
-  LF_TRY(fp2_fft(c, true, npair, (u32)P, Z, W));
-  hipLaunchKernelGGL(p256_rs_pointwise_kernel, gp, dim3(256), 0, c->stream, (u32)P, (const fp2_t*)dyhat, Z);
-  LF_TRY(fp2_fft(c, false, npair, (u32)P, Z, W));
+  hipLaunchKernelGGL(p256_rs_pre_kernel, gp, dim3(256), 0, c->stream, (u32)n, (u32)P, (u32)nrow, t.binom, (const elt32_t*)d_T, ld, Z);
+  LF_TRY(fp2_fft(c, true, npair, (u32)P, Z, t.W));
+  hipLaunchKernelGGL(p256_rs_pointwise_kernel, gp, dim3(256), 0, c->stream, (u32)P, t.yhat, Z);
+  LF_TRY(fp2_fft(c, false, npair, (u32)P, Z, t.W));
   const dim3 go((u32)((m - n + 255) / 256), (u32)npair);
-  hipLaunchKernelGGL(p256_rs_post_kernel, go, dim3(256), 0, c->stream, (u32)n, (u32)m, (u32)P, (u32)nrow, (const elt32_t*)dlead, (const fp2_t*)Z,
-                     (elt32_t*)d_T, ld);
+  hipLaunchKernelGGL(p256_rs_post_kernel, go, dim3(256), 0, c->stream, (u32)n, (u32)m, (u32)P, (u32)nrow, t.lead, (const fp2_t*)Z, (elt32_t*)d_T, ld);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+
+// ---- the batched commit's encoder (zk256.hip: lig256_commit_batch)
+// The tables of the extension n -> m exist when this returns: called for every shape of a chain before anything is enqueued, so
+// that the chain itself never meets the first-use set-up (synchronous copies and a synchronise)
+int lf_p256_rs_prepare(lfgpu_ctx* c, size_t n, size_t m) {
+  if (n == 0 || m < n) return lf_fail(c, LFGPU_ERR_ARG, "p256_rs_prepare: need 0 < n <= m");
+  if (m == n) return LFGPU_OK;
+  P256RsTables t;
+  return p256_rs_tables(c, "p256_rs_prepare", n, m, &t);
+}
+// convolution scratch of `rows` rows of an extension to m, in bytes; 0: more row pairs than one launch's gridDim.y holds
+size_t lf_p256_rs_batch_scratch(size_t rows, size_t m) {
+  size_t P = 1;
+  while (P < m) P <<= 1;
+  const size_t pairs = (rows + 1) / 2;
+  return pairs <= 65535 ? pairs * P * sizeof(fp2_t) : 0;
+}
+// One row group of cb tableaux (statement b at T.p[b], stride ld), gr rows each, n values long, extended to m in place through
+// ONE convolution of cb * gr rows: group row r is tableau row base + r, from r = seg on base + r + skip.  Z: the convolution
+// scratch, lf_p256_rs_batch_scratch(cb * gr, m) bytes.  Enqueue only.
+int lf_p256_rs_rows_batch(lfgpu_ctx* c, size_t cb, const LfBatchPtrs& T, size_t base, size_t seg, size_t skip, size_t gr, size_t n, size_t m, size_t ld,
+                          void* d_Z) {
+  if (cb == 0 || gr == 0 || m == n) return LFGPU_OK;
+  const size_t total = cb * gr, npair = (total + 1) / 2;
+  if (cb > LFGPU_SC_BATCH_MAX || npair > 65535 || n == 0 || m < n || ld < m || !d_Z) return lf_fail(c, LFGPU_ERR_ARG, "p256_rs_rows_batch: bad argument");
+  P256RsTables t;
+  LF_TRY(p256_rs_tables(c, "p256_rs_rows_batch", n, m, &t));  // (a lookup: lf_p256_rs_prepare has run)
+  const u32 P = (u32)t.P;
+  fp2_t* Z = (fp2_t*)d_Z;
+  const P256RowGroup g{(u32)total, (u32)gr, (u32)base, (u32)seg, (u32)skip};
+  const dim3 gp((P + 255) / 256, (u32)npair);
+  hipLaunchKernelGGL(p256_rs_pre_batch_kernel, gp, dim3(256), 0, c->stream, (u32)n, P, g, t.binom, T, ld, Z);
+  LF_TRY(fp2_fft(c, true, npair, P, Z, t.W));
+  hipLaunchKernelGGL(p256_rs_pointwise_kernel, gp, dim3(256), 0, c->stream, P, t.yhat, Z);
+  LF_TRY(fp2_fft(c, false, npair, P, Z, t.W));
+  const dim3 go((u32)((m - n + 255) / 256), (u32)npair);
+  hipLaunchKernelGGL(p256_rs_post_batch_kernel, go, dim3(256), 0, c->stream, (u32)n, (u32)m, P, g, t.lead, (const fp2_t*)Z, T, ld);
   LF_HIP(c, hipGetLastError());
   return LFGPU_OK;
 }
@@ -252,11 +344,8 @@ extern "C" int lfgpu_fp256_rs_encode_rows_host(lfgpu_ctx* c, size_t nrow, size_t
 // ------------------------------------------------------------------ column hash, 32-byte elements
 // leaf_j = SHA256(nonce_j[32] || canon(T[0][col0+j]) || ... ), canon = 32 little-endian bytes of the value out of
 // Montgomery form.  One lane per column; a row read is two coalesced 16 B/lane loads per lane.
-__global__ __launch_bounds__(256) void column_leaves32_kernel(u32 nrow, size_t ld, size_t col0, u32 ncols, const elt32_t* __restrict__ T,
-                                                              const uint4* __restrict__ nonces, uint4* __restrict__ out, size_t out0) {
-  const u32 j = blockIdx.x * 256 + threadIdx.x;
-  if (j >= ncols) return;
-  const elt32_t* col = T + col0 + j;
+// (the body of column_leaves32_kernel and of its batched twin: col = the column's first element, nonce = its 32 bytes, out = its leaf)
+__device__ __forceinline__ void column_leaf32(u32 nrow, size_t ld, const elt32_t* __restrict__ col, const uint4* __restrict__ nonce, uint4* __restrict__ out) {
   sha_state st;
   sha_init(st);
   const u32 nch = 2 + 2 * nrow;                  // 16-byte chunks of message
@@ -270,7 +359,7 @@ __global__ __launch_bounds__(256) void column_leaves32_kernel(u32 nrow, size_t l
       const u32 ch = 4 * bi + q;
       uint4 v = make_uint4(0, 0, 0, 0);
       if (ch < 2) {
-        const uint4 nb = nonces[2 * (size_t)j + ch];
+        const uint4 nb = nonce[ch];
         v = make_uint4(bswap32(nb.x), bswap32(nb.y), bswap32(nb.z), bswap32(nb.w));
       } else if (ch < nch) {
         const u32 e = ch - 2;
@@ -291,13 +380,35 @@ __global__ __launch_bounds__(256) void column_leaves32_kernel(u32 nrow, size_t l
     }
     sha_compress(st, w);
   }
-  out[2 * (out0 + j)] = make_uint4(bswap32(st.h[0]), bswap32(st.h[1]), bswap32(st.h[2]), bswap32(st.h[3]));
-  out[2 * (out0 + j) + 1] = make_uint4(bswap32(st.h[4]), bswap32(st.h[5]), bswap32(st.h[6]), bswap32(st.h[7]));
+  out[0] = make_uint4(bswap32(st.h[0]), bswap32(st.h[1]), bswap32(st.h[2]), bswap32(st.h[3]));
+  out[1] = make_uint4(bswap32(st.h[4]), bswap32(st.h[5]), bswap32(st.h[6]), bswap32(st.h[7]));
+}
+__global__ __launch_bounds__(256) void column_leaves32_kernel(u32 nrow, size_t ld, size_t col0, u32 ncols, const elt32_t* __restrict__ T,
+                                                              const uint4* __restrict__ nonces, uint4* __restrict__ out, size_t out0) {
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= ncols) return;
+  column_leaf32(nrow, ld, T + col0 + j, nonces + 2 * (size_t)j, out + 2 * (out0 + j));
+}
+// nb tableaux of one shape: statement blockIdx.y hashes its columns with nonces [b][ncols][32] into leaf level ncols of its own heap
+__global__ __launch_bounds__(256) void column_leaves32_batch_kernel(u32 nrow, size_t ld, size_t col0, u32 ncols, LfBatchPtrs T, const uint4* __restrict__ nonces,
+                                                                    LfBatchPtrs layers) {
+  const u32 b = blockIdx.y;
+  const u32 j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= ncols) return;
+  column_leaf32(nrow, ld, (const elt32_t*)T.p[b] + col0 + j, nonces + 2 * ((size_t)b * ncols + j), (uint4*)layers.p[b] + 2 * ((size_t)ncols + j));
 }
 int lf_column_leaves32(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, const void* d_T, const void* d_nonces, void* d_out,
                        size_t out0) {
   hipLaunchKernelGGL(column_leaves32_kernel, dim3((u32)((ncols + 255) / 256)), dim3(256), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols,
                      (const elt32_t*)d_T, (const uint4*)d_nonces, (uint4*)d_out, out0);
+  LF_HIP(c, hipGetLastError());
+  return LFGPU_OK;
+}
+// enqueue only; the caller has checked the shape (lfgpu_column_commit_batch256)
+int lf_column_leaves32_batch(lfgpu_ctx* c, size_t nrow, size_t ld, size_t col0, size_t ncols, size_t nb, const LfBatchPtrs& T, const void* d_nonces,
+                             const LfBatchPtrs& layers) {
+  hipLaunchKernelGGL(column_leaves32_batch_kernel, dim3((u32)((ncols + 255) / 256), (u32)nb), dim3(256), 0, c->stream, (u32)nrow, ld, col0, (u32)ncols, T,
+                     (const uint4*)d_nonces, layers);
   LF_HIP(c, hipGetLastError());
   return LFGPU_OK;
 }

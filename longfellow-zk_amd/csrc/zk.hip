@@ -919,6 +919,24 @@ extern "C" int lfgpu_zk_prove_batch256(lfgpu_zk_batch256* bt, lfgpu_zk_prover* c
   return zk256_prove_batch(bt->bt, z.data(), nb, h_W, ts, ok);  // (a prover that has not committed, a transcript without the sized hooks: found there, first)
 }
 
+// ZkProver::commit for nb Fp256Base provers: the handles are checked here, the commit is zk256.hip's (zk256_commit_batch)
+extern "C" int lfgpu_zk_commit_batch256(lfgpu_zk_batch256* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng,
+                                        void* const* rng_user, const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
+  if (!bt || !zk || !h_W || !rng || !ts) return LFGPU_ERR_ARG;
+  lfgpu_ctx* c = bt->c;
+  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
+  std::vector<Zk256*> z(nb);
+  for (size_t b = 0; b < nb; ++b) {
+    if (!zk[b] || !h_W[b] || !rng[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: null argument for statement %zu", b);
+    if (zk[b]->c != c || zk[b]->C != bt->C || !zk[b]->z256) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: prover %zu belongs to another context or circuit", b);
+    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_commit_batch256: prover %zu has a communicator (the batch runs on one GPU)", b);
+    for (size_t a = 0; a < b; ++a)
+      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: prover %zu appears twice", b);
+    z[b] = zk[b]->z256;
+  }
+  return zk256_commit_batch(bt->bt, z.data(), nb, h_W, rng, rng_user, ts, roots_out);
+}
+
 extern "C" int lfgpu_zk_batch256_free(lfgpu_zk_batch256* bt) {
   if (!bt) return LFGPU_ERR_ARG;
   delete bt;

@@ -2308,6 +2308,122 @@ int lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const s
 }
 Lig32* lig32_of(Lig256* L) { return reinterpret_cast<Lig32*>(L); }
 
+// ---- nb commits of one shape in one chain of dispatches (lfgpu_ligero_commit_batch256, zk256_commit_batch): what
+// lfgpu_ligero_commit_batch is for the 16-byte fields.  A single commit is a chain of short launches -- three row groups, each
+// pre, forward transform, pointwise product, inverse transform, post; then leaves and tree -- over a tableau of a few MB, so nb
+// provers pay the chain nb times.  Here the rows [0, idot) and [iquad + 1, nrow) of every statement of a chunk (all encode
+// `block` values with the same tables) go through ONE chain, the two dblock rows of every statement through a second, and the
+// leaves and trees of all statements follow (lfgpu_column_commit_batch256).
+// Statements per chain: the row pairs of the larger group fit one launch's gridDim.y and their convolution scratch stays below
+// LF_CB_SCRATCH_CAP; LFGPU_CB_CHUNK overrides (read once).  0: not even one statement fits -- the single path's encoder.
+size_t commit_batch256_chunk(const lfgpu_ligero_param& p, size_t nb) {
+  static const long env = getenv("LFGPU_CB_CHUNK") ? atol(getenv("LFGPU_CB_CHUNK")) : 0;
+  const size_t rows = std::max<size_t>(p.nrow - 2, 2);
+  size_t P = 1;
+  while (P < p.block_enc) P <<= 1;
+  const size_t pairs_max = std::min<size_t>(65535, LF_CB_SCRATCH_CAP / (P * sizeof(fp2_t)));
+  size_t chunk = std::min(nb, 2 * pairs_max / rows);
+  if (env > 0) chunk = std::min(chunk, (size_t)env);
+  return chunk;
+}
+// W[b]: witness || pads of statement b; users may be null.  On success out[b] is statement b's prover and roots[32 b ..] its root;
+// on any error no prover is returned.  Draws, staging and errors: the contract of lfgpu_ligero_commit_batch256 (lfgpu.h).
+int lig256_commit_batch(lfgpu_ctx* c, const lfgpu_ligero_param& p, size_t nb, const E* const* W, const size_t* lqc, const lfgpu_rng_fn* rng, void* const* users,
+                        uint8_t* roots, Lig32** out) {
+  static const char* const who = "ligero_commit_batch256";
+  if (p.ildt != 0 || p.idot != 1 || p.iquad != 2 || p.iw != 3 || p.nrow < 3) return lf_fail(c, LFGPU_ERR_ARG, "ligero256: row order");
+  for (size_t b = 0; b < nb; ++b) out[b] = nullptr;
+  auto user = [&](size_t b) { return users ? users[b] : nullptr; };
+  auto drop = [&](int rc) {  // no prover is returned: their buffers go back to the pool scrubbed (~Slab)
+    for (size_t b = 0; b < nb; ++b) {
+      delete out[b];
+      out[b] = nullptr;
+    }
+    return rc;
+  };
+  static const int batched = getenv("LFGPU_COMMIT_BATCH256") ? atoi(getenv("LFGPU_COMMIT_BATCH256")) : 1;
+  if (!batched) {  // the A/B switch: the same semantics over the single-statement device path
+    for (size_t b = 0; b < nb; ++b) {
+      const int rc = lig256_commit(c, p, W[b], lqc, rng[b], user(b), roots + 32 * b, &out[b]);
+      if (rc) return drop(rc);
+    }
+    return LFGPU_OK;
+  }
+  const size_t ld = p.block_enc, hw = p.dblock, ncols = p.block_ext;
+  LF_HIP(c, hipSetDevice(c->device));
+  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
+  const double tv0 = lig::clock_ms();
+  // pinned staging: [nb][nrow][dblock] un-encoded images, then [nb][ncols][32] nonces
+  const size_t img = p.nrow * hw * sizeof(E), used = nb * (img + ncols * 32);
+  uint8_t* stage = nullptr;
+  LF_TRY(lig::cb_stage(c, who, used, &stage));
+  uint8_t* const h_non = stage + nb * img;
+  const lig::CbScrub scrub{stage, used};
+  // the host half, statement by statement in index order: all draws of statement b from rng[b]
+  for (size_t b = 0; b < nb; ++b) {
+    char err[256] = {0};
+    const int rc = lig::layout(L32(), p, W[b], 0, lqc, rng[b], user(b), c->rng_exact != 0, 0, p.nrow, (E*)(stage + b * img), h_non + b * ncols * 32, err);
+    if (rc) return lf_fail(c, rc, "%s (statement %zu)", err, b);
+  }
+  const double tv1 = lig::clock_ms();
+  // Everything that may synchronise comes before the first enqueue: the encoder's tables of both shapes (first use: synchronous
+  // copies and a synchronise) and the growth of the scratch slots.  The slots of the chain: the convolution scratch Z is scratch2,
+  // the nonces scratch3, the roots scratch (lfgpu_column_commit_batch256); the tableaux and heaps are the provers' own.
+  const size_t chunk = commit_batch256_chunk(p, nb), g1 = p.nrow - 2;
+  void *d_Z = nullptr, *d_non = nullptr, *d_roots = nullptr;
+  if (chunk) {
+    LF_TRY(lf_p256_rs_prepare(c, p.block, p.block_enc));
+    LF_TRY(lf_p256_rs_prepare(c, p.dblock, p.block_enc));
+    LF_TRY(lf_scratch2(c, lf_p256_rs_batch_scratch(chunk * std::max<size_t>(g1, 2), p.block_enc), &d_Z));
+  }
+  LF_TRY(lf_scratch3(c, nb * ncols * 32, &d_non));
+  LF_TRY(lf_scratch(c, LFGPU_SC_BATCH_MAX * 32, &d_roots));
+  // After a failed enqueue the stream may still read the staging memory: wait before it is scrubbed
+  auto fail = [&](int rc) {
+    (void)hipStreamSynchronize(c->stream);
+    return drop(rc);
+  };
+  E* d_T[LFGPU_SC_BATCH_MAX];
+  void* d_L[LFGPU_SC_BATCH_MAX];
+  int rc = LFGPU_OK;
+  for (size_t b = 0; b < nb; ++b) {
+    Lig32* L = out[b] = new Lig32();
+    L->init(c, p, nullptr);
+    L->nonces.assign(h_non + b * ncols * 32, h_non + (b + 1) * ncols * 32);
+    if ((rc = L->alloc())) return fail(rc);
+    d_T[b] = L->d_T;
+    d_L[b] = L->d_layers;
+  }
+  for (size_t b = 0; b < nb; ++b)
+    if (hipMemcpy2DAsync(d_T[b], ld * sizeof(E), stage + b * img, hw * sizeof(E), hw * sizeof(E), p.nrow, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+      return fail(lf_fail(c, LFGPU_ERR_HIP, "%s: upload failed (statement %zu)", who, b));
+  for (size_t b0 = 0; b0 < nb; b0 += std::max<size_t>(chunk, 1)) {
+    if (!chunk) {  // a row group of one statement overflows a launch or the cap: the single path's encoder
+      if ((rc = lig::extend_slab(c, L32(), p, 0, p.nrow, d_T[b0]))) return fail(rc);
+      continue;
+    }
+    const size_t cb = std::min(chunk, nb - b0);
+    LfBatchPtrs pt{};
+    for (size_t b = 0; b < cb; ++b) pt.p[b] = d_T[b0 + b];
+    if ((rc = lf_p256_rs_rows_batch(c, cb, pt, 0, p.idot, 2, g1, p.block, p.block_enc, ld, d_Z))) return fail(rc);   // [0, idot) + [iquad + 1, nrow)
+    if ((rc = lf_p256_rs_rows_batch(c, cb, pt, p.idot, 2, 0, 2, p.dblock, p.block_enc, ld, d_Z))) return fail(rc);  // idot, iquad
+  }
+  // the nonces go up behind the encode, as in lig::commit_rows
+  if (hipMemcpyAsync(d_non, h_non, nb * ncols * 32, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+    return fail(lf_fail(c, LFGPU_ERR_HIP, "%s: nonce upload failed", who));
+  double tv2 = 0;
+  if (verbose) {
+    (void)hipStreamSynchronize(c->stream);
+    tv2 = lig::clock_ms();
+  }
+  // (ends with the one stream synchronise of the call: the uploads above are over when it returns)
+  if ((rc = lfgpu_column_commit_batch256(c, p.nrow, ld, p.dblock, ncols, nb, (const void* const*)d_T, d_non, d_L, roots))) return fail(rc);
+  if (verbose)
+    fprintf(stderr, "lfgpu ligero_commit_batch256: %zu x %zu rows x %zu (block %zu, dblock %zu): host layout + draws %.2f ms | upload + RS encode %.2f | column hash + tree %.2f\n",
+            nb, p.nrow, ld, p.block, p.dblock, tv1 - tv0, tv2 - tv1, lig::clock_ms() - tv2);
+  return LFGPU_OK;
+}
+
 // ---- lfgpu_ligero_prove_batch256 / lfgpu_ligero_open_batch256 (lfgpu.h): the provers of lfgpu_ligero_commit(field = P256) through
 // lig::prove_batch / lig::open_batch (ligero_slab.h), which the ZK driver calls on its Lig32 directly (P32).
 // The records behind the handles.  The range of nb and a NULL entry are lig::batch_core's to refuse: the conversion stops there.
@@ -2347,6 +2463,13 @@ int lf_lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param* p, const void* h_W,
   LF_TRY(lig256_commit(c, *p, (const E*)h_W, h_lqc, rng, user, root, &L));
   *out = reinterpret_cast<Lig256*>(L);
   return LFGPU_OK;
+}
+int lf_lig256_commit_batch(lfgpu_ctx* c, const lfgpu_ligero_param* p, size_t nb, const void* const* h_W, const size_t* h_lqc, const lfgpu_rng_fn* rng,
+                           void* const* rng_user, uint8_t* roots, Lig256** out) {
+  Lig32* L[LFGPU_SC_BATCH_MAX] = {};
+  const int rc = lig256_commit_batch(c, *p, nb, (const E* const*)h_W, h_lqc, rng, rng_user, roots, L);
+  for (size_t b = 0; b < nb; ++b) out[b] = reinterpret_cast<Lig256*>(L[b]);
+  return rc;
 }
 void lf_lig256_free(Lig256* L) { delete lig32_of(L); }  // ~Slab scrubs the buffers and returns them to the context's pool
 void* lf_lig256_tableau(Lig256* L) { return lig32_of(L)->d_T; }
@@ -2757,6 +2880,68 @@ int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* co
   };
   const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max, bt->d_eq};
   return zkp::prove_batch<P32>(c, bt->C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
+}
+
+// ZkProver::commit for nb provers: zk256_commit's one-GPU branch per statement around ONE lig256_commit_batch.  The argument
+// errors left to this file -- a transcript without the sized hooks, provers with different parameters -- are found before the
+// first draw.
+int zk256_commit_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng, void* const* rng_user,
+                       const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
+  lfgpu_ctx* c = bt->c;
+  for (size_t b = 0; b < nb; ++b) {
+    LF_TRY(ts256_ok(c, ts[b]));
+    if (memcmp(&z[b]->st.param, &z[0]->st.param, sizeof(lfgpu_ligero_param)) != 0)
+      return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: prover %zu has another LigeroParam (rate, nreq or block_enc) than prover 0", b);
+  }
+  const double t0 = now_ms();
+  LF_HIP(c, hipSetDevice(c->device));
+  const lfgpu_ligero_param& p = z[0]->st.param;
+  const size_t nl = bt->C->layers.size();
+  // whatever happens from here on, no prover of the call keeps an earlier commitment or proof
+  for (size_t b = 0; b < nb; ++b) {
+    delete z[b]->lp;
+    z[b]->lp = nullptr;
+    z[b]->st.have_proof = false;
+    z[b]->st.wire_valid = false;
+  }
+  // witness || pads of every statement; fill_pad's draws of statement b come from rng[b], before its Ligero draws (the pads of
+  // ALL statements are drawn before the first Ligero layout: a statement's own order -- pads, then layout -- is the single
+  // path's as long as its engine is its own, which the header asks for)
+  std::vector<E> Wv(nb * p.nw);
+  LF_SCRUB_ON_EXIT(Wv);
+  std::vector<const E*> Wp(nb);
+  std::vector<void*> users(nb);
+  static const F256 F;  // (for fill_pad's wc0 * wc1: the constants are built once)
+  for (size_t b = 0; b < nb; ++b) {
+    auto& st = z[b]->st;
+    lfgpu_rng_fn r = rng[b];
+    void* u = users[b] = rng_user ? rng_user[b] : nullptr;
+    std::vector<E> pads(st.pad_size - nl);  // every element fill_pad draws, in order (zk256_commit)
+    LF_SCRUB_ON_EXIT(pads);
+    auto fill = [&](uint8_t* buf, size_t n) { r(u, buf, n); };
+    if (c->rng_exact) for (size_t i = 0; i < pads.size(); ++i) h256_sample_many(&pads[i], 1, fill);
+    else h256_sample_many(pads.data(), pads.size(), fill);
+    size_t pd = 0;
+    auto draw = [&] { return pads[pd++]; };
+    E* W = Wv.data() + b * p.nw;
+    memcpy(W, (const E*)h_W[b] + st.npub, st.n_witness * 32);
+    if (zkp::pad_layout<P32>(F, bt->C, st.n_witness, st.lqc, draw, &st.pad, W) != p.nw)
+      return lf_fail(c, LFGPU_ERR_ASSERT, "zk_commit_batch256: witness layout (statement %zu)", b);
+    Wp[b] = W;
+  }
+  std::vector<uint8_t> roots(nb * 32);
+  std::vector<Lig32*> lps(nb, nullptr);
+  // (the lqc triples are the circuit's: the same for every prover)
+  LF_TRY(lig256_commit_batch(c, p, nb, Wp.data(), z[0]->st.lqc.data(), rng, users.data(), roots.data(), lps.data()));
+  for (size_t b = 0; b < nb; ++b) {
+    z[b]->lp = lps[b];
+    memcpy(z[b]->st.proof.root, &roots[32 * b], 32);
+    ts[b]->write_bytes(ts[b]->user, z[b]->st.proof.root, 32);  // LigeroTranscript::write_commitment
+  }
+  if (roots_out) memcpy(roots_out, roots.data(), nb * 32);
+  const double dt = now_ms() - t0;
+  for (size_t b = 0; b < nb; ++b) z[b]->st.ms[0] = dt;
+  return LFGPU_OK;
 }
 
 int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof, size_t proof_len, const void* h_pub,

@@ -60,6 +60,10 @@ int lf_ligero_dot_terms(lfgpu_ligero_prover* pr, const LfLigeroTerms* t, void* h
 struct Lig256;
 int lf_lig256_commit(lfgpu_ctx* c, const lfgpu_ligero_param* p, const void* h_W, const size_t* h_lqc, lfgpu_rng_fn rng, void* user, uint8_t root[32],
                      Lig256** out);
+// nb commits of one shape in one chain of dispatches (lfgpu_ligero_commit_batch256): out[b] = statement b's record, or every
+// entry NULL on an error
+int lf_lig256_commit_batch(lfgpu_ctx* c, const lfgpu_ligero_param* p, size_t nb, const void* const* h_W, const size_t* h_lqc, const lfgpu_rng_fn* rng,
+                           void* const* rng_user, uint8_t* roots, Lig256** out);
 void lf_lig256_free(Lig256* L);
 void* lf_lig256_tableau(Lig256* L);
 int lf_lig256_low_degree(Lig256* L, const void* h_u, void* h_y);
@@ -94,4 +98,9 @@ int lf256_eval_quad_batch_async(lfgpu_quad* q, size_t nb, const void* d_W, size_
 struct Zk256Batch;
 int zk256_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, Zk256Batch** out);
 int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_transcript_ops* const* ts, int* ok);
+// ZkProver::commit for nb provers around one batched Ligero commit (lfgpu_zk_commit_batch256 of zk.hip checks the handles as
+// above, and the engines and transcripts for NULL); the remaining argument errors -- a transcript without the sized hooks, provers
+// with different parameters -- are found here before the first draw
+int zk256_commit_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng, void* const* rng_user,
+                       const lfgpu_transcript_ops* const* ts, uint8_t* roots_out);
 void zk256_batch_free(Zk256Batch* bt);
