@@ -122,6 +122,9 @@ int lfgpu_zk_proof_write(const lfgpu_zk_prover* zk, uint8_t* buf, size_t cap, si
 /* host milliseconds spent in the last commit / prove, split by phase:
  * [0] commit total, [1] prove total, [2] eval_circuit, [3] sumcheck, [4] constraints, [5] ligero prove */
 int lfgpu_zk_timings(const lfgpu_zk_prover* zk, double ms[6]);
+/* Lifetimes: a prover may be FREED after its circuit (the scrub of its device buffers goes by the byte sizes recorded when they
+ * were allocated, not by the circuit handle), but not USED after it: commit, prove and proof_write read the circuit.  The
+ * context must outlive both. */
 int lfgpu_zk_prover_free(lfgpu_zk_prover* zk);
 
 /* ---- ZkProver::prove for a batch of committed provers ----
@@ -149,7 +152,8 @@ int lfgpu_zk_prover_free(lfgpu_zk_prover* zk);
  * read-back, the EQ tables over the inputs), allocated once in lfgpu_zk_batch_new.  lfgpu_zk_prove_batch frees no device
  * memory; what it may allocate is the context's pooled scratch, which grows on the first call at a shape and is kept.  The
  * slabs that hold functions of the witnesses are scrubbed when the batch is freed (the EQ tables depend on challenges only).
- * The batch may be freed before or after the provers; the context must outlive it.
+ * The batch may be freed before or after the provers, and like a prover after the circuit (but not used after it); the
+ * context must outlive it.  The same holds for lfgpu_zk_batch256.
  * The library stays single-threaded per call: the host work per statement -- the Fiat-Shamir preamble (SHA-256 over nterms
  * zero bytes), the constraints, proof_write -- is serial inside one batch.  A caller that wants more throughput runs several
  * batches in several contexts (lfgpu_own_stream, lfgpu_circuit_share), as examples/zk_throughput.cc does with provers.

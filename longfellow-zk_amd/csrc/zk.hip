@@ -17,7 +17,7 @@
 #include <algorithm>
 #include <memory>
 
-#include "zk_proto.h"
+#include "zk_driver.h"
 
 extern "C" int lfgpu_raw_eq2(lfgpu_ctx*, int, size_t, size_t, const void*, const void*, const uint64_t*, void*);
 
@@ -266,6 +266,18 @@ extern "C" int lfgpu_circuit_free(lfgpu_circuit* C) {
 
 // ------------------------------------------------------------------ the 16-byte policy
 namespace {
+// The EQ table over the circuit inputs is context-owned and grown on demand: it stays valid until the next run on this context
+int zk_eq_reserve(lfgpu_ctx* c, size_t ninputs) {
+  if (c->zk_eq_bytes >= ninputs * 16) return LFGPU_OK;
+  LF_HIP(c, hipSetDevice(c->device));
+  LF_HIP(c, hipStreamSynchronize(c->stream));
+  if (c->zk_eq) hipFree(c->zk_eq);
+  c->zk_eq = nullptr;
+  c->zk_eq_bytes = 0;
+  if (hipMalloc(&c->zk_eq, ninputs * 16) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk: EQ table over the inputs");
+  c->zk_eq_bytes = ninputs * 16;
+  return LFGPU_OK;
+}
 // Wire16 (zk_proto.h) plus the device steps behind lfgpu.h.  elt_t is {lo, hi}: the scalars the C ABI takes as uint64_t[2]
 // are copied here and nowhere else.
 struct P16 : zkp::Wire16 {
@@ -456,63 +468,65 @@ struct P16 : zkp::Wire16 {
     };
     return verifier_ext_with(c, F.field, 4, p, a_rows, pr, idx, ext);
   }
+  // ---- the driver layer (zk_driver.h)
+  static constexpr const char *kName = "zk", *kCommitName = "zk_commit", *kCommitBatchName = "zk_commit_batch", *kBatchNewName = "zk_batch_new";
+  static constexpr int kLigeroK = 4;
+  struct ProverExtra {
+    zkp::SubfieldSolver sub;  // GF(2^128): the wire format's subfield runs
+    static constexpr void* d_eq = nullptr;  // (the EQ table over the inputs is the context's: eq_store)
+    int init(lfgpu_ctx* c, int field, int k, size_t, zkp::Owned*) {
+      if (field != LFGPU_FIELD_GF2_128) return LFGPU_OK;
+      const GfHostCtx* g = lf_gf_ctx(c, k);
+      if (!g) return LFGPU_ERR_ARG;
+      sub.build(g);
+      return LFGPU_OK;
+    }
+  };
+  static P16 make(lfgpu_ctx* c, int field, int k, const ProverExtra* ex) {
+    P16 pol;
+    pol.field = field;
+    pol.g = lf_gf_ctx(c, k);
+    pol.sub = ex ? &ex->sub : nullptr;
+    return pol;
+  }
+  static int ts_ok(lfgpu_ctx*, const lfgpu_transcript_ops*) { return LFGPU_OK; }
+  static bool ligero_param_ok(const lfgpu_ligero_param&) { return true; }
+  static int eq_store(lfgpu_ctx* c, size_t ninputs, void*, E** d_eq) {
+    LF_TRY(zk_eq_reserve(c, ninputs));
+    *d_eq = (E*)c->zk_eq;
+    return LFGPU_OK;
+  }
+  // (the per-statement path of prove_batch then finds the context's EQ table in place)
+  static int batch_prepare(lfgpu_ctx* c, size_t ninputs) { return zk_eq_reserve(c, ninputs); }
+  // the Ligero commit behind lfgpu.h; the witness starts at the private inputs, so the subfield boundary moves down by npub
+  static size_t sfb(const lfgpu_circuit_info& I) { return I.subfield_boundary >= I.npub_in ? I.subfield_boundary - I.npub_in : 0; }
+  static int lig_commit(lfgpu_ctx* c, const lfgpu_circuit_info& I, const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user,
+                        uint8_t root[32], Lig** out, const lfgpu_comm_ops* shard) {
+    if (shard) return lfgpu_ligero_commit_sharded(c, I.field, kLigeroK, &p, W, sfb(I), lqc, rng, user, shard, root, out);
+    return lfgpu_ligero_commit(c, I.field, kLigeroK, &p, W, sfb(I), lqc, rng, user, root, out);
+  }
+  static int lig_commit_batch(lfgpu_ctx* c, const lfgpu_circuit_info& I, const lfgpu_ligero_param& p, size_t nb, const E* const* W, const size_t* lqc,
+                              const lfgpu_rng_fn* rng, void* const* users, uint8_t* roots, Lig** out) {
+    return lfgpu_ligero_commit_batch(c, I.field, kLigeroK, &p, nb, (const void* const*)W, sfb(I), lqc, rng, users, roots, out);
+  }
+  static void lig_free(Lig* lp) { lfgpu_ligero_free(lp); }
+  // (with a communicator this width records and replays its two random streams in lfgpu_zk_commit instead)
+  static int draws_only(lfgpu_ctx*, const lfgpu_ligero_param&, const E*, const size_t*, lfgpu_rng_fn, void*) { return LFGPU_ERR_UNSUPPORTED; }
 };
-P16 policy16(lfgpu_ctx* c, int field, const zkp::SubfieldSolver* sub, int k = 4) {
-  P16 pol;
-  pol.field = field;
-  pol.g = lf_gf_ctx(c, k);
-  pol.sub = sub;
-  return pol;
-}
-// The EQ table over the circuit inputs is context-owned and grown on demand: it stays valid until the next run on this context
-int zk_eq_reserve(lfgpu_ctx* c, size_t ninputs) {
-  if (c->zk_eq_bytes >= ninputs * 16) return LFGPU_OK;
-  LF_HIP(c, hipSetDevice(c->device));
-  LF_HIP(c, hipStreamSynchronize(c->stream));
-  if (c->zk_eq) hipFree(c->zk_eq);
-  c->zk_eq = nullptr;
-  c->zk_eq_bytes = 0;
-  if (hipMalloc(&c->zk_eq, ninputs * 16) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk: EQ table over the inputs");
-  c->zk_eq_bytes = ninputs * 16;
-  return LFGPU_OK;
-}
 }  // namespace
 
 // ------------------------------------------------------------------ ZkProver
+// The ABI's prover handle dispatches on the circuit's field: the record is zkp::Prover<P16> here, or zk256.hip's for Fp256Base.
 struct lfgpu_zk_prover {
   lfgpu_ctx* c = nullptr;
-  const lfgpu_circuit* C = nullptr;
-  Zk256* z256 = nullptr;  // Fp256Base circuits: the whole prover lives in zk256.hip
-  zkp::ProverState<P16> st;  // pads, the held proof, its wire bytes, timings
-  zkp::SubfieldSolver sub;   // GF(2^128): the wire format's subfield runs
-  lfgpu_ligero_prover* lp = nullptr;
-  // device buffers of the layer inputs (eval_circuit) and the circuit output
-  std::vector<void*> d_in;
-  void* d_V = nullptr;
-  void* h_V = nullptr;  // pinned: outputs (nv elements) then the assert-zero flag, read back without blocking the host
-  // lfgpu_zk_prover_set_comm: Ligero tableaux of at least comm_min_bytes are committed with their rows sharded over the
-  // communicator's GPUs (lfgpu_ligero_commit_sharded); everything else -- and the whole sumcheck -- runs replicated
-  bool have_comm = false;
-  lfgpu_comm_ops comm{};
-  size_t comm_min_bytes = 0;
+  const lfgpu_circuit* C = nullptr;  // compared and passed on, never dereferenced at destruction
+  zkp::Prover<P16> p;                // the 16-byte fields
+  Zk256* z256 = nullptr;             // Fp256Base circuits: the whole prover lives in zk256.hip
+  bool wide() const { return z256 != nullptr; }
+  const lfgpu_comm_ops* comm() const { return z256 ? zk256_comm(z256) : p.have_comm ? &p.comm : nullptr; }
+  bool have_comm() const { return comm() != nullptr; }
   ~lfgpu_zk_prover() {
     if (z256) zk256_free(z256);
-    if (lp) lfgpu_ligero_free(lp);
-    // the layers' wire values are functions of the witness: scrubbed before the memory goes back to the allocator (as the
-    // Ligero tableau is, lfgpu_ligero_free; the host copies of the pads: ~ProverState)
-    if (c && C && !d_in.empty()) {
-      for (size_t l = 0; l < d_in.size(); ++l)
-        if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, C->layers[l].nw * 16, c->stream);
-      if (d_V) (void)hipMemsetAsync(d_V, 0, C->info.nv * 16, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-    }
-    for (void* p : d_in)
-      if (p) (void)hipFree(p);
-    if (d_V) (void)hipFree(d_V);
-    if (h_V) {
-      if (C) memset(h_V, 0, C->info.nv * 16 + 16);
-      (void)hipHostFree(h_V);
-    }
   }
 };
 
@@ -522,166 +536,124 @@ extern "C" int lfgpu_zk_prover_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t 
   std::unique_ptr<lfgpu_zk_prover> zk(new lfgpu_zk_prover());
   zk->c = c;
   zk->C = C;
-  if (C->info.field == LFGPU_FIELD_P256) {
-    LF_TRY(zk256_new(c, C, rateinv, nreq, block_enc, &zk->z256));
-    *out = zk.release();
-    return LFGPU_OK;
-  }
-  zk->st.init(C);
-  // ZkProof: LigeroParam(n_witness + pad_size, nl quadratic constraints, rate, nreq[, block_enc]) (zk_proof.h:63-76)
-  LF_TRY(lfgpu_ligero_param_init(&zk->st.param, C->info.field, 4, zk->st.n_witness + zk->st.pad_size, C->info.nl, rateinv, nreq, block_enc));
-  if (C->info.field == LFGPU_FIELD_GF2_128) {
-    const GfHostCtx* g = lf_gf_ctx(c, 4);
-    if (!g) return LFGPU_ERR_ARG;
-    zk->sub.build(g);
-  }
-  LF_HIP(c, hipSetDevice(c->device));
-  zk->d_in.assign(C->layers.size(), nullptr);
-  for (size_t l = 0; l < C->layers.size(); ++l)
-    if (hipMalloc(&zk->d_in[l], C->layers[l].nw * 16) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk: layer %zu inputs", l);
-  if (hipMalloc(&zk->d_V, C->info.nv * 16) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk: outputs");
-  if (hipHostMalloc(&zk->h_V, C->info.nv * 16 + 16, hipHostMallocDefault) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk: pinned outputs");
+  if (C->info.field == LFGPU_FIELD_P256) LF_TRY(zk256_new(c, C, rateinv, nreq, block_enc, &zk->z256));
+  else LF_TRY(zkp::prover_init<P16>(zk->p, c, C, rateinv, nreq, block_enc));
   *out = zk.release();
   return LFGPU_OK;
 }
 
 extern "C" int lfgpu_zk_prover_set_comm(lfgpu_zk_prover* zk, const lfgpu_comm_ops* comm, size_t min_tableau_bytes) {
   if (!zk) return LFGPU_ERR_ARG;
-  if (!comm) {
-    zk->have_comm = false;
-    if (zk->z256) zk256_set_comm(zk->z256, nullptr, 0);
+  if (comm && (comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world || !comm->all_gather || !comm->all_to_all || !comm->broadcast))
+    return lf_fail(zk->c, LFGPU_ERR_ARG, "zk_prover_set_comm: incomplete communicator");
+  if (zk->z256) {
+    zk256_set_comm(zk->z256, comm, min_tableau_bytes);
     return LFGPU_OK;
   }
-  if (comm->world < 1 || comm->rank < 0 || comm->rank >= comm->world || !comm->all_gather || !comm->all_to_all || !comm->broadcast)
-    return lf_fail(zk->c, LFGPU_ERR_ARG, "zk_prover_set_comm: incomplete communicator");
-  zk->have_comm = true;
-  zk->comm = *comm;
-  zk->comm_min_bytes = min_tableau_bytes;
-  if (zk->z256) zk256_set_comm(zk->z256, &zk->comm, min_tableau_bytes);
+  zk->p.have_comm = comm != nullptr;
+  if (comm) {
+    zk->p.comm = *comm;
+    zk->p.comm_min_bytes = min_tableau_bytes;
+  }
   return LFGPU_OK;
 }
 extern "C" int lfgpu_zk_prover_param(const lfgpu_zk_prover* zk, lfgpu_ligero_param* p) {
   if (!zk || !p) return LFGPU_ERR_ARG;
   if (zk->z256) return zk256_param(zk->z256, p);
-  *p = zk->st.param;
+  *p = zk->p.st.param;
   return LFGPU_OK;
 }
 
 extern "C" int lfgpu_zk_commit(lfgpu_zk_prover* zk, const void* h_W, lfgpu_rng_fn rng, void* rng_user,
                                const lfgpu_transcript_ops* ts, uint8_t root_out[32]) {
   if (!zk || !h_W || !rng || !ts) return LFGPU_ERR_ARG;
+  const lfgpu_comm_ops* comm = zk->comm();
+  const bool multi = comm && comm->world > 1;
   if (zk->z256) {
     // Fp256Base: with a communicator the ranks share ONE RandomEngine -- rank 0's draws of the whole commit (pads, then the
     // Ligero layout) are recorded and broadcast, the other ranks replay them; zk256_commit then shards the tableau's rows when
-    // it is above the threshold (lig256_commit; the mdoc signature circuit's 2.5 MB tableau normally stays replicated)
-    if (!(zk->have_comm && zk->comm.world > 1)) return zk256_commit(zk->z256, h_W, rng, rng_user, ts, root_out);
+    // it is above the threshold (the mdoc signature circuit's 2.5 MB tableau normally stays replicated)
+    if (!multi) return zk256_commit(zk->z256, h_W, rng, rng_user, ts, root_out);
     std::vector<uint8_t> stream;
     LF_SCRUB_ON_EXIT(stream);
     alignas(16) unsigned char store[64];
     lfgpu_rng_fn r2 = rng;
     void* u2 = rng_user;
-    if (zk->comm.rank == 0) {  // all draws first (no device work, no collective), so that the stream can go out before any collective
+    if (comm->rank == 0) {  // all draws first (no device work, no collective), so that the stream can go out before any collective
       lf_record_rng(rng, rng_user, &stream, &r2, &u2, store);
       const int rc = zk256_commit(zk->z256, h_W, r2, u2, ts, root_out, /*draws_only=*/true);
-      if (lf_comm_bcast_blob(&zk->comm, stream)) return lf_fail(zk->c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
+      if (lf_comm_bcast_blob(comm, stream)) return lf_fail(zk->c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
       if (rc) return rc;
-    } else if (lf_comm_bcast_blob(&zk->comm, stream)) {
+    } else if (lf_comm_bcast_blob(comm, stream)) {
       return lf_fail(zk->c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
     }
     lf_replay_rng(&stream, &r2, &u2, store);
     return zk256_commit(zk->z256, h_W, r2, u2, ts, root_out);
   }
-  const double t0 = now_ms();
-  lfgpu_ctx* c = zk->c;
-  const lfgpu_circuit* C = zk->C;
-  const int field = C->info.field;
-  const HostField F(c, field);
+  zkp::Prover<P16>& z = zk->p;
+  if (!multi) return zkp::commit<P16>(z, h_W, rng, rng_user, ts, root_out);
   // More than one rank (lfgpu_zk_prover_set_comm): every rank runs this function with the same arguments, but there is ONE
   // RandomEngine -- rank 0's.  Its pad draws are recorded and broadcast, the other ranks replay them (the Ligero commit does
   // the same for its own draws), so all ranks hold the same pads, the same commitment and, with their own copies of the
   // transcript, the same proof.
-  const bool multi = zk->have_comm && zk->comm.world > 1;
-  const bool shard_rows = multi && zk->st.param.nrow * zk->st.param.block_enc * 16 >= zk->comm_min_bytes;
+  const double t0 = now_ms();
+  lfgpu_ctx* c = zk->c;
+  const lfgpu_circuit_info& I = zk->C->info;
+  const bool shard_rows = z.st.param.nrow * z.st.param.block_enc * 16 >= z.comm_min_bytes;
   std::vector<uint8_t> pad_stream;
   LF_SCRUB_ON_EXIT(pad_stream);
   alignas(16) unsigned char rng_store[64];
-  if (multi) {
-    if (zk->comm.rank == 0) {
-      lf_record_rng(rng, rng_user, &pad_stream, &rng, &rng_user, rng_store);
-    } else {
-      if (lf_comm_bcast_blob(&zk->comm, pad_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
-      lf_replay_rng(&pad_stream, &rng, &rng_user, rng_store);
-    }
+  if (comm->rank == 0) {
+    lf_record_rng(rng, rng_user, &pad_stream, &rng, &rng_user, rng_store);
+  } else {
+    if (lf_comm_bcast_blob(comm, pad_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
+    lf_replay_rng(&pad_stream, &rng, &rng_user, rng_store);
   }
-  auto draw = [&]() {  // RandomEngine::elt = Field::sample
-    return zkp::elt_sample(field, [&](uint8_t* b, size_t n) { rng(rng_user, b, n); });
-  };
-  // witness = private inputs || pad; fill_pad draws, per layer: (t0, t2) for hand 0 then hand 1 of every round,
-  // then wc0, wc1 and stores wc0*wc1 (zk_prover.h:152-188, logc = 0)
-  std::vector<elt_t> Wv(zk->st.param.nw);  // witness || pads
+  const P16 pol = z.policy();
+  std::vector<elt_t> Wv(z.st.param.nw);  // witness || pads
   LF_SCRUB_ON_EXIT(Wv);
-  memcpy(Wv.data(), (const elt_t*)h_W + zk->st.npub, zk->st.n_witness * 16);
-  const size_t pi = zkp::pad_layout<P16>(F, C, zk->st.n_witness, zk->st.lqc, draw, &zk->st.pad, Wv.data());
+  const size_t pi = zkp::stage_witness(pol, pol.host_field(c), zk->C, z.st, h_W, c->rng_exact != 0, [&](uint8_t* b, size_t n) { rng(rng_user, b, n); }, Wv.data());
   // (rank 0 first sends what the other ranks are waiting for, whatever went wrong here)
-  if (multi && zk->comm.rank == 0 && lf_comm_bcast_blob(&zk->comm, pad_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
-  if (pi != zk->st.param.nw) return lf_fail(c, LFGPU_ERR_ASSERT, "zk_commit: witness layout");
-  const size_t sfb = C->info.subfield_boundary >= zk->st.npub ? C->info.subfield_boundary - zk->st.npub : 0;
-  if (zk->lp) {
-    lfgpu_ligero_free(zk->lp);
-    zk->lp = nullptr;
-  }
-  zk->st.have_proof = false;
-  zk->st.wire_valid = false;
+  if (comm->rank == 0 && lf_comm_bcast_blob(comm, pad_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
+  if (pi != z.st.param.nw) return lf_fail(c, LFGPU_ERR_ASSERT, "zk_commit: witness layout");
+  z.drop_commitment();
   if (shard_rows) {
-    LF_TRY(lfgpu_ligero_commit_sharded(c, field, 4, &zk->st.param, Wv.data(), sfb, zk->st.lqc.data(), rng, rng_user, &zk->comm, zk->st.proof.root, &zk->lp));
-  } else if (multi) {  // a small tableau stays whole on every rank (replicas): the one random stream still comes from rank 0
-    lfgpu_comm_ops one = zk->comm;
+    LF_TRY(P16::lig_commit(c, I, z.st.param, Wv.data(), z.st.lqc.data(), rng, rng_user, z.st.proof.root, &z.lp, comm));
+  } else {  // a small tableau stays whole on every rank (replicas): the one random stream still comes from rank 0
     std::vector<uint8_t> lig_stream;
     LF_SCRUB_ON_EXIT(lig_stream);
     alignas(16) unsigned char st2[64];
     lfgpu_rng_fn r2 = rng;
     void* u2 = rng_user;
-    if (zk->comm.rank == 0) lf_record_rng(rng, rng_user, &lig_stream, &r2, &u2, st2);
+    if (comm->rank == 0) lf_record_rng(rng, rng_user, &lig_stream, &r2, &u2, st2);
     else {
-      if (lf_comm_bcast_blob(&one, lig_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
+      if (lf_comm_bcast_blob(comm, lig_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
       lf_replay_rng(&lig_stream, &r2, &u2, st2);
     }
-    const int rc = lfgpu_ligero_commit(c, field, 4, &zk->st.param, Wv.data(), sfb, zk->st.lqc.data(), r2, u2, zk->st.proof.root, &zk->lp);
+    const int rc = P16::lig_commit(c, I, z.st.param, Wv.data(), z.st.lqc.data(), r2, u2, z.st.proof.root, &z.lp, nullptr);
     // (also after a failed commit: the other ranks are waiting in this broadcast)
-    if (zk->comm.rank == 0 && lf_comm_bcast_blob(&one, lig_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
+    if (comm->rank == 0 && lf_comm_bcast_blob(comm, lig_stream)) return lf_fail(c, LFGPU_ERR_HIP, "zk_commit: broadcast hook failed");
     if (rc) return rc;
-  } else {
-    LF_TRY(lfgpu_ligero_commit(c, field, 4, &zk->st.param, Wv.data(), sfb, zk->st.lqc.data(), rng, rng_user, zk->st.proof.root, &zk->lp));
   }
-  ts->write_bytes(ts->user, zk->st.proof.root, 32);  // LigeroTranscript::write_commitment
-  if (root_out) memcpy(root_out, zk->st.proof.root, 32);
-  zk->st.ms[0] = now_ms() - t0;
+  zkp::commit_done(z, ts, root_out, t0);
   return LFGPU_OK;
 }
 
 extern "C" int lfgpu_zk_prove(lfgpu_zk_prover* zk, const void* h_W, const lfgpu_transcript_ops* tso, int* ok) {
   if (!zk || !h_W || !tso || !ok) return LFGPU_ERR_ARG;
-  if (zk->z256) return zk256_prove(zk->z256, h_W, tso, ok);
-  lfgpu_ctx* c = zk->c;
-  if (!zk->lp) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove: must run commit before prove");
-  auto eq_table = [&](elt_t** d_eq) {
-    LF_TRY(zk_eq_reserve(c, zk->C->info.ninputs));
-    *d_eq = (elt_t*)c->zk_eq;
-    return (int)LFGPU_OK;
-  };
-  return zkp::prove<P16>(c, zk->C, policy16(c, zk->C->info.field, &zk->sub), zk->st, zk->lp, zk->d_in.data(), zk->d_V, zk->h_V, eq_table, h_W, tso, ok);
+  return zk->z256 ? zk256_prove(zk->z256, h_W, tso, ok) : zkp::prove<P16>(zk->p, h_W, tso, ok);
 }
 
 extern "C" int lfgpu_zk_proof_write(const lfgpu_zk_prover* zk, uint8_t* buf, size_t cap, size_t* nbytes) {
   if (!zk || !nbytes) return LFGPU_ERR_ARG;
   if (zk->z256) return zk256_proof_write(zk->z256, buf, cap, nbytes);
-  return zkp::proof_write_cached(zk->c, policy16(zk->c, zk->C->info.field, &zk->sub), zk->C, zk->st, buf, cap, nbytes);
+  return zkp::proof_write_cached(zk->c, zk->p.policy(), zk->C, zk->p.st, buf, cap, nbytes);
 }
 
 extern "C" int lfgpu_zk_timings(const lfgpu_zk_prover* zk, double ms[6]) {
   if (!zk || !ms) return LFGPU_ERR_ARG;
   if (zk->z256) return zk256_timings(zk->z256, ms);
-  memcpy(ms, zk->st.ms, sizeof(zk->st.ms));
+  memcpy(ms, zk->p.st.ms, sizeof(zk->p.st.ms));
   return LFGPU_OK;
 }
 
@@ -691,194 +663,11 @@ extern "C" int lfgpu_zk_prover_free(lfgpu_zk_prover* zk) {
   return LFGPU_OK;
 }
 
-// ------------------------------------------------------------------ ZkProver::prove for a batch of committed provers
-// The batch owns what the lock-step needs B times: the layers' input slabs (statement b of layer l at d_in[l] + b * ldw[l]
-// elements), the outputs, one assert-zero flag per statement, their pinned read-back and nb_max EQ tables over the inputs (the
-// dense blocks of the batched dot proofs).  All of it is allocated in _new and nothing is freed inside prove_batch (hipFree waits
-// for every stream of the device); the only device memory a call may allocate is the context's pooled scratch, which grows on the
-// first call at a shape.
-struct lfgpu_zk_batch {
-  lfgpu_ctx* c = nullptr;
-  const lfgpu_circuit* C = nullptr;
-  size_t nb_max = 0;
-  std::vector<void*> d_in;
-  std::vector<size_t> ldw;
-  // the sizes of the allocations, recorded here: the scrub at destruction does not look at the circuit handle (which the caller
-  // may have freed first)
-  std::vector<size_t> in_bytes;
-  void* d_V = nullptr;
-  size_t ldv = 0, v_bytes = 0;
-  int* d_fail = nullptr;
-  void* h_V = nullptr;
-  size_t h_bytes = 0;
-  void* d_eq = nullptr;  // [nb_max][ninputs]: functions of the challenges only, not scrubbed
-  ~lfgpu_zk_batch() {
-    // the slabs hold the wire values of every statement -- functions of the witnesses: scrubbed before the memory goes back
-    if (c) {
-      (void)hipSetDevice(c->device);
-      for (size_t l = 0; l < d_in.size(); ++l)
-        if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, in_bytes[l], c->stream);
-      if (d_V) (void)hipMemsetAsync(d_V, 0, v_bytes, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-    }
-    for (void* p : d_in)
-      if (p) (void)hipFree(p);
-    if (d_V) (void)hipFree(d_V);
-    if (d_fail) (void)hipFree(d_fail);
-    if (d_eq) (void)hipFree(d_eq);
-    if (h_V) {
-      memset(h_V, 0, h_bytes);
-      (void)hipHostFree(h_V);
-    }
-  }
-};
-
-extern "C" int lfgpu_zk_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, lfgpu_zk_batch** out) {
-  if (!c || !C || !out || C->c != c) return LFGPU_ERR_ARG;
-  if (nb_max == 0 || nb_max > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch_new: nb_max must be 1..%d", LFGPU_SC_BATCH_MAX);
-  if (C->info.field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_batch_new: an Fp256Base circuit (lfgpu_zk_batch256_new serves those)");
-  std::unique_ptr<lfgpu_zk_batch> bt(new lfgpu_zk_batch());
-  bt->c = c;
-  bt->C = C;
-  bt->nb_max = nb_max;
-  LF_HIP(c, hipSetDevice(c->device));
-  auto pad4 = [](size_t n) { return (n + 3) & ~(size_t)3; };  // slabs start on 64-byte lines
-  const size_t nl = C->layers.size();
-  bt->d_in.assign(nl, nullptr);
-  bt->ldw.assign(nl, 0);
-  bt->in_bytes.assign(nl, 0);
-  auto alloc = [&](void** p, size_t bytes) {
-    if (hipMalloc(p, bytes) == hipSuccess) return true;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return false;
-  };
-  for (size_t l = 0; l < nl; ++l) {
-    bt->ldw[l] = pad4(C->layers[l].nw);
-    bt->in_bytes[l] = nb_max * bt->ldw[l] * 16;
-    if (!alloc(&bt->d_in[l], bt->in_bytes[l])) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: %zu slabs of layer %zu (%zu bytes)", nb_max, l, bt->in_bytes[l]);
-  }
-  bt->ldv = pad4(C->info.nv);
-  bt->v_bytes = nb_max * bt->ldv * 16;
-  bt->h_bytes = bt->v_bytes + nb_max * sizeof(int);
-  if (!alloc(&bt->d_V, bt->v_bytes) || !alloc((void**)&bt->d_fail, nb_max * sizeof(int))) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: outputs");
-  if (hipHostMalloc(&bt->h_V, bt->h_bytes, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    bt->h_V = nullptr;
-    return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: pinned outputs");
-  }
-  if (!alloc(&bt->d_eq, std::max<size_t>(nb_max * C->info.ninputs, 1) * 16)) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch_new: %zu EQ tables over the inputs", nb_max);
-  LF_TRY(zk_eq_reserve(c, C->info.ninputs));  // (the per-statement path of prove_batch then finds the context's EQ table in place)
-  *out = bt.release();
-  return LFGPU_OK;
-}
-
-extern "C" int lfgpu_zk_prove_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
-                                    const lfgpu_transcript_ops* const* ts, int* ok) {
-  if (!bt || !zk || !h_W || !ts || !ok) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = bt->c;
-  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!zk[b] || !h_W[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: null argument for statement %zu", b);
-    if (zk[b]->c != c || zk[b]->C != bt->C) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: prover %zu belongs to another context or circuit", b);
-    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_prove_batch: prover %zu has a communicator (the batch runs on one GPU)", b);
-    if (zk[b]->z256 || !zk[b]->lp) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: prover %zu must run commit before prove", b);
-    for (size_t a = 0; a < b; ++a)
-      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch: prover %zu appears twice", b);
-  }
-  const lfgpu_circuit* C = bt->C;
-  std::vector<P16> pol;
-  std::vector<zkp::ProverState<P16>*> st(nb);
-  std::vector<lfgpu_ligero_prover*> lp(nb);
-  pol.reserve(nb);
-  for (size_t b = 0; b < nb; ++b) {
-    pol.push_back(policy16(c, C->info.field, &zk[b]->sub));
-    st[b] = &zk[b]->st;
-    lp[b] = zk[b]->lp;
-  }
-  auto eq_table = [&](elt_t** d_eq) {
-    LF_TRY(zk_eq_reserve(c, C->info.ninputs));
-    *d_eq = (elt_t*)c->zk_eq;
-    return (int)LFGPU_OK;
-  };
-  const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max, bt->d_eq};
-  return zkp::prove_batch<P16>(c, C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
-}
-
-// ZkProver::commit for nb provers: lfgpu_zk_commit's one-GPU branch per statement around ONE lfgpu_ligero_commit_batch
-extern "C" int lfgpu_zk_commit_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng,
-                                     void* const* rng_user, const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
-  if (!bt || !zk || !h_W || !rng || !ts) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = bt->c;
-  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!zk[b] || !h_W[b] || !rng[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: null argument for statement %zu", b);
-    if (zk[b]->c != c || zk[b]->C != bt->C || zk[b]->z256) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: prover %zu belongs to another context or circuit", b);
-    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_commit_batch: prover %zu has a communicator (the batch runs on one GPU)", b);
-    if (memcmp(&zk[b]->st.param, &zk[0]->st.param, sizeof(lfgpu_ligero_param)) != 0)
-      return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: prover %zu has another LigeroParam (rate, nreq or block_enc) than prover 0", b);
-    for (size_t a = 0; a < b; ++a)
-      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch: prover %zu appears twice", b);
-  }
-  const double t0 = now_ms();
-  const lfgpu_circuit* C = bt->C;
-  const int field = C->info.field;
-  const HostField F(c, field);
-  const lfgpu_ligero_param& p = zk[0]->st.param;
-  // whatever happens from here on, no prover of the call keeps an earlier commitment or proof
-  for (size_t b = 0; b < nb; ++b) {
-    if (zk[b]->lp) {
-      lfgpu_ligero_free(zk[b]->lp);
-      zk[b]->lp = nullptr;
-    }
-    zk[b]->st.have_proof = false;
-    zk[b]->st.wire_valid = false;
-  }
-  // witness || pads of every statement; fill_pad's draws of statement b come from rng[b], before its Ligero draws
-  std::vector<elt_t> Wv(nb * p.nw);
-  LF_SCRUB_ON_EXIT(Wv);
-  // (the pads of ALL statements are drawn before the first Ligero layout: a statement's own order -- pads, then layout -- is
-  // the single path's as long as its engine is its own, which the header asks for)
-  std::vector<const void*> Wp(nb);
-  std::vector<void*> users(nb);
-  std::vector<uint8_t> roots(nb * 32);
-  std::vector<lfgpu_ligero_prover*> lps(nb, nullptr);
-  const size_t sfb = C->info.subfield_boundary >= zk[0]->st.npub ? C->info.subfield_boundary - zk[0]->st.npub : 0;
-  auto pads = [&](size_t b) {
-    lfgpu_rng_fn r = rng[b];
-    void* u = rng_user ? rng_user[b] : nullptr;
-    auto draw = [&]() { return zkp::elt_sample(field, [&](uint8_t* buf, size_t n) { r(u, buf, n); }); };
-    elt_t* W = Wv.data() + b * p.nw;
-    memcpy(W, (const elt_t*)h_W[b] + zk[b]->st.npub, zk[b]->st.n_witness * 16);
-    const size_t pi = zkp::pad_layout<P16>(F, C, zk[b]->st.n_witness, zk[b]->st.lqc, draw, &zk[b]->st.pad, W);
-    Wp[b] = W;
-    users[b] = u;
-    return pi == p.nw;
-  };
-  for (size_t b = 0; b < nb; ++b)
-    if (!pads(b)) return lf_fail(c, LFGPU_ERR_ASSERT, "zk_commit_batch: witness layout (statement %zu)", b);
-  // (the lqc triples are the circuit's: the same for every prover)
-  LF_TRY(lfgpu_ligero_commit_batch(c, field, 4, &p, nb, Wp.data(), sfb, zk[0]->st.lqc.data(), rng, users.data(), roots.data(), lps.data()));
-  for (size_t b = 0; b < nb; ++b) {
-    zk[b]->lp = lps[b];
-    memcpy(zk[b]->st.proof.root, &roots[32 * b], 32);
-    ts[b]->write_bytes(ts[b]->user, zk[b]->st.proof.root, 32);  // LigeroTranscript::write_commitment
-  }
-  if (roots_out) memcpy(roots_out, roots.data(), nb * 32);
-  const double dt = now_ms() - t0;
-  for (size_t b = 0; b < nb; ++b) zk[b]->st.ms[0] = dt;
-  return LFGPU_OK;
-}
-
-extern "C" int lfgpu_zk_batch_free(lfgpu_zk_batch* bt) {
-  if (!bt) return LFGPU_ERR_ARG;
-  delete bt;
-  return LFGPU_OK;
-}
-
-// ------------------------------------------------------------------ ... over Fp256Base
-// The same contract with names of their own (lfgpu_zk_batch_new / lfgpu_zk_prove_batch keep refusing the field): the handles are
-// checked here, the batch and the proof are zk256.hip's (Zk256Batch, zk256_prove_batch).
+// ------------------------------------------------------------------ ZkProver::commit / prove for a batch of provers
+// lfgpu_zk_batch (16-byte fields) and lfgpu_zk_batch256 (Fp256Base) are distinct ABI types with one contract: each holds a
+// zkp::Batch<P> (zk_driver.h), the second through zk256.hip.  An entry point checks the handles (zkp::check_batch_call) and hands
+// the width's records to zkp::prove_batch / zkp::commit_batch, which find what is left to refuse.
+struct lfgpu_zk_batch : zkp::Batch<P16> {};
 struct lfgpu_zk_batch256 {
   lfgpu_ctx* c = nullptr;
   const lfgpu_circuit* C = nullptr;
@@ -888,7 +677,28 @@ struct lfgpu_zk_batch256 {
     if (bt) zk256_batch_free(bt);
   }
 };
+namespace {
+std::vector<zkp::Prover<P16>*> records16(lfgpu_zk_prover* const* zk, size_t nb) {
+  std::vector<zkp::Prover<P16>*> z(nb);
+  for (size_t b = 0; b < nb; ++b) z[b] = &zk[b]->p;
+  return z;
+}
+std::vector<Zk256*> records256(lfgpu_zk_prover* const* zk, size_t nb) {
+  std::vector<Zk256*> z(nb);
+  for (size_t b = 0; b < nb; ++b) z[b] = zk[b]->z256;
+  return z;
+}
+}  // namespace
 
+extern "C" int lfgpu_zk_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, lfgpu_zk_batch** out) {
+  if (!c || !C || !out || C->c != c) return LFGPU_ERR_ARG;
+  if (nb_max == 0 || nb_max > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch_new: nb_max must be 1..%d", LFGPU_SC_BATCH_MAX);
+  if (C->info.field == LFGPU_FIELD_P256) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_batch_new: an Fp256Base circuit (lfgpu_zk_batch256_new serves those)");
+  std::unique_ptr<lfgpu_zk_batch> bt(new lfgpu_zk_batch());
+  LF_TRY(zkp::batch_init<P16>(*bt, c, C, nb_max));
+  *out = bt.release();
+  return LFGPU_OK;
+}
 extern "C" int lfgpu_zk_batch256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, lfgpu_zk_batch256** out) {
   if (!c || !C || !out || C->c != c) return LFGPU_ERR_ARG;
   if (nb_max == 0 || nb_max > LFGPU_SC_BATCH_MAX) return lf_fail(c, LFGPU_ERR_ARG, "zk_batch256_new: nb_max must be 1..%d", LFGPU_SC_BATCH_MAX);
@@ -902,41 +712,37 @@ extern "C" int lfgpu_zk_batch256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_
   return LFGPU_OK;
 }
 
+extern "C" int lfgpu_zk_prove_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
+                                    const lfgpu_transcript_ops* const* ts, int* ok) {
+  if (!bt || !zk || !h_W || !ts || !ok) return LFGPU_ERR_ARG;
+  LF_TRY(zkp::check_batch_call("zk_prove_batch", bt->c, bt->C, bt->nb_max, false, zk, nb, h_W, nullptr, ts));
+  return zkp::prove_batch<P16>(*bt, records16(zk, nb).data(), nb, h_W, ts, ok);
+}
 extern "C" int lfgpu_zk_prove_batch256(lfgpu_zk_batch256* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W,
                                        const lfgpu_transcript_ops* const* ts, int* ok) {
   if (!bt || !zk || !h_W || !ts || !ok) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = bt->c;
-  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
-  std::vector<Zk256*> z(nb);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!zk[b] || !h_W[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: null argument for statement %zu", b);
-    if (zk[b]->c != c || zk[b]->C != bt->C || !zk[b]->z256) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: prover %zu belongs to another context or circuit", b);
-    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_prove_batch256: prover %zu has a communicator (the batch runs on one GPU)", b);
-    for (size_t a = 0; a < b; ++a)
-      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: prover %zu appears twice", b);
-    z[b] = zk[b]->z256;
-  }
-  return zk256_prove_batch(bt->bt, z.data(), nb, h_W, ts, ok);  // (a prover that has not committed, a transcript without the sized hooks: found there, first)
+  LF_TRY(zkp::check_batch_call("zk_prove_batch256", bt->c, bt->C, bt->nb_max, true, zk, nb, h_W, nullptr, ts));
+  return zk256_prove_batch(bt->bt, records256(zk, nb).data(), nb, h_W, ts, ok);
 }
 
-// ZkProver::commit for nb Fp256Base provers: the handles are checked here, the commit is zk256.hip's (zk256_commit_batch)
+extern "C" int lfgpu_zk_commit_batch(lfgpu_zk_batch* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng,
+                                     void* const* rng_user, const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
+  if (!bt || !zk || !h_W || !rng || !ts) return LFGPU_ERR_ARG;
+  LF_TRY(zkp::check_batch_call("zk_commit_batch", bt->c, bt->C, bt->nb_max, false, zk, nb, h_W, rng, ts));
+  return zkp::commit_batch<P16>(*bt, records16(zk, nb).data(), nb, h_W, rng, rng_user, ts, roots_out);
+}
 extern "C" int lfgpu_zk_commit_batch256(lfgpu_zk_batch256* bt, lfgpu_zk_prover* const* zk, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng,
                                         void* const* rng_user, const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
   if (!bt || !zk || !h_W || !rng || !ts) return LFGPU_ERR_ARG;
-  lfgpu_ctx* c = bt->c;
-  if (nb == 0 || nb > bt->nb_max) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: nb = %zu, the batch holds 1..%zu statements", nb, bt->nb_max);
-  std::vector<Zk256*> z(nb);
-  for (size_t b = 0; b < nb; ++b) {
-    if (!zk[b] || !h_W[b] || !rng[b] || !ts[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: null argument for statement %zu", b);
-    if (zk[b]->c != c || zk[b]->C != bt->C || !zk[b]->z256) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: prover %zu belongs to another context or circuit", b);
-    if (zk[b]->have_comm) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "zk_commit_batch256: prover %zu has a communicator (the batch runs on one GPU)", b);
-    for (size_t a = 0; a < b; ++a)
-      if (zk[a] == zk[b]) return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: prover %zu appears twice", b);
-    z[b] = zk[b]->z256;
-  }
-  return zk256_commit_batch(bt->bt, z.data(), nb, h_W, rng, rng_user, ts, roots_out);
+  LF_TRY(zkp::check_batch_call("zk_commit_batch256", bt->c, bt->C, bt->nb_max, true, zk, nb, h_W, rng, ts));
+  return zk256_commit_batch(bt->bt, records256(zk, nb).data(), nb, h_W, rng, rng_user, ts, roots_out);
 }
 
+extern "C" int lfgpu_zk_batch_free(lfgpu_zk_batch* bt) {
+  if (!bt) return LFGPU_ERR_ARG;
+  delete bt;
+  return LFGPU_OK;
+}
 extern "C" int lfgpu_zk_batch256_free(lfgpu_zk_batch256* bt) {
   if (!bt) return LFGPU_ERR_ARG;
   delete bt;
@@ -997,12 +803,8 @@ static int zk_verify_impl(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, 
   lfgpu_ligero_param p{};
   LF_TRY(lfgpu_ligero_param_init(&p, I.field, 4, I.ninputs - I.npub_in + zkp::pad_size(C), C->layers.size(), rateinv, nreq, block_enc));
   if (!lf_gf_ctx(c, 4)) return LFGPU_ERR_ARG;
-  auto eq_table = [&](elt_t** d_eq) {
-    LF_TRY(zk_eq_reserve(c, I.ninputs));
-    *d_eq = (elt_t*)c->zk_eq;
-    return (int)LFGPU_OK;
-  };
-  return zkp::verify<P16>(c, C, policy16(c, I.field, nullptr), p, proof, proof_len, h_pub, tso, committed, eq_table, ok, why_out);
+  auto eq_table = [&](elt_t** d_eq) { return P16::eq_store(c, I.ninputs, nullptr, d_eq); };
+  return zkp::verify<P16>(c, C, P16::make(c, I.field, 4, nullptr), p, proof, proof_len, h_pub, tso, committed, eq_table, ok, why_out);
 }
 extern "C" int lfgpu_zk_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof,
                                size_t proof_len, const void* h_pub, const lfgpu_transcript_ops* tso, int* ok, const char** why_out) {
@@ -1014,102 +816,40 @@ extern "C" int lfgpu_zk_verify_committed(lfgpu_ctx* c, const lfgpu_circuit* C, s
 }
 
 // ------------------------------------------------------------------ LigeroProver::prove / LigeroVerifier::verify on a caller's statement
-// A second, small driver over zkp::ligero_prove / ligero_verify / com_proof_write / com_proof_read (zk_proto.h): the ZK paths keep
-// their own A step (dense EQ block + host-folded sparse terms), these two accumulate A on the device from the caller's term list.
+// zkp::ligero_prove_entry / ligero_verify_entry (zk_driver.h) over the 16-byte fields: the checks of the field and its subfield
+// in front, the A step from the term list in ligero.hip.
 namespace {
-// the host scan in front of the first transcript call or launch
-bool ligero_statement_ok(const lfgpu_ligero_param& p, size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm, const size_t* h_lqc) {
-  if ((nllterm && !llterm) || (p.nq && !h_lqc)) return false;
-  if (nllterm >= ((size_t)1 << 32) || nllterm + 6 * p.nq >= ((size_t)1 << 32)) return false;
-  for (size_t t = 0; t < nllterm; ++t)
-    if (llterm[t].c >= nl || llterm[t].w >= p.nw) return false;
-  for (size_t i = 0; i < 3 * p.nq; ++i)
-    if (h_lqc[i] >= p.nw) return false;
-  return true;
-}
-int wire_copy_out(lfgpu_ctx* c, const std::vector<uint8_t>& wire, uint8_t* buf, size_t cap, size_t* nbytes) {
-  *nbytes = wire.size();
-  if (cap < wire.size()) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: buffer too small (%zu < %zu)", cap, wire.size());
-  memcpy(buf, wire.data(), wire.size());
+int ligero16_ok(lfgpu_ctx* c, const char* who, int field, int k) {
+  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "%s: field", who);
+  if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, k)) return lf_fail(c, LFGPU_ERR_ARG, "%s: subfield_log_bits must be 4 or 5", who);
   return LFGPU_OK;
 }
 }  // namespace
 
 extern "C" int lfgpu_ligero_prove(lfgpu_ligero_prover* lp, const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm,
                                   const uint8_t hash_of_llterm[32], const size_t* h_lqc, uint8_t* buf, size_t cap, size_t* nbytes) {
-  if (!lp || !tso || !hash_of_llterm || !nbytes) return LFGPU_ERR_ARG;
-  LfLigeroView v;
-  lf_ligero_prover_view(lp, &v);
-  lfgpu_ctx* c = v.c;
-  const lfgpu_ligero_param& p = v.p;
-  if (v.field != LFGPU_FIELD_GF2_128 && v.field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: field");
-  if (!ligero_statement_ok(p, nl, nllterm, llterm, h_lqc))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 terms)");
-  if (!v.whole) return lf_fail(c, LFGPU_ERR_UNSUPPORTED, "ligero_prove: the prover must hold the whole tableau on one GPU");
-  if (v.field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, v.k)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove: subfield_log_bits must be 4 or 5");
-  if (buf && *v.wire_held) {  // the copy that follows a size query: the same serialisation
-    LF_TRY(wire_copy_out(c, *v.wire, buf, cap, nbytes));
-    *v.wire_held = false;
-    return LFGPU_OK;
-  }
-  *v.wire_held = false;
-  zkp::SubfieldSolver sub;
-  if (v.field == LFGPU_FIELD_GF2_128) sub.build(lf_gf_ctx(c, v.k));
-  const P16 pol = policy16(c, v.field, &sub, v.k);
-  const zkp::Ts<P16> ts{&pol, tso, tso->user};
-  zkp::ComProof<elt_t> pr;
-  double tq[6];
-  auto dot = [&](const std::vector<elt_t>& alphal, const std::vector<elt_t>& alphaq, elt_t* y_dot) {
-    const LfLigeroTerms t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
-    return lf_ligero_dot_terms(lp, &t, y_dot);
+  auto pre = [&](const LfLigeroView& v, lfgpu_ligero_prover** lig) {
+    *lig = lp;
+    LF_TRY(ligero16_ok(v.c, "ligero_prove", v.field, v.k));
+    if (!v.whole) return lf_fail(v.c, LFGPU_ERR_UNSUPPORTED, "ligero_prove: the prover must hold the whole tableau on one GPU");
+    return (int)LFGPU_OK;
   };
-  LF_TRY(zkp::ligero_prove<P16>(p, lp, ts, hash_of_llterm, nl, dot, pr, tq));
-  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-  if (verbose)
-    fprintf(stderr, "lfgpu ligero_prove: ldt %.2f ms | challenges %.2f | A from %zu terms + dot %.2f | quad %.2f | challenges+open %.2f\n", tq[1] - tq[0],
-            tq[2] - tq[1], nllterm, tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
-  v.wire->clear();
-  zkp::com_proof_write(pol, pr, *v.wire);
-  if (!buf) {
-    *nbytes = v.wire->size();
-    *v.wire_held = true;
-    return LFGPU_OK;
-  }
-  *v.wire_held = true;  // kept if the buffer turns out too small
-  LF_TRY(wire_copy_out(c, *v.wire, buf, cap, nbytes));
-  *v.wire_held = false;
-  return LFGPU_OK;
+  auto dot = [&](lfgpu_ligero_prover* lig, const std::vector<elt_t>& alphal, const std::vector<elt_t>& alphaq, elt_t* y_dot) {
+    const LfLigeroTerms t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
+    return lf_ligero_dot_terms(lig, &t, y_dot);
+  };
+  return zkp::ligero_prove_entry<P16>("ligero_prove", lp, tso, nl, nllterm, llterm, hash_of_llterm, h_lqc, buf, cap, nbytes, pre, dot);
 }
 
 extern "C" int lfgpu_ligero_verify(lfgpu_ctx* c, int field, int k, const lfgpu_ligero_param* pp, const uint8_t root[32], const uint8_t* proof, size_t proof_len,
                                    const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm* llterm,
                                    const uint8_t hash_of_llterm[32], const void* h_b, const size_t* h_lqc, int* ok, const char** why_out) {
-  if (!c || !pp || !root || !proof || !tso || !hash_of_llterm || !ok || (nl && !h_b)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: null argument");
-  *ok = 0;
-  if (field != LFGPU_FIELD_GF2_128 && field != LFGPU_FIELD_FP128) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: field");
-  if (field == LFGPU_FIELD_GF2_128 && !lf_gf_ctx(c, k)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: subfield_log_bits must be 4 or 5");
-  const lfgpu_ligero_param& p = *pp;
-  if (!ligero_statement_ok(p, nl, nllterm, llterm, h_lqc))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 terms)");
-  const P16 pol = policy16(c, field, nullptr, k);
-  const HostField F = pol.host_field(c);
-  auto fail = [&](int w) {
-    if (why_out) *why_out = zkp::why_string(w);
-    return (int)LFGPU_OK;
-  };
-  zkp::ComProof<elt_t> pr;
-  zkp::WireReader<P16> rd{pol, proof, proof_len};
-  if (!zkp::com_proof_read(rd, p, pr) || rd.bad || rd.left != 0) return fail(zkp::kWhyParse);
-  LF_HIP(c, hipSetDevice(c->device));
-  const zkp::Ts<P16> ts{&pol, tso, tso->user};
-  auto ext_fn = [&](const std::vector<elt_t>& alphal, const std::vector<elt_t>& alphaq, const size_t* idx, std::vector<elt_t>& ext) {
+  auto pre = [&] { return ligero16_ok(c, "ligero_verify", field, k); };
+  auto ext = [&](const zkp::ComProof<elt_t>& pr, const std::vector<elt_t>& alphal, const std::vector<elt_t>& alphaq, const size_t* idx, std::vector<elt_t>& out) {
     const LfLigeroTerms t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
-    auto a_rows = [&](elt_t* d_T, size_t ld) { return lf_ligero_a_rows_terms(c, field, &p, ld, &t, d_T); };
-    return P16::verifier_ext_with(c, field, k, p, a_rows, pr, idx, ext);
+    auto a_rows = [&](elt_t* d_T, size_t ld) { return lf_ligero_a_rows_terms(c, field, pp, ld, &t, d_T); };
+    return P16::verifier_ext_with(c, field, k, *pp, a_rows, pr, idx, out);
   };
-  int w = zkp::kWhyOk;
-  double tv[6];
-  LF_TRY(zkp::ligero_verify<P16>(pol, F, p, root, pr, ts, hash_of_llterm, nl, (const elt_t*)h_b, ext_fn, &w, tv));
-  if (w == zkp::kWhyOk) *ok = 1;
-  return fail(w);
+  return zkp::ligero_verify_entry<P16>("ligero_verify", c, field, k, pp, root, proof, proof_len, tso, nl, nllterm, llterm, hash_of_llterm, h_b, h_lqc, ok, why_out,
+                                       pre, ext);
 }

@@ -24,7 +24,7 @@
 #include <string>
 
 #include "ligero_slab.h"  // the Ligero prover record, its commit and prove side (and the host layout), over the policy L32 below
-#include "zk_proto.h"  // F256 (the host field), the protocol layer and Wire32
+#include "zk_driver.h"  // zk_proto.h -- F256 (the host field), the protocol layer and Wire32 -- and the driver layer around it
 
 typedef elt32_t E;
 #define Z_THREADS 256
@@ -2535,7 +2535,10 @@ struct P32 : zkp::Wire32 {
   using Lig = Lig32;
   using Layer = lfgpu_circuit::Layer;
   static constexpr const char* kProveName = "zk256_prove";
-  static F256 host_field(lfgpu_ctx*) { return F256(); }
+  static const F256& host_field(lfgpu_ctx*) {  // (the constants are built once)
+    static const F256 F;
+    return F;
+  }
   static constexpr bool kDeferGh = false;  // Quad::bind_gh_all synchronises per layer
   static int eval_layer(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail) { return lf256_eval_quad_async(q, d_W, d_V, d_fail); }
   static int sumcheck_layer(lfgpu_quad* q, const F256& F, size_t logv, const E* G0, const E* G1, const E& alpha, const E& beta, size_t logw, size_t nw,
@@ -2655,56 +2658,58 @@ struct P32 : zkp::Wire32 {
     ext.resize(nrows_dev * p.nreq);
     return lfgpu_memcpy_d2h(c, ext.data(), d_req, ext.size() * 32);
   }
+  // ---- the driver layer (zk_driver.h)
+  static constexpr const char *kName = "zk256", *kCommitName = "zk256_commit", *kCommitBatchName = "zk_commit_batch256", *kBatchNewName = "zk_batch256_new";
+  static constexpr int kLigeroK = 0;
+  struct ProverExtra {
+    // the prover's own EQ table of the input constraint: a function of the challenges only, cleared with the prover's other
+    // buffers all the same
+    void* d_eq = nullptr;
+    int init(lfgpu_ctx* c, int, int, size_t ninputs, zkp::Owned* mem) {
+      if (mem && !mem->alloc(&d_eq, ninputs * 32, true)) return lf_fail(c, LFGPU_ERR_NOMEM, "zk256: EQ table over the inputs");
+      return LFGPU_OK;
+    }
+  };
+  static P32 make(lfgpu_ctx*, int, int, const ProverExtra*) { return P32(); }
+  static int ts_ok(lfgpu_ctx* c, const lfgpu_transcript_ops* ts) {
+    if (!ts->write_elt_sized || !ts->write_elt_array_sized)
+      return lf_fail(c, LFGPU_ERR_ARG, "zk256: the transcript hooks lack write_elt_sized / write_elt_array_sized (32-byte elements)");
+    return LFGPU_OK;
+  }
+  // a hand-made lfgpu_ligero_param: the flat positions of a_terms256_kernel
+  static bool ligero_param_ok(const lfgpu_ligero_param& p) { return p.nw <= p.nwrow * p.w && p.nq <= p.nqtriples * p.w && p.nwqrow * p.w < 0xffffffffull; }
+  static int eq_store(lfgpu_ctx*, size_t, void* own, E** d_eq) {  // the prover's own table, or the batch's first
+    *d_eq = (E*)own;
+    return LFGPU_OK;
+  }
+  static int batch_prepare(lfgpu_ctx* c, size_t) { return scb256_mailbox(c); }  // the context's pinned mailbox of the batched sumcheck
+  static int lig_commit(lfgpu_ctx* c, const lfgpu_circuit_info&, const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user,
+                        uint8_t root[32], Lig** out, const lfgpu_comm_ops* shard) {
+    return lig256_commit(c, p, W, lqc, rng, user, root, out, shard);
+  }
+  static int lig_commit_batch(lfgpu_ctx* c, const lfgpu_circuit_info&, const lfgpu_ligero_param& p, size_t nb, const E* const* W, const size_t* lqc,
+                              const lfgpu_rng_fn* rng, void* const* users, uint8_t* roots, Lig** out) {
+    return lig256_commit_batch(c, p, nb, W, lqc, rng, users, roots, out);
+  }
+  static void lig_free(Lig* lp) { delete lp; }  // ~Slab scrubs the buffers and returns them to the context's pool
+  // the Ligero layout's draws on the empty slab: no image, the nonces dropped
+  static int draws_only(lfgpu_ctx* c, const lfgpu_ligero_param& p, const E* W, const size_t* lqc, lfgpu_rng_fn rng, void* user) {
+    char err[256] = {0};
+    const int rc = lig::layout(L32(), p, W, 0, lqc, rng, user, c->rng_exact != 0, 0, 0, (E*)nullptr, nullptr, err);
+    return rc ? lf_fail(c, rc, "%s", err) : LFGPU_OK;
+  }
 };
 }  // namespace
 
 // ------------------------------------------------------------------ ZkProver<Fp256Base>
-struct Zk256 {
-  lfgpu_ctx* c = nullptr;
-  const lfgpu_circuit* C = nullptr;
-  zkp::ProverState<P32> st;  // pads, the held proof, its wire bytes, timings
-  Lig32* lp = nullptr;
-  std::vector<void*> d_in;  // the layers' inputs (eval_circuit), resident for the sumcheck
-  void* d_V = nullptr;
-  void* h_V = nullptr;  // pinned: outputs then the assert-zero flag
-  void* d_eq = nullptr;  // EQ table of the input constraint
-  // lfgpu_zk_prover_set_comm: a tableau of at least comm_min_bytes is committed with its rows sharded over the communicator's GPUs
-  bool have_comm = false;
-  lfgpu_comm_ops comm{};
-  size_t comm_min_bytes = 0;
-  ~Zk256() {
-    delete lp;
-    // the layers' wire values are functions of the witness: scrubbed before the memory goes back to the allocator (as the
-    // tableau is, ~Slab of ligero_slab.h; the host copies of the pads: ~ProverState)
-    for (size_t l = 0; l < d_in.size(); ++l)
-      if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, C->layers[l].nw * 32, c->stream);
-    if (d_V) (void)hipMemsetAsync(d_V, 0, C->info.nv * 32, c->stream);
-    if (d_eq) (void)hipMemsetAsync(d_eq, 0, C->info.ninputs * 32, c->stream);
-    (void)hipStreamSynchronize(c->stream);
-    for (void* p : d_in)
-      if (p) (void)hipFree(p);
-    if (d_V) (void)hipFree(d_V);
-    if (d_eq) (void)hipFree(d_eq);
-    if (h_V) {
-      memset(h_V, 0, C->info.nv * 32 + 16);
-      (void)hipHostFree(h_V);
-    }
-  }
-};
+// P32, L32 and the kernels stay in this file (zkint.h), so the cross-file functions below are where the driver layer of
+// zk_driver.h is instantiated for the policy: the records are zkp::Prover<P32> / zkp::Batch<P32>, every function one call.
+struct Zk256 : zkp::Prover<P32> {};
+struct Zk256Batch : zkp::Batch<P32> {};
 
 int zk256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, Zk256** out) {
   std::unique_ptr<Zk256> z(new Zk256());
-  z->c = c;
-  z->C = C;
-  z->st.init(C);
-  LF_TRY(lfgpu_ligero_param_init(&z->st.param, LFGPU_FIELD_P256, 0, z->st.n_witness + z->st.pad_size, C->info.nl, rateinv, nreq, block_enc));
-  LF_HIP(c, hipSetDevice(c->device));
-  z->d_in.assign(C->layers.size(), nullptr);
-  for (size_t l = 0; l < C->layers.size(); ++l)
-    if (hipMalloc(&z->d_in[l], C->layers[l].nw * 32) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk256: layer %zu inputs", l);
-  if (hipMalloc(&z->d_V, C->info.nv * 32) != hipSuccess || hipMalloc(&z->d_eq, C->info.ninputs * 32) != hipSuccess)
-    return lf_fail(c, LFGPU_ERR_NOMEM, "zk256: outputs");
-  if (hipHostMalloc(&z->h_V, C->info.nv * 32 + 16, hipHostMallocDefault) != hipSuccess) return lf_fail(c, LFGPU_ERR_NOMEM, "zk256: pinned outputs");
+  LF_TRY(zkp::prover_init<P32>(*z, c, C, rateinv, nreq, block_enc));
   *out = z.release();
   return LFGPU_OK;
 }
@@ -2717,237 +2722,37 @@ void zk256_set_comm(Zk256* z, const lfgpu_comm_ops* comm, size_t min_tableau_byt
   if (comm) z->comm = *comm;
   z->comm_min_bytes = min_tableau_bytes;
 }
+const lfgpu_comm_ops* zk256_comm(const Zk256* z) { return z->have_comm ? &z->comm : nullptr; }
 void zk256_free(Zk256* z) { delete z; }
 int zk256_timings(const Zk256* z, double ms[6]) {
   memcpy(ms, z->st.ms, sizeof(z->st.ms));
   return LFGPU_OK;
 }
-
-static int ts256_ok(lfgpu_ctx* c, const lfgpu_transcript_ops* ts) {
-  if (!ts->write_elt_sized || !ts->write_elt_array_sized)
-    return lf_fail(c, LFGPU_ERR_ARG, "zk256: the transcript hooks lack write_elt_sized / write_elt_array_sized (32-byte elements)");
-  return LFGPU_OK;
-}
-
-// ZkProver::commit (zk_prover.h:72-96): fill_pad from rng, Ligero-commit witness || pad, root -> transcript
-// draws_only: perform every RandomEngine draw of the commit (pads, then the Ligero layout) and stop -- rank 0 of a communicator
-// records its engine's stream this way before any collective runs
 int zk256_commit(Zk256* z, const void* h_W, lfgpu_rng_fn rng, void* rng_user, const lfgpu_transcript_ops* ts, uint8_t root_out[32], bool draws_only) {
-  lfgpu_ctx* c = z->c;
-  LF_TRY(ts256_ok(c, ts));
-  const double t0 = now_ms();
-  auto& st = z->st;
-  const size_t nl = z->C->layers.size();
-  LF_HIP(c, hipSetDevice(c->device));
-  std::vector<E> pads(st.pad_size - nl);  // every element fill_pad draws (the product wc0 * wc1 is computed), in order
-  LF_SCRUB_ON_EXIT(pads);
-  if (c->rng_exact) for (size_t i = 0; i < pads.size(); ++i) h256_sample_many(&pads[i], 1, [&](uint8_t* b, size_t n) { rng(rng_user, b, n); });
-  else h256_sample_many(pads.data(), pads.size(), [&](uint8_t* b, size_t n) { rng(rng_user, b, n); });
-  size_t pd = 0;
-  auto draw = [&] { return pads[pd++]; };
-  std::vector<E> Wv(st.param.nw);  // witness || pads
-  LF_SCRUB_ON_EXIT(Wv);
-  memcpy(Wv.data(), (const E*)h_W + st.npub, st.n_witness * 32);
-  static const F256 F;  // (for fill_pad's wc0 * wc1: the constants are built once)
-  const size_t pi = zkp::pad_layout<P32>(F, z->C, st.n_witness, st.lqc, draw, &st.pad, Wv.data());
-  if (pi != st.param.nw) return lf_fail(c, LFGPU_ERR_ASSERT, "zk256_commit: witness layout");
-  if (draws_only) {  // the empty slab: no image, the nonces dropped
-    char err[256] = {0};
-    const int rc = lig::layout(L32(), st.param, Wv.data(), 0, st.lqc.data(), rng, rng_user, c->rng_exact != 0, 0, 0, (E*)nullptr, nullptr, err);
-    return rc ? lf_fail(c, rc, "%s", err) : LFGPU_OK;
-  }
-  delete z->lp;
-  z->lp = nullptr;
-  st.have_proof = false;
-  st.wire_valid = false;
-  const bool shard_rows = z->have_comm && z->comm.world > 1 && st.param.nrow * st.param.block_enc * 32 >= z->comm_min_bytes;
-  LF_TRY(lig256_commit(c, st.param, Wv.data(), st.lqc.data(), rng, rng_user, st.proof.root, &z->lp, shard_rows ? &z->comm : nullptr));
-  ts->write_bytes(ts->user, st.proof.root, 32);  // LigeroTranscript::write_commitment
-  if (root_out) memcpy(root_out, st.proof.root, 32);
-  st.ms[0] = now_ms() - t0;
-  return LFGPU_OK;
+  return zkp::commit<P32>(*z, h_W, rng, rng_user, ts, root_out, draws_only);
 }
-
-// ZkProver::prove (zk_prover.h:98-149), ZkProof::write (zk_proof.h:90-185), ZkVerifier::verify (zk_verifier.h:68-94): zk_proto.h
-int zk256_prove(Zk256* z, const void* h_W, const lfgpu_transcript_ops* tso, int* ok) {
-  LF_TRY(ts256_ok(z->c, tso));
-  if (!z->lp) return lf_fail(z->c, LFGPU_ERR_ARG, "zk256_prove: must run commit before prove");
-  auto eq_table = [&](E** d_eq) {  // the prover's own
-    *d_eq = (E*)z->d_eq;
-    return (int)LFGPU_OK;
-  };
-  return zkp::prove<P32>(z->c, z->C, P32(), z->st, z->lp, z->d_in.data(), z->d_V, z->h_V, eq_table, h_W, tso, ok);
-}
+int zk256_prove(Zk256* z, const void* h_W, const lfgpu_transcript_ops* tso, int* ok) { return zkp::prove<P32>(*z, h_W, tso, ok); }
 int zk256_proof_write(const Zk256* z, uint8_t* buf, size_t cap, size_t* nbytes) { return zkp::proof_write_cached(z->c, P32(), z->C, z->st, buf, cap, nbytes); }
-
-// ------------------------------------------------------------------ ZkProver::prove for a batch of committed provers
-// What lfgpu_zk_batch (zk.hip) is for the 16-byte fields, over 32-byte elements: the batch owns what the lock-step needs nb_max
-// times -- the layers' input slabs (statement b of layer l at d_in[l] + b * ldw[l] elements), the outputs, one assert-zero flag
-// per statement, their pinned read-back and nb_max EQ tables over the inputs (the dense blocks of the batched dot proofs).  All
-// of it is allocated in zk256_batch_new and nothing is allocated or freed inside zk256_prove_batch (hipFree waits for every
-// stream of the device); the only device memory a call may allocate is the context's pooled scratch, which grows on the first
-// call at a shape.
-struct Zk256Batch {
-  lfgpu_ctx* c = nullptr;
-  const lfgpu_circuit* C = nullptr;
-  size_t nb_max = 0;
-  std::vector<void*> d_in;
-  std::vector<size_t> ldw;
-  // the sizes of the allocations, recorded here: the scrub at destruction does not look at the circuit handle (which the caller
-  // may have freed first)
-  std::vector<size_t> in_bytes;
-  void* d_V = nullptr;
-  size_t ldv = 0, v_bytes = 0;
-  int* d_fail = nullptr;
-  void* h_V = nullptr;
-  size_t h_bytes = 0;
-  void* d_eq = nullptr;  // [nb_max][ninputs]: functions of the challenges only, not scrubbed
-  ~Zk256Batch() {
-    // the slabs hold the wire values of every statement -- functions of the witnesses: scrubbed before the memory goes back
-    if (c) {
-      (void)hipSetDevice(c->device);
-      for (size_t l = 0; l < d_in.size(); ++l)
-        if (d_in[l]) (void)hipMemsetAsync(d_in[l], 0, in_bytes[l], c->stream);
-      if (d_V) (void)hipMemsetAsync(d_V, 0, v_bytes, c->stream);
-      (void)hipStreamSynchronize(c->stream);
-    }
-    for (void* p : d_in)
-      if (p) (void)hipFree(p);
-    if (d_V) (void)hipFree(d_V);
-    if (d_fail) (void)hipFree(d_fail);
-    if (d_eq) (void)hipFree(d_eq);
-    if (h_V) {
-      memset(h_V, 0, h_bytes);
-      (void)hipHostFree(h_V);
-    }
-  }
-};
 
 int zk256_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, Zk256Batch** out) {
   std::unique_ptr<Zk256Batch> bt(new Zk256Batch());
-  bt->c = c;
-  bt->C = C;
-  bt->nb_max = nb_max;
-  LF_HIP(c, hipSetDevice(c->device));
-  auto pad2 = [](size_t n) { return (n + 1) & ~(size_t)1; };  // slabs start on 64-byte lines
-  const size_t nl = C->layers.size();
-  bt->d_in.assign(nl, nullptr);
-  bt->ldw.assign(nl, 0);
-  bt->in_bytes.assign(nl, 0);
-  auto alloc = [&](void** p, size_t bytes) {
-    if (hipMalloc(p, bytes) == hipSuccess) return true;
-    (void)hipGetLastError();
-    *p = nullptr;
-    return false;
-  };
-  for (size_t l = 0; l < nl; ++l) {
-    bt->ldw[l] = pad2(C->layers[l].nw);
-    bt->in_bytes[l] = nb_max * bt->ldw[l] * 32;
-    if (!alloc(&bt->d_in[l], bt->in_bytes[l])) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: %zu slabs of layer %zu (%zu bytes)", nb_max, l, bt->in_bytes[l]);
-  }
-  bt->ldv = pad2(C->info.nv);
-  bt->v_bytes = nb_max * bt->ldv * 32;
-  bt->h_bytes = bt->v_bytes + nb_max * sizeof(int);
-  if (!alloc(&bt->d_V, bt->v_bytes) || !alloc((void**)&bt->d_fail, nb_max * sizeof(int))) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: outputs");
-  if (hipHostMalloc(&bt->h_V, bt->h_bytes, hipHostMallocDefault) != hipSuccess) {
-    (void)hipGetLastError();
-    bt->h_V = nullptr;
-    return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: pinned outputs");
-  }
-  if (!alloc(&bt->d_eq, std::max<size_t>(nb_max * C->info.ninputs, 1) * 32)) return lf_fail(c, LFGPU_ERR_NOMEM, "zk_batch256_new: %zu EQ tables over the inputs", nb_max);
-  LF_TRY(scb256_mailbox(c));  // the context's pinned mailbox of the batched sumcheck: here, not inside the first proof
+  LF_TRY(zkp::batch_init<P32>(*bt, c, C, nb_max));
   *out = bt.release();
   return LFGPU_OK;
 }
 void zk256_batch_free(Zk256Batch* bt) { delete bt; }
-
 int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_transcript_ops* const* ts, int* ok) {
-  lfgpu_ctx* c = bt->c;
-  for (size_t b = 0; b < nb; ++b) {
-    LF_TRY(ts256_ok(c, ts[b]));
-    if (!z[b]->lp) return lf_fail(c, LFGPU_ERR_ARG, "zk_prove_batch256: prover %zu must run commit before prove", b);
-  }
-  std::vector<P32> pol(nb);
-  std::vector<zkp::ProverState<P32>*> st(nb);
-  std::vector<Lig32*> lp(nb);
-  for (size_t b = 0; b < nb; ++b) {
-    st[b] = &z[b]->st;
-    lp[b] = z[b]->lp;
-  }
-  auto eq_table = [&](E** d_eq) {  // the per-statement tail: the batch's first table, one statement after the other in stream order
-    *d_eq = (E*)bt->d_eq;
-    return (int)LFGPU_OK;
-  };
-  const zkp::BatchBufs bb{bt->d_in.data(), bt->ldw.data(), bt->d_V, bt->ldv, bt->d_fail, bt->h_V, bt->nb_max, bt->d_eq};
-  return zkp::prove_batch<P32>(c, bt->C, pol.data(), st.data(), lp.data(), bb, nb, eq_table, h_W, ts, ok);
+  return zkp::prove_batch<P32>(*bt, z, nb, h_W, ts, ok);
 }
-
-// ZkProver::commit for nb provers: zk256_commit's one-GPU branch per statement around ONE lig256_commit_batch.  The argument
-// errors left to this file -- a transcript without the sized hooks, provers with different parameters -- are found before the
-// first draw.
 int zk256_commit_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng, void* const* rng_user,
                        const lfgpu_transcript_ops* const* ts, uint8_t* roots_out) {
-  lfgpu_ctx* c = bt->c;
-  for (size_t b = 0; b < nb; ++b) {
-    LF_TRY(ts256_ok(c, ts[b]));
-    if (memcmp(&z[b]->st.param, &z[0]->st.param, sizeof(lfgpu_ligero_param)) != 0)
-      return lf_fail(c, LFGPU_ERR_ARG, "zk_commit_batch256: prover %zu has another LigeroParam (rate, nreq or block_enc) than prover 0", b);
-  }
-  const double t0 = now_ms();
-  LF_HIP(c, hipSetDevice(c->device));
-  const lfgpu_ligero_param& p = z[0]->st.param;
-  const size_t nl = bt->C->layers.size();
-  // whatever happens from here on, no prover of the call keeps an earlier commitment or proof
-  for (size_t b = 0; b < nb; ++b) {
-    delete z[b]->lp;
-    z[b]->lp = nullptr;
-    z[b]->st.have_proof = false;
-    z[b]->st.wire_valid = false;
-  }
-  // witness || pads of every statement; fill_pad's draws of statement b come from rng[b], before its Ligero draws (the pads of
-  // ALL statements are drawn before the first Ligero layout: a statement's own order -- pads, then layout -- is the single
-  // path's as long as its engine is its own, which the header asks for)
-  std::vector<E> Wv(nb * p.nw);
-  LF_SCRUB_ON_EXIT(Wv);
-  std::vector<const E*> Wp(nb);
-  std::vector<void*> users(nb);
-  static const F256 F;  // (for fill_pad's wc0 * wc1: the constants are built once)
-  for (size_t b = 0; b < nb; ++b) {
-    auto& st = z[b]->st;
-    lfgpu_rng_fn r = rng[b];
-    void* u = users[b] = rng_user ? rng_user[b] : nullptr;
-    std::vector<E> pads(st.pad_size - nl);  // every element fill_pad draws, in order (zk256_commit)
-    LF_SCRUB_ON_EXIT(pads);
-    auto fill = [&](uint8_t* buf, size_t n) { r(u, buf, n); };
-    if (c->rng_exact) for (size_t i = 0; i < pads.size(); ++i) h256_sample_many(&pads[i], 1, fill);
-    else h256_sample_many(pads.data(), pads.size(), fill);
-    size_t pd = 0;
-    auto draw = [&] { return pads[pd++]; };
-    E* W = Wv.data() + b * p.nw;
-    memcpy(W, (const E*)h_W[b] + st.npub, st.n_witness * 32);
-    if (zkp::pad_layout<P32>(F, bt->C, st.n_witness, st.lqc, draw, &st.pad, W) != p.nw)
-      return lf_fail(c, LFGPU_ERR_ASSERT, "zk_commit_batch256: witness layout (statement %zu)", b);
-    Wp[b] = W;
-  }
-  std::vector<uint8_t> roots(nb * 32);
-  std::vector<Lig32*> lps(nb, nullptr);
-  // (the lqc triples are the circuit's: the same for every prover)
-  LF_TRY(lig256_commit_batch(c, p, nb, Wp.data(), z[0]->st.lqc.data(), rng, users.data(), roots.data(), lps.data()));
-  for (size_t b = 0; b < nb; ++b) {
-    z[b]->lp = lps[b];
-    memcpy(z[b]->st.proof.root, &roots[32 * b], 32);
-    ts[b]->write_bytes(ts[b]->user, z[b]->st.proof.root, 32);  // LigeroTranscript::write_commitment
-  }
-  if (roots_out) memcpy(roots_out, roots.data(), nb * 32);
-  const double dt = now_ms() - t0;
-  for (size_t b = 0; b < nb; ++b) z[b]->st.ms[0] = dt;
-  return LFGPU_OK;
+  return zkp::commit_batch<P32>(*bt, z, nb, h_W, rng, rng_user, ts, roots_out);
 }
 
 int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof, size_t proof_len, const void* h_pub,
                  const lfgpu_transcript_ops* tso, bool committed, int* ok, const char** why_out) {
   *ok = 0;
-  LF_TRY(ts256_ok(c, tso));
+  LF_TRY(P32::ts_ok(c, tso));
   const lfgpu_circuit_info& I = C->info;
   lfgpu_ligero_param p{};
   LF_TRY(lfgpu_ligero_param_init(&p, LFGPU_FIELD_P256, 0, I.ninputs - I.npub_in + zkp::pad_size(C), C->layers.size(), rateinv, nreq, block_enc));
@@ -2961,97 +2766,34 @@ int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nr
 }
 
 // ------------------------------------------------------------------ LigeroProver::prove / LigeroVerifier::verify on a caller's statement
-// lfgpu_ligero_prove / lfgpu_ligero_verify (zk.hip) over Fp256Base: thin drivers over zkp::ligero_prove / ligero_verify /
-// com_proof_write / com_proof_read with the policy P32; the A step is L32::a_rows_terms on the caller's term list.
-namespace {
-// the host scan in front of the first transcript call or launch (the summand bound: see a_terms256_kernel)
-bool terms256_ok(const lfgpu_ligero_param& p, size_t nl, size_t nllterm, const lfgpu_ligero_llterm256* llterm, const size_t* h_lqc) {
-  if ((nllterm && !llterm) || (p.nq && !h_lqc)) return false;
-  if (nllterm >= ((size_t)1 << 32) || nllterm + 6 * p.nq >= ((size_t)1 << 32)) return false;
-  if (p.nw > p.nwrow * p.w || p.nq > p.nqtriples * p.w || p.nwqrow * p.w >= 0xffffffffull) return false;  // a hand-made lfgpu_ligero_param: the flat positions
-  for (size_t t = 0; t < nllterm; ++t)
-    if (llterm[t].c >= nl || llterm[t].w >= p.nw) return false;
-  for (size_t i = 0; i < 3 * p.nq; ++i)
-    if (h_lqc[i] >= p.nw) return false;
-  return true;
-}
-}  // namespace
-
+// zkp::ligero_prove_entry / ligero_verify_entry (zk_driver.h) over Fp256Base: the sized hooks checked in front (the parameter
+// checks of the kernel's flat positions: P32::ligero_param_ok), the A step is L32::a_rows_terms on the caller's term list.
 extern "C" int lfgpu_ligero_prove256(lfgpu_ligero_prover* lp, const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm256* llterm,
                                      const uint8_t hash_of_llterm[32], const size_t* h_lqc, uint8_t* buf, size_t cap, size_t* nbytes) {
-  if (!lp || !tso || !hash_of_llterm || !nbytes) return LFGPU_ERR_ARG;
-  LfLigeroView v;
-  lf_ligero_prover_view(lp, &v);
-  lfgpu_ctx* c = v.c;
-  const lfgpu_ligero_param& p = v.p;
-  if (!v.lig256) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove256: the prover is not over Fp256Base (lfgpu_ligero_prove serves the 16-byte fields)");
-  LF_TRY(ts256_ok(c, tso));
-  if (!terms256_ok(p, nl, nllterm, llterm, h_lqc))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove256: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 summands)");
-  auto copy_out = [&]() {
-    *nbytes = v.wire->size();
-    if (cap < v.wire->size()) return lf_fail(c, LFGPU_ERR_ARG, "ligero_prove256: buffer too small (%zu < %zu)", cap, v.wire->size());
-    memcpy(buf, v.wire->data(), v.wire->size());
-    *v.wire_held = false;
-    return (int)LFGPU_OK;
+  auto pre = [&](const LfLigeroView& v, Lig32** lig) {
+    if (!v.lig256) return lf_fail(v.c, LFGPU_ERR_ARG, "ligero_prove256: the prover is not over Fp256Base (lfgpu_ligero_prove serves the 16-byte fields)");
+    *lig = lig32_of(v.lig256);
+    return P32::ts_ok(v.c, tso);
   };
-  if (buf && *v.wire_held) return copy_out();  // the copy that follows a size query: the same serialisation
-  *v.wire_held = false;
-  LF_HIP(c, hipSetDevice(c->device));
-  Lig32* L = lig32_of(v.lig256);
-  const P32 pol;
-  const zkp::Ts<P32> ts{&pol, tso, tso->user};
-  zkp::ComProof<E> pr;
-  double tq[6];
-  auto dot = [&](const std::vector<E>& alphal, const std::vector<E>& alphaq, E* y_dot) {
+  auto dot = [&](Lig32* L, const std::vector<E>& alphal, const std::vector<E>& alphaq, E* y_dot) {
     const Terms256 t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
     return lig::dot_terms(L, L32(), t, y_dot);
   };
-  LF_TRY(zkp::ligero_prove<P32>(p, L, ts, hash_of_llterm, nl, dot, pr, tq));
-  static const bool verbose = getenv("LFGPU_VERBOSE") != nullptr;
-  if (verbose)
-    fprintf(stderr, "lfgpu ligero_prove256: ldt %.2f ms | challenges %.2f | A from %zu terms + dot %.2f | quad %.2f | challenges+open %.2f\n", tq[1] - tq[0],
-            tq[2] - tq[1], nllterm, tq[3] - tq[2], tq[4] - tq[3], tq[5] - tq[4]);
-  v.wire->clear();
-  zkp::com_proof_write(pol, pr, *v.wire);
-  *v.wire_held = true;  // kept after a size query, and if the buffer turns out too small
-  if (!buf) {
-    *nbytes = v.wire->size();
-    return LFGPU_OK;
-  }
-  return copy_out();
+  return zkp::ligero_prove_entry<P32>("ligero_prove256", lp, tso, nl, nllterm, llterm, hash_of_llterm, h_lqc, buf, cap, nbytes, pre, dot);
 }
 
 extern "C" int lfgpu_ligero_verify256(lfgpu_ctx* c, const lfgpu_ligero_param* pp, const uint8_t root[32], const uint8_t* proof, size_t proof_len,
                                       const lfgpu_transcript_ops* tso, size_t nl, size_t nllterm, const lfgpu_ligero_llterm256* llterm,
                                       const uint8_t hash_of_llterm[32], const void* h_b, const size_t* h_lqc, int* ok, const char** why_out) {
-  if (!c || !pp || !root || !proof || !tso || !hash_of_llterm || !ok || (nl && !h_b)) return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify256: null argument");
-  *ok = 0;
-  LF_TRY(ts256_ok(c, tso));
-  const lfgpu_ligero_param& p = *pp;
-  if (!terms256_ok(p, nl, nllterm, llterm, h_lqc))
-    return lf_fail(c, LFGPU_ERR_ARG, "ligero_verify256: bad statement (null list, term with c >= nl or w >= nw, lqc index >= nw, or 2^32 summands)");
-  const P32 pol;
-  static const F256 F;
-  auto fail = [&](int w) {
-    if (why_out) *why_out = zkp::why_string(w);
-    return (int)LFGPU_OK;
-  };
-  zkp::ComProof<E> pr;
-  zkp::WireReader<P32> rd{pol, proof, proof_len};
-  if (!zkp::com_proof_read(rd, p, pr) || rd.bad || rd.left != 0) return fail(zkp::kWhyParse);
-  LF_HIP(c, hipSetDevice(c->device));
-  const zkp::Ts<P32> ts{&pol, tso, tso->user};
-  auto ext_fn = [&](const std::vector<E>& alphal, const std::vector<E>& alphaq, const size_t* idx, std::vector<E>& ext) {
+  auto pre = [&] { return P32::ts_ok(c, tso); };
+  auto ext = [&](const zkp::ComProof<E>& pr, const std::vector<E>& alphal, const std::vector<E>& alphaq, const size_t* idx, std::vector<E>& out) {
+    const lfgpu_ligero_param& p = *pp;
     const Terms256 t{llterm, nllterm, alphal.data(), nl, h_lqc, alphaq.data()};
     auto a_rows = [&](E* d_T, size_t ld) { return L32::a_rows_terms(c, p, ld, t, d_T); };
     void* dv = nullptr;
     LF_TRY(lf_scratch4(c, (p.nwqrow + 3) * (p.block_enc + p.nreq) * 32 + 256, &dv));
-    return P32::verifier_ext_with(c, p, (E*)dv, a_rows, pr, idx, ext);
+    return P32::verifier_ext_with(c, p, (E*)dv, a_rows, pr, idx, out);
   };
-  int w = zkp::kWhyOk;
-  double tv[6];
-  LF_TRY(zkp::ligero_verify<P32>(pol, F, p, root, pr, ts, hash_of_llterm, nl, (const E*)h_b, ext_fn, &w, tv));
-  if (w == zkp::kWhyOk) *ok = 1;
-  return fail(w);
+  return zkp::ligero_verify_entry<P32>("ligero_verify256", c, LFGPU_FIELD_P256, 0, pp, root, proof, proof_len, tso, nl, nllterm, llterm, hash_of_llterm, h_b, h_lqc,
+                                       ok, why_out, pre, ext);
 }

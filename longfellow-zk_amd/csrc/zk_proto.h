@@ -189,6 +189,11 @@ struct Wire16 {  // GF(2^128) and Fp128; HostField dispatches on the field id
   bool of_bytes(const uint8_t* in, E& e) const { return elt_of_bytes(field, in, e); }
   template <class Fill>
   E sample(Fill fill) const { return elt_sample(field, fill); }
+  // fill_pad's draws (stage_witness): use(draw), where draw() is RandomEngine::elt at the moment pad_layout asks for an element
+  template <class Fill, class Use>
+  size_t with_pad_draw(size_t, bool, Fill fill, Use use) const {
+    return use([&] { return elt_sample(field, fill); });
+  }
   void ts_write_elt(const lfgpu_transcript_ops* o, void* u, const uint8_t* b) const { o->write_elt(u, b); }
   void ts_write_array(const lfgpu_transcript_ops* o, void* u, const uint8_t* b, size_t n) const { o->write_elt_array(u, b, n); }
   // the elements as the transcript wants them, when that is their storage (GF(2^128)); else nullptr: convert one by one
@@ -217,6 +222,17 @@ struct Wire32 {  // Fp256Base: every element is in the subfield, encoded at full
   static bool of_bytes(const uint8_t* in, E& e) { return h256_of_bytes(in, e); }
   template <class Fill>
   static E sample(Fill fill) { return h256_sample(fill); }
+  // fill_pad's draws (stage_witness): all ndraw elements first -- ONE bulk h256_sample_many, or under exact calls one call of 1
+  // per element -- into a scrubbed vector, then use(draw), where draw() hands them out in order
+  template <class Fill, class Use>
+  static size_t with_pad_draw(size_t ndraw, bool exact, Fill fill, Use use) {
+    std::vector<E> pads(ndraw);
+    LF_SCRUB_ON_EXIT(pads);
+    if (exact) for (auto& e : pads) h256_sample_many(&e, 1, fill);
+    else h256_sample_many(pads.data(), ndraw, fill);
+    size_t pd = 0;
+    return use([&] { return pads[pd++]; });
+  }
   static void ts_write_elt(const lfgpu_transcript_ops* o, void* u, const uint8_t* b) { o->write_elt_sized(u, b, 32); }
   static void ts_write_array(const lfgpu_transcript_ops* o, void* u, const uint8_t* b, size_t n) { o->write_elt_array_sized(u, b, n, 32); }
   static const uint8_t* raw_image(const E*) { return nullptr; }
@@ -350,6 +366,16 @@ size_t pad_layout(const typename P::Field& F, const lfgpu_circuit* C, size_t n_w
     pi += layer_size(logw);
   }
   return pi;
+}
+// The witness of ZkProver::commit (zk_prover.h:72-96) into Wv[param.nw]: the private inputs of h_W, then fill_pad's elements
+// drawn from fill(bytes, n) the policy's way (with_pad_draw: every element but the computed wc0 * wc1 of each layer).  Returns
+// pad_layout's length, which is param.nw.
+template <class P, class Fill>
+size_t stage_witness(const P& pol, const typename P::Field& F, const lfgpu_circuit* C, ProverState<P>& st, const void* h_W, bool rng_exact, Fill fill,
+                     typename P::E* Wv) {
+  memcpy(Wv, (const typename P::E*)h_W + st.npub, st.n_witness * sizeof(typename P::E));
+  return pol.with_pad_draw(st.pad_size - C->layers.size(), rng_exact, fill,
+                           [&](auto draw) { return pad_layout<P>(F, C, st.n_witness, st.lqc, draw, &st.pad, Wv); });
 }
 
 // ------------------------------------------------------------------ ZkProof::write / read

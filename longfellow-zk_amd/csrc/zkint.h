@@ -23,17 +23,27 @@ struct lfgpu_circuit {
   }
 };
 
-// ---- zk256.hip: ZkProver<Fp256Base, .> (BASELINE config 5, the mdoc signature circuit).  Same entry points as the
-// 16-byte fields (lfgpu_zk_prover_new / commit / prove / proof_write dispatch on the circuit's field id).
+// ---- zk256.hip: ZkProver<Fp256Base, .> (BASELINE config 5, the mdoc signature circuit).  The policy P32, the Ligero policy L32
+// and the kernels never leave that file, so these functions are where the driver layer of zk_driver.h is instantiated for them:
+// Zk256 is zkp::Prover<P32>, Zk256Batch is zkp::Batch<P32>, each function one call of the generic one.  The entry points of
+// zk.hip dispatch here on the circuit's field id, after their NULL checks and, for a batch, zkp::check_batch_call.
 struct Zk256;
+struct Zk256Batch;
 int zk256_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, Zk256** out);
 int zk256_param(const Zk256* z, lfgpu_ligero_param* p);
+// draws_only: every RandomEngine draw of the commit and nothing else (rank 0 of a communicator, lfgpu_zk_commit)
 int zk256_commit(Zk256* z, const void* h_W, lfgpu_rng_fn rng, void* rng_user, const lfgpu_transcript_ops* ts, uint8_t root_out[32], bool draws_only = false);
 int zk256_prove(Zk256* z, const void* h_W, const lfgpu_transcript_ops* ts, int* ok);
 int zk256_proof_write(const Zk256* z, uint8_t* buf, size_t cap, size_t* nbytes);
 int zk256_timings(const Zk256* z, double ms[6]);
 void zk256_free(Zk256* z);
 void zk256_set_comm(Zk256* z, const lfgpu_comm_ops* comm, size_t min_tableau_bytes);  // comm == nullptr: one GPU
+const lfgpu_comm_ops* zk256_comm(const Zk256* z);                                      // nullptr: none set
+int zk256_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, Zk256Batch** out);
+int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_transcript_ops* const* ts, int* ok);
+int zk256_commit_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng, void* const* rng_user,
+                       const lfgpu_transcript_ops* const* ts, uint8_t* roots_out);
+void zk256_batch_free(Zk256Batch* bt);
 int zk256_verify(lfgpu_ctx* c, const lfgpu_circuit* C, size_t rateinv, size_t nreq, size_t block_enc, const uint8_t* proof, size_t proof_len, const void* h_pub,
                  const lfgpu_transcript_ops* ts, bool committed, int* ok, const char** why);
 // MerkleTreeVerifier::verify_compressed_proof (lib/merkle/merkle_tree.h:160-209), host (zk.hip)
@@ -91,16 +101,3 @@ int lf256_eval_quad_async(lfgpu_quad* q, const void* d_W, void* d_V, int* d_fail
 // ... for nb statements in two launches (the asynchronous twin of lfgpu_eval_quad_batch256): statement b's wires at d_W + b * ldw,
 // its outputs at d_V + b * ldv (32-byte elements), its assert-zero failures ORed into d_fail[b]; arguments already checked
 int lf256_eval_quad_batch_async(lfgpu_quad* q, size_t nb, const void* d_W, size_t ldw, void* d_V, size_t ldv, int* d_fail);
-// ---- zk256.hip: ZkProver::prove for a batch of committed Fp256Base provers (lfgpu_zk_batch256_new / lfgpu_zk_prove_batch256 /
-// lfgpu_zk_batch256_free of zk.hip, which checks the handles: non-null, one context and circuit, no communicator, no prover
-// twice).  zk256_prove_batch finds the remaining argument errors -- a prover that has not committed, a transcript without the
-// sized hooks -- before it enqueues anything or touches a transcript.
-struct Zk256Batch;
-int zk256_batch_new(lfgpu_ctx* c, const lfgpu_circuit* C, size_t nb_max, Zk256Batch** out);
-int zk256_prove_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_transcript_ops* const* ts, int* ok);
-// ZkProver::commit for nb provers around one batched Ligero commit (lfgpu_zk_commit_batch256 of zk.hip checks the handles as
-// above, and the engines and transcripts for NULL); the remaining argument errors -- a transcript without the sized hooks, provers
-// with different parameters -- are found here before the first draw
-int zk256_commit_batch(Zk256Batch* bt, Zk256* const* z, size_t nb, const void* const* h_W, const lfgpu_rng_fn* rng, void* const* rng_user,
-                       const lfgpu_transcript_ops* const* ts, uint8_t* roots_out);
-void zk256_batch_free(Zk256Batch* bt);

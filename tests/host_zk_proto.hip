@@ -1,5 +1,5 @@
 // Host-only harness of tests/test_zk_proto_host.py: the parts of csrc/zk_proto.h that need no device context (transcript
-// view, ZkProof::write / read, inner_product_sparse) behind a small C ABI.  Compiled with hipcc --cuda-host-only and linked
+// view, ZkProof::write / read, inner_product_sparse, stage_witness) behind a small C ABI.  Compiled with hipcc --cuda-host-only and linked
 // against liblfgpu.so for the host helpers the header calls (field inverses, the GF(2^128) constants).
 // Elements cross this ABI as their to_bytes_field images (canonical little-endian values), never in Montgomery form.
 #include "../longfellow-zk_amd/csrc/zk_proto.h"
@@ -23,12 +23,13 @@ zkp::Wire16 wire16(int field) {
   }
   return w;
 }
-// f(policy, host field) for the field id; the prime fields' host fields need no context
+// f(policy, host field) for the field id; the prime fields' host fields need no context, GF(2^128)'s only the constants of one
 template <class Fn>
 int with_field(int field, Fn f) {
   if (field == LFGPU_FIELD_P256) return f(zkp::Wire32(), F256());
   if (field == LFGPU_FIELD_FP128) return f(wire16(field), HostField(nullptr, field));
-  return LFGPU_ERR_UNSUPPORTED;
+  static lfgpu_ctx no_device;  // (never initialised: lf_gf_ctx builds its host tables in place)
+  return f(wire16(field), HostField(&no_device, field));
 }
 template <class Fn>
 int with_wire(int field, Fn f) {
@@ -138,6 +139,57 @@ int hzp_inner_product_sparse(int field, const lfgpu_ligero_param* p, size_t na, 
     put(pol, val, val_out);
     *n_out = idx.size();
     return 0;
+  });
+}
+
+// A RandomEngine that hands out `stream` in order (zeros and *over = true past its end) and records the size of every call
+struct ScriptedRng {
+  const uint8_t* stream;
+  size_t len, *calls, cap, ncalls = 0, pos = 0;
+  bool over = false;
+  void operator()(uint8_t* b, size_t n) {
+    if (ncalls < cap) calls[ncalls] = n;
+    ++ncalls;
+    if (n > len - pos) {
+      over = true;
+      memset(b, 0, n);
+      return;
+    }
+    memcpy(b, stream + pos, n);
+    pos += n;
+  }
+};
+// zkp::stage_witness for a circuit of nl layers (logw[]) with npub public among ninputs inputs (h_W: all of them) over the
+// scripted engine: the staged vector (n_witness + pad_size elements), lqc[3 nl], the returned length, the engine's call sizes.
+// bulk_model != 0 (Fp256Base): not stage_witness but ONE h256_sample_many over the same stream, placed by pad_layout.
+int hzp_stage_witness(int field, const size_t* logw, size_t nl, size_t npub, size_t ninputs, const uint8_t* h_W, int exact, int bulk_model, const uint8_t* stream,
+                      size_t stream_len, size_t* calls, size_t calls_cap, size_t* ncalls, uint8_t* Wv_out, size_t* lqc_out, size_t* len_out) {
+  return with_field(field, [&](auto pol, const auto& F) {
+    using P = decltype(pol);
+    using E = typename P::E;
+    lfgpu_circuit C;
+    layers_of(C, logw, nl);
+    C.info.npub_in = npub;
+    C.info.ninputs = ninputs;
+    zkp::ProverState<P> st;
+    st.init(&C);
+    std::vector<E> W, Wv(st.n_witness + st.pad_size, P::zero());
+    if (!get(pol, h_W, ninputs, W)) return -1;
+    ScriptedRng rng{stream, stream_len, calls, calls_cap};
+    if constexpr (P::kBytes == 32) {
+      if (bulk_model) {
+        std::vector<E> pads(st.pad_size - nl);
+        h256_sample_many(pads.data(), pads.size(), [&](uint8_t* b, size_t n) { rng(b, n); });
+        size_t pd = 0;
+        memcpy(Wv.data(), W.data() + npub, st.n_witness * 32);
+        *len_out = zkp::pad_layout<P>(F, &C, st.n_witness, st.lqc, [&] { return pads[pd++]; }, &st.pad, Wv.data());
+      }
+    }
+    if (!bulk_model) *len_out = zkp::stage_witness(pol, F, &C, st, W.data(), exact != 0, [&](uint8_t* b, size_t n) { rng(b, n); }, Wv.data());
+    *ncalls = rng.ncalls;
+    put(pol, Wv, Wv_out);
+    std::copy(st.lqc.begin(), st.lqc.end(), lqc_out);
+    return rng.over ? -2 : 0;
   });
 }
 

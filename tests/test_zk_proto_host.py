@@ -1,5 +1,5 @@
 """csrc/zk_proto.h on the host: the field-generic protocol layer's wire format (ZkProof::write / read), the sparse share of
-inner_product_vector and the transcript view, compiled without device code (tests/host_zk_proto.hip) and checked against
+inner_product_vector, the transcript view and the staging of ZkProver::commit's witness, compiled without device code (tests/host_zk_proto.hip) and checked against
 independent Python models.  No GPU: the device steps of the policies are not instantiated here."""
 import ctypes as C
 import os
@@ -284,3 +284,107 @@ def test_transcript_view(field):
     h = Hooks(pkg)
     assert L.hzp_write_elt(C.c_int(field), C.byref(h.ops), _enc(field, elts[0])) == 0
     assert h.calls == ([("elt_sized", _enc(field, elts[0]), 32)] if field == P256 else [("elt", _enc(field, elts[0]))])
+
+
+# ---- zkp::stage_witness: the witness of ZkProver::commit (private inputs || fill_pad) against a model of the reference
+def _gf_mul(a, b):
+    """GF(2^128) = GF(2)[x] / (x^128 + x^7 + x^2 + x + 1), bit i of the integer = the coefficient of x^i"""
+    r = 0
+    for i in range(128):
+        if (b >> i) & 1:
+            r ^= a << i
+    for i in range(254, 127, -1):
+        if (r >> i) & 1:
+            r ^= (1 << i) | (0x87 << (i - 128))
+    return r
+
+
+class ScriptedEngine:
+    """RandomEngine over a fixed byte stream; Field::sample as the reference draws it: kBytes per attempt, one bytes() call each,
+    rejected when the little-endian value is >= p (lib/algebra/fp_generic.h:360-371; every 16-byte string is in GF(2^128))"""
+
+    def __init__(self, stream):
+        self.stream, self.pos, self.calls = stream, 0, []
+
+    def bytes(self, n):
+        assert self.pos + n <= len(self.stream)
+        self.calls.append(n)
+        self.pos += n
+        return self.stream[self.pos - n:self.pos]
+
+    def elt(self, field):
+        while True:
+            v = int.from_bytes(self.bytes(NBYTES[field]), "little")
+            if field == GF or v < PRIME[field]:
+                return v
+
+
+def _fill_pad_model(field, rng, inputs, npub):
+    """(witness, lqc): the private inputs, then ZkProver::fill_pad (zk_prover.h:152-188, logc = 0) -- per layer and round p(0) and
+    p(2) of hand 0 then hand 1, then wc0, wc1 and the computed product -- with setup_lqc's indices of the last three (zk_common.h)"""
+    mul = _gf_mul if field == GF else (lambda a, b: a * b % PRIME[field])
+    w, lqc = list(inputs[npub:]), []
+    for lw in LOGW:
+        for _ in range(lw):
+            for _h in range(2):
+                for k in range(3):
+                    if k != 1:
+                        w.append(rng.elt(field))
+        wc = [rng.elt(field), rng.elt(field)]
+        lqc += [len(w), len(w) + 1, len(w) + 2]
+        w += wc + [mul(wc[0], wc[1])]
+    return w, lqc
+
+
+STAGE_NPUB, STAGE_NIN = 2, 7
+
+
+def _stage_stream():
+    """16-byte blocks: the first 32 bytes 0xff (>= p for Fp128 and P-256: the first attempt is rejected in both prime fields), a
+    second such pair further in, pseudo-random bytes elsewhere"""
+    rng = random.Random(20)
+    blocks = [bytes(rng.randrange(256) for _ in range(16)) for _ in range(160)]
+    for i in (0, 1, 10, 11):
+        blocks[i] = b"\xff" * 16
+    return b"".join(blocks)
+
+
+def _stage(L, field, inputs, exact, bulk_model=False):
+    nb = NBYTES[field]
+    stream = _stage_stream()
+    nw = STAGE_NIN - STAGE_NPUB + sum(4 * lw + 3 for lw in LOGW)
+    calls, ncalls = (C.c_size_t * 256)(), C.c_size_t(0)
+    out, lqc, n = C.create_string_buffer(nw * nb), (C.c_size_t * (3 * len(LOGW)))(), C.c_size_t(0)
+    rc = L.hzp_stage_witness(C.c_int(field), (C.c_size_t * len(LOGW))(*LOGW), C.c_size_t(len(LOGW)), C.c_size_t(STAGE_NPUB), C.c_size_t(STAGE_NIN),
+                             b"".join(_enc(field, v) for v in inputs), C.c_int(exact), C.c_int(bulk_model), stream, C.c_size_t(len(stream)), calls, C.c_size_t(256),
+                             C.byref(ncalls), out, lqc, C.byref(n))
+    assert rc == 0 and ncalls.value <= 256
+    return [int.from_bytes(out.raw[nb * i:nb * (i + 1)], "little") for i in range(nw)], list(lqc), n.value, list(calls[:ncalls.value])
+
+
+@pytest.mark.parametrize("field", [GF, FP128, P256])
+def test_stage_witness_exact_calls_matches_fill_pad_model(field):
+    L, _ = _lib()
+    rng = random.Random(300 + field)
+    inputs = [_rand_elt(rng, field) for _ in range(STAGE_NIN)]
+    ref = ScriptedEngine(_stage_stream())
+    want, want_lqc = _fill_pad_model(field, ref, inputs, STAGE_NPUB)
+    got, lqc, n, calls = _stage(L, field, inputs, exact=1)
+    ndraw = sum(4 * lw + 2 for lw in LOGW)
+    assert len(ref.calls) == ndraw + (0 if field == GF else 4 if field == FP128 else 2)  # the rejected attempts: 16-byte blocks 0, 1, 10, 11
+    assert calls == ref.calls  # one hook call per attempt, of the reference's size
+    assert got == want  # the private inputs, the draws in fill_pad's order, wc0 * wc1 computed at every lqc[3 ly + 2]
+    assert lqc == want_lqc and n == len(want)
+
+
+def test_stage_witness_bulk_p256_is_one_sample_many():
+    L, _ = _lib()
+    rng = random.Random(301)
+    inputs = [_rand_elt(rng, P256) for _ in range(STAGE_NIN)]
+    got = _stage(L, P256, inputs, exact=0)
+    model = _stage(L, P256, inputs, exact=0, bulk_model=True)
+    assert got == model
+    ndraw = sum(4 * lw + 2 for lw in LOGW)
+    assert got[3] == [32 * ndraw, 32 * 2]  # one bulk call, then one for the two rejected attempts
+    # the accepted 32-byte chunks of one long draw are the exact-calls elements, so the staged vector is the same
+    assert got[:3] == _stage(L, P256, inputs, exact=1)[:3]
